@@ -5,14 +5,18 @@ One "step" = one complete tran! of the per-GPU sweep batch: CedarTranOp-style DC
 the 0-700 ns transient of every resident sweep instance, results gathered (RCCL all_gather, inside the timed region --
 the only collective of the path).
 
-Two workloads are timed in every run and printed in the same JSON line (rank 0):
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, runs W warm-up steps, times K steps and prints one JSON line
+(rank 0) with the headline and the figures of those timed steps only:
   value        : WEAK scaling -- every rank integrates ``--instances`` corner points (default 4096 = BASELINE.json config 4's
                  32-value Vdd axis x 128 temperatures); with N ranks the temperature axis is refined N-fold over the same
-                 range, so N GPUs process N x 4096 independent transients.
+                 range, so N GPUs process N x 4096 independent transients.  ms_per_step = wall time of one timed step.
+``--dump-outputs DIR`` then writes what the last timed step handed its caller (DC operating points, the recorded transient of
+the observed node, per-instance counters) as DIR/<name>.npy, float64; the inputs are the same in every run with the same arguments.
+
+``--full`` adds everything else to the same line (rank 0; the objects marked N=1 are measured only without other ranks):
   strong_1024  : STRONG scaling, BASELINE.json config 4 as worded -- the 32 x 32 = 1024-point Vdd x temp sweep split into
                  contiguous blocks of 1024 / N points per GPU.
-
-Further objects of the line (rank 0; the ones marked N=1 are measured only without other ranks):
+  full_newton  : the same batch with full Newton (newton_mode 0), what the default Jacobian-reuse mode is compared with.
   roofline     : the dominant kernel against the roof that bounds it.  The fused Newton kernel keeps its working set in LDS
                  and registers (65 B of HBM traffic per Newton round), so its roof is vector-instruction issue:
                  bound "valu_issue", achieved = SIMD cycles/s with a vector instruction in flight, peak = SIMDs x clock,
@@ -258,12 +262,19 @@ def main(argv=None):
                     help="0 = one kernel per op (the kernels behind the callback ABI), non-zero = fused Newton kernel (default)")
     ap.add_argument("--newton-mode", type=int, default=-1, help="1 = the nonlinear iteration as the reference's IDA runs it (Jacobian reuse, rate test: "
                     "csrc/tran_ctrl.hpp; fused kernel and CPU port), 0 = full Newton with a fixed update tolerance; default: 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step handed its caller to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: strong scaling, roofline (profiled step, "
+                    "rocprofv3 counter passes), full-Newton comparison, stamping-kernel / single-instance / callback / PSP103 ring legs, "
+                    "CPU baseline; a plain run only times the steps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true", help="skip the rocprofv3 child passes (roofline falls back to the committed profile)")
     ap.add_argument("--no-extras", action="store_true", help="skip stamp_kernel / single-instance / callback legs")
     ap.add_argument("--probe", action="store_true", help="internal: child of a rocprofv3 pass")
     ap.add_argument("--calib-copy", type=int, default=0, help="also run the fp64 calibration copy of this many MiB (HBM counter passes)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.newton_mode < 0:
         args.newton_mode = 1          # (per-op path: the convergence test only -- it refactors every round)
     if args.probe:
@@ -335,7 +346,7 @@ def run(args, rank, world, local_rank, dist, dev, sync, reduce_max, reduce_sum, 
                 raise RuntimeError("%d transient(s) failed on rank %d" % (stats["n_failed"], rank))
             if gather and world > 1:   # final gather of the result blocks over RCCL / xGMI: every rank calls it, or none
                 sweep_shard.gather_blocks(out, world, dev)
-            return stats["newton_iters"] + dcs["newton_iters"], out, stats
+            return stats["newton_iters"] + dcs["newton_iters"], {"dc_u0": u0, "tran_out": out, "tran_per_instance": per}, stats
         return sim, one_step
 
     def timed(one_step, steps, warmup):
@@ -345,9 +356,9 @@ def run(args, rank, world, local_rank, dist, dev, sync, reduce_max, reduce_sum, 
             dist.barrier()
         sync()
         t0 = time.perf_counter()
-        iters, last = 0, None
+        iters, last, outputs = 0, None, None
         for _ in range(steps):
-            n_it, _, last = one_step()
+            n_it, outputs, last = one_step()
             iters += n_it
         sync()
         if dist is not None:
@@ -356,114 +367,119 @@ def run(args, rank, world, local_rank, dist, dev, sync, reduce_max, reduce_sum, 
         if dist is not None:
             elapsed = reduce_max(float(elapsed))
             iters = reduce_sum(int(iters))
-        return iters, elapsed, last
+        return iters, elapsed, last, outputs
 
     # ---- weak scaling: the headline value -------------------------------------------------------------------------------------
     pts, _ = sweep_shard.rank_points(args.instances, rank, world)
     B = len(pts)
     sim, one_step = workload(pts)
     st = sim.st
-    iters, elapsed, last = timed(one_step, args.steps, args.warmup)
+    iters, elapsed, last, outputs = timed(one_step, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs, rank, world, dev)
 
-    # ---- strong scaling: BASELINE.json config 4 as worded (1024 points over the GPUs), every rank takes part ---------------------
+    # ---- --full only from here on (a plain run is set-up, warm-up and the timed steps); the profiled step, roofline, full Newton,
+    # ---- single-GPU legs and CPU baseline follow on rank 0.  Strong scaling: BASELINE.json config 4 as worded (1024 points over the
+    # ---- GPUs), every rank takes part ----------------------------------------------------------------------------------------------
     strong = None
-    if args.total_instances > 0:
+    if args.full and args.total_instances > 0:
         spts, _ = sweep_shard.strong_points(args.total_instances, rank, world)
         ssim, s_step = workload(spts)
-        s_iters, s_elapsed, _ = timed(s_step, max(1, min(args.steps, 3)), 1)
+        s_iters, s_elapsed, _, _ = timed(s_step, max(1, min(args.steps, 3)), 1)
         ssim.close()
         strong = {"value": round(s_iters / s_elapsed, 1), "unit": "newton_iters/s", "ms_per_step": round(1e3 * s_elapsed / max(1, min(args.steps, 3)), 3),
                   "instances_total": args.total_instances, "instances_per_gpu": len(spts), "scaling": "strong"}
 
     result = None
     if rank == 0:
-        # ---- per-kernel launch durations: one extra, event-timed step on THIS rank only (no collective inside) -------------------
-        sim.h.profile(True)
-        _, _, pstats = one_step(gather=False)
-        prof = sim.h.profile_read()
-        sim.h.profile(False)
-        nnz_lu = sim.h.lu_stats()["nnz_lu"]
-        ab = algorithmic_bytes(st, B, nnz_lu)
-        dom = max(prof.items(), key=lambda kv: kv[1][0])
-        kernels = {k: {"ms_total": round(v[0], 3), "calls": int(v[1]), "avg_us": round(1e3 * v[0] / max(v[1], 1), 3)} for k, v in prof.items()}
-        name = dom[0]
-        avg_s = dom[1][0] / max(dom[1][1], 1) * 1e-3
         value = iters / elapsed
-        roof = {"kernel": name, "avg_launch_us": round(avg_s * 1e6, 3), "kernels": kernels, "B_iter_per_instance": int(ab["B_iter_per_instance"])}
-        live = None
-        if world == 1 and not args.no_live_pmc:
-            live = live_counters(B, int(args.fused), args.newton_mode)
-        if name.startswith("fused"):
-            iters_per_launch = pstats["newton_iters"] / max(dom[1][1], 1)
-            roof.update({"bound": "valu_issue", "unit": "G SIMD-cycles/s", "peak": round(SIMDS * CLOCK_HZ / 1e9, 1),
-                         "newton_iters_per_launch": round(iters_per_launch, 1)})
-            src = None
-            if live and "fused" in live and "valu_busy_simd_cycles" in live["fused"]:
-                f = live["fused"]
-                roof["achieved"] = round(f["valu_busy_simd_cycles"] / f["kernel_ns"], 2)     # SIMD cycles with a VALU instruction in flight per ns
-                roof["per_newton_round"] = {k: round(v, 1) for k, v in f["per_newton_round"].items()}
-                roof["wave_time_shares"] = {k: round(v, 3) for k, v in f["wave_time_shares"].items()}
-                roof["valu_insts_per_s"] = round(f["per_newton_round"]["valu_insts"] * value / 1e9, 2)   # G wave-instructions/s at the timed rate
-                src = "live rocprofv3 --pmc pass of this workload (child process)"
-                if "hbm_bytes_per_launch" in f:
-                    roof["traffic"] = int(f["hbm_bytes_per_launch"])
-                    roof["hbm"] = {"bound": "hbm", "achieved": round(f["hbm_bytes_per_launch"] / avg_s / 1e9, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                   "frac": round(f["hbm_bytes_per_launch"] / avg_s / 1e9 / HBM_PEAK_GBS, 6),
-                                   "bytes_per_newton_round": round(f["hbm_bytes_per_launch"] / max(iters_per_launch, 1), 1),
-                                   "calibration": live.get("calibration")}
+        roof, cpu, extras = None, None, {}
+        if args.full:
+            # ---- per-kernel launch durations: one extra, event-timed step on THIS rank only (no collective inside) -------------------
+            sim.h.profile(True)
+            _, _, pstats = one_step(gather=False)
+            prof = sim.h.profile_read()
+            sim.h.profile(False)
+            nnz_lu = sim.h.lu_stats()["nnz_lu"]
+            ab = algorithmic_bytes(st, B, nnz_lu)
+            dom = max(prof.items(), key=lambda kv: kv[1][0])
+            kernels = {k: {"ms_total": round(v[0], 3), "calls": int(v[1]), "avg_us": round(1e3 * v[0] / max(v[1], 1), 3)} for k, v in prof.items()}
+            name = dom[0]
+            avg_s = dom[1][0] / max(dom[1][1], 1) * 1e-3
+            roof = {"kernel": name, "avg_launch_us": round(avg_s * 1e6, 3), "kernels": kernels, "B_iter_per_instance": int(ab["B_iter_per_instance"])}
+            live = None
+            if world == 1 and not args.no_live_pmc:
+                live = live_counters(B, int(args.fused), args.newton_mode)
+            if name.startswith("fused"):
+                iters_per_launch = pstats["newton_iters"] / max(dom[1][1], 1)
+                roof.update({"bound": "valu_issue", "unit": "G SIMD-cycles/s", "peak": round(SIMDS * CLOCK_HZ / 1e9, 1),
+                             "newton_iters_per_launch": round(iters_per_launch, 1)})
+                src = None
+                if live and "fused" in live and "valu_busy_simd_cycles" in live["fused"]:
+                    f = live["fused"]
+                    roof["achieved"] = round(f["valu_busy_simd_cycles"] / f["kernel_ns"], 2)     # SIMD cycles with a VALU instruction in flight per ns
+                    roof["per_newton_round"] = {k: round(v, 1) for k, v in f["per_newton_round"].items()}
+                    roof["wave_time_shares"] = {k: round(v, 3) for k, v in f["wave_time_shares"].items()}
+                    roof["valu_insts_per_s"] = round(f["per_newton_round"]["valu_insts"] * value / 1e9, 2)   # G wave-instructions/s at the timed rate
+                    src = "live rocprofv3 --pmc pass of this workload (child process)"
+                    if "hbm_bytes_per_launch" in f:
+                        roof["traffic"] = int(f["hbm_bytes_per_launch"])
+                        roof["hbm"] = {"bound": "hbm", "achieved": round(f["hbm_bytes_per_launch"] / avg_s / 1e9, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                       "frac": round(f["hbm_bytes_per_launch"] / avg_s / 1e9 / HBM_PEAK_GBS, 6),
+                                       "bytes_per_newton_round": round(f["hbm_bytes_per_launch"] / max(iters_per_launch, 1), 1),
+                                       "calibration": live.get("calibration")}
+                else:
+                    try:
+                        pmc = json.load(open(os.path.join(ROOT, "profiles", COMMITTED_PMC)))["fused2_newton"]
+                        roof["achieved"] = round(pmc["valu_busy_simd_cycles_per_ns"], 2)
+                        roof["per_newton_round"] = pmc["per_newton_round"]
+                        roof["wave_time_shares"] = pmc["wave_time_shares"]
+                        roof["traffic"] = pmc.get("hbm_bytes_per_launch")
+                        src = "committed profile profiles/%s (no live counter pass in this run)" % COMMITTED_PMC
+                    except (OSError, ValueError, KeyError):
+                        roof["achieved"] = None
+                roof["source"] = src
+                roof["frac"] = None if roof.get("achieved") is None else round(roof["achieved"] / roof["peak"], 4)
+                roof["algorithmic_GBps_info"] = round(ab["B_iter_per_instance"] * iters_per_launch / avg_s / 1e9, 1)
+                roof["note"] = ("the fused kernel holds J, rhs, u and the history in LDS / registers: HBM is not its roof (see roofline.hbm); frac = share of "
+                                "SIMD cycles with a vector instruction in flight (SQ_ACTIVE_INST_VALU x 4 / (1024 SIMDs x kernel time x 2.4 GHz)); "
+                                "algorithmic_GBps_info is SURVEY 8d's B_iter x iterations / time, a bytes-avoided figure, not a utilisation")
             else:
-                try:
-                    pmc = json.load(open(os.path.join(ROOT, "profiles", COMMITTED_PMC)))["fused2_newton"]
-                    roof["achieved"] = round(pmc["valu_busy_simd_cycles_per_ns"], 2)
-                    roof["per_newton_round"] = pmc["per_newton_round"]
-                    roof["wave_time_shares"] = pmc["wave_time_shares"]
-                    roof["traffic"] = pmc.get("hbm_bytes_per_launch")
-                    src = "committed profile profiles/%s (no live counter pass in this run)" % COMMITTED_PMC
-                except (OSError, ValueError, KeyError):
-                    roof["achieved"] = None
-            roof["source"] = src
-            roof["frac"] = None if roof.get("achieved") is None else round(roof["achieved"] / roof["peak"], 4)
-            roof["algorithmic_GBps_info"] = round(ab["B_iter_per_instance"] * iters_per_launch / avg_s / 1e9, 1)
-            roof["note"] = ("the fused kernel holds J, rhs, u and the history in LDS / registers: HBM is not its roof (see roofline.hbm); frac = share of "
-                            "SIMD cycles with a vector instruction in flight (SQ_ACTIVE_INST_VALU x 4 / (1024 SIMDs x kernel time x 2.4 GHz)); "
-                            "algorithmic_GBps_info is SURVEY 8d's B_iter x iterations / time, a bytes-avoided figure, not a utilisation")
-        else:
-            per_launch = ab.get(name)
-            roof.update({"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS, "traffic": None, "source": "HIP events, algorithmic bytes (SURVEY 8d)"})
-            roof["achieved"] = None if per_launch is None else round(per_launch / avg_s / 1e9, 3)
-            roof["frac"] = None if per_launch is None else round(per_launch / avg_s / 1e9 / HBM_PEAK_GBS, 5)
+                per_launch = ab.get(name)
+                roof.update({"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS, "traffic": None, "source": "HIP events, algorithmic bytes (SURVEY 8d)"})
+                roof["achieved"] = None if per_launch is None else round(per_launch / avg_s / 1e9, 3)
+                roof["frac"] = None if per_launch is None else round(per_launch / avg_s / 1e9 / HBM_PEAK_GBS, 5)
 
-        extras = {}
-        if args.newton_mode and int(args.fused):
-            # the same sweep with full Newton (every round restamps and refactors, converged at update norm < 1e-3): round 1's iteration
-            fn = []
-            for _ in range(2):
-                sync(); t0 = time.perf_counter()
-                n_it, _, fst = one_step(gather=False, newton_mode=0)
-                sync(); fn.append((time.perf_counter() - t0, n_it, fst))
-            dt, n_it, fst = min(fn, key=lambda x: x[0])
-            extras["full_newton"] = {"value": round(n_it / dt, 1), "unit": "newton_iters/s", "ms_per_step": round(1e3 * dt, 3), "newton_iters_per_step": int(n_it),
-                                     "accepted": int(fst["steps_accepted"]), "rejected": int(fst["steps_rejected"]),
-                                     "note": "newton_mode 0 on the same batch: what newton_mode 1 (IDA's Jacobian reuse and rate test) is compared with"}
-        if world == 1 and not args.no_extras:
-            # ---- north_star's stamping-kernel line, single-instance latency, callback sequence ------------------------------------
-            sk = stamp_kernel_leg(circ)
-            # north_star: "rocprof achieved-HBM-GB/s on the stamping kernel against the chip's peak" -- `frac` is the COUNTER figure (HBM bytes the
-            # kernel really moved / its duration / 8 TB/s) whenever a counter pass ran; SURVEY 8d's algorithmic bytes (which count the per-slot
-            # contributions although they never leave LDS) stay beside it as frac_algorithmic
-            sk["frac_algorithmic"] = sk["frac"]
-            sk["frac_source"] = "algorithmic bytes (no counter pass in this run)"
-            if live and "stamp" in live and "hbm_bytes_per_launch" in live["stamp"]:
-                sk["traffic"] = int(live["stamp"]["hbm_bytes_per_launch"])
-                sk["traffic_GBps"] = round(live["stamp"]["hbm_bytes_per_launch"] / (sk["avg_us"] * 1e3), 1)
-                sk["frac"] = round(sk["traffic_GBps"] / HBM_PEAK_GBS, 4)
-                sk["frac_source"] = "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this run (calibrated)"
-            extras["stamp_kernel"] = sk
-            extras.update(single_and_callback(circ, local_rank, args))
-            extras["psp103_ring"] = psp103_ring_leg(local_rank)
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(args, circ, sim, pts, save_t)
+            extras = {}
+            if args.newton_mode and int(args.fused):
+                # the same sweep with full Newton (every round restamps and refactors, converged at update norm < 1e-3): round 1's iteration
+                fn = []
+                for _ in range(2):
+                    sync(); t0 = time.perf_counter()
+                    n_it, _, fst = one_step(gather=False, newton_mode=0)
+                    sync(); fn.append((time.perf_counter() - t0, n_it, fst))
+                dt, n_it, fst = min(fn, key=lambda x: x[0])
+                extras["full_newton"] = {"value": round(n_it / dt, 1), "unit": "newton_iters/s", "ms_per_step": round(1e3 * dt, 3), "newton_iters_per_step": int(n_it),
+                                         "accepted": int(fst["steps_accepted"]), "rejected": int(fst["steps_rejected"]),
+                                         "note": "newton_mode 0 on the same batch: what newton_mode 1 (IDA's Jacobian reuse and rate test) is compared with"}
+            if world == 1 and not args.no_extras:
+                # ---- north_star's stamping-kernel line, single-instance latency, callback sequence ------------------------------------
+                sk = stamp_kernel_leg(circ)
+                # north_star: "rocprof achieved-HBM-GB/s on the stamping kernel against the chip's peak" -- `frac` is the COUNTER figure (HBM bytes the
+                # kernel really moved / its duration / 8 TB/s) whenever a counter pass ran; SURVEY 8d's algorithmic bytes (which count the per-slot
+                # contributions although they never leave LDS) stay beside it as frac_algorithmic
+                sk["frac_algorithmic"] = sk["frac"]
+                sk["frac_source"] = "algorithmic bytes (no counter pass in this run)"
+                if live and "stamp" in live and "hbm_bytes_per_launch" in live["stamp"]:
+                    sk["traffic"] = int(live["stamp"]["hbm_bytes_per_launch"])
+                    sk["traffic_GBps"] = round(live["stamp"]["hbm_bytes_per_launch"] / (sk["avg_us"] * 1e3), 1)
+                    sk["frac"] = round(sk["traffic_GBps"] / HBM_PEAK_GBS, 4)
+                    sk["frac_source"] = "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this run (calibrated)"
+                extras["stamp_kernel"] = sk
+                extras.update(single_and_callback(circ, local_rank, args))
+                extras["psp103_ring"] = psp103_ring_leg(local_rank)
+            if world == 1 and not args.no_cpu_baseline:
+                cpu = cpu_baseline(args, circ, sim, pts, save_t)
         result = {
             "metric": "newton_iters_per_sec", "value": round(value, 1), "unit": "newton_iters/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
@@ -480,11 +496,37 @@ def run(args, rank, world, local_rank, dist, dev, sync, reduce_max, reduce_sum, 
             "rejected_step_share": round(last["steps_rejected"] / max(last["steps_accepted"] + last["steps_rejected"], 1), 4),
             "value_note": "Newton iterations of rejected steps (rejected_step_share of all steps) and of the DC initialisation are counted in `value`: it is the kernel's iteration rate; "
                           "transients_per_s is the work rate",
-            "strong_1024": strong, "roofline": roof, "cpu_baseline": cpu, "reference_published": REFERENCE_PUBLISHED,
+            "reference_published": REFERENCE_PUBLISHED,
         }
-        result.update(extras)
+        if args.full:
+            result.update({"strong_1024": strong, "roofline": roof, "cpu_baseline": cpu})
+            result.update(extras)
     sim.close()
     return result
+
+
+DUMP_LIMIT = 60 * 10 ** 6        # bytes of array data --dump-outputs may write in all
+
+
+def dump_outputs(dirname, outputs, rank, world, dev):
+    """--dump-outputs: what the timed path's last step handed its caller -- the DC operating points (dc_u0, [B, n]), the recorded
+    transient of the observed node (tran_out, [B, save points, 1]) and the per-instance counters of tran_run (tran_per_instance,
+    [B, 4]) -- gathered over the ranks in sweep order, written by rank 0 as float64 DIR/<name>.npy.  Beyond DUMP_LIMIT bytes the same
+    fixed, seeded sample of instances is kept in every array and its indices are written as instance_index.npy."""
+    from cadnip_jl_amd import sweep_shard
+    full = {k: sweep_shard.gather_blocks(np.ascontiguousarray(outputs[k]), world, dev) for k in sorted(outputs)}   # every rank, same order
+    if rank != 0:
+        return
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in full.items()}
+    B = arrays["dc_u0"].shape[0]
+    row_bytes = sum(a.nbytes for a in arrays.values()) // B
+    if B * row_bytes > DUMP_LIMIT:
+        idx = np.sort(np.random.default_rng(0).choice(B, DUMP_LIMIT // (row_bytes + 8), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["instance_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def psp103_ring_leg(device):

@@ -14,12 +14,14 @@ if [ -n "$EXT_LIST" ]; then
   (cd ../.. && python3 -m cadnip_jl_amd.va.hipgen --ext cadnip.jl_amd/csrc/va_ext $EXT_LIST) > va_generated_ext.hpp.tmp
   cmp -s va_generated_ext.hpp.tmp va_generated_ext.hpp || mv va_generated_ext.hpp.tmp va_generated_ext.hpp; rm -f va_generated_ext.hpp.tmp
 fi
+# parallel jobs: one per CPU, at most $MAX_JOBS (default 16) -- a shared build host may grant fewer CPUs than nproc shows
+JOBS=$(nproc); CAP=${MAX_JOBS:-16}; [ "$JOBS" -gt "$CAP" ] && JOBS=$CAP
 # `build.sh --trace` builds the diagnostic library (cycle timeline of one wave, devices.hpp CADNIP_TRACE_POINT)
 if [ "${1:-}" = "--trace" ]; then
   # --trace [1|2]: 1 = phase boundaries only, 2 (default) = every point (devices.hpp)
-  make -j"$(nproc)" OUT=../libcadnip_hip_trace.so OBJ=_obj_trace${2:-2} EXTRA=-DCADNIP_TRACE=${2:-2}
+  make -j"$JOBS" OUT=../libcadnip_hip_trace.so OBJ=_obj_trace${2:-2} EXTRA=-DCADNIP_TRACE=${2:-2}
   echo "built $(realpath ../libcadnip_hip_trace.so)"
 else
-  make -j"$(nproc)"
+  make -j"$JOBS"
   echo "built $(realpath ../libcadnip_hip.so)"
 fi

@@ -69,11 +69,18 @@ def main():
         return float(t.item()) if isinstance(x, float) else int(t.item())
 
     args = types.SimpleNamespace(steps=2, warmup=1, instances=64, total_instances=96, fused=2, no_cpu_baseline=True, no_live_pmc=True,
-                                 no_extras=True, cpu_sample=8, newton_mode=1)
+                                 no_extras=True, cpu_sample=8, newton_mode=1, full=True, dump_outputs=None)
     res = bench.run(args, rank, world, rank, dist, None, sync=lambda: None, reduce_max=lambda x: allreduce(x, "max"),
                     reduce_sum=lambda x: allreduce(x, "sum"), simulator=StubSim)
+    # a plain run: warm-up and timed steps only, and the last step's outputs gathered over the ranks into --dump-outputs
+    n_full = len(CALLS)
+    dump = sys.argv[1]
+    plain = bench.run(types.SimpleNamespace(**dict(vars(args), full=False, dump_outputs=dump)), rank, world, rank, dist, None, sync=lambda: None,
+                      reduce_max=lambda x: allreduce(x, "max"), reduce_sum=lambda x: allreduce(x, "sum"), simulator=StubSim)
     dist.barrier()
     dist.destroy_process_group()
+    assert len(CALLS) - n_full == 3, CALLS
+    del CALLS[n_full:]
     # weak: (1 warmup + 2 timed) steps; strong: (1 + 2); rank 0: + 1 profiled step and 2 full-Newton comparison steps, none of them gathering
     assert CALLS.count("tran") == 6 + (3 if rank == 0 else 0), CALLS
     if rank == 0:
@@ -81,9 +88,17 @@ def main():
         assert res["config"]["newton_iters_per_step"] == 110 * 64 * world                  # SUM over ranks
         assert res["strong_1024"]["instances_total"] == 96 and res["strong_1024"]["instances_per_gpu"] == 96 // world
         assert res["roofline"]["kernel"] == "fused2_newton" and res["roofline"]["bound"] == "valu_issue"
+        for key in ("strong_1024", "roofline", "cpu_baseline", "full_newton"):
+            assert key not in plain, key
+        assert plain["steps"] == 2 and plain["ms_per_step"] > 0 and plain["config"]["newton_iters_per_step"] == 110 * 64 * world
+        out = np.load(os.path.join(dump, "tran_out.npy"))
+        assert out.dtype == np.float64 and out.shape == (64 * world, 71, 1)
+        assert np.array_equal(out[:, 0, 0], np.repeat(np.arange(world, dtype=float), 64))          # rank blocks in sweep order
+        assert np.load(os.path.join(dump, "dc_u0.npy")).shape[0] == 64 * world
+        assert np.load(os.path.join(dump, "tran_per_instance.npy")).shape == (64 * world, 4)
         print("BENCH_FLOW_OK " + json.dumps({"value": res["value"], "strong": res["strong_1024"]["value"]}))
     else:
-        assert res is None
+        assert res is None and plain is None
 
 
 if __name__ == "__main__":

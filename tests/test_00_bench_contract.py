@@ -5,13 +5,13 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 def test_bench_line_contract(capsys):
-    """bench.py in-process on a small sweep: ONE JSON line with the contract fields, the roofline object of the dominant
+    """bench.py --full in-process on a small sweep: ONE JSON line with the contract fields, the roofline object of the dominant
     kernel (live HIP-event timing) and the CPU baseline of the oracle's port."""
     import json
     import torch
     assert torch.cuda.is_available()
     import bench
-    bench.main(["--steps", "1", "--warmup", "0", "--instances", "64", "--cpu-sample", "32", "--total-instances", "64"])
+    bench.main(["--full", "--steps", "1", "--warmup", "0", "--instances", "64", "--cpu-sample", "32", "--total-instances", "64"])
     lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -40,3 +40,30 @@ def test_bench_line_contract(capsys):
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == d["unit"] and "sample" in c
 
+
+
+def test_bench_plain_run_and_dumped_outputs(capsys, tmp_path):
+    """A plain run: ONE JSON line with the headline fields and nothing that needs runs of its own; --steps sets the timed steps;
+    --dump-outputs writes the last timed step's arrays, the same in two runs with the same arguments."""
+    import json
+    import torch
+    assert torch.cuda.is_available()
+    import bench
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        bench.main(["--steps", "2", "--warmup", "1", "--instances", "64", "--dump-outputs", str(d)])
+        lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+        assert len(lines) == 1
+        r = json.loads(lines[0])
+        assert r["metric"] == "newton_iters_per_sec" and r["unit"] == "newton_iters/s" and r["higher_is_better"] is True and r["dtype"] == "f64"
+        assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["value"] > 1e6
+        assert abs(r["value"] - r["config"]["newton_iters_per_step"] / (r["ms_per_step"] * 1e-3)) <= 1e-2 * r["value"]
+        for key in ("strong_1024", "roofline", "cpu_baseline", "full_newton", "stamp_kernel", "psp103_ring"):
+            assert key not in r, key
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert sorted(a) == ["dc_u0", "tran_out", "tran_per_instance"]
+    assert a["tran_out"].shape == (64, 71, 1) and a["dc_u0"].shape[0] == 64 and a["tran_per_instance"].shape == (64, 4)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.all(np.isfinite(a[k])) and np.array_equal(a[k], b[k]), k

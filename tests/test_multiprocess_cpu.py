@@ -56,14 +56,15 @@ def test_strong_partition_and_unequal_blocks():
     assert n == 96 and len(pts) == 48 and pts[0] == sweep_shard.corner_points(32, 3)[48]
 
 
-def test_bench_control_flow_world_2():
+def test_bench_control_flow_world_2(tmp_path):
     """bench.run on two gloo ranks with a stub simulator: no rank-0-only collective (the N > 1 deadlock of round 1), weak and
-    strong workloads on every rank, SUM / MAX reductions, rank 0 assembles the line."""
+    strong workloads on every rank, SUM / MAX reductions, rank 0 assembles the line; then a plain run (no --full): the timed
+    steps alone, and --dump-outputs gathers the last step's arrays over the ranks."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), WORLD_SIZE="2")
     procs = []
     for r in range(2):
         e = dict(env, RANK=str(r), LOCAL_RANK=str(r))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "_bench_worker.py")], env=e,
+        procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "_bench_worker.py"), str(tmp_path / "dump")], env=e,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
     outs = [p.communicate(timeout=240)[0] for p in procs]
     assert all(p.returncode == 0 for p in procs), outs

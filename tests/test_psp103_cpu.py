@@ -48,7 +48,6 @@ def test_committed_fixtures_are_current(name):
         assert np.array_equal(extra["packed%d" % i], x0["packed%d" % i])
 
 
-@needs_source
 def test_oracle_passes_the_reference_psp103_dc_tests():
     """test/mna/psp103_integration.jl:40-122 on the oracle: V(d) = 1.2, V(g) = 0.6, |Id| in (100 uA, 1 mA) with the default card
     and in (10 uA, 10 mA) with the partial VACASK card."""

@@ -18,14 +18,16 @@ import numpy as np
 import pytest
 
 from cadnip_jl_amd.va import frontend as F, host_eval
-from cadnip_jl_amd import benchmarks as bm
+from cadnip_jl_amd import benchmarks as bm, va
 from oracle import mna_ref as M, va_ref
 from oracle.mna_ref import MNAContext, ZERO_VECTOR
 from oracle.va_mos1_ref import Mos1Model, stamp_mos1
 
 VA_DIR = "/root/reference/models/VADistillerModels.jl/va"
 PSP_DIR = "/root/reference/models/PSPModels.jl/va"
-pytestmark = pytest.mark.skipif(not os.path.isdir(VA_DIR), reason="the reference checkout is not present")
+TM_DIR = os.path.join(va.REFERENCE_ROOT, "test", "mna", "fixtures", "table_model")
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+needs_reference = pytest.mark.skipif(not os.path.isdir(VA_DIR), reason="the reference checkout is not present")
 
 # file -> (nodes, branches, reactive branches, $limit sites, node-collapse statements)
 EXPECTED = {
@@ -41,10 +43,10 @@ REFUSED = {os.path.join(PSP_DIR, "psp103_nqs.va"): "idt"}
 
 
 def test_table_model_interpolator_numerics():
-    """test/mna/table_model.jl:43-69: the 1-D and 2-D interpolators on the reference's fixture tables -- sample, interior, linear extrapolation
-    below and above the range -- in the product's host evaluator and in the oracle's restatement."""
+    """test/mna/table_model.jl:43-69: the 1-D and 2-D interpolators on the reference's fixture tables (data, kept as tests/golden/tm_*.tbl)
+    -- sample, interior, linear extrapolation below and above the range -- in the product's host evaluator and in the oracle's restatement."""
     from cadnip_jl_amd.va import table_model as T
-    d = "/root/reference/test/mna/fixtures/table_model/"
+    d = GOLD + os.sep
     for f in (T.lookup, va_ref.table_model_value):
         assert f(d + "tm_1d.tbl", "1L;1", [1.55]) == pytest.approx(0.02) and f(d + "tm_1d.tbl", "1L;1", [1.545]) == pytest.approx(0.015)
         assert abs(f(d + "tm_1d.tbl", "1L;1", [1.53])) < 1e-12 and f(d + "tm_1d.tbl", "1L;1", [1.57]) == pytest.approx(0.04)
@@ -53,12 +55,18 @@ def test_table_model_interpolator_numerics():
         assert f(d + "tm_1d.tbl", "1C;1", [1.57]) == pytest.approx(0.03)
         with pytest.raises(ValueError):
             f(d + "tm_1d.tbl", "1E;1", [1.57])
-    m = F.parse_file(d + "tm_1d.va")
-    assert len(m.table_calls) == 1 and m.shape()[4] == len(m.params) + 3 + 1
     with pytest.raises(F.VAError):          # a look-up of a bias-dependent quantity has no host-side value
         F.parse_module('module x(a); electrical a; analog I(a) <+ $table_model(V(a), "t.tbl", "1L;1"); endmodule')
 
 
+@needs_reference
+def test_table_model_fixture_module_parses():
+    """test/mna/table_model.jl's Verilog-A module (model text: read where it lies): one $table_model call on a parameter."""
+    m = F.parse_file(os.path.join(TM_DIR, "tm_1d.va"))
+    assert len(m.table_calls) == 1 and m.shape()[4] == len(m.params) + 3 + 1
+
+
+@needs_reference
 @pytest.mark.parametrize("fn", sorted(EXPECTED))
 def test_reference_model_parses(fn):
     m = F.parse_file(os.path.join(VA_DIR, fn))
@@ -66,6 +74,7 @@ def test_reference_model_parses(fn):
     assert len(m.ports) in (2, 3, 4, 5) and m.name.startswith("sp_")
 
 
+@needs_reference
 @pytest.mark.parametrize("fn", sorted(REFUSED))
 def test_unsupported_models_are_refused_with_a_reason(fn):
     with pytest.raises(F.VAError) as ei:
@@ -73,6 +82,7 @@ def test_unsupported_models_are_refused_with_a_reason(fn):
     assert REFUSED[fn] in str(ei.value)
 
 
+@needs_reference
 def test_potential_contributions_of_inductor_and_vdmos():
     """inductor.va: `V(br) <+ req*I(br)+veq` with veq = ddt(L * I(br)) -- a named branch at the top level of the analog block: its current is
     allocated up front, I(br) reads it as a plain number, the value carries ddt() (vasim.jl:3253-3266, 3632-3640, 3669-3746).  vdmos.va: the
@@ -87,6 +97,7 @@ def test_potential_contributions_of_inductor_and_vdmos():
     assert v.short_current_name(1, "m1") == "m1_I_V_t_0"
 
 
+@needs_reference
 def test_other_model_packages_parse():
     """models/CMCModels.jl (BSIM-CMG 107: 905 parameters, 2 internal nodes with the series-resistance option compiled in) and the self-heating
     PSP103 (a fifth, thermal terminal; Temp() / Pwr() access functions)."""
@@ -96,6 +107,7 @@ def test_other_model_packages_parse():
     assert (t.name, t.ports, t.n_internal, len(t.branches)) == ("PSP103TVA", ["D", "G", "S", "B", "DT"], 8, 19)
 
 
+@needs_reference
 def test_psp103_and_juncap_parse_through_their_includes():
     m = F.parse_file(os.path.join(PSP_DIR, "psp103.va"))
     assert m.name == "PSP103VA" and m.ports == ["D", "G", "S", "B"]
@@ -151,6 +163,7 @@ CARDS = {
 }
 
 
+@needs_reference
 @pytest.mark.parametrize("name", list(CARDS))
 @pytest.mark.parametrize("mode", ["tran", "dcop"])
 def test_reference_mos1_text_equals_the_hand_transcription(name, mode):
@@ -169,6 +182,7 @@ def test_reference_mos1_text_equals_the_hand_transcription(name, mode):
             assert np.array_equal(wsA.dctx.b, wsB.dctx.b) and np.array_equal(wsA.dctx.limit_w, wsB.dctx.limit_w)
 
 
+@needs_reference
 def test_reference_resistor_and_capacitor_text_stamp_the_closed_forms():
     spec = M.MNASpec(mode="tran", temp=27.0)
     for fn, card, which, want in (("resistor.va", dict(resistance=2e3), "G", 1.0 / 2e3), ("capacitor.va", dict(capacitance=3e-12), "C", 3e-12),
@@ -194,6 +208,7 @@ def test_reference_resistor_and_capacitor_text_stamp_the_closed_forms():
         assert np.allclose(A, want * np.array([[1.0, -1.0], [-1.0, 1.0]]), rtol=1e-12, atol=0.0), (fn, A)
 
 
+@needs_reference
 def test_reference_bjt_text_is_a_gummel_poon_transistor():
     """bjt.va (11 nodes; V(sub) <+ 0 ties the substrate terminal to ground through a branch current, two internal-internal shorts): the
     oracle's interpretation in a common-emitter stage -- Vbe = 0.7 V, bf = 100, is at its default 1e-16 A -- gives the textbook numbers
@@ -247,6 +262,7 @@ def _device_compile(header_text, tmp_path, opt="-O1"):
     assert os.path.getsize(tmp_path / "tu.o") > 1000
 
 
+@needs_reference
 def test_reference_models_generate_hip_that_compiles_for_gfx950(tmp_path):
     """resistor, capacitor, diode and mos1 of the reference -> one generated header -> device code for gfx950.  (The numbers the
     generated functions produce are pinned module by module on the GPU for the modules that ship with the library --
@@ -259,6 +275,7 @@ def test_reference_models_generate_hip_that_compiles_for_gfx950(tmp_path):
     _device_compile(text, tmp_path)
 
 
+@needs_reference
 @pytest.mark.parametrize("which", ["bsim4v8", "psp103"])
 def test_big_reference_models_generate_and_compile(which, tmp_path):
     """BSIM4 v8 (9 950 lines, 928 parameters, string version tests) and PSP103.4 (through its five include files, 782

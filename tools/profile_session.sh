@@ -13,7 +13,7 @@ OUT=$ROOT/gpurun_out
 P=$OUT/profiles_$TAG
 mkdir -p $OUT $P
 export TMPDIR=/tmp
-timeout -k 10 600 python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout -k 10 600 python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo "bench line done"
 B=$(python3 -c "import json;print(json.load(open('$OUT/${TAG}_bench.json'))['config']['instances_per_gpu'])")
 LEAN="--no-live-pmc --no-cpu-baseline --no-extras --total-instances 0"
