@@ -713,6 +713,31 @@ int cadnip_solve(CadnipHandle* h, const double* rhs_host, double* x_host) {
   return stage_finish(h);
 }
 
+int cadnip_factor_solve(CadnipHandle* h, const double* gamma_host, const double* rhs_host, const int32_t* active_host, int32_t kernel,
+                        double* x_host, int32_t* flags_host, int32_t* info) {
+  if (!h || !gamma_host || !rhs_host || !x_host || !flags_host || !info || kernel < CADNIP_LUK_AUTO || kernel > CADNIP_LUK_PLAIN) return CADNIP_BADARG;
+  if (!h->analyzed) return CADNIP_NOTREADY;
+  const size_t B = h->B, n = h->n;
+  TRY(launch_factor_solve(h, true, h->d_resid, h->d_delta, kernel, info, true));     // the choice first: a kernel that does not apply launches nothing
+  stage_begin(h);
+  TRY(stage_up(h, h->d_gamma, gamma_host, B * sizeof(double)));
+  TRY(stage_up(h, h->d_resid, rhs_host, B * n * sizeof(double)));
+  TRY(stage_up(h, h->d_delta, x_host, B * n * sizeof(double)));
+  TRY_RC(dev_zero_async(h, h->d_flags, B * sizeof(int)));
+  // the mask last: from its upload on, every exit goes through the restore below (the drivers expect every instance active)
+  int rc = active_host ? stage_up(h, h->d_active, active_host, B * sizeof(int)) : CADNIP_OK;
+  if (!rc) rc = launch_factor_solve(h, true, h->d_resid, h->d_delta, kernel, info);
+  if (!rc) rc = stage_down(h, x_host, h->d_delta, B * n * sizeof(double));
+  if (!rc) rc = stage_down(h, flags_host, h->d_flags, B * sizeof(int));
+  if (!rc) rc = stage_finish(h);
+  if (active_host) {
+    std::vector<int> ones(B, 1);
+    if (hipStreamSynchronize(h->stream) != hipSuccess || hipMemcpy(h->d_active, ones.data(), B * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+      if (!rc) rc = CADNIP_HIPERROR;
+  }
+  return rc;
+}
+
 int cadnip_lu_stats(CadnipHandle* h, int32_t* nnz_lu, int32_t* n_terms, int32_t* n_levels, int32_t* n_fwd, int32_t* n_bwd) {
   if (!h || !h->analyzed) return CADNIP_NOTREADY;
   if (nnz_lu) *nnz_lu = h->lu.nnz_lu;

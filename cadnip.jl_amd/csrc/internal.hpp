@@ -212,7 +212,10 @@ int launch_residual(CadnipHandle* h, const double* d_du);  // d_resid = C du + G
 int launch_jacobian(CadnipHandle* h);                      // d_J = G + gamma C
 int launch_factor(CadnipHandle* h, bool fuse_jacobian);    // LU of J (or of G + gamma C)
 int launch_solve(CadnipHandle* h, const double* d_rhs, double* d_x);
-int launch_factor_solve(CadnipHandle* h, bool fuse_jacobian, const double* d_rhs, double* d_x);
+// kernel: CADNIP_LUK_* (auto: the drivers' choice); info [6] (optional): what ran (cadnip_factor_solve).  dry: choose, fill info, launch
+// nothing.  A forced kernel that does not apply: CADNIP_BADARG
+int launch_factor_solve(CadnipHandle* h, bool fuse_jacobian, const double* d_rhs, double* d_x, int kernel = CADNIP_LUK_AUTO, int* info = nullptr,
+                        bool dry = false);
 int upload_lu(CadnipHandle* h);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

@@ -383,10 +383,17 @@ __global__ void __launch_bounds__(64 * NW) k_lu_steps(LuStepArgs f) {
   if (wave_any(bad) && lane == 0) atomicOr(&f.flags[inst], 1);
 }
 
-// 0 = done with the program kernel; 1 = not applicable (the caller falls back to k_lu); < 0 never
-int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x) {
+// 0 = done with the program kernel; 1 = not applicable (auto: the caller falls back to k_lu; a forced kernel: CADNIP_BADARG); < 0 never.
+// kernel: CADNIP_LUK_AUTO (the choice below, CADNIP_LU_* switches included) or one forced kernel (switches and batch rules ignored, the
+// LDS limits kept; W of k_lu_f2s / k_lu_f2 still from B).  info [6] (optional): kernel, waves per workgroup, waves per instance, nc, steps
+// or passes before / after the dense core.  dry: choose and fill info, launch nothing
+int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x, int kernel, int* info, bool dry) {
   if (!h->analyzed || !fused2_tables_ready(h)) return 1;   // (only the linear-solve prefix of the tables has to fit: checked below)
-  ProfScope ps(h, "lu_factor_solve");
+  const bool any = kernel == CADNIP_LUK_AUTO;
+  auto chosen = [&](int k, int wpb, int wpi, int pre, int post) {
+    if (info) { info[0] = k; info[1] = wpb; info[2] = wpi; info[3] = h->f2_nc; info[4] = pre; info[5] = post; }
+    return dry;
+  };
   LuF2Args f;
   f.tab = h->d_f2tab; for (int i = 0; i < S_NSEC; ++i) f.off[i] = h->f2off[i]; f.tab_len = h->f2_lu_len;
   f.tab_lo = 0; f.steps = nullptr; f.steps_len = 0; f.ts_pre = f.ts_post = 0;
@@ -394,11 +401,13 @@ int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x) {
   f.B = h->B; f.n = h->n; f.nnz = h->nnz; f.lu_words = h->f2_lu_words; f.n_pre = h->f2_n_pre; f.n_post = h->f2_n_post; f.nc = h->f2_nc; f.dn0 = h->f2_dn0;
   const size_t tab_dbl = (size_t)h->f2_lu_len / 2, per = (size_t)h->f2_lu_words + h->n + F2_TRASH;
   // at most two instances per CU: the straight-line steps of a team of four waves per instance (k_lu_steps).  CADNIP_LU_STEPS = 0 | 1 forces the choice
-  {
-    const char* e = getenv("CADNIP_LU_STEPS");
-    const bool steps = e ? atoi(e) != 0 : h->B <= 2 * h->n_cu_hint();
+  if (any || kernel == CADNIP_LUK_STEPS4) {
+    const char* e = any ? getenv("CADNIP_LU_STEPS") : nullptr;
+    const bool steps = !any || (e ? atoi(e) != 0 : h->B <= 2 * h->n_cu_hint());
     const size_t shmem_s = (per + 2) * 8;
     if (steps && h->d_steps4 && shmem_s <= 160 * 1024) {
+      if (chosen(CADNIP_LUK_STEPS4, 4, 4, h->steps4[0], h->steps4[1])) return CADNIP_OK;
+      ProfScope ps(h, "lu_factor_solve");
       LuStepArgs g;
       g.desc = (const uint4*)h->d_steps4; g.n_pre = h->steps4[0]; g.n_post = h->steps4[1];
       g.loadpos = (const u16*)(h->d_f2tab + h->f2off[S_LOADPOS]); g.rowof = (const u16*)(h->d_f2tab + h->f2off[S_ROWOF]); g.qinv = (const u16*)(h->d_f2tab + h->f2off[S_QINV]);
@@ -409,27 +418,33 @@ int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x) {
       HIP_TRY(hipGetLastError());
       return CADNIP_OK;
     }
+    if (!any) return 1;
   }
   // a few instances of a circuit with many passes: several waves per instance (k_lu_f2_mw).  CADNIP_LU_WPI forces 1 / 4 (diagnostic)
-  {
-    const char* e = getenv("CADNIP_LU_WPI");
-    const int wpi = e ? atoi(e) : (h->B * 4 <= h->n_cu_hint() && h->f2_n_pre + h->f2_n_post >= 32 ? 4 : 1);
+  if (any || kernel == CADNIP_LUK_F2MW) {
+    const char* e = any ? getenv("CADNIP_LU_WPI") : nullptr;
+    const int wpi = !any ? 4 : e ? atoi(e) : (h->B * 4 <= h->n_cu_hint() && h->f2_n_pre + h->f2_n_post >= 32 ? 4 : 1);
     const size_t shmem_mw = (tab_dbl + per) * 8;
     if (wpi == 4 && shmem_mw <= 160 * 1024) {
+      if (chosen(CADNIP_LUK_F2MW, 4, 4, h->f2_n_pre, h->f2_n_post)) return CADNIP_OK;
+      ProfScope ps(h, "lu_factor_solve");
       if (shmem_mw > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_lu_f2_mw<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_mw));
       hipLaunchKernelGGL(k_lu_f2_mw<4>, dim3(h->B), dim3(256), shmem_mw, h->stream, f);
       HIP_TRY(hipGetLastError());
       return CADNIP_OK;
     }
+    if (!any) return 1;
   }
   // many instances: one wave each.  On the step program when its descriptors fit beside eight work arrays (CADNIP_LU_F2S = 0 keeps the passes)
-  if (h->d_steps1 && !(getenv("CADNIP_LU_F2S") && atoi(getenv("CADNIP_LU_F2S")) == 0)) {
+  if ((any && h->d_steps1 && !(getenv("CADNIP_LU_F2S") && atoi(getenv("CADNIP_LU_F2S")) == 0)) || (kernel == CADNIP_LUK_F2S && h->d_steps1)) {
     const int lo = h->f2off[S_LOADPOS] & ~3;
     const size_t tabs = (size_t)(h->f2_lu_len - lo) / 2, desc = (size_t)h->steps1_len, pers = per + 2;
     int wpb = 8;
     while (wpb > 1 && h->B < 256 * wpb / 2) wpb >>= 1;
     const size_t shmem = (tabs + desc + wpb * pers) * 8;
     if ((tabs + desc + 8 * pers) * 8 <= 160 * 1024) {
+      if (chosen(CADNIP_LUK_F2S, wpb, 1, h->steps1[0], h->steps1[1])) return CADNIP_OK;
+      ProfScope ps(h, "lu_factor_solve");
       f.tab_lo = lo; f.tab_len = h->f2_lu_len - lo;
       f.steps = (const uint4*)h->d_steps1; f.steps_len = h->steps1_len; f.ts_pre = h->steps1[0]; f.ts_post = h->steps1[1];
       const int grid = (h->B + wpb - 1) / wpb;
@@ -441,10 +456,13 @@ int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x) {
       return CADNIP_OK;
     }
   }
+  if (!any && kernel != CADNIP_LUK_F2) return 1;
   int wpb = 8;
   while (wpb > 1 && ((tab_dbl + wpb * per) * 8 > 160 * 1024 || h->B < 256 * wpb / 2)) wpb >>= 1;
   const size_t shmem = (tab_dbl + wpb * per) * 8;
   if (shmem > 160 * 1024) return 1;
+  if (chosen(CADNIP_LUK_F2, wpb, 1, h->f2_n_pre, h->f2_n_post)) return CADNIP_OK;
+  ProfScope ps(h, "lu_factor_solve");
   const int grid = (h->B + wpb - 1) / wpb;
 #define LAUNCH(W) do { if (shmem > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_lu_f2<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
     hipLaunchKernelGGL(k_lu_f2<W>, dim3(grid), dim3(64 * W), shmem, h->stream, f); } while (0)

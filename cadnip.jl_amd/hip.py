@@ -21,7 +21,7 @@ STATUS_NAMES = {0: "CADNIP_OK", 1: "CADNIP_BADARG", 2: "CADNIP_SINGULAR", 3: "CA
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free",
@@ -155,6 +155,9 @@ def _check(code, where):
 
 
 MODE = {"dcop": 0, "tran": 1, "tranop": 2}
+
+# cadnip_factor_solve's kernel argument (CADNIP_LUK_*): auto, k_lu_steps<4>, k_lu_f2_mw<4>, k_lu_f2s<W>, k_lu_f2<W>, k_lu with the fused Jacobian
+LU_KERNELS = ("auto", "steps4", "mw4", "f2s", "f2", "plain")
 
 MODE_NAMES = ("dcop", "tran", "tranop")
 
@@ -312,6 +315,21 @@ class Handle:
         x = np.empty_like(r)
         _check(self.lib.cadnip_solve(self.h, _dp(r), _dp(x)), "cadnip_solve")
         return x
+
+    def factor_solve(self, gamma, rhs, kernel="auto", active=None, x0=None):
+        """cadnip_factor_solve: the drivers' per-op refactor + solve x = (G + gamma C)^-1 rhs on the G / C of the last rebuild, with one chosen
+        kernel (``LU_KERNELS``; plain launches).  ``active``: [B] (None = all); an inactive instance returns its row of ``x0`` (default zeros).
+        Returns (x [B, n], flags [B], info) with info = {kernel, wpb, wpi, nc, n_pre, n_post} of the kernel that ran.  A forced kernel that does
+        not apply to this circuit raises CadnipError(CADNIP_BADARG)."""
+        k = LU_KERNELS.index(kernel) if isinstance(kernel, str) else int(kernel)
+        g, r = self._b(gamma), self._bn(rhs)
+        x = np.array(self._bn(0.0 if x0 is None else x0))
+        act = None if active is None else np.ascontiguousarray(np.broadcast_to(np.asarray(active, dtype=np.int32), (self.B,)))
+        flags = np.zeros(self.B, dtype=np.int32)
+        info = np.zeros(6, dtype=np.int32)
+        _check(self.lib.cadnip_factor_solve(self.h, _dp(g), _dp(r), None if act is None else _ip(act), C.c_int32(k), _dp(x), _ip(flags), _ip(info)),
+               "cadnip_factor_solve")
+        return x, flags, dict(zip(("kernel", "wpb", "wpi", "nc", "n_pre", "n_post"), [LU_KERNELS[info[0]]] + [int(v) for v in info[1:]]))
 
     def newton_step(self, u, du, gamma=None, t=None, refresh=True, want_resid=False, fused=False):
         """cadnip_newton_step: resid = C du + G u - b, [J = G + gamma C refactored,] delta = J^-1 resid -- one call, one synchronisation.

@@ -187,6 +187,24 @@ int cadnip_analyze_values(CadnipHandle* h, const double* J_csr_host);
 int cadnip_factor(CadnipHandle* h);
 int cadnip_solve(CadnipHandle* h, const double* rhs_host, double* x_host);
 
+/* The per-op refactor + solve of the drivers (x = (G + gamma C)^-1 rhs on the G / C of the last cadnip_rebuild) with a chosen kernel:
+ * plain launches, for testing every kernel of that step.  gamma [B], rhs [B][n]; x [B][n] holds the initial contents on entry (what an
+ * inactive instance returns) and the solutions on return; active [B] may be NULL (all active) and is reset to all ones before returning;
+ * flags [B] receives the per-instance flags (bit 0: zero / non-finite pivot or non-finite solution).  A forced kernel that does not apply
+ * to this circuit (no program, tables beyond LDS) returns CADNIP_BADARG and launches nothing.  info [6]: kernel run, waves per workgroup,
+ * waves per instance, dense core size nc, and the steps (k_lu_steps, k_lu_f2s) or passes (k_lu_f2_mw, k_lu_f2) before and after the core
+ * (zeros for k_lu). */
+enum {
+  CADNIP_LUK_AUTO = 0,     /* the drivers' choice (csrc/lu_f2.hip: launch_factor_solve_f2), CADNIP_LU_* environment switches included */
+  CADNIP_LUK_STEPS4 = 1,   /* k_lu_steps<4>: straight-line steps, four waves per instance */
+  CADNIP_LUK_F2MW = 2,     /* k_lu_f2_mw<4>: the pass program, four waves per instance */
+  CADNIP_LUK_F2S = 3,      /* k_lu_f2s<W>: straight-line steps, one wave per instance, W instances per workgroup */
+  CADNIP_LUK_F2 = 4,       /* k_lu_f2<W>: the pass program, one wave per instance */
+  CADNIP_LUK_PLAIN = 5     /* k_lu, fused Jacobian: level by level on the LU program */
+};
+int cadnip_factor_solve(CadnipHandle* h, const double* gamma_host, const double* rhs_host, const int32_t* active_host, int32_t kernel,
+                        double* x_host, int32_t* flags_host, int32_t* info);
+
 /* One Newton iteration of the DAE form in one call -- what a host integrator that keeps the nonlinear loop to itself (IDA behind the Julia
  * shim: residual!, then jacobian! + klu_refactor when it decides on a set-up, then klu_solve; src/mna/precompile.jl:546-585,
  * src/mna/solve.jl:2138-2160, src/sweeps.jl:600) otherwise does with five entry points and five synchronisations:

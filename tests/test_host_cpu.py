@@ -951,3 +951,80 @@ def test_port_external_stamper_reproduces_its_own_transient():
     assert sa["status"] == 1 and np.array_equal(oa, ob) and (sa["newton_iters"], sa["accepted"], sa["rejected"]) == (sb["newton_iters"], sb["accepted"], sb["rejected"])
     for p in (a, b, helper):
         p.close()
+
+
+def test_factor_solve_entry_point_checks_its_arguments():
+    """cadnip_factor_solve (the per-op LU with a chosen kernel, tests/test_gpu_lu_kernels.py) is exported, and a null handle is refused with
+    CADNIP_BADARG for every kernel id, valid or not, before anything touches a GPU.  (The null data pointers of a real handle:
+    test_gpu_lu_kernels.py::test_factor_solve_refuses_null_pointers.)"""
+    lib = hip.load_library()
+    f = lib.cadnip_factor_solve
+    assert "cadnip_factor_solve" in hip.EXPORTS
+    g, r, x = np.zeros(1), np.zeros(4), np.zeros(4)
+    act, fl, info = np.ones(1, np.int32), np.zeros(1, np.int32), np.zeros(6, np.int32)
+    for k in range(-1, len(hip.LU_KERNELS) + 1):
+        assert f(None, hip._dp(g), hip._dp(r), hip._ip(act), ctypes.c_int32(k), hip._dp(x), hip._ip(fl), hip._ip(info)) == hip.BADARG, k
+    assert not np.any(x) and not np.any(fl) and not np.any(info)
+    assert hip.LU_KERNELS == ("auto", "steps4", "mw4", "f2s", "f2", "plain")
+
+
+def _badly_scaled_mna():
+    """6 x 6 MNA matrix: five nodes joined by conductances from 1e3 to 1e-12 S, a 1 fF node at gamma = 1e12, gmin leaks and a voltage
+    source's current (zero diagonal).  kappa_inf ~ 1e9."""
+    g = {(0, 1): 1e3, (1, 2): 1e-12, (2, 3): 3.7e-6, (3, 4): 2.2e1, (0, 4): 1e-9}
+    A = np.zeros((6, 6))
+    for (i, j), v in g.items():
+        A[i, i] += v; A[j, j] += v; A[i, j] -= v; A[j, i] -= v
+    A[2, 2] += 1e12 * 1e-15 + 1e-12
+    A[3, 3] += 1e-12
+    A[4, 4] += 1e-12
+    A[0, 5] = A[5, 0] = 1.0
+    return A
+
+
+def test_lu_reference_matches_mpmath():
+    """The reference of the LU kernel tests (tests/lu_ref.py) against mpmath at 40 digits: the refined solve is accurate to 1e-12 relative
+    on a badly scaled MNA matrix (a plain float64 solve: ~1e-10) and the long-double backward error is mpmath's to 1 %."""
+    import mpmath
+    from tests import lu_ref as R
+    A = _badly_scaled_mna()
+    b = np.random.default_rng(7).standard_normal(6) * np.array([1e-3, 1, 1e-9, 1, 1e3, 1])
+    assert R.cond_inf(A) > 1e8
+    with mpmath.workdps(40):
+        Am, bm_ = mpmath.matrix(A.tolist()), mpmath.matrix(b.tolist())
+        xm = mpmath.lu_solve(Am, bm_)
+        scale = max(abs(v) for v in xm)
+        err = lambda x: float(max(abs(mpmath.mpf(np.format_float_scientific(x[i], unique=True)) - xm[i]) for i in range(6)) / scale)
+        x_ref = R.refined_solve(A, b)
+        x64 = np.linalg.solve(A, b)
+        e_ref, e64 = err(x_ref), err(x64)
+        assert e_ref <= 1e-12 and e_ref <= 1e-2 * e64, (e_ref, e64)
+        # omega of the float64 solve: mpmath vs long double
+        xv = mpmath.matrix([mpmath.mpf(float(v)) for v in x64])
+        r = bm_ - Am * xv
+        den = [sum(abs(Am[i, j]) * abs(xv[j]) for j in range(6)) + abs(bm_[i]) for i in range(6)]
+        w_mp = float(max(abs(r[i]) / den[i] for i in range(6)))
+    rows, cols = np.nonzero(A)
+    w = R.backward_error(A[rows, cols].astype(R.LD)[None], rows, cols, x64[None], b[None])[0]
+    # (b - A x of a backward-stable solve cancels ~17 of long double's 19 digits: 1 % is what it can promise, and ample next to 1e-12)
+    assert w_mp > 0 and abs(w - w_mp) <= 1e-2 * w_mp, (w, w_mp)
+
+
+def test_static_order_solve_follows_the_given_order():
+    """lu_ref.static_order_solve (the ring's order check): a symmetric order (pivots on the diagonal) solves a diagonally dominant system;
+    on a matrix whose leading entry is
+    tiny, the identity order (no pivoting) loses what partial pivoting keeps, and the order that puts a large entry first does not."""
+    from tests import lu_ref as R
+    rng = np.random.default_rng(2)
+    A = rng.standard_normal((40, 40)) + 40 * np.eye(40)
+    b = rng.standard_normal(40)
+    x = np.linalg.solve(A, b)
+    for _ in range(3):
+        p = rng.permutation(40)
+        assert np.max(np.abs(R.static_order_solve(A, b, p, p) - x)) <= 1e-13 * np.max(np.abs(x))
+    A2 = np.array([[1e-17, 1.0], [1.0, 1.0]])
+    b2 = np.array([1.0, 2.0])
+    rows, cols = np.nonzero(A2)
+    w = lambda x: R.backward_error(A2[rows, cols].astype(R.LD)[None], rows, cols, x[None], b2[None])[0]
+    ident, swap = np.arange(2), np.array([1, 0])
+    assert w(R.static_order_solve(A2, b2, ident, ident)) > 1e-3 and w(R.static_order_solve(A2, b2, swap, ident)) < 1e-15
