@@ -345,8 +345,8 @@ static int launch_stamp_csr_pass(CadnipHandle* h, DeviceBlock& b, bool dump_only
                  b.d_cache, b.n_cache, dump_only ? h->d_dump : nullptr, h->ns, b.g_base, h->ns_g + b.c_base, h->ns_g + h->ns_c + b.b_base,
                  dump_only ? nullptr : P.rowoff, rows, dump_only ? 1 : 0};
   const unsigned grid = (unsigned)b.sp_chunks * (unsigned)((h->B + ipw - 1) / ipw);
-  if (getenv("CADNIP_SC_DEBUG")) fprintf(stderr, "[cadnip stamp] type %d count %d cs %d chunks %d ipw %d lpd %d slots %d rows %d scratch %d tile_words %zu shmem %zu grid %u levels %d%s\n",
-                                         TYPE, b.count, b.sp_cs, b.sp_chunks, ipw, lpd, nslots, rows, P.scratch, tile_words, shmem, grid, P.levels, dump_only ? " (read-out pass)" : "");
+  if (getenv("CADNIP_SC_DEBUG")) fprintf(stderr, "[cadnip stamp] type %d count %d cs %d chunks %d ipw %d lpd %d slots %d rows %d scratch %d tile_words %zu shmem %zu grid %u levels %d u_lds %d%s\n",
+                                         TYPE, b.count, b.sp_cs, b.sp_chunks, ipw, lpd, nslots, rows, P.scratch, tile_words, shmem, grid, P.levels, u_lds, dump_only ? " (read-out pass)" : "");
   if (TYPE == CADNIP_DEV_VA && b.va_tl) {           // external model: its own kernel (va_ext/<module>.hip)
     const int ext = b.va_model - CADNIP_VA_NBUILTIN;
     if (ext < 0 || ext >= CADNIP_VA_NEXT) return CADNIP_BADARG;

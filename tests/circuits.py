@@ -279,3 +279,54 @@ def inverter_chain(stages=8, vin=0.0):
         c.MOS1("mn%d" % k, "n%d" % (k + 1), "n%d" % k, "0", "0", dict(bm.NFET_06V0), l=0.6e-6, w=0.36e-6)
         c.MOS1("mp%d" % k, "n%d" % (k + 1), "n%d" % k, "vdd", "vdd", dict(bm.PFET_06V0), l=0.5e-6, w=0.495e-6)
     return c
+
+
+def tiled(base, K, shared=("0",), cap_node=None, param=None):
+    """K copies of the circuit ``base`` with renamed devices and nodes (copy k: ``<name>_t<k>``); the nodes in ``shared`` are common
+    to every copy (rails fed by every chunk of a device type), and node references inside behavioural expressions are renamed
+    with their nodes.  ``cap_node``: one more node, shared, that only capacitors touch (one per copy, to ground): its G diagonal
+    is stamped by nobody and carries gshunt alone.  ``param``: a sweep parameter name; the dc value (and waveform) of the first
+    voltage source of every copy is scaled by it (default 1)."""
+    import re
+    from cadnip_jl_amd.circuit import Device
+    keep = set(shared) | {"0", "gnd", "gnd!"}
+    ren = lambda nd, k: nd if nd in keep else "%s_t%d" % (nd, k)
+
+    def expr(e, k):
+        return re.sub(r"V\(([^)]*)\)", lambda m: "V(%s)" % ", ".join(ren(x.strip(), k) for x in m.group(1).split(",")), e)
+
+    c = cj.Circuit("%s x %d" % (base.title, K))
+    for k in range(K):
+        for d in base.devices:
+            p = dict(d.params)
+            if "expr" in p:
+                p["expr"] = expr(p["expr"], k)
+            if param is not None and d is next(x for x in base.devices if x.type == "V"):
+                p["dc"] = cj.Param(param, scale=float(p["dc"]))
+                if d.wave is not None:
+                    p["scale"] = cj.Param(param, scale=float(p["scale"]))
+            c.devices.append(Device(d.type, "%s_t%d" % (d.name, k), tuple(ren(n, k) for n in d.nodes), p, d.wave, d.model))
+        if cap_node is not None:
+            c.C("ccap_t%d" % k, cap_node, "0", 1e-12 * (1 + 0.01 * k))
+    return c
+
+
+# Circuits that reach the multi-tile paths of the per-op stamping kernels (csrc/stamp_csr.hip; tests/test_gpu_stamp_kernels.py):
+# several chunks per device type (sp_mos1: 32 devices per chunk; the other built-in types 64), rails shared across chunks (fp64
+# atomics, k_stamp_prep pre-set words), u not staged in LDS, deep 5-ary reduction trees, rows above 512 entries.
+TILED_STAMP = {
+    "linear_zoo_x65": (lambda: tiled(linear_zoo(), 65, shared=("a", "b", "c", "f"), cap_node="cq", param="vs"), {"vs": 1.0}),
+    "nonlinear_zoo_x65": (lambda: tiled(nonlinear_zoo(), 65, shared=("out", "in"), cap_node="cq", param="vs"), {"vs": 1.0}),
+    "behavioral_x65": (lambda: tiled(behavioral(), 65, shared=("x", "z"), param="vs"), {"vs": 1.0}),
+    "va_zoo_x33": (lambda: tiled(va_zoo(), 33, shared=("k", "out"), cap_node="cq", param="vs"), {"vs": 1.0}),
+    "va_limited_x65": (lambda: tiled(va_limited(), 65, shared=("out", "x"), param="vs"), {"vs": 1.0}),
+    "va_mos_inverter_x65": (lambda: tiled(va_mos_inverter(), 65, shared=("out", "y"), param="vs"), {"vs": 1.0}),
+}
+def param_supply(c, name="vdd"):
+    """The circuit with its voltage source ``name``'s dc value scaled by the sweep parameter ``name`` (default 1)."""
+    d = next(x for x in c.devices if x.type == "V" and x.name == name)
+    d.params["dc"] = cj.Param(name, scale=float(d.params["dc"]))
+    return c
+
+
+CHAIN_STAMP = {"chain%d" % s: ((lambda s=s: param_supply(inverter_chain(s, vin=5.0))), {"vdd": 1.0}) for s in (16, 17, 40, 200, 520)}

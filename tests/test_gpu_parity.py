@@ -10,6 +10,7 @@ from cadnip_jl_amd import api as api_mod
 from oracle import mna_ref as M
 from oracle.netlist_ref import make_builder
 from tests.circuits import ALL_STAMP
+from tests import stamp_ref as SR
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +40,14 @@ def _close(a, b, scale=None):
     return np.max(np.abs(a - b)) <= RTOL * scale + 1e-300
 
 
+def _per_entry(st, stamper, u, t, G, C, b):
+    """Entry by entry against the oracle's exact sums (tests/stamp_ref.py): _close above is one tolerance for the whole array, which
+    the largest entry sets -- blind on the small ones."""
+    ref = stamper.rebuild(u, t)
+    for c in SR.check_stamp(G[st.to_ref_nz], C[st.to_ref_nz], b, ref, rho=SR.RHO, st=st, u=u):
+        assert c.ok, c
+
+
 @pytest.mark.parametrize("name", list(ALL_STAMP))
 @pytest.mark.parametrize("mode,t", [("tran", 0.0), ("tran", 1.3e-3), ("dcop", 0.0)])
 def test_rebuild_matches_oracle(name, mode, t):
@@ -49,6 +58,7 @@ def test_rebuild_matches_oracle(name, mode, t):
     cs, ws = _oracle(circ, params, mode)
     st, h = _handle(circ, params, mode=mode)
     assert st.n == cs.n and st.nnz == cs.G.nnz
+    stamper = SR.OracleStamper(circ, params, mode=mode, st=st)
     rng = np.random.default_rng(42)
     for trial in range(3):
         u = (rng.random(st.n) * 2 - 0.5) * (1.0 if trial else 0.0)
@@ -60,6 +70,7 @@ def test_rebuild_matches_oracle(name, mode, t):
         for got, ref in ((G[0], cs.G.data), (C[0], cs.C.data), (b[0], ws.dctx.b)):
             # entries are sums of stamps: compare relative to the largest stamp magnitude in the array
             assert _close(got, ref), (name, trial, np.max(np.abs(got - ref)), np.max(np.abs(ref)))
+        _per_entry(st, stamper, u, t, G[0], C[0], b[0])
         if st.n_limits:
             assert _close(lw[0], ws.dctx.limit_w, scale=max(1.0, np.max(np.abs(ws.dctx.limit_w))))
         du = rng.random(st.n)
@@ -85,8 +96,11 @@ def test_rebuild_matches_oracle(name, mode, t):
 def test_rebuild_of_a_batch_matches_oracle(B):
     """The stamping kernels' launch geometry depends on the batch (csrc/stamp_csr.hip: instances per wave for small device types, tiles per
     chunk, grid): a batch of B flip-flop corners with their own supplies, temperatures, states and times -- B not a multiple of anything --
-    restamped in one call; several instances against the oracle at 1e-12, and every instance against its own single-instance restamp bit
-    for bit (the per-op path has one writer per word and sums in the reference's COO order: no batch dependence at all)."""
+    restamped in one call; several instances against the oracle at 1e-12 and entry by entry (tests/stamp_ref.py), and every instance
+    against its own single-instance restamp bit for bit.  (Every word of the flip-flop has one writer -- one chunk per device type: 30
+    sp_mos1, 61 capacitors -- which sums in the reference's COO order: no batch dependence at all.  Where a type spans several chunks,
+    the words the chunks share are accumulated with fp64 atomics and only the other words are bit-for-bit batch-independent:
+    tests/test_gpu_stamp_kernels.py.)"""
     mk, params = ALL_STAMP["dff"]
     circ = mk()
     rng = np.random.default_rng(B)
@@ -106,6 +120,7 @@ def test_rebuild_of_a_batch_matches_oracle(B):
         M.fast_rebuild(ws, u[i], float(t[i]))
         for got, ref in ((G[i], cs.G.data), (C[i], cs.C.data), (b[i], ws.dctx.b)):
             assert _close(got, ref), (B, i, np.max(np.abs(got - ref)), np.max(np.abs(ref)))
+        _per_entry(st, SR.OracleStamper(circ, {"vdd": float(vdds[i])}, temp=float(temps[i]), st=st), u[i], float(t[i]), G[i], C[i], b[i])
         st1, h1 = _handle(circ, {"vdd": float(vdds[i])}, temps=float(temps[i]))
         h1.rebuild(u[i], float(t[i]))
         G1, C1, b1, lw1 = h1.get_GCb()
