@@ -86,6 +86,10 @@ int cadnip_create(const CadnipStructure* s, int32_t n_instances, int32_t device,
   h->h_colidx.assign(s->colidx, s->colidx + s->nnz);
   h->h_to_ref.assign(s->to_ref_nz, s->to_ref_nz + s->nnz);
   h->h_limit_init.assign(s->limit_init, s->limit_init + s->n_limits);
+  h->h_g_ptr.assign(s->g_ptr, s->g_ptr + s->nnz + 1); h->h_c_ptr.assign(s->c_ptr, s->c_ptr + s->nnz + 1); h->h_b_ptr.assign(s->b_ptr, s->b_ptr + s->n + 1);
+  if (s->g_slots) h->h_g_slots.assign(s->g_slots, s->g_slots + s->g_ptr[s->nnz]);
+  if (s->c_slots) h->h_c_slots.assign(s->c_slots, s->c_slots + s->c_ptr[s->nnz]);
+  if (s->b_slots) h->h_b_slots.assign(s->b_slots, s->b_slots + s->b_ptr[s->n]);
   CREATE_TRY(dev_upload(&h->d_rowptr, s->rowptr, (size_t)s->n + 1));
   CREATE_TRY(dev_upload(&h->d_colidx, s->colidx, (size_t)s->nnz));
   CREATE_TRY(dev_upload(&h->d_to_ref, s->to_ref_nz, (size_t)s->nnz));
@@ -174,7 +178,7 @@ int cadnip_create(const CadnipStructure* s, int32_t n_instances, int32_t device,
       }
       if (!ok) { cadnip_destroy(h); return CADNIP_BADARG; }
       b.va_model = id;
-      if (id >= CADNIP_VA_NBUILTIN) { static const int tl_lanes[] = {CADNIP_VA_EXT_TL_LANES 0}, n_cache[] = {CADNIP_VA_EXT_NCACHE 0}; h->va_ext = true; b.va_tl = tl_lanes[id - CADNIP_VA_NBUILTIN]; b.n_cache = n_cache[id - CADNIP_VA_NBUILTIN]; }   // a large external model (PSP103): per-op kernels only (fused2_fits)
+      if (id >= CADNIP_VA_NBUILTIN) { static const int tl_lanes[] = {CADNIP_VA_EXT_TL_LANES 0}, n_cache[] = {CADNIP_VA_EXT_NCACHE 0}; h->va_ext = true; b.va_tl = tl_lanes[id - CADNIP_VA_NBUILTIN]; b.n_cache = n_cache[id - CADNIP_VA_NBUILTIN]; }   // a large external model (PSP103): per-op kernels only (fused2_plan)
     }
     b.h_nodes.assign(sb.nodes, sb.nodes + (size_t)b.n_nodes * b.count);
     h->blocks.push_back(b);                      // registered first: a failing upload below is cleaned up by cadnip_destroy
@@ -213,10 +217,7 @@ void cadnip_destroy(CadnipHandle* h) {
                   h->d_ent_diag, h->d_ent_ptr, h->d_term_a, h->d_term_b, h->d_lev_ptr, h->d_lu_rowptr, h->d_lu_col, h->d_lu_diag, h->d_rperm,
                   h->d_cperm, h->d_fwd_rows, h->d_fwd_lev_ptr, h->d_bwd_rows, h->d_bwd_lev_ptr};
   for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (h->d_f2tab) (void)hipFree(h->d_f2tab);
-  for (int k = 0; k < 2; ++k) if (h->d_team_desc[k]) (void)hipFree(h->d_team_desc[k]);
-  if (h->d_steps1) (void)hipFree(h->d_steps1);
-  if (h->d_steps4) (void)hipFree(h->d_steps4);
+  h->f2.release();
   for (auto& g : h->step_graph) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (auto& b : h->blocks) {
     void* bp[] = {b.d_nodes, b.d_ipar, b.d_par, b.d_sp_tptr, b.d_sp_info, b.d_sp_rec, b.d_cache, b.d_sp_rowoff,
@@ -225,9 +226,6 @@ void cadnip_destroy(CadnipHandle* h) {
   }
   if (h->h_pinned) (void)hipHostFree(h->h_pinned);
   if (h->h_stage) (void)hipHostFree(h->h_stage);
-  if (h->d_f2queue) (void)hipFree(h->d_f2queue);
-  if (h->d_f2_lufac) (void)hipFree(h->d_f2_lufac);
-  if (h->d_f2blk) (void)hipFree(h->d_f2blk);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -252,7 +250,7 @@ int cadnip_set_params(CadnipHandle* h, int32_t block, const double* par_host) {
     }
     b.mos1_plain = plain;
   }
-  h->f2_blk_dirty = true;
+  h->f2.blk_dirty = true;
   if (b.n_cache > 0) {       // generated external model: its bias-independent statements run now, once for this parameter set
     int rc = cadnip::launch_va_setup(h, b);
     if (rc) return rc;
@@ -605,7 +603,7 @@ int cadnip_newton_step(CadnipHandle* h, const double* u_host, const double* du_h
   stage_begin(h);
   char *s_u = stage_take(h, vec), *s_du = stage_take(h, vec), *s_g = stage_take(h, B * 8), *s_t = stage_take(h, B * 8), *s_d = stage_take(h, vec),
        *s_r = stage_take(h, vec), *s_nrm = stage_take(h, B * 8), *s_nf = stage_take(h, B * 4), *s_fl = stage_take(h, B * 4);
-  if (!s_fl) {
+  if (!s_u || !s_du || !s_g || !s_t || !s_d || !s_r || !s_nrm || !s_nf || !s_fl) {   // (a small request can still fit behind a large one that did not)
     // too large for the staging area: the five entry points (blocking copies), same results
     TRY(cadnip_rebuild(h, u_host, t_host));
     std::vector<double> r(B * n);
@@ -666,7 +664,7 @@ int cadnip_newton_step_fused(CadnipHandle* h, const double* u_host, const double
   stage_begin(h);
   char *s_u = stage_take(h, vec), *s_du = stage_take(h, vec), *s_g = stage_take(h, B * 8), *s_t = stage_take(h, B * 8), *s_d = stage_take(h, vec),
        *s_r = stage_take(h, vec), *s_nrm = stage_take(h, B * 8), *s_fl = stage_take(h, B * 4);
-  if (!s_fl) return CADNIP_BADARG;
+  if (!s_u || !s_du || !s_g || !s_t || !s_d || !s_r || !s_nrm || !s_fl) return CADNIP_BADARG;   // (a small request can still fit behind a large one that did not)
   auto dv = [&](char* p) { return h->d_stage + (p - h->h_stage); };
   // ONE launch: the kernel reads u, du, gamma, t from the mapped pinned staging area (a few KB across the bus, once) and writes the Newton
   // step, the residual, its norm and the failure flags back there; gamma / t stay what they were on the device when not given
@@ -867,7 +865,7 @@ int upload_lu(CadnipHandle* h) {
   TRY(dev_upload(&h->d_bwd_rows, P.bwd_rows)); TRY(dev_upload(&h->d_bwd_lev_ptr, P.bwd_lev_ptr));
   TRY(dev_alloc(&h->d_LU, (size_t)h->B * P.nnz_lu));
   h->analyzed = true;
-  h->fused2_dirty = true;
+  h->f2.dirty = true;
   return CADNIP_OK;
 }
 }  // namespace cadnip

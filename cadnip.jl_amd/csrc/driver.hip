@@ -245,7 +245,7 @@ int dc_newton(CadnipHandle* h, double abstol, int maxiters, int use_pcnr, int co
   int saved_initjct = h->initjct;
   h->initjct = (cold_start && a.use_pcnr) ? 1 : 0;   // armed for the first stamping only (solve.jl:624,632)
   int rc = CADNIP_OK;
-  if (fused && h->analyzed && !h->homotopy && h->spec.gshunt == 0.0 && h->spec.srcFact >= 1.0 && !h->va_ext && fused2_fits(h)) {
+  if (fused && fused2_plan(h, F2_DC, 0).rc == CADNIP_OK) {
     // the whole Newton loop of every instance in the fused kernel; the host only looks at the running count
     TranArgs ta{};
     ta.u = h->d_u; ta.limit_w = h->d_limit_w; ta.status = d->status; ta.cnt = d->cnt; ta.active = h->d_active; ta.flags = h->d_flags;
@@ -572,7 +572,7 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
   if (!h->analyzed) return CADNIP_NOTREADY;              // the symbolic LU phase (cadnip_analyze*) comes first
   // the per-op kernels take over where the fused kernel cannot run: external generated models (they exist in the per-op stamping kernel only), a
   // circuit too large for the LDS-resident kernel, Newton mode 1 on a circuit outside the lean device set
-  const bool use_fused = o->fused && !h->va_ext && fused2_fits(h) && (!o->newton_mode || fused2_mode1_ok(h));
+  const bool use_fused = o->fused && fused2_plan(h, F2_TRAN, o->newton_mode).circuit_ok;
   struct ModeGuard { CadnipHandle* h; int saved; ~ModeGuard() { h->spec.mode = saved; } } mode_guard{h, h->spec.mode};
   h->spec.mode = 1;   // :tran (restored on every exit path)
   hipLaunchKernelGGL(k_tran_init, dim3(h->B), dim3(64), 0, h->stream, a);

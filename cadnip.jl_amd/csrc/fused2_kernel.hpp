@@ -6,6 +6,7 @@
 #include "devices.hpp"
 #include "internal.hpp"
 #include "tran_ctrl.hpp"
+#include "lds_layout.hpp"
 
 namespace cadnip {
 
@@ -15,7 +16,6 @@ typedef unsigned long long u64;
 #define F2_NCMAX 16   // largest core the in-register dense solve is unrolled for
 #define F2_JU 18      // J*u entries per lane and chunk
 #define F2_MAX_BLOCKS 32   // device blocks of one circuit (one per built-in type, one per Verilog-A module); more: per-op path
-#define F2_TRASH 64   // per-instance trash words (one per lane) that absorb stamps into ground rows / columns
 
 // table sections (offsets in 32-bit words, every section 8-byte aligned)
 enum { S_GPOS = 0, S_CDESC, S_BROW, S_NZ, S_ENT, S_TERM, S_LEV, S_QINV, S_NODES, S_ROWOF, S_LOADPOS, S_NSEC };   // S_LOADPOS: csr entry -> W word (lu_f2.hip)
@@ -344,21 +344,19 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   }
   const TranArgs& a = f.t;
   const unsigned* tab = (const unsigned*)sm;
-  const int tab_dbl = f.tab_len / 2;
   // lean variant: the linear solve as straight-line steps (f2_program.cpp: f2_build_steps), their 16-byte lane descriptors staged behind the tables
-  const uint4* tdesc = (const uint4*)(sm + tab_dbl);
-  const int desc_dbl = LEAN ? f.team_desc_len : 0;
+  const LdsSweep<double*> L = lds_sweep((double*)sm, f.tab_len, LEAN ? f.team_desc_len : 0, f.nnz_lu, n, w, WPB);
+  const uint4* tdesc = (const uint4*)L.desc;
   if constexpr (LEAN) {
     const uint2* src = (const uint2*)f.team_desc;
-    uint2* dst = (uint2*)(sm + tab_dbl);
+    uint2* dst = (uint2*)L.desc;
     for (int i = tid; i < f.team_desc_len; i += 64 * WPB) dst[i] = src[i];
   }
   __syncthreads();
-  const int nW = f.nnz_lu + n + F2_TRASH;                 // LU | rhs | trash : zeroed every round
-  const int per = nW + 2 + 2 * n;                         // ... | the steps' constant words 0.0, 1.0 | u | beta
-  double* W = sm + tab_dbl + desc_dbl + (size_t)w * per;
-  double* us = W + nW + 2;
-  double* betas = us + n;
+  const int nW = L.nW;                                    // LU | rhs | trash : zeroed every round
+  double* W = L.W;
+  double* us = L.u;
+  double* betas = L.beta;
   if (lane0 == 0) { W[nW] = 0.0; W[nW + 1] = 1.0; }
   const int tlo = f.tab_lo;                               // (a section's offset minus tab_lo first: every pointer formed here lies inside the staged range)
   const u16* gpos = (const u16*)(tab + (f.off[S_GPOS] - tlo));
@@ -825,8 +823,22 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   }
 }
 
+#ifdef CADNIP_TRACE
+// the trace counters are per translation unit (devices.hpp): reads (and clears) those of the unit this is called in
+static int trace_read_unit(unsigned long long* sum, unsigned long long* cnt, int reset) {
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpyFromSymbol(sum, HIP_SYMBOL(g_trace_sum), 64 * sizeof(unsigned long long)));
+  HIP_TRY(hipMemcpyFromSymbol(cnt, HIP_SYMBOL(g_trace_cnt), 64 * sizeof(unsigned long long)));
+  if (reset) {
+    unsigned long long z[64] = {0};
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace_sum), z, sizeof(z)));
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace_cnt), z, sizeof(z)));
+  }
+  return CADNIP_OK;
+}
+#endif
 
-// launch of one instantiation (defined in fused2_v<VAR>.hip); shmem > 64 KB is enabled there
+// launch of one instantiation (defined in fused2_v<VAR>.hip)
 template <int VAR> int f2_launch_variant(int wpb, bool dc, int grid, size_t shmem, hipStream_t stream, const F2Args& f);
 
 }  // namespace cadnip

@@ -3,33 +3,15 @@
 
 namespace cadnip {
 
-template <int NW>
-static int fteam_launch_one(int grid, size_t shmem, hipStream_t stream, const F2Args& f) {
-  if (shmem > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_fteam<NW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL((k_fteam<NW, false>), dim3(grid), dim3(64 * NW), shmem, stream, f);
-  return CADNIP_OK;
-}
-
 int fteam_launch(int nw, int grid, size_t shmem, hipStream_t stream, const F2Args& f) {
-  return nw == 4 ? fteam_launch_one<4>(grid, shmem, stream, f) : fteam_launch_one<2>(grid, shmem, stream, f);
+  return nw == 4 ? lds_launch(k_fteam<4, false>, grid, 256, shmem, stream, f) : lds_launch(k_fteam<2, false>, grid, 128, shmem, stream, f);
 }
 
-int fteam_launch_step(int grid, size_t shmem, hipStream_t stream, const F2Args& f) {
-  if (shmem > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_fteam<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL((k_fteam<4, true>), dim3(grid), dim3(256), shmem, stream, f);
-  return CADNIP_OK;
-}
+int fteam_launch_step(int grid, size_t shmem, hipStream_t stream, const F2Args& f) { return lds_launch(k_fteam<4, true>, grid, 256, shmem, stream, f); }
 
 #ifdef CADNIP_TRACE
 int trace_read_team(unsigned long long* sum, unsigned long long* cnt, int reset, int wave) {
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpyFromSymbol(sum, HIP_SYMBOL(g_trace_sum), 64 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemcpyFromSymbol(cnt, HIP_SYMBOL(g_trace_cnt), 64 * sizeof(unsigned long long)));
-  if (reset) {
-    unsigned long long z[64] = {0};
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace_sum), z, sizeof(z)));
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace_cnt), z, sizeof(z)));
-  }
+  TRY_RC(trace_read_unit(sum, cnt, reset));
   HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_trace_wave), &wave, sizeof(int)));
   return CADNIP_OK;
 }

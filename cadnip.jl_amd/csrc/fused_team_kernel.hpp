@@ -132,23 +132,23 @@ __global__ void __launch_bounds__(64 * NW) k_fteam(F2Args f) {
   __syncthreads();
   const TranArgs& a = f.t;
   const unsigned* tab = (const unsigned*)sm;
-  const int tab_dbl = f.tab_len / 2;
-  const int nW = f.nnz_lu + n + F2_TRASH;                 // LU | rhs | trash
-  double* W = sm + tab_dbl;
+  const LdsTeam<double*> L = lds_team((double*)sm, f.tab_len, f.team_desc_len, f.nnz_lu, n, f.par_words, NW);
+  const int nW = L.nW;                                    // LU | rhs | trash
+  double* W = L.W;
   if (tid == 0) { W[nW] = 0.0; W[nW + 1] = 1.0; }         // the linear solve's constant words, directly behind the trash words (f2_build_team); never cleared
-  double* red = W + nW + 2;                               // [NW][4] exchange words of the update's reductions
-  double* us = red + 4 * NW;
-  double* betas = us + n;
-  double* parc = betas + n;                               // sp_mos1 parameter rows of the resident instance (F2Block::lds_par)
+  double* red = L.red;                                    // [NW][4] exchange words of the update's reductions
+  double* us = L.u;
+  double* betas = L.beta;
+  double* parc = L.par;                                   // sp_mos1 parameter rows of the resident instance (F2Block::lds_par)
   const int par_words = f.par_words;
-  uint4* tdesc = (uint4*)(parc + ((par_words + 1) & ~1));  // step descriptors of the linear solve (f2_program.cpp: f2_build_steps, 16 bytes per lane and step)
+  uint4* tdesc = (uint4*)L.desc;                          // step descriptors of the linear solve (f2_program.cpp: f2_build_steps, 16 bytes per lane and step)
   for (int i = tid; i < f.team_desc_len; i += NT) ((u64*)tdesc)[i] = f.team_desc[i];
   // Reproducible sums.  Four waves adding into one word with LDS atomics would do so in the order in which they happen to arrive, and a
   // floating-point sum depends on that order: the last bits of a transient would change from run to run.  So only wave 0 accumulates into
   // W itself; every other wave has a private copy of the work array (matrix words and right-hand side), and after the stamping barrier the
   // copies are added to W in wave order (and cleared for the next round by the thread that reads them).  Within a wave the atomics of one
   // instruction are applied in lane order and the instructions in program order (as in k_fused2), so every word's sum is a fixed sequence.
-  double* const WP = (double*)((u64*)tdesc + f.team_desc_len);  // [NW - 1][nW]
+  double* const WP = L.priv;                              // [NW - 1][nW]
   for (int i = tid; i < (NW - 1) * nW; i += NT) WP[i] = 0.0;
   double* const Wacc = w == 0 ? W : WP + (size_t)(w - 1) * nW;
 

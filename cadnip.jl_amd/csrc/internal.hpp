@@ -101,6 +101,37 @@ struct DeviceBlock {
 
 struct ProfEntry { const char* name; double ms = 0; int64_t calls = 0; };
 
+// step descriptors of one linear-solve program in device memory (f2_program.cpp: f2_build_steps / f2_build_team)
+struct StepList { unsigned long long* d = nullptr; int len = 0, n_steps[3] = {0, 0, 0}; };   // len: 64-bit words; n_steps: pre-core, post-core, forward-only (kept factors)
+
+// Everything the LDS-resident kernels (fused Newton kernels, program LU) keep per handle; built on demand by fused2.hip, rebuilt when the
+// LU program changes (`dirty`) or cadnip_set_params changed a block (`blk_dirty`)
+struct FusedState {
+  bool dirty = true, blk_dirty = true;
+  // packed structure tables (fused2.hip: f2_prepare) and the linear-solve program they belong to
+  unsigned int* d_tab = nullptr;
+  int off[16] = {0};          // section offsets in 32-bit words
+  int lu_len = 0;             // 32-bit words of the linear-solve prefix (entry program, load map, permutations): what the program LU stages
+  int lean_lo = 0, lean_end = 0;   // the words [lo, end) the lean kernels stage (permutations, stamp tables, node tables)
+  int full_len = 0;           // words the full-table kernels stage
+  int lu_words = 0, nc = 0, dn0 = 0, n_pre = 0, n_post = 0, n_fwd = 0;
+  std::vector<int> nodes_off; // per device block: offset (int16 units) of its node table inside the NODES section
+  StepList steps1;            // one wave per instance (lean sweep kernel, k_lu_f2s): three-term list-scheduled steps, two words per lane
+  StepList steps4;            // ... for a team of four waves, read from global memory (k_lu_steps)
+  StepList team[2];           // team kernel: teams of 2 (three-term steps) / 4 waves (one-term level-aligned steps)
+  // device-block descriptors and what they decide (fused2.hip: fused2_blocks)
+  void* d_blk = nullptr;
+  int n_blk = 0, rc_blk = -1, src_blk = -1;   // first capacitor / resistor block, first independent-source block of the list
+  int par_words = 0;          // team kernel: doubles of the LDS-staged sp_mos1 parameter rows of one instance
+  bool lean = false;          // only device types of the lean kernel variant
+  // buffers of the launches
+  int* d_queue = nullptr;     // dynamic instance queue
+  double* d_lufac = nullptr; size_t lufac_cap = 0;   // Newton mode 1: kept factors of the non-resident instances [B][lu_words]
+  int n_cu = 0;               // compute units of the device (queried by the first fused launch; MI355X: 256)
+  int n_cu_hint() const { return n_cu > 0 ? n_cu : 256; }
+  void release();             // frees every device buffer; the next use builds everything again
+};
+
 }  // namespace cadnip
 
 struct CadnipHandle {
@@ -110,6 +141,7 @@ struct CadnipHandle {
   // structure (host copies kept for the symbolic phase)
   int n = 0, n_nodes = 0, n_currents = 0, n_charges = 0, n_limits = 0, nnz = 0;
   std::vector<int> h_rowptr, h_colidx, h_to_ref;
+  std::vector<int> h_g_ptr, h_g_slots, h_c_ptr, h_c_slots, h_b_ptr, h_b_slots;   // gather lists: the fused kernel's tables invert them (fused2.hip)
   int ns_g = 0, ns_c = 0, ns_b = 0, ns = 0;
   std::vector<cadnip::DeviceBlock> blocks;
   std::vector<double> h_limit_init;
@@ -146,37 +178,10 @@ struct CadnipHandle {
   int *d_term_a = nullptr, *d_term_b = nullptr, *d_lev_ptr = nullptr;
   int *d_lu_rowptr = nullptr, *d_lu_col = nullptr, *d_lu_diag = nullptr, *d_rperm = nullptr, *d_cperm = nullptr;
   int *d_fwd_rows = nullptr, *d_fwd_lev_ptr = nullptr, *d_bwd_rows = nullptr, *d_bwd_lev_ptr = nullptr;
-  // fused kernel: packed structure tables (fused2.hip), rebuilt when the LU program changes
-  unsigned int* d_f2tab = nullptr;
-  int f2off[16] = {0};      // section offsets in 32-bit words
-  int f2len = 0;            // 32-bit words
-  int f2_lu_words = 0, f2_nc = 0, f2_dn0 = 0, f2_n_pre = 0, f2_n_post = 0, f2_n_fwd = 0;
-  double* d_f2_lufac = nullptr; size_t f2_lufac_cap = 0;   // Newton mode 1: kept factors of the non-resident instances [B][f2_lu_words]   // linear-solve program of the fused kernel
-  std::vector<int> f2_nodes_off;   // per device block: offset (int16 units) of its node table inside the NODES section
-  bool fused2_dirty = true;
-  int* d_f2queue = nullptr;   // fused kernel: dynamic instance queue
-  void* d_f2blk = nullptr;    // fused kernel: device-block descriptors
-  bool f2_blk_dirty = true;
-  int f2_n_blk = 0, f2_rc_blk = -1;
-  unsigned long long* d_team_desc[2] = {nullptr, nullptr};   // team kernel: step descriptors for teams of 2 / 4 waves (f2_build_team), built with the tables
-  int team_steps[2][3] = {{0, 0, 0}, {0, 0, 0}};
-  int team_desc_len[2] = {0, 0};   // 64-bit words each
-  unsigned long long* d_steps1 = nullptr;   // one wave per instance, lean variant: step descriptors (f2_build_steps), two words per lane
-  int steps1[3] = {0, 0, 0}, steps1_len = 0;
-  unsigned long long* d_steps4 = nullptr;   // ... for a team of four waves (the per-op step LU, lu_f2.hip: k_lu_steps)
-  int steps4[3] = {0, 0, 0};
-  int f2_lean_lo = 0, f2_lean_end = 0;      // the table words [lo, end) the lean kernels stage in LDS (permutations, stamp tables, node tables)
-  int f2_lds_len = 0;         // 32-bit words of the table that the fused kernels copy to LDS (f2len; the team kernel's step lists lie behind)
-  int f2_par_words = 0;       // team kernel: doubles of the LDS-staged sp_mos1 parameter rows of one instance
-  bool f2_direct = false;     // devices emit their residuals directly: no J*u pass (off: CADNIP_F2_NODIRECT=1)
   std::vector<unsigned char> leaf_unit_ok;   // per unknown: its diagonal is one constant G stamp, no C stamp (leaf-first pivot order, symbolic.cpp)
   cadnip::LULeaves leaves;    // charge / limit ranges of the unknown layout [V | I | q | lim]
-  int f2_lu_len = 0;          // 32-bit words of the table's linear-solve prefix (entry program, permutations, load map)
-  int n_cu_hint() const { return n_cu > 0 ? n_cu : 256; }   // compute units of the device (queried by the first fused launch; MI355X: 256)
   bool va_ext = false;        // the circuit uses an external generated model (va_generated_ext.hpp): not compiled into the fused kernel
-  bool f2_lean = false;       // only device types of the lean kernel variant (fused2.hip: dispatch_stamp2)
-  int f2_src_blk = -1;        // first independent-source block of the fused block list
-  int n_cu = 0;
+  cadnip::FusedState f2;      // the LDS-resident kernels' tables, step lists and buffers (fused2.hip, lu_f2.hip)
   // driver state (allocated lazily)
   struct Driver* drv = nullptr;
   // profiling
@@ -234,9 +239,19 @@ int launch_fused2_rounds(CadnipHandle* h, const TranArgs& t, int rounds); // fus
 struct FusedStepIO { const double *u, *du, *gamma, *t; double *gamma_keep, *t_keep, *delta, *resid, *norm; int* flags; int reps = 1, skip = 0; };   // reps / skip: measurement (cadnip_debug_step_time)
 int launch_fused_step(CadnipHandle* h, int refresh, const FusedStepIO& io);
 int launch_va_setup(CadnipHandle* h, DeviceBlock& b);                        // stamp_csr.hip: the setup pass of a generated external model's block
-bool fused2_tables_ready(CadnipHandle* h);                                 // the packed tables exist (built on demand)
-bool fused2_fits(CadnipHandle* h);                                        // false: circuit too large for the LDS-resident kernel
-bool fused2_mode1_ok(CadnipHandle* h);                                    // Newton mode 1 can run in the fused kernel (lean device set, direct residuals)
+int fused2_tables(CadnipHandle* h);                                        // builds the packed tables on demand; CADNIP_OK: they exist
+// What a fused launch would run (fused2.hip: fused2_plan).  rc != CADNIP_OK: the fused kernels do not apply now, and launch_fused2_* return
+// rc; !circuit_ok: they never apply to this circuit / Newton mode -- the drivers take the per-op kernels (still on the GPU) instead
+enum F2Mode { F2_TRAN, F2_DC, F2_STEP };
+struct F2Plan {
+  int rc = CADNIP_OK; bool circuit_ok = false;
+  int nw = 0;                 // team kernel k_fteam<nw>; 0: sweep kernel k_fused2<wpb, dc, var>
+  int var = 0, wpb = 0, grid = 0; size_t shmem = 0;
+  int tab_lo = 0, tab_len = 0;          // staged table range (32-bit words)
+  const StepList* steps = nullptr;      // step descriptors staged behind it (null: the pass program of the full table)
+  bool keep_factors = false;  // Newton mode 1 / single step: kept factors in HBM
+};
+F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode);
 int launch_fused2_dc(CadnipHandle* h, const TranArgs& t, int rounds, double abstol, int maxiters, int use_pcnr, int mode, int initjct, int* d_dcstate);
 struct ProfScope {
   CadnipHandle* h; int idx;

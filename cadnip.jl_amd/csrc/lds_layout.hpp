@@ -1,0 +1,84 @@
+// lds_layout.hpp -- THE map of the dynamic LDS block of every LDS-resident kernel (k_fused2, k_fteam, k_lu_*).  The kernels take their
+// pointers from it and the launchers their `shmem`: nobody else adds up table, descriptor or work-array words.  Plain C++ behind the
+// __host__ __device__ markers (tests/test_lds_layout.py compiles it with the host compiler).
+//
+// Every function is generic in the base P: with the kernel's `extern __shared__ double sm[]` it returns the region pointers, with
+// (size_t)0 on the host the same regions as offsets in doubles, `end` being the size of the block (lds_bytes).  Alignment: the staged
+// tables are a multiple of 4 32-bit words (fused2.hip: pad4), a step list a multiple of 128 words (16 bytes per lane), lu_words + n is even
+// (f2_program.cpp) -- so every work array W (cleared as double2) and every descriptor area (read as uint4) starts on 16 bytes.
+#pragma once
+#include <stddef.h>
+#ifdef __HIPCC__
+#include <type_traits>
+#define LDS_HD __host__ __device__ __forceinline__
+#else
+#define LDS_HD inline
+#endif
+
+#define F2_TRASH 64        // per-instance trash words (one per lane) that absorb stamps into ground rows / columns
+#define LDS_BUDGET ((size_t)160 * 1024)   // LDS of a gfx950 compute unit = the most one workgroup may ask for
+#define LDS_OPTIN ((size_t)64 * 1024)     // above this a kernel needs hipFuncAttributeMaxDynamicSharedMemorySize raised (lds_launch)
+
+namespace cadnip {
+
+// one work array: L\U entries (lu_words) | rhs in pivot-row order (n) | trash words; the part a Newton round clears
+LDS_HD int lds_work_words(int lu_words, int n) { return lu_words + n + F2_TRASH; }
+#define LDS_CONSTS 2       // the step programs' constant words 0.0, 1.0 directly behind the trash words (f2_build_steps / f2_build_team)
+
+// sweep kernel k_fused2<WPB>: tables | step descriptors (lean variant) | WPB x [ W | consts | u | beta ]; W, u, beta: of instance w
+template <class P> struct LdsSweep { P desc, W, u, beta, end; int nW, per; };   // nW, per: doubles of one work array / one instance
+template <class P> LDS_HD LdsSweep<P> lds_sweep(P base, int tab_len, int desc_len, int lu_words, int n, int w, int wpb) {
+  LdsSweep<P> L;
+  L.nW = lds_work_words(lu_words, n);
+  L.per = L.nW + LDS_CONSTS + 2 * n;
+  L.desc = base + tab_len / 2;
+  L.W = L.desc + desc_len + (size_t)w * L.per;
+  L.u = L.W + L.nW + LDS_CONSTS; L.beta = L.u + n;
+  L.end = L.desc + desc_len + (size_t)wpb * L.per;
+  return L;
+}
+
+// team kernel k_fteam<NW>: tables | W | consts | red [NW][4] | u | beta | sp_mos1 parameter rows (rounded up to even) | step descriptors |
+// NW - 1 private copies of W
+template <class P> struct LdsTeam { P W, red, u, beta, par, desc, priv, end; int nW; };
+template <class P> LDS_HD LdsTeam<P> lds_team(P base, int tab_len, int desc_len, int lu_words, int n, int par_words, int nw) {
+  LdsTeam<P> L;
+  L.nW = lds_work_words(lu_words, n);
+  L.W = base + tab_len / 2;
+  L.red = L.W + L.nW + LDS_CONSTS; L.u = L.red + 4 * nw; L.beta = L.u + n; L.par = L.beta + n;
+  L.desc = L.par + ((par_words + 1) & ~1); L.priv = L.desc + desc_len;
+  L.end = L.priv + (nw ? (size_t)(nw - 1) * L.nW : 0);
+  return L;
+}
+
+// refactor + solve kernels k_lu_*: tables | step descriptors | waves x [ W | consts (step programs only) ]; W: of wave w.  k_lu_f2_mw and
+// k_lu_steps keep one work array per workgroup (waves = 1), k_lu_steps stages neither tables nor descriptors
+template <class P> struct LdsLu { P desc, W, end; int nW, per; };
+template <class P> LDS_HD LdsLu<P> lds_lu(P base, int tab_len, int desc_len, int lu_words, int n, bool consts, int w, int waves) {
+  LdsLu<P> L;
+  L.nW = lds_work_words(lu_words, n);
+  L.per = L.nW + (consts ? LDS_CONSTS : 0);
+  L.desc = base + tab_len / 2;
+  L.W = L.desc + desc_len + (size_t)w * L.per;
+  L.end = L.desc + desc_len + (size_t)waves * L.per;
+  return L;
+}
+template <class L> LDS_HD size_t lds_bytes(const L& l) { return (size_t)l.end * 8; }   // of a layout taken from base (size_t)0
+
+#ifdef __HIPCC__
+// launch `kernel` with `shmem` bytes of dynamic LDS, opting in to more than LDS_OPTIN first
+template <class K, class A>
+static int lds_launch(K kernel, int grid, int threads, size_t shmem, hipStream_t stream, const A& args) {
+  if (shmem > LDS_OPTIN) HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), shmem, stream, args);
+  return CADNIP_OK;
+}
+// the kernels are instantiated for 1, 2, 4, 8 waves per workgroup: fn(std::integral_constant<int, W>) for the one that matches
+template <class F>
+static int with_wpb(int wpb, F&& fn) {
+  return wpb == 8 ? fn(std::integral_constant<int, 8>()) : wpb == 4 ? fn(std::integral_constant<int, 4>())
+       : wpb == 2 ? fn(std::integral_constant<int, 2>()) : fn(std::integral_constant<int, 1>());
+}
+#endif
+
+}  // namespace cadnip

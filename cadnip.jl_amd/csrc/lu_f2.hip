@@ -35,8 +35,9 @@ __global__ void __launch_bounds__(64 * WPB) k_lu_f2(LuF2Args f) {
   const int inst = blockIdx.x * WPB + w;
   if (inst >= f.B || !f.active[inst]) return;
   const unsigned* tab = (const unsigned*)sm;
-  const int nW = f.lu_words + n + F2_TRASH;
-  double* W = sm + f.tab_len / 2 + (size_t)w * nW;
+  const LdsLu<double*> L = lds_lu((double*)sm, f.tab_len, 0, f.lu_words, n, false, w, WPB);
+  const int nW = L.nW;
+  double* W = L.W;
   const u16* loadpos = (const u16*)(tab + f.off[S_LOADPOS]);
   const u64* laned = (const u64*)(tab + f.off[S_ENT]);
   const unsigned* term = tab + f.off[S_TERM];
@@ -129,16 +130,17 @@ __global__ void __launch_bounds__(64 * WPB) k_lu_f2s(LuF2Args f) {
     uint2* dst = (uint2*)sm;
     for (int i = tid; i < f.tab_len / 2; i += 64 * WPB) dst[i] = src[i];
     const uint2* s2 = (const uint2*)f.steps;
-    uint2* d2 = (uint2*)(sm + f.tab_len / 2);
+    uint2* d2 = (uint2*)lds_lu((double*)sm, f.tab_len, f.steps_len, f.lu_words, n, true, w, WPB).desc;
     for (int i = tid; i < f.steps_len; i += 64 * WPB) d2[i] = s2[i];
   }
   __syncthreads();
   const int inst = blockIdx.x * WPB + w;
   if (inst >= f.B || !f.active[inst]) return;
   const unsigned* tab = (const unsigned*)sm;
-  const uint4* tdesc = (const uint4*)(sm + f.tab_len / 2);
-  const int nW = f.lu_words + n + F2_TRASH;
-  double* W = sm + f.tab_len / 2 + f.steps_len + (size_t)w * (nW + 2);
+  const LdsLu<double*> L = lds_lu((double*)sm, f.tab_len, f.steps_len, f.lu_words, n, true, w, WPB);
+  const uint4* tdesc = (const uint4*)L.desc;
+  const int nW = L.nW;
+  double* W = L.W;
   const u16* loadpos = (const u16*)(tab + (f.off[S_LOADPOS] - f.tab_lo));
   const u16* qinv = (const u16*)(tab + (f.off[S_QINV] - f.tab_lo));
   const u16* rowof = (const u16*)(tab + (f.off[S_ROWOF] - f.tab_lo));
@@ -216,8 +218,9 @@ __global__ void __launch_bounds__(64 * WPI) k_lu_f2_mw(LuF2Args f) {
   const int inst = blockIdx.x;
   if (inst >= f.B || !f.active[inst]) return;                 // (uniform over the workgroup: nobody is left waiting at a barrier)
   const unsigned* tab = (const unsigned*)sm;
-  const int nW = f.lu_words + n + F2_TRASH;
-  double* W = sm + f.tab_len / 2;
+  const LdsLu<double*> L = lds_lu((double*)sm, f.tab_len, 0, f.lu_words, n, false, 0, 1);
+  const int nW = L.nW;
+  double* W = L.W;
   const u16* loadpos = (const u16*)(tab + f.off[S_LOADPOS]);
   const u64* laned = (const u64*)(tab + f.off[S_ENT]);
   const unsigned* term = tab + f.off[S_TERM];
@@ -308,8 +311,9 @@ __global__ void __launch_bounds__(64 * NW) k_lu_steps(LuStepArgs f) {
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), n = f.n;
   const int inst = blockIdx.x;
   if (inst >= f.B || !f.active[inst]) return;                 // (uniform over the workgroup)
-  const int nW = f.lu_words + n + F2_TRASH;
-  double* W = sm;
+  const LdsLu<double*> L = lds_lu((double*)sm, 0, 0, f.lu_words, n, true, 0, 1);
+  const int nW = L.nW;
+  double* W = L.W;
   for (int i = tid; i < (nW >> 1); i += NT) ((double2*)W)[i] = make_double2(0.0, 0.0);
   if (tid == 0) { W[nW] = 0.0; W[nW + 1] = 1.0; }            // the steps' constant words (f2_build_steps)
   // this thread's descriptors of the first chunk: requested before the matrix is loaded
@@ -383,91 +387,76 @@ __global__ void __launch_bounds__(64 * NW) k_lu_steps(LuStepArgs f) {
   if (wave_any(bad) && lane == 0) atomicOr(&f.flags[inst], 1);
 }
 
-// 0 = done with the program kernel; 1 = not applicable (auto: the caller falls back to k_lu; a forced kernel: CADNIP_BADARG); < 0 never.
-// kernel: CADNIP_LUK_AUTO (the choice below, CADNIP_LU_* switches included) or one forced kernel (switches and batch rules ignored, the
-// LDS limits kept; W of k_lu_f2s / k_lu_f2 still from B).  info [6] (optional): kernel, waves per workgroup, waves per instance, nc, steps
-// or passes before / after the dense core.  dry: choose and fill info, launch nothing
-int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x, int kernel, int* info, bool dry) {
-  if (!h->analyzed || !fused2_tables_ready(h)) return 1;   // (only the linear-solve prefix of the tables has to fit: checked below)
+// What launch_factor_solve_f2 runs -- the one place that decides, and the only reader of CADNIP_LU_STEPS / _WPI / _F2S.
+// kernel: CADNIP_LUK_AUTO (the choice below, switches included) or one forced kernel (switches and batch rules ignored, the LDS limits kept;
+// W of k_lu_f2s / k_lu_f2 still from B).  The batch rules count 256 compute units where the device has not been asked yet (DESIGN.md
+// section 6, findings)
+struct LuPlan { int kernel, wpb, wpi, pre, post, tab_lo, tab_len; size_t shmem; };   // kernel -1: the program kernels do not apply
+static LuPlan lu_f2_plan(CadnipHandle* h, int kernel) {
+  const FusedState& S = h->f2;
   const bool any = kernel == CADNIP_LUK_AUTO;
-  auto chosen = [&](int k, int wpb, int wpi, int pre, int post) {
-    if (info) { info[0] = k; info[1] = wpb; info[2] = wpi; info[3] = h->f2_nc; info[4] = pre; info[5] = post; }
-    return dry;
-  };
-  LuF2Args f;
-  f.tab = h->d_f2tab; for (int i = 0; i < S_NSEC; ++i) f.off[i] = h->f2off[i]; f.tab_len = h->f2_lu_len;
-  f.tab_lo = 0; f.steps = nullptr; f.steps_len = 0; f.ts_pre = f.ts_post = 0;
-  f.G = h->d_G; f.C = h->d_C; f.gamma = h->d_gamma; f.rhs = d_rhs; f.x = d_x; f.active = h->d_active; f.flags = h->d_flags;
-  f.B = h->B; f.n = h->n; f.nnz = h->nnz; f.lu_words = h->f2_lu_words; f.n_pre = h->f2_n_pre; f.n_post = h->f2_n_post; f.nc = h->f2_nc; f.dn0 = h->f2_dn0;
-  const size_t tab_dbl = (size_t)h->f2_lu_len / 2, per = (size_t)h->f2_lu_words + h->n + F2_TRASH;
+  const LuPlan none{-1, 0, 0, 0, 0, 0, 0, 0};
+  auto bytes = [&](int tab_len, int desc_len, bool consts, int waves) { return lds_bytes(lds_lu((size_t)0, tab_len, desc_len, S.lu_words, h->n, consts, 0, waves)); };
   // at most two instances per CU: the straight-line steps of a team of four waves per instance (k_lu_steps).  CADNIP_LU_STEPS = 0 | 1 forces the choice
   if (any || kernel == CADNIP_LUK_STEPS4) {
     const char* e = any ? getenv("CADNIP_LU_STEPS") : nullptr;
-    const bool steps = !any || (e ? atoi(e) != 0 : h->B <= 2 * h->n_cu_hint());
-    const size_t shmem_s = (per + 2) * 8;
-    if (steps && h->d_steps4 && shmem_s <= 160 * 1024) {
-      if (chosen(CADNIP_LUK_STEPS4, 4, 4, h->steps4[0], h->steps4[1])) return CADNIP_OK;
-      ProfScope ps(h, "lu_factor_solve");
-      LuStepArgs g;
-      g.desc = (const uint4*)h->d_steps4; g.n_pre = h->steps4[0]; g.n_post = h->steps4[1];
-      g.loadpos = (const u16*)(h->d_f2tab + h->f2off[S_LOADPOS]); g.rowof = (const u16*)(h->d_f2tab + h->f2off[S_ROWOF]); g.qinv = (const u16*)(h->d_f2tab + h->f2off[S_QINV]);
-      g.G = h->d_G; g.C = h->d_C; g.gamma = h->d_gamma; g.rhs = d_rhs; g.x = d_x; g.active = h->d_active; g.flags = h->d_flags;
-      g.B = h->B; g.n = h->n; g.nnz = h->nnz; g.lu_words = h->f2_lu_words; g.nc = h->f2_nc; g.dn0 = h->f2_dn0;
-      if (shmem_s > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_lu_steps<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_s));
-      hipLaunchKernelGGL(k_lu_steps<4>, dim3(h->B), dim3(256), shmem_s, h->stream, g);
-      HIP_TRY(hipGetLastError());
-      return CADNIP_OK;
-    }
-    if (!any) return 1;
+    const bool steps = !any || (e ? atoi(e) != 0 : h->B <= 2 * S.n_cu_hint());
+    if (steps && S.steps4.d && bytes(0, 0, true, 1) <= LDS_BUDGET) return LuPlan{CADNIP_LUK_STEPS4, 4, 4, S.steps4.n_steps[0], S.steps4.n_steps[1], 0, 0, bytes(0, 0, true, 1)};
+    if (!any) return none;
   }
   // a few instances of a circuit with many passes: several waves per instance (k_lu_f2_mw).  CADNIP_LU_WPI forces 1 / 4 (diagnostic)
   if (any || kernel == CADNIP_LUK_F2MW) {
     const char* e = any ? getenv("CADNIP_LU_WPI") : nullptr;
-    const int wpi = !any ? 4 : e ? atoi(e) : (h->B * 4 <= h->n_cu_hint() && h->f2_n_pre + h->f2_n_post >= 32 ? 4 : 1);
-    const size_t shmem_mw = (tab_dbl + per) * 8;
-    if (wpi == 4 && shmem_mw <= 160 * 1024) {
-      if (chosen(CADNIP_LUK_F2MW, 4, 4, h->f2_n_pre, h->f2_n_post)) return CADNIP_OK;
-      ProfScope ps(h, "lu_factor_solve");
-      if (shmem_mw > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_lu_f2_mw<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem_mw));
-      hipLaunchKernelGGL(k_lu_f2_mw<4>, dim3(h->B), dim3(256), shmem_mw, h->stream, f);
-      HIP_TRY(hipGetLastError());
-      return CADNIP_OK;
-    }
-    if (!any) return 1;
+    const int wpi = !any ? 4 : e ? atoi(e) : (h->B * 4 <= S.n_cu_hint() && S.n_pre + S.n_post >= 32 ? 4 : 1);
+    if (wpi == 4 && bytes(S.lu_len, 0, false, 1) <= LDS_BUDGET) return LuPlan{CADNIP_LUK_F2MW, 4, 4, S.n_pre, S.n_post, 0, S.lu_len, bytes(S.lu_len, 0, false, 1)};
+    if (!any) return none;
   }
-  // many instances: one wave each.  On the step program when its descriptors fit beside eight work arrays (CADNIP_LU_F2S = 0 keeps the passes)
-  if ((any && h->d_steps1 && !(getenv("CADNIP_LU_F2S") && atoi(getenv("CADNIP_LU_F2S")) == 0)) || (kernel == CADNIP_LUK_F2S && h->d_steps1)) {
-    const int lo = h->f2off[S_LOADPOS] & ~3;
-    const size_t tabs = (size_t)(h->f2_lu_len - lo) / 2, desc = (size_t)h->steps1_len, pers = per + 2;
-    int wpb = 8;
-    while (wpb > 1 && h->B < 256 * wpb / 2) wpb >>= 1;
-    const size_t shmem = (tabs + desc + wpb * pers) * 8;
-    if ((tabs + desc + 8 * pers) * 8 <= 160 * 1024) {
-      if (chosen(CADNIP_LUK_F2S, wpb, 1, h->steps1[0], h->steps1[1])) return CADNIP_OK;
-      ProfScope ps(h, "lu_factor_solve");
-      f.tab_lo = lo; f.tab_len = h->f2_lu_len - lo;
-      f.steps = (const uint4*)h->d_steps1; f.steps_len = h->steps1_len; f.ts_pre = h->steps1[0]; f.ts_post = h->steps1[1];
-      const int grid = (h->B + wpb - 1) / wpb;
-#define LAUNCH(W) do { if (shmem > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_lu_f2s<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-    hipLaunchKernelGGL(k_lu_f2s<W>, dim3(grid), dim3(64 * W), shmem, h->stream, f); } while (0)
-      if (wpb == 8) LAUNCH(8); else if (wpb == 4) LAUNCH(4); else if (wpb == 2) LAUNCH(2); else LAUNCH(1);
-#undef LAUNCH
-      HIP_TRY(hipGetLastError());
-      return CADNIP_OK;
-    }
-  }
-  if (!any && kernel != CADNIP_LUK_F2) return 1;
+  // many instances: one wave each, 8 per workgroup unless fewer still put a workgroup on every CU
   int wpb = 8;
-  while (wpb > 1 && ((tab_dbl + wpb * per) * 8 > 160 * 1024 || h->B < 256 * wpb / 2)) wpb >>= 1;
-  const size_t shmem = (tab_dbl + wpb * per) * 8;
-  if (shmem > 160 * 1024) return 1;
-  if (chosen(CADNIP_LUK_F2, wpb, 1, h->f2_n_pre, h->f2_n_post)) return CADNIP_OK;
+  while (wpb > 1 && h->B < 256 * wpb / 2) wpb >>= 1;
+  // ... on the step program when its descriptors fit beside eight work arrays (CADNIP_LU_F2S = 0 keeps the passes); staged: the table from the load map on
+  const char* e = any ? getenv("CADNIP_LU_F2S") : nullptr;
+  if (S.steps1.d && (any ? !(e && atoi(e) == 0) : kernel == CADNIP_LUK_F2S)) {
+    const int lo = S.off[S_LOADPOS] & ~3;
+    if (bytes(S.lu_len - lo, S.steps1.len, true, 8) <= LDS_BUDGET)
+      return LuPlan{CADNIP_LUK_F2S, wpb, 1, S.steps1.n_steps[0], S.steps1.n_steps[1], lo, S.lu_len - lo, bytes(S.lu_len - lo, S.steps1.len, true, wpb)};
+  }
+  if (!any && kernel != CADNIP_LUK_F2) return none;
+  while (wpb > 1 && bytes(S.lu_len, 0, false, wpb) > LDS_BUDGET) wpb >>= 1;
+  if (bytes(S.lu_len, 0, false, wpb) > LDS_BUDGET) return none;
+  return LuPlan{CADNIP_LUK_F2, wpb, 1, S.n_pre, S.n_post, 0, S.lu_len, bytes(S.lu_len, 0, false, wpb)};
+}
+
+// 0 = done with the program kernel; 1 = not applicable (auto: the caller falls back to k_lu; a forced kernel: CADNIP_BADARG); < 0 never.
+// info [6] (optional): kernel, waves per workgroup, waves per instance, nc, steps or passes before / after the dense core.  dry: choose and
+// fill info, launch nothing
+int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x, int kernel, int* info, bool dry) {
+  if (!h->analyzed || fused2_tables(h)) return 1;          // (only the linear-solve prefix of the tables has to fit: the plan checks)
+  const FusedState& S = h->f2;
+  const LuPlan p = lu_f2_plan(h, kernel);
+  if (p.kernel < 0) return 1;
+  if (info) { info[0] = p.kernel; info[1] = p.wpb; info[2] = p.wpi; info[3] = S.nc; info[4] = p.pre; info[5] = p.post; }
+  if (dry) return CADNIP_OK;
   ProfScope ps(h, "lu_factor_solve");
-  const int grid = (h->B + wpb - 1) / wpb;
-#define LAUNCH(W) do { if (shmem > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_lu_f2<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-    hipLaunchKernelGGL(k_lu_f2<W>, dim3(grid), dim3(64 * W), shmem, h->stream, f); } while (0)
-  if (wpb == 8) LAUNCH(8); else if (wpb == 4) LAUNCH(4); else if (wpb == 2) LAUNCH(2); else LAUNCH(1);
-#undef LAUNCH
+  const int grid = p.wpi > 1 ? h->B : (h->B + p.wpb - 1) / p.wpb;   // a workgroup per instance, or per wpb instances
+  if (p.kernel == CADNIP_LUK_STEPS4) {
+    LuStepArgs g;
+    g.desc = (const uint4*)S.steps4.d; g.n_pre = p.pre; g.n_post = p.post;
+    g.loadpos = (const u16*)(S.d_tab + S.off[S_LOADPOS]); g.rowof = (const u16*)(S.d_tab + S.off[S_ROWOF]); g.qinv = (const u16*)(S.d_tab + S.off[S_QINV]);
+    g.G = h->d_G; g.C = h->d_C; g.gamma = h->d_gamma; g.rhs = d_rhs; g.x = d_x; g.active = h->d_active; g.flags = h->d_flags;
+    g.B = h->B; g.n = h->n; g.nnz = h->nnz; g.lu_words = S.lu_words; g.nc = S.nc; g.dn0 = S.dn0;
+    TRY_RC(lds_launch(k_lu_steps<4>, grid, 256, p.shmem, h->stream, g));
+  } else {
+    LuF2Args f{};
+    f.tab = S.d_tab; for (int i = 0; i < S_NSEC; ++i) f.off[i] = S.off[i];
+    f.tab_lo = p.tab_lo; f.tab_len = p.tab_len;
+    if (p.kernel == CADNIP_LUK_F2S) { f.steps = (const uint4*)S.steps1.d; f.steps_len = S.steps1.len; f.ts_pre = p.pre; f.ts_post = p.post; }
+    f.G = h->d_G; f.C = h->d_C; f.gamma = h->d_gamma; f.rhs = d_rhs; f.x = d_x; f.active = h->d_active; f.flags = h->d_flags;
+    f.B = h->B; f.n = h->n; f.nnz = h->nnz; f.lu_words = S.lu_words; f.n_pre = S.n_pre; f.n_post = S.n_post; f.nc = S.nc; f.dn0 = S.dn0;
+    if (p.kernel == CADNIP_LUK_F2MW) TRY_RC(lds_launch(k_lu_f2_mw<4>, grid, 256, p.shmem, h->stream, f));
+    else if (p.kernel == CADNIP_LUK_F2S) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_lu_f2s<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, f); }));
+    else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_lu_f2<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, f); }));
+  }
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }
