@@ -197,9 +197,7 @@ int cadnip_create(const CadnipStructure* s, int32_t n_instances, int32_t device,
   CREATE_TRY(dev_alloc(&h->d_gshunt, B)); CREATE_TRY(dev_alloc(&h->d_srcfact, B)); CREATE_TRY(dev_alloc(&h->d_cold, B));
   CREATE_TRY(upload_homotopy(h, nullptr, nullptr));
   CREATE_TRY(build_stamp_plan(h, s));
-  std::vector<int> ones(B, 1);
-  CREATE_HIP_TRY(hipMemcpy(h->d_active, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
-  CREATE_HIP_TRY(hipMemcpy(h->d_cold, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
+  CREATE_TRY(restore_masks(h, true));
   *out = h;
   return CADNIP_OK;
 }
@@ -729,8 +727,7 @@ int cadnip_factor_solve(CadnipHandle* h, const double* gamma_host, const double*
   if (!rc) rc = stage_down(h, flags_host, h->d_flags, B * sizeof(int));
   if (!rc) rc = stage_finish(h);
   if (active_host) {
-    std::vector<int> ones(B, 1);
-    if (hipStreamSynchronize(h->stream) != hipSuccess || hipMemcpy(h->d_active, ones.data(), B * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipStreamSynchronize(h->stream) != hipSuccess || restore_masks(h, false) != CADNIP_OK)
       if (!rc) rc = CADNIP_HIPERROR;
   }
   return rc;
@@ -832,6 +829,13 @@ int cadnip_profile_read(CadnipHandle* h, int32_t max_entries, const char** names
 }  // extern "C"
 
 namespace cadnip {
+int restore_masks(CadnipHandle* h, bool cold) {
+  const std::vector<int> ones((size_t)h->B, 1);
+  if (cold) HIP_TRY(hipMemcpy(h->d_cold, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->d_active, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice));
+  return CADNIP_OK;
+}
+
 int upload_homotopy(CadnipHandle* h, const double* gshunt, const double* srcfact) {
   ++h->graph_epoch;
   const size_t B = (size_t)h->B;

@@ -20,12 +20,10 @@
 //     clipped to [0.2, 2]; Newton failure -> h/4; restart at order 1 on every breakpoint.
 #include <hip/hip_runtime.h>
 #include <chrono>
-#include <math.h>
 #include <string.h>
-#include <stdlib.h>
-#include <stdio.h>
 #include <vector>
 #include "internal.hpp"
+#include "dc_chain.hpp"
 
 using namespace cadnip;
 
@@ -42,9 +40,7 @@ struct Driver {
   int* nactive = nullptr;
   int* part = nullptr;        // [B] 1 = the instance takes part in the DC Newton run being started (k_dc_init)
   size_t out_cap = 0, brk_cap = 0, save_cap = 0, obs_cap = 0;
-  // what the DC fallback chain did, one entry per (instance, Newton run): cadnip_dc_log_*
-  struct DCLogEntry { int inst, stage; double value; int ok; long long iters; };
-  std::vector<DCLogEntry> dc_log;
+  std::vector<DCLogEntry> dc_log;   // what the DC fallback chain did, one entry per (instance, Newton run): cadnip_dc_log_*
 };
 
 namespace {
@@ -52,18 +48,25 @@ namespace {
 template <class T> int dalloc(T** p, size_t c) { if (*p) return CADNIP_OK; HIP_TRY(hipMalloc((void**)p, (c ? c : 1) * sizeof(T))); HIP_TRY(hipMemset(*p, 0, (c ? c : 1) * sizeof(T))); return CADNIP_OK; }
 template <class T> int drealloc(T** p, size_t* cap, size_t c) { if (*p && *cap >= c) return CADNIP_OK; if (*p) (void)hipFree(*p); *p = nullptr; *cap = c; return dalloc(p, c); }
 
+// Every device buffer of the driver with the element count it is allocated with; ensure_driver allocates and cadnip_driver_free
+// releases by walking this one list
+template <class F> int each_buffer(Driver* d, size_t B, size_t n, F f) {
+  const size_t later = 0;   // sized by the run that needs it (cadnip_tran_run: dalloc / drealloc)
+  TRY(f(&d->t, B)); TRY(f(&d->h, B)); TRY(f(&d->hprev, B)); TRY(f(&d->hpp, B));
+  TRY(f(&d->nhist, B)); TRY(f(&d->order, B)); TRY(f(&d->k, B)); TRY(f(&d->status, B));
+  TRY(f(&d->bp_idx, B)); TRY(f(&d->save_idx, B)); TRY(f(&d->dcstate, B)); TRY(f(&d->action, B));
+  TRY(f(&d->cnt, B * 4));
+  TRY(f(&d->mn_a0f, B)); TRY(f(&d->mn_ss, B)); TRY(f(&d->mn_dnp, B)); TRY(f(&d->mn_flags, B));
+  TRY(f(&d->u0, B * n)); TRY(f(&d->u1, B * n)); TRY(f(&d->u2, B * n)); TRY(f(&d->up, B * n)); TRY(f(&d->beta, B * n));
+  TRY(f(&d->atol, n)); TRY(f(&d->emask, n)); TRY(f(&d->nactive, 2)); TRY(f(&d->part, B));
+  TRY(f(&d->u3, later)); TRY(f(&d->hp3, later));
+  TRY(f(&d->breaks, later)); TRY(f(&d->save_t, later)); TRY(f(&d->obs, later)); TRY(f(&d->out, later));
+  return CADNIP_OK;
+}
+
 int ensure_driver(CadnipHandle* h) {
   if (!h->drv) h->drv = new Driver();
-  Driver* d = h->drv;
-  size_t B = h->B, n = h->n;
-  TRY(dalloc(&d->t, B)); TRY(dalloc(&d->h, B)); TRY(dalloc(&d->hprev, B)); TRY(dalloc(&d->hpp, B));
-  TRY(dalloc(&d->nhist, B)); TRY(dalloc(&d->order, B)); TRY(dalloc(&d->k, B)); TRY(dalloc(&d->status, B));
-  TRY(dalloc(&d->bp_idx, B)); TRY(dalloc(&d->save_idx, B)); TRY(dalloc(&d->dcstate, B)); TRY(dalloc(&d->action, B));
-  TRY(dalloc(&d->cnt, B * 4));
-  TRY(dalloc(&d->mn_a0f, B)); TRY(dalloc(&d->mn_ss, B)); TRY(dalloc(&d->mn_dnp, B)); TRY(dalloc(&d->mn_flags, B));
-  TRY(dalloc(&d->u0, B * n)); TRY(dalloc(&d->u1, B * n)); TRY(dalloc(&d->u2, B * n)); TRY(dalloc(&d->up, B * n)); TRY(dalloc(&d->beta, B * n));
-  TRY(dalloc(&d->atol, n)); TRY(dalloc(&d->emask, n)); TRY(dalloc(&d->nactive, 2)); TRY(dalloc(&d->part, B));
-  return CADNIP_OK;
+  return each_buffer(h->drv, h->B, h->n, [](auto** p, size_t c) { return c ? dalloc(p, c) : CADNIP_OK; });
 }
 
 }  // namespace
@@ -223,21 +226,58 @@ __global__ void __launch_bounds__(64) k_dc_update(DCArgs a) {
   if (tid == 0) a.active[inst] = (a.status[inst] == 0) ? 1 : 0;   // next round's rebuild mask
 }
 
-int count_running(CadnipHandle* h, int* out) {
+// enqueues the count of the instances still running (status 0) and its publication in pinned slot `slot` (0 / 1)
+int enqueue_running_count(CadnipHandle* h, int slot) {
   Driver* d = h->drv;
-  TRY_RC(dev_zero_async(h, d->nactive, sizeof(int)));
-  hipLaunchKernelGGL(k_count_running, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, d->status, h->B, d->nactive);
-  hipLaunchKernelGGL(k_publish_int, dim3(1), dim3(64), 0, h->stream, (const int*)d->nactive, h->d_pinned);
+  TRY_RC(dev_zero_async(h, d->nactive + slot, sizeof(int)));
+  hipLaunchKernelGGL(k_count_running, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, d->status, h->B, d->nactive + slot);
+  hipLaunchKernelGGL(k_publish_int, dim3(1), dim3(64), 0, h->stream, (const int*)(d->nactive + slot), h->d_pinned + slot);
+  return CADNIP_OK;
+}
+
+int count_running(CadnipHandle* h, int* out) {
+  TRY_RC(enqueue_running_count(h, 0));
   HIP_TRY(hipStreamSynchronize(h->stream));
   *out = ((volatile int*)h->h_pinned)[0];
   return CADNIP_OK;
 }
 
-// one DC Newton run on the whole batch with the handle's current spec; returns per-instance status in drv->status
-int dc_newton(CadnipHandle* h, double abstol, int maxiters, int use_pcnr, int cold_start, long long* iters_total, int fused = 0, const int* d_part = nullptr) {
+DCArgs dc_args(CadnipHandle* h, double abstol, int maxiters, int use_pcnr) {
   Driver* d = h->drv;
-  DCArgs a{h->d_u, h->d_resid, h->d_delta, h->d_limit_w, h->d_limit_init, h->d_active, h->d_flags, d->status, d->dcstate, d->action, h->d_cold, d->cnt,
-           h->B, h->n, h->n_limits, (use_pcnr && h->n_limits > 0) ? 1 : 0, maxiters, abstol};
+  DCArgs a{};
+  a.u = h->d_u; a.resid = h->d_resid; a.delta = h->d_delta; a.limit_w = h->d_limit_w; a.limit_init = h->d_limit_init;
+  a.active = h->d_active; a.flags = h->d_flags; a.status = d->status; a.dcstate = d->dcstate; a.action = d->action; a.cold = h->d_cold; a.cnt = d->cnt;
+  a.B = h->B; a.n = h->n; a.n_limits = h->n_limits; a.use_pcnr = (use_pcnr && h->n_limits > 0) ? 1 : 0; a.maxiters = maxiters; a.abstol = abstol;
+  return a;
+}
+
+// The arguments of the transient kernels.  o = null: the DC mode of the fused kernel, which reads the state, its bookkeeping and the sizes only
+TranArgs tran_args(CadnipHandle* h, const CadnipTranOpts* o = nullptr, int n_obs = 0, int n_err = 0) {
+  Driver* d = h->drv;
+  TranArgs a{};
+  a.u = h->d_u; a.limit_w = h->d_limit_w; a.active = h->d_active; a.flags = h->d_flags; a.status = d->status; a.cnt = d->cnt;
+  a.B = h->B; a.n = h->n; a.n_limits = h->n_limits;
+  if (!o) return a;
+  a.du = h->d_du; a.delta = h->d_delta; a.tcur = h->d_t; a.gamma = h->d_gamma;
+  a.t = d->t; a.h = d->h; a.hprev = d->hprev; a.hpp = d->hpp; a.nhist = d->nhist; a.order = d->order; a.k = d->k; a.bp_idx = d->bp_idx; a.save_idx = d->save_idx;
+  a.u0 = d->u0; a.u1 = d->u1; a.u2 = d->u2; a.up = d->up; a.beta = d->beta;
+  a.atol = d->atol; a.emask = d->emask; a.breaks = d->breaks; a.save_t = d->save_t; a.obs = d->obs; a.out = d->out; a.nactive = d->nactive;
+  a.n_break = o->n_break; a.n_save = o->n_save; a.n_obs = n_obs; a.n_err = n_err;
+  const double span = o->t1 - o->t0;
+  a.t0 = o->t0; a.t1 = o->t1; a.reltol = o->reltol;
+  a.h0 = o->h0 > 0 ? o->h0 : span * 1e-6; a.hmin = o->hmin > 0 ? o->hmin : span * 1e-14; a.hmax = o->hmax > 0 ? o->hmax : span / 50.0;
+  a.newton_tol = o->newton_tol > 0 ? o->newton_tol : 1e-3;
+  a.max_newton = o->max_newton > 0 ? o->max_newton : 10; a.max_order = o->max_order > 0 ? (o->max_order > 3 ? 3 : o->max_order) : 2; a.use_pcnr = o->use_pcnr;
+  a.newton_mode = o->newton_mode ? 1 : 0; a.mn_a0f = d->mn_a0f; a.mn_ss = d->mn_ss; a.mn_dnp = d->mn_dnp; a.mn_flags = d->mn_flags;
+  a.step_rule = o->step_rule ? 1 : 0;
+  if (a.max_order >= 3) { a.u3 = d->u3; a.hp3 = d->hp3; }   // variable-step BDF3: a fourth history vector and a third step size per instance
+  return a;
+}
+
+// one DC Newton run on the whole batch with the handle's current spec; returns per-instance status in drv->status
+int dc_newton(CadnipHandle* h, double abstol, int maxiters, int use_pcnr, int cold_start, int fused = 0, const int* d_part = nullptr) {
+  Driver* d = h->drv;
+  const DCArgs a = dc_args(h, abstol, maxiters, use_pcnr);
   hipLaunchKernelGGL(k_dc_init, dim3(h->B), dim3(64), 0, h->stream, a, cold_start, d_part);
   TRY_RC(dev_zero_async(h, h->d_gamma, (size_t)h->B * sizeof(double)));
   TRY_RC(dev_zero_async(h, h->d_du, (size_t)h->B * h->n * sizeof(double)));
@@ -247,9 +287,7 @@ int dc_newton(CadnipHandle* h, double abstol, int maxiters, int use_pcnr, int co
   int rc = CADNIP_OK;
   if (fused && fused2_plan(h, F2_DC, 0).rc == CADNIP_OK) {
     // the whole Newton loop of every instance in the fused kernel; the host only looks at the running count
-    TranArgs ta{};
-    ta.u = h->d_u; ta.limit_w = h->d_limit_w; ta.status = d->status; ta.cnt = d->cnt; ta.active = h->d_active; ta.flags = h->d_flags;
-    ta.B = h->B; ta.n = h->n; ta.n_limits = h->n_limits;
+    const TranArgs ta = tran_args(h);
     int first = h->initjct;
     for (int launch = 0; launch < 4; ++launch) {
       rc = launch_fused2_dc(h, ta, 2 * maxiters + 4, abstol, maxiters, a.use_pcnr, h->spec.mode, first, d->dcstate); if (rc) break;
@@ -311,10 +349,7 @@ extern "C" {
 void cadnip_driver_free(CadnipHandle* h) {
   if (!h || !h->drv) return;
   Driver* d = h->drv;
-  void* ptrs[] = {d->t, d->h, d->hprev, d->hpp, d->nhist, d->order, d->k, d->status, d->bp_idx, d->save_idx, d->dcstate, d->action, d->cnt,
-                  d->u0, d->u1, d->u2, d->up, d->beta, d->atol, d->emask, d->breaks, d->save_t, d->out, d->obs, d->nactive, d->part,
-                  d->mn_a0f, d->mn_ss, d->mn_dnp, d->mn_flags, d->u3, d->hp3};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
+  (void)each_buffer(d, 0, 0, [](auto** p, size_t) { if (*p) (void)hipFree(*p); return CADNIP_OK; });
   delete d;
   h->drv = nullptr;
 }
@@ -329,16 +364,10 @@ int cadnip_tran_state(CadnipHandle* h, double* t_host, double* h_host, int32_t* 
   return CADNIP_OK;
 }
 
-// DC operating point with the reference's fallback chain (_dc_solve_with_fallbacks, solve.jl:871-929), PER INSTANCE: sweep
-// points are independent circuits (sweeps.jl:696-703), so an instance leaves the chain at the first stage that converges for
-// it and its solution is never touched again; only the instances still unsolved take part in the later stages, each on its
-// own homotopy ladder (per-instance gshunt / srcFact, kernels.hip: k_assemble).
-//   stage 0  PCNR Newton from the caller's start point (solve.jl:599-698)  -- or plain Newton when use_pcnr is off
-//   stage 1  plain Newton from the caller's start point (solve.jl:899-903)
-//   stage 2  gshunt stepping from zero: 1e-3, /10 ... 1e-12, then the target; a failed rung restores the last solution
-//            and takes the square root of the factor until it is <= 1.5 (solve.jl:720-783)
-//   stage 3  source stepping from zero: srcFact 0, +0.1 ... 1; a failed rung halves the raise (solve.jl:805-850)
-// Every Newton run of every instance is logged (cadnip_dc_log_*): stage, rung value, converged, Newton solves.
+// DC operating point with the reference's fallback chain, per instance.  The chain itself -- who takes part in which stage, the gshunt
+// ladder and the source ramp, the log -- is dc_chain.hpp; this is the device under it: every Newton run the chain asks for is one
+// dc_newton on the batch, with the instances' start states, participation mask and homotopy terms (per-instance gshunt / srcFact,
+// kernels.hip: k_assemble) uploaded before it and status, states and Newton counts downloaded after it.
 int cadnip_dc_run(CadnipHandle* h, const CadnipDCOpts* o, double* u_host, int32_t* converged_host, CadnipRunStats* st) {
   if (!h || !o || !u_host) return CADNIP_BADARG;
   TRY(ensure_driver(h));
@@ -349,8 +378,7 @@ int cadnip_dc_run(CadnipHandle* h, const CadnipDCOpts* o, double* u_host, int32_
   // the symbolic phase needs one numeric Jacobian: stamp once at the start point
   if (!h->analyzed) {
     HIP_TRY(hipMemcpy(h->d_u, u_host, B * n * sizeof(double), hipMemcpyHostToDevice));
-    std::vector<int> ones(B, 1);
-    HIP_TRY(hipMemcpy(h->d_active, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
+    TRY(restore_masks(h, false));
     TRY_RC(dev_zero_async(h, h->d_gamma, B * sizeof(double)));
     TRY_RC(dev_zero_async(h, h->d_t, B * sizeof(double)));
     // pattern-complete sample: G + 1e9*C makes every structural entry of the unified pattern visible
@@ -370,150 +398,33 @@ int cadnip_dc_run(CadnipHandle* h, const CadnipDCOpts* o, double* u_host, int32_
     CadnipHandle* h;
     ~HomotopyGuard() { (void)upload_homotopy(h, nullptr, nullptr); }
   } guard{h};
-  // per-instance start state of the next run / states after the last run.  `start` and `U` are built only when the first run leaves
-  // someone unsolved: the usual case -- everybody converges in stage 0 -- moves the state once up and once down, nothing more
-  std::vector<double> start, U, R(B * n);
-  std::vector<int> fin(B, 0), status(B), part(B, 1), out_of_run(B, 0);
-  if (o->participate)
-    for (size_t i = 0; i < B; ++i) if (!o->participate[i]) { part[i] = 0; out_of_run[i] = 1; fin[i] = 1; }   // (fin: no stage picks them up)
   std::vector<long long> cnt(B * 4);
-  std::vector<double> gsh(B, h->spec.gshunt), sfc(B, h->spec.srcFact);
-  long long iters = 0;
-  bool direct = false;
-  // one Newton run of the instances in `part`, each from U[i] with its own (gsh[i], sfc[i]); results in status / R / cnt
-  auto run = [&](int use_pcnr, int cold_start, int fused, int stage, const std::vector<double>& rung) -> int {
+  auto device_run = [&](const DCRun& r) -> int {
     // (blocking copies: the stream is idle here, and the start state must be in place before the first kernel is queued -- see k_publish_int)
-    HIP_TRY(hipMemcpy(h->d_u, U.empty() ? u_host : U.data(), B * n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d->part, part.data(), B * sizeof(int), hipMemcpyHostToDevice));
-    TRY(upload_homotopy(h, gsh.data(), sfc.data()));
-    TRY(dc_newton(h, o->abstol, o->maxiters, use_pcnr, cold_start, nullptr, fused, d->part));
-    HIP_TRY(hipMemcpy(status.data(), d->status, B * sizeof(int), hipMemcpyDeviceToHost));
-    direct = stage == 0 && !o->participate;
-    for (size_t i = 0; i < B && direct; ++i) direct = status[i] == 1;
-    HIP_TRY(hipMemcpy(direct ? u_host : R.data(), h->d_u, B * n * sizeof(double), hipMemcpyDeviceToHost));   // direct: the first run solved everybody -- straight to the caller
+    HIP_TRY(hipMemcpy(h->d_u, r.u, B * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->part, r.part, B * sizeof(int), hipMemcpyHostToDevice));
+    TRY(upload_homotopy(h, r.gshunt, r.srcFact));
+    TRY(dc_newton(h, o->abstol, o->maxiters, r.use_pcnr, r.cold_start, r.fused, d->part));
+    HIP_TRY(hipMemcpy(r.status, d->status, B * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(r.dest(), h->d_u, B * n * sizeof(double), hipMemcpyDeviceToHost));   // (straight to the caller when the first run solved everybody)
     HIP_TRY(hipMemcpy(cnt.data(), d->cnt, B * 4 * sizeof(long long), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < B; ++i)
-      if (part[i]) { iters += cnt[i * 4]; d->dc_log.push_back({(int)i, stage, rung[i], status[i] == 1 ? 1 : 0, cnt[i * 4]}); }
+    for (size_t i = 0; i < B; ++i) r.iters[i] = cnt[i * 4];
     return CADNIP_OK;
   };
-  auto take = [&](size_t i) { std::copy(R.begin() + i * n, R.begin() + (i + 1) * n, U.begin() + i * n); };
-  auto n_open = [&]() { int k = 0; for (size_t i = 0; i < B; ++i) k += !fin[i]; return k; };
-  const std::vector<double> none(B, 0.0);
-  // ---- stage 0: PCNR (or plain Newton) from the caller's start point
-  TRY(run(o->use_pcnr, o->cold_start, o->fused, 0, none));
-  if (direct) {
-    // everybody converged in the first run: the device holds the solutions already, the caller's array has them too
-    if (converged_host) for (size_t i = 0; i < B; ++i) converged_host[i] = 1;
-    std::vector<int> ones(B, 1);
-    HIP_TRY(hipMemcpy(h->d_cold, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));      // (d_active: dc_newton left every instance active)
-    HIP_TRY(hipMemcpy(h->d_active, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
-    if (st) { memset(st, 0, sizeof(*st)); st->newton_iters = iters; st->n_failed = 0; st->wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count(); }
-    return CADNIP_OK;
-  }
-  start.assign(u_host, u_host + B * n);
-  U = start;
-  for (size_t i = 0; i < B; ++i) if (part[i]) { take(i); if (status[i] == 1) fin[i] = 1; }
-  // ---- stage 1: plain Newton from the caller's start point, for those PCNR did not solve
-  if (n_open() && o->use_pcnr && h->n_limits > 0) {
-    for (size_t i = 0; i < B; ++i) { part[i] = !fin[i]; if (part[i]) std::copy(start.begin() + i * n, start.begin() + (i + 1) * n, U.begin() + i * n); }
-    TRY(run(0, 0, 0, 1, none));
-    for (size_t i = 0; i < B; ++i) if (part[i]) { take(i); if (status[i] == 1) fin[i] = 1; }
-  }
-  if (n_open() && o->use_stepping) {
-    // ---- stage 2: gshunt stepping, one ladder per open instance
-    const double target = h->spec.gshunt, gfloor = fmax(target, 1e-12);
-    struct Rung { double g = 1e-3, factor = 10.0; int steps = 0; bool finalizing = false, over = false; std::vector<double> u, saved; };
-    std::vector<Rung> L(B);
-    for (size_t i = 0; i < B; ++i) { L[i].over = fin[i]; if (!fin[i]) { L[i].u.assign(n, 0.0); L[i].saved.assign(n, 0.0); } }
-    for (;;) {
-      int k = 0;
-      for (size_t i = 0; i < B; ++i) {
-        part[i] = !L[i].over;
-        if (!part[i]) { gsh[i] = h->spec.gshunt; continue; }
-        ++k;
-        gsh[i] = L[i].finalizing ? target : L[i].g;
-        std::copy(L[i].u.begin(), L[i].u.end(), U.begin() + i * n);
-      }
-      if (!k) break;
-      TRY(run(0, 0, 0, 2, gsh));
-      for (size_t i = 0; i < B; ++i) {
-        if (!part[i]) continue;
-        Rung& r = L[i];
-        const bool ok = status[i] == 1;
-        if (r.finalizing) {                                   // the solve at the exact target ends the ladder either way
-          if (ok) { take(i); fin[i] = 1; } else std::copy(r.u.begin(), r.u.end(), U.begin() + i * n);
-          r.over = true;
-          continue;
-        }
-        ++r.steps;
-        if (ok) {
-          r.u.assign(R.begin() + i * n, R.begin() + (i + 1) * n);
-          r.saved = r.u;
-          if (r.g <= gfloor) {
-            if (r.g != target) r.finalizing = true;
-            else { take(i); fin[i] = 1; r.over = true; }
-          } else { r.g /= r.factor; if (r.g < gfloor) r.g = gfloor; }
-        } else {
-          if (r.factor <= 1.5) r.over = true;                 // cannot make progress
-          else { r.factor = sqrt(r.factor); r.u = r.saved; }
-        }
-        if (!r.over && !r.finalizing && r.steps >= 20) r.over = true;   // max_steps
-        if (r.over && !fin[i]) std::copy(r.u.begin(), r.u.end(), U.begin() + i * n);
-      }
-    }
-    for (size_t i = 0; i < B; ++i) gsh[i] = h->spec.gshunt;
-    // ---- stage 3: source stepping for the rest
-    if (n_open()) {
-      struct Ramp { double src = 0.0, conv = 0.0, raise = 0.1; int steps = 0; bool over = false; std::vector<double> u, saved; };
-      std::vector<Ramp> S(B);
-      for (size_t i = 0; i < B; ++i) { S[i].over = fin[i]; if (!fin[i]) { S[i].u.assign(n, 0.0); S[i].saved.assign(n, 0.0); } }
-      for (;;) {
-        int k = 0;
-        for (size_t i = 0; i < B; ++i) {
-          part[i] = !S[i].over;
-          if (!part[i]) { sfc[i] = h->spec.srcFact; continue; }
-          ++k;
-          sfc[i] = S[i].src;
-          std::copy(S[i].u.begin(), S[i].u.end(), U.begin() + i * n);
-        }
-        if (!k) break;
-        TRY(run(0, 0, 0, 3, sfc));
-        for (size_t i = 0; i < B; ++i) {
-          if (!part[i]) continue;
-          Ramp& r = S[i];
-          ++r.steps;
-          if (status[i] == 1) {
-            r.conv = r.src;
-            r.u.assign(R.begin() + i * n, R.begin() + (i + 1) * n);
-            r.saved = r.u;
-            if (r.src >= 1.0) { take(i); fin[i] = 1; r.over = true; }
-            else r.src = fmin(r.src + r.raise, 1.0);
-          } else {
-            if (r.src - r.conv < 1e-6) r.over = true;
-            else { r.raise /= 2.0; r.src = r.conv + r.raise; r.u = r.saved; }
-          }
-          if (!r.over && r.steps >= 50) r.over = true;
-          if (r.over && !fin[i]) std::copy(r.u.begin(), r.u.end(), U.begin() + i * n);
-        }
-      }
-      for (size_t i = 0; i < B; ++i) sfc[i] = h->spec.srcFact;
-    }
-  }
-  const int n_failed = n_open();
-  memcpy(u_host, U.data(), B * n * sizeof(double));
-  HIP_TRY(hipMemcpy(h->d_u, U.data(), B * n * sizeof(double), hipMemcpyHostToDevice));
-  if (converged_host) for (size_t i = 0; i < B; ++i) converged_host[i] = out_of_run[i] ? 0 : fin[i];
-  // leave every instance active for subsequent ABI calls (and subject to a cadnip_set_initjct of the caller's)
-  std::vector<int> ones(B, 1);
-  HIP_TRY(hipMemcpy(h->d_active, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_cold, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
+  const DCChainOpts chain{o->use_pcnr, o->cold_start, o->fused, o->use_stepping, h->n_limits > 0, h->spec.gshunt, h->spec.srcFact, o->participate};
+  DCChainResult res;
+  TRY(dc_chain(chain, h->B, h->n, u_host, converged_host, device_run, d->dc_log, res));
+  // the device holds the final states (after a direct run it does already); every instance is left active for subsequent ABI calls
+  // (and subject to a cadnip_set_initjct of the caller's)
+  if (!res.direct) HIP_TRY(hipMemcpy(h->d_u, u_host, B * n * sizeof(double), hipMemcpyHostToDevice));
+  TRY(restore_masks(h, true));
   if (st) {
     memset(st, 0, sizeof(*st));
-    st->newton_iters = iters;
-    st->n_failed = n_failed;
+    st->newton_iters = res.iters;
+    st->n_failed = res.n_failed;
     st->wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
   }
-  return n_failed ? CADNIP_NOCONV : CADNIP_OK;
+  return res.n_failed ? CADNIP_NOCONV : CADNIP_OK;
 }
 
 // the log of the last cadnip_dc_run: entries in execution order, per (instance, Newton run)
@@ -530,7 +441,7 @@ int cadnip_dc_log_get(CadnipHandle* h, int32_t* inst, int32_t* stage, double* va
 
 int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, int64_t* per_inst_host, CadnipRunStats* st) {
   if (!h || !o || !o->abstol || o->t1 <= o->t0 || o->n_save < 0 || o->n_break < 0) return CADNIP_BADARG;
-  if (!h->analyzed) return CADNIP_NOTREADY;
+  if (!h->analyzed) return CADNIP_NOTREADY;              // the symbolic LU phase (cadnip_analyze*) comes first
   for (int i = 1; i < o->n_break; ++i) if (!(o->breaks[i] > o->breaks[i - 1])) return CADNIP_BADARG;
   for (int i = 1; i < o->n_save; ++i) if (!(o->save_t[i] >= o->save_t[i - 1])) return CADNIP_BADARG;
   for (int i = 0; i < o->n_obs; ++i) if (o->obs[i] < 0 || o->obs[i] >= h->n) return CADNIP_BADARG;
@@ -553,23 +464,8 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
   if (o->err_mask) { n_err = 0; for (size_t i = 0; i < n; ++i) { emask[i] = o->err_mask[i] != 0.0 ? 1.0 : 0.0; n_err += emask[i] != 0.0; } }
   HIP_TRY(hipMemcpy(d->emask, emask.data(), n * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  const double span = o->t1 - o->t0;
-  double hmax = o->hmax > 0 ? o->hmax : span / 50.0;
-  double h0 = o->h0 > 0 ? o->h0 : span * 1e-6;
-  double hmin = o->hmin > 0 ? o->hmin : span * 1e-14;
-  TranArgs a{h->d_u, h->d_du, h->d_delta, h->d_limit_w, h->d_t, h->d_gamma, h->d_active, h->d_flags,
-             d->t, d->h, d->hprev, d->hpp, d->nhist, d->order, d->k, d->status, d->bp_idx, d->save_idx, d->cnt,
-             d->u0, d->u1, d->u2, d->up, d->beta, d->atol, d->emask, d->breaks, d->save_t, d->obs, d->out, d->nactive,
-             h->B, h->n, h->n_limits, o->n_break, o->n_save, n_obs, n_err,
-             o->t0, o->t1, o->reltol, h0, hmin, hmax, o->newton_tol > 0 ? o->newton_tol : 1e-3,
-             o->max_newton > 0 ? o->max_newton : 10, o->max_order > 0 ? o->max_order : 2, o->use_pcnr,
-             o->newton_mode ? 1 : 0, d->mn_a0f, d->mn_ss, d->mn_dnp, d->mn_flags, o->step_rule ? 1 : 0, nullptr, nullptr};
-  if (a.max_order > 3) a.max_order = 3;
-  if (a.max_order >= 3) {                                 // variable-step BDF3: a fourth history vector and a third step size per instance
-    TRY(dalloc(&d->u3, (size_t)h->B * h->n)); TRY(dalloc(&d->hp3, (size_t)h->B));
-    a.u3 = d->u3; a.hp3 = d->hp3;
-  }
-  if (!h->analyzed) return CADNIP_NOTREADY;              // the symbolic LU phase (cadnip_analyze*) comes first
+  if (o->max_order >= 3) { TRY(dalloc(&d->u3, B * n)); TRY(dalloc(&d->hp3, B)); }
+  const TranArgs a = tran_args(h, o, n_obs, n_err);
   // the per-op kernels take over where the fused kernel cannot run: external generated models (they exist in the per-op stamping kernel only), a
   // circuit too large for the LDS-resident kernel, Newton mode 1 on a circuit outside the lean device set
   const bool use_fused = o->fused && fused2_plan(h, F2_TRAN, o->newton_mode).circuit_ok;
@@ -597,9 +493,7 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
     while (launches < max_it) {
       rc = launch_fused2_rounds(h, a, check_every); if (rc) break;
       launches += check_every;
-      if (dev_zero_async(h, d->nactive + slot, sizeof(int)) != CADNIP_OK) { rc = CADNIP_HIPERROR; break; }
-      hipLaunchKernelGGL(k_count_running, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, d->status, h->B, d->nactive + slot);
-      hipLaunchKernelGGL(k_publish_int, dim3(1), dim3(64), 0, h->stream, (const int*)(d->nactive + slot), h->d_pinned + slot);
+      rc = enqueue_running_count(h, slot); if (rc) break;
       if (hipEventRecord(ev[slot], h->stream) != hipSuccess) { rc = CADNIP_HIPERROR; break; }
       if (have_prev) {
         if (hipEventSynchronize(ev[1 - slot]) != hipSuccess) { rc = CADNIP_HIPERROR; break; }
@@ -643,8 +537,7 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
   }
   s.launches = launches; s.wall_seconds = wall;
   if (st) *st = s;
-  std::vector<int> ones(B, 1);
-  HIP_TRY(hipMemcpy(h->d_active, ones.data(), B * sizeof(int), hipMemcpyHostToDevice));
+  TRY(restore_masks(h, false));
   return s.n_failed ? CADNIP_NOCONV : CADNIP_OK;
 }
 

@@ -223,6 +223,7 @@ int launch_factor_solve(CadnipHandle* h, bool fuse_jacobian, const double* d_rhs
                         bool dry = false);
 int upload_lu(CadnipHandle* h);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
+int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);
 #define TRY_RC(x) do { int _rc_ = (x); if (_rc_) return _rc_; } while (0)
 struct MultiCopy { struct Seg { unsigned* dst; const unsigned* src; size_t words; }; Seg seg[8]; int n = 0;

@@ -105,7 +105,7 @@ struct TranArgs {
   int newton_mode;
   double *mn_a0f, *mn_ss, *mn_dnp; int* mn_flags;
   int step_rule;   // 0 = classical step controller, 1 = IDA's eta rule (CadnipTranOpts::step_rule)
-  double *u3, *hp3;   // max_order >= 3: u at the fourth-last accepted point [B][n], the third-last step size [B] (set by the driver behind the aggregate)
+  double *u3, *hp3;   // max_order >= 3: u at the fourth-last accepted point [B][n], the third-last step size [B] (null below that)
 };
 #define MN_NEED 1     // the next round must refactor
 #define MN_JCUR 2     // a refactorisation happened in this step attempt
