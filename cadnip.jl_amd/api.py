@@ -539,6 +539,7 @@ class ACSol:
     def __init__(self, st, G, C, b_ac, dc_x, freqs):
         self.st, self.G, self.C, self.b_ac, self.dc_x, self.freqs = st, G, C, b_ac, dc_x, np.asarray(freqs, dtype=float)
         self._cache = {}
+        self.stats = {}          # ac(..., solver="gpu" | "auto"): what the batched GPU sweep did (``ac_gpu_sweep``); empty on the host path
 
     def _solve(self, omegas):
         key = tuple(np.asarray(omegas, dtype=float))
@@ -587,12 +588,82 @@ def rhs_ac(st, circuit, params):
     return b
 
 
-def ac(target, freqs=(), gmin=1e-12, device=0):
+# A GPU system is accepted when its componentwise backward error is at most AC_BERR_MAX; otherwise (or when its flag is set) the host's dense
+# solve replaces it.  Measured, not chosen: 16 x the largest backward error np.linalg.solve -- the reference path -- itself leaves over the
+# systems of the AC test circuits (tests/ac_ref.py CASES, on the CPU port's G, C at the DC points), and not below 64 eps.  16 is what this
+# project grants another summation order (tests/test_gpu_lu_kernels.py).  The measurement gave 1.0: the unrefined dense solve is normwise
+# stable (6e-17 on every system) but leaves rows of the flip-flop whose terms are all of order 1e-19 -- switched-off transistors at 1 kHz --
+# with a residual as large as the terms themselves.  At 16 the gate therefore only rejects non-finite or grossly wrong rows (singular
+# pivots are caught by the flag); the kernel's own rows measure 2e-16.  DESIGN.md section 6.
+AC_BERR_MAX = max(16 * 1.0, 64 * float(np.finfo(np.float64).eps))
+
+
+def ac_pivot_sample(st, G_csr, C_csr, omegas, gmin):
+    """The sample the GPU sweep's pivot order is analysed on ([nnz], the structure's CSR order): element-wise maximum over the instances
+    ([B, nnz]) of |G| + w_g |C| with gmin on the voltage-node diagonals, w_g the geometric mean of the non-zero grid frequencies."""
+    w = np.asarray(omegas, dtype=float)
+    w = w[w > 0]
+    wg = float(np.exp(np.mean(np.log(w)))) if w.size else 0.0
+    s = np.max(np.abs(np.atleast_2d(G_csr)) + wg * np.abs(np.atleast_2d(C_csr)), axis=0)
+    d = np.asarray(st.diag_nz)[:st.n_nodes]
+    s[d[d >= 0]] += gmin
+    return s
+
+
+def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats):
+    """The frequency sweep of one structure class on the GPU: ``h`` (a hip.Handle holding the restamp at the DC points) re-analyses its
+    pivot order on ``ac_pivot_sample`` and solves all points x all frequencies in ONE ``ac_solve`` call; every ACSol of ``sols`` gets the
+    rows of its point into its cache under the key ``tuple(omegas)``.  A system whose flag is set or whose backward error exceeds
+    AC_BERR_MAX is solved again by the host's dense solve, which replaces the GPU row.  ``stats`` (shared by the call) is updated:
+    gpu_systems / host_systems, max_berr over the accepted GPU rows, wpb.  A circuit that does not fit the launch plan raises with
+    solver="gpu"; with "auto" nothing is cached -- the sols solve on the host on demand -- and stats["fallback"] says why."""
+    from . import hip
+    omegas = np.asarray(omegas, dtype=float)
+    B, F = len(sols), omegas.size
+    key = tuple(omegas)
+    if F == 0:
+        for s in sols:
+            s._cache[key] = np.zeros((0, st.n), complex)
+        return
+    to_ref = np.asarray(st.to_ref_nz)
+    sample_ref = np.empty(st.nnz)
+    sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+    h.analyze_values(sample_ref)
+    try:
+        x, berr, flags, info = h.ac_solve(omegas, gmin, np.array([s.b_ac for s in sols]))
+    except hip.CadnipError as e:
+        if solver == "auto" and e.code == hip.BADARG:
+            stats["host_systems"] += B * F
+            stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
+            return
+        raise
+    redo = (flags != 0) | ~(berr <= AC_BERR_MAX)
+    for k, s in enumerate(sols):
+        rows = np.array(x[k])
+        for f in np.flatnonzero(redo[k]):
+            rows[f] = np.linalg.solve(s.G + 1j * omegas[f] * s.C, s.b_ac)
+        s._cache[key] = rows
+    kept = berr[~redo]
+    stats["gpu_systems"] += int((~redo).sum())
+    stats["host_systems"] += int(redo.sum())
+    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
+    stats["wpb"] = info["wpb"]
+
+
+def ac(target, freqs=(), gmin=1e-12, device=0, solver="host"):
     """ac!(circuit, freqs; gmin) -- src/ac.jl:113-170.  The DC operating point and the restamp at it run on the GPU (cadnip_dc_run,
     cadnip_rebuild: the linearisation IS the stamping); G gets ``gmin`` on the voltage-node diagonals (assemble_G(ctx; gshunt=gmin),
     ac.jl:127).  The frequency sweep is the reference's own dense ``(jw C + G)^-1 b_ac`` on the host: n is a circuit's size, not a
-    batch dimension.  A CircuitSweep returns one ACSol per point (one resident batch per structure class)."""
+    batch dimension.  A CircuitSweep returns one ACSol per point (one resident batch per structure class).
+    ``solver``: "host" (default) as above; "gpu" solves the grid of every point on the device as well -- points x frequencies complex
+    sparse systems in one batched kernel per structure class (``ac_gpu_sweep``) -- and fills the ACSols' caches for the grid, so ``sol[name]``,
+    ``magnitude_db`` and ``phase_deg`` read GPU results while ``freqresp`` at other frequencies still solves on the host; ``sol.stats`` =
+    {"gpu_systems", "host_systems", "max_berr", "wpb"} of the call.  "gpu" raises for a circuit too large for the kernel, "auto" takes the
+    host path for it and says so in ``stats``."""
     import scipy.sparse as sp
+    if solver not in ("host", "gpu", "auto"):
+        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
     sweep = isinstance(target, CircuitSweep)
     mc0 = target.circuit if sweep else target
     mc = MNACircuit(mc0.circuit, mc0.params, MNASpec(temp=mc0.spec.temp, mode="dcop", gmin=mc0.spec.gmin))
@@ -613,8 +684,13 @@ def ac(target, freqs=(), gmin=1e-12, device=0):
                 Gd[np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
                 p_i = {kk: float(v[k]) for kk, v in sim.params.items()}
                 sols[i] = ACSol(st, Gd, Cd, rhs_ac(st, mc.circuit, p_i), u[k].copy(), freqs)
+            if solver != "host":
+                ac_gpu_sweep(sim.h, st, [sols[i] for i in idx], G, C, 2.0 * np.pi * np.asarray(freqs, dtype=float), gmin, solver, stats)
         finally:
             sim.close()
+    if solver != "host":
+        for s in sols:
+            s.stats = stats
     return SweepResult(pts, sols) if sweep else sols[0]
 
 

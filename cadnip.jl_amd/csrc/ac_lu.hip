@@ -1,0 +1,258 @@
+// ac_lu.hip -- the AC frequency sweep (src/ac.jl:113-170: x = (G + jw C)^-1 b_ac at the DC point) as a batched complex sparse LU.  The
+// B instances x F frequencies of a sweep are S = B F independent systems with ONE pattern and ONE pivot order: one 64-lane wave per system
+// (b, f), W systems per workgroup, all synchronisation wave-level (as k_lu_f2, lu_f2.hip).  Per system the complex factors and three complex
+// n-vectors live in LDS (lds_layout.hpp: lds_ac); the index tables of the plain LUProgram (symbolic.cpp) are shared by every system and are
+// read from global memory -- they stay in L2.  The wave
+//   1. loads A = G[b] + gmin [node diagonals] + j w_f C[b] through load_dst (fill positions zeroed first).  A voltage node whose diagonal is
+//      not in the pattern (a node that only source and inductor branches touch) has no word for its gmin: the factors leave it out, the
+//      residuals of steps 4 and 5 carry it (`nodiag`), so the refinement step corrects for it -- to O((gmin |A^-1|)^2) -- and the backward
+//      error is measured against the same A the host path solves,
+//   2. factors entry-wise, level by level: lu[pos] = (lu[pos] - sum lu[a] lu[b]) [* 1 / piv].  The reciprocal of a pivot is taken ONCE per
+//      row, in place, when the row's diagonal is final (the pivot lists of ac_lu_prepare): nothing reads a diagonal entry but the entries
+//      that divide by it, and those sit in later levels.  Constant-1 pivots (LUProgram::unit) take no division: their word is set to 1,
+//   3. solves for b_ac[b] (forward, backward),
+//   4. refines once: r = b - A x from the G and C arrays in HBM (not from the factors), solve, x += correction,
+//   5. recomputes r and the componentwise backward error max_i |r_i| / (|A| |x| + |b|)_i, 0 / 0 = 0 (tests/lu_ref.py with complex moduli),
+//   6. stores x (interleaved re, im), berr and the flag (bit 0: zero / non-finite pivot or non-finite solution -- a flag, never a trap).
+// Every multiply-add is an explicit fma: the W instantiations compute the same doubles.
+#include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+#include "internal.hpp"
+#include "tran_ctrl.hpp"
+#include "lds_layout.hpp"
+
+namespace cadnip {
+
+struct AcArgs {
+  const double *G, *C, *omega, *bac; const unsigned char *diag_flag, *nodiag; double gmin;
+  double *x, *berr; int* flags;
+  const int *rowptr, *colidx, *load_dst, *ent_pos, *ent_diag, *ent_ptr, *term_a, *term_b, *lev_ptr;
+  const int *lu_rowptr, *lu_col, *lu_diag, *rperm, *cperm, *fwd_rows, *fwd_lev_ptr, *bwd_rows, *bwd_lev_ptr;
+  const int *piv_rows, *piv_lev_ptr;
+  int n, nnz, nnz_lu, n_lev, n_fwd_lev, n_bwd_lev, n_freq, n_sys;
+  long s0;
+};
+
+// acc - a b
+__device__ __forceinline__ double2 cmsub(double2 acc, double2 a, double2 b) {
+  return make_double2(fma(-a.x, b.x, fma(a.y, b.y, acc.x)), fma(-a.x, b.y, fma(-a.y, b.x, acc.y)));
+}
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x)); }
+// 1 / p, scaled by the power of two of max(|re|, |im|): |p|^2 neither overflows nor underflows.  p = 0 / non-finite: the caller has flagged it
+__device__ __forceinline__ double2 crecip(double2 p) {
+  int e;
+  (void)frexp(fmax(fabs(p.x), fabs(p.y)), &e);
+  const double a = ldexp(p.x, -e), b = ldexp(p.y, -e);            // max(|a|, |b|) in [0.5, 1)
+  const double d = fma(a, a, b * b);
+  return make_double2(ldexp(a / d, -e), ldexp(-b / d, -e));
+}
+__device__ __forceinline__ double cabs2(double2 a) { return hypot(a.x, a.y); }
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu(AcArgs a) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = a.n;
+  const int ls = blockIdx.x * W + w;                           // system of this wave inside the launch
+  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  const LdsAc<double*> L = lds_ac((double*)sm, a.nnz_lu, n, w, W);
+  double2 *lu = (double2*)L.lu, *x = (double2*)L.x, *r = (double2*)L.r, *y = (double2*)L.y;
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
+  const double om = a.omega[fi], gmin = a.gmin;
+  auto entry = [&](int e) { return make_double2(G[e] + (a.diag_flag[e] ? gmin : 0.0), om * C[e]); };   // A at CSR position e
+  int bad = 0;
+  // ---- 1. load
+  for (int p = lane; p < a.nnz_lu; p += 64) lu[p] = make_double2(0.0, 0.0);
+  CADNIP_WAVE_SYNC();
+  for (int e = lane; e < a.nnz; e += 64) lu[a.load_dst[e]] = entry(e);
+  CADNIP_WAVE_SYNC();
+  // ---- 2. factor; the pivots of list l are final before level l runs (list 0: after the load)
+  auto pivots = [&](int l) {
+    const int k1 = a.piv_lev_ptr[l + 1];
+    for (int k = a.piv_lev_ptr[l] + lane; k < k1; k += 64) {
+      const int i = a.piv_rows[k], dp = a.lu_diag[i < 0 ? ~i : i];
+      if (i < 0) { lu[dp] = make_double2(1.0, 0.0); continue; }
+      const double2 pv = lu[dp];
+      if ((pv.x == 0.0 && pv.y == 0.0) || !isfinite(pv.x) || !isfinite(pv.y)) bad = 1;
+      lu[dp] = crecip(pv);
+    }
+    CADNIP_WAVE_SYNC();
+  };
+  pivots(0);
+  for (int lev = 0; lev < a.n_lev; ++lev) {
+    const int e1 = a.lev_ptr[lev + 1];
+    for (int e = a.lev_ptr[lev] + lane; e < e1; e += 64) {
+      const int pos = a.ent_pos[e], t1 = a.ent_ptr[e + 1], dg = a.ent_diag[e];
+      double2 acc = lu[pos];
+      for (int t = a.ent_ptr[e]; t < t1; ++t) acc = cmsub(acc, lu[a.term_a[t]], lu[a.term_b[t]]);
+      if (dg >= 0) acc = cmul(acc, lu[dg]);
+      lu[pos] = acc;
+    }
+    CADNIP_WAVE_SYNC();
+    pivots(lev + 1);
+  }
+  // ---- 3. / 4. y := A^-1 y through the factors (y in pivot-row order on entry, pivot-column order on return)
+  auto solve = [&]() {
+    for (int lev = 0; lev < a.n_fwd_lev; ++lev) {
+      const int r1 = a.fwd_lev_ptr[lev + 1];
+      for (int q = a.fwd_lev_ptr[lev] + lane; q < r1; q += 64) {
+        const int i = a.fwd_rows[q], p1 = a.lu_diag[i];
+        double2 acc = y[i];
+        for (int p = a.lu_rowptr[i]; p < p1; ++p) acc = cmsub(acc, lu[p], y[a.lu_col[p]]);
+        y[i] = acc;
+      }
+      CADNIP_WAVE_SYNC();
+    }
+    for (int lev = 0; lev < a.n_bwd_lev; ++lev) {
+      const int r1 = a.bwd_lev_ptr[lev + 1];
+      for (int q = a.bwd_lev_ptr[lev] + lane; q < r1; q += 64) {
+        const int i = a.bwd_rows[q], dp = a.lu_diag[i], p1 = a.lu_rowptr[i + 1];
+        double2 acc = y[i];
+        for (int p = dp + 1; p < p1; ++p) acc = cmsub(acc, lu[p], y[a.lu_col[p]]);
+        y[i] = cmul(acc, lu[dp]);                               // the diagonal word holds 1 / pivot
+      }
+      CADNIP_WAVE_SYNC();
+    }
+  };
+  // r = b - A x, one row per lane; with DEN the backward error of the wave's rows is returned
+  auto residual = [&](auto den_tag) -> double {
+    constexpr bool DEN = decltype(den_tag)::value;
+    double worst = 0.0;
+    for (int i = lane; i < n; i += 64) {
+      const double2 bi = bac[i];
+      double2 acc = bi;
+      double den = DEN ? cabs2(bi) : 0.0;
+      const int p1 = a.rowptr[i + 1];
+      for (int p = a.rowptr[i]; p < p1; ++p) {
+        const double2 av = entry(p), xv = x[a.colidx[p]];
+        acc = cmsub(acc, av, xv);
+        if (DEN) den = fma(cabs2(av), cabs2(xv), den);
+      }
+      if (a.nodiag[i]) {                                        // gmin of a node diagonal outside the pattern
+        const double2 xv = x[i];
+        acc = cmsub(acc, make_double2(gmin, 0.0), xv);
+        if (DEN) den = fma(gmin, cabs2(xv), den);
+      }
+      r[i] = acc;
+      if (DEN) {
+        const double num = cabs2(acc);
+        const double q = num == 0.0 ? 0.0 : num / den;
+        worst = (q > worst || q != q) ? q : worst;              // a NaN stays
+      }
+    }
+    CADNIP_WAVE_SYNC();
+    return worst;
+  };
+  for (int i = lane; i < n; i += 64) y[i] = bac[a.rperm[i]];
+  CADNIP_WAVE_SYNC();
+  solve();
+  for (int i = lane; i < n; i += 64) x[a.cperm[i]] = y[i];
+  CADNIP_WAVE_SYNC();
+  (void)residual(std::false_type());
+  for (int i = lane; i < n; i += 64) y[i] = r[a.rperm[i]];
+  CADNIP_WAVE_SYNC();
+  solve();
+  for (int i = lane; i < n; i += 64) { const int j = a.cperm[i]; const double2 xv = x[j], dv = y[i]; x[j] = make_double2(xv.x + dv.x, xv.y + dv.y); }
+  CADNIP_WAVE_SYNC();
+  // ---- 5. backward error
+  double worst = residual(std::true_type());
+  int nan = worst != worst;
+  if (nan) worst = 0.0;
+  for (int off = 32; off >= 1; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
+  nan = wave_any(nan);
+  // ---- 6. store
+  double2* xo = (double2*)a.x + (size_t)ls * n;
+  for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; xo[i] = v; }
+  bad = wave_any(bad);
+  if (lane == 0) { a.berr[ls] = nan ? __builtin_nan("") : worst; a.flags[ls] = bad ? 1 : 0; }
+}
+
+// The launch plan -- the one place that sizes the LDS block and picks W, and the only reader of CADNIP_AC_WPB.  A compute unit holds
+// min(32 waves, LDS_BUDGET / block) workgroups' worth of systems: the plan takes the W with the most resident systems (ties: the largest),
+// then halves it while the launch would not put a workgroup on half of the 256 compute units.
+AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req) {
+  AcPlan none;
+  if (!h->analyzed || n_sys <= 0) return none;
+  auto bytes = [&](int wpb) { return lds_bytes(lds_ac((size_t)0, h->lu.nnz_lu, h->n, 0, wpb)); };
+  if (wpb_req == 0) if (const char* e = getenv("CADNIP_AC_WPB")) wpb_req = atoi(e);
+  if (wpb_req != 0) {
+    if ((wpb_req != 1 && wpb_req != 2 && wpb_req != 4 && wpb_req != 8) || bytes(wpb_req) > LDS_BUDGET) return none;
+    AcPlan p; p.wpb = wpb_req; p.shmem = bytes(wpb_req);
+    return p;
+  }
+  if (bytes(1) > LDS_BUDGET) return none;
+  int best = 1; size_t best_res = 0;
+  for (int wpb = 1; wpb <= 8; wpb *= 2) {
+    if (bytes(wpb) > LDS_BUDGET) break;
+    const size_t res = std::min<size_t>(32, (LDS_BUDGET / bytes(wpb)) * wpb);
+    if (res >= best_res) { best = wpb; best_res = res; }
+  }
+  while (best > 1 && n_sys < 128L * best) best >>= 1;
+  AcPlan p; p.wpb = best; p.shmem = bytes(best);
+  return p;
+}
+
+namespace {
+template <class T> int ac_upload(T** p, const std::vector<T>& v) {
+  if (*p) { (void)hipFree(*p); *p = nullptr; }
+  HIP_TRY(hipMalloc((void**)p, std::max<size_t>(v.size(), 1) * sizeof(T)));
+  if (!v.empty()) HIP_TRY(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return CADNIP_OK;
+}
+}  // namespace
+
+int ac_lu_prepare(CadnipHandle* h) {
+  if (!h->analyzed) return CADNIP_NOTREADY;
+  if (!h->ac.dirty) return CADNIP_OK;
+  const LUProgram& P = h->lu;
+  const int n_lev = (int)P.lev_ptr.size() - 1;
+  // the factor level that computes each position (-1: final as loaded); a diagonal is only ever read as a pivot, by entries of later levels
+  std::vector<int> lev_of(P.nnz_lu, -1);
+  for (int l = 0; l < n_lev; ++l) for (int e = P.lev_ptr[l]; e < P.lev_ptr[l + 1]; ++e) lev_of[P.ent_pos[e]] = l;
+  std::vector<int> ptr(n_lev + 2, 0), rows(h->n);
+  for (int i = 0; i < h->n; ++i) ++ptr[lev_of[P.lu_diag[i]] + 2];
+  for (int l = 1; l < n_lev + 2; ++l) ptr[l] += ptr[l - 1];
+  std::vector<int> at(ptr.begin(), ptr.end() - 1);
+  for (int i = 0; i < h->n; ++i) rows[at[lev_of[P.lu_diag[i]] + 1]++] = (!P.unit.empty() && P.unit[i]) ? ~i : i;
+  if (!h->ac.d_nodiag) {
+    std::vector<unsigned char> nd(h->n, 0);
+    for (int i = 0; i < h->n_nodes; ++i) {
+      nd[i] = 1;
+      for (int p = h->h_rowptr[i]; p < h->h_rowptr[i + 1]; ++p) if (h->h_colidx[p] == i) nd[i] = 0;
+    }
+    TRY_RC(ac_upload(&h->ac.d_nodiag, nd));
+  }
+  TRY_RC(ac_upload(&h->ac.d_piv_rows, rows));
+  TRY_RC(ac_upload(&h->ac.d_piv_lev_ptr, ptr));
+  h->ac.dirty = false;
+  return CADNIP_OK;
+}
+
+int launch_ac_lu(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin) {
+  if (p.wpb <= 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
+  ProfScope ps(h, "ac_lu");
+  const LUProgram& P = h->lu;
+  AcArgs a;
+  a.G = h->d_G; a.C = h->d_C; a.omega = h->ac.d_omega; a.bac = h->ac.d_bac; a.diag_flag = h->d_diag_flag; a.nodiag = h->ac.d_nodiag; a.gmin = gmin;
+  a.x = h->ac.d_x; a.berr = h->ac.d_berr; a.flags = h->ac.d_flags;
+  a.rowptr = h->d_rowptr; a.colidx = h->d_colidx; a.load_dst = h->d_load_dst; a.ent_pos = h->d_ent_pos; a.ent_diag = h->d_ent_diag;
+  a.ent_ptr = h->d_ent_ptr; a.term_a = h->d_term_a; a.term_b = h->d_term_b; a.lev_ptr = h->d_lev_ptr;
+  a.lu_rowptr = h->d_lu_rowptr; a.lu_col = h->d_lu_col; a.lu_diag = h->d_lu_diag; a.rperm = h->d_rperm; a.cperm = h->d_cperm;
+  a.fwd_rows = h->d_fwd_rows; a.fwd_lev_ptr = h->d_fwd_lev_ptr; a.bwd_rows = h->d_bwd_rows; a.bwd_lev_ptr = h->d_bwd_lev_ptr;
+  a.piv_rows = h->ac.d_piv_rows; a.piv_lev_ptr = h->ac.d_piv_lev_ptr;
+  a.n = h->n; a.nnz = h->nnz; a.nnz_lu = P.nnz_lu; a.n_lev = (int)P.lev_ptr.size() - 1;
+  a.n_fwd_lev = (int)P.fwd_lev_ptr.size() - 1; a.n_bwd_lev = (int)P.bwd_lev_ptr.size() - 1;
+  a.n_freq = n_freq; a.n_sys = n_sys; a.s0 = s0;
+  const int grid = (n_sys + p.wpb - 1) / p.wpb;
+  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, a); }));
+  HIP_TRY(hipGetLastError());
+  return CADNIP_OK;
+}
+
+}  // namespace cadnip

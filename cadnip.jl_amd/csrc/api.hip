@@ -213,7 +213,8 @@ void cadnip_destroy(CadnipHandle* h) {
                   h->d_diag_flag, h->d_prep, h->d_long_rows, h->d_wave, h->d_limit_init, h->d_u, h->d_du, h->d_t, h->d_gamma, h->d_G, h->d_C, h->d_b, h->d_J,
                   h->d_resid, h->d_delta, h->d_limit_w, h->d_LU, h->d_tmp, h->d_flags, h->d_active, h->d_nonfinite, h->d_gshunt, h->d_srcfact, h->d_cold, h->d_load_src, h->d_load_dst, h->d_ent_pos,
                   h->d_ent_diag, h->d_ent_ptr, h->d_term_a, h->d_term_b, h->d_lev_ptr, h->d_lu_rowptr, h->d_lu_col, h->d_lu_diag, h->d_rperm,
-                  h->d_cperm, h->d_fwd_rows, h->d_fwd_lev_ptr, h->d_bwd_rows, h->d_bwd_lev_ptr};
+                  h->d_cperm, h->d_fwd_rows, h->d_fwd_lev_ptr, h->d_bwd_rows, h->d_bwd_lev_ptr,
+                  h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_bac, h->ac.d_omega, h->ac.d_x, h->ac.d_berr, h->ac.d_flags};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   h->f2.release();
   for (auto& g : h->step_graph) if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -733,6 +734,52 @@ int cadnip_factor_solve(CadnipHandle* h, const double* gamma_host, const double*
   return rc;
 }
 
+int cadnip_lu_order(CadnipHandle* h, int32_t* rperm, int32_t* cperm) {
+  if (!h || !rperm || !cperm) return CADNIP_BADARG;
+  if (!h->analyzed) return CADNIP_NOTREADY;
+  memcpy(rperm, h->lu.rperm.data(), (size_t)h->n * sizeof(int));
+  memcpy(cperm, h->lu.cperm.data(), (size_t)h->n * sizeof(int));
+  return CADNIP_OK;
+}
+
+// The AC sweep x[b][f] = (G[b] + gmin [node diagonals] + j omega[f] C[b])^-1 b_ac[b] on the G / C of the last cadnip_rebuild, with the handle's
+// pivot order: S = B n_freq systems through k_ac_lu (ac_lu.hip).  Uploads are blocking copies at entry (the stream is idle), downloads follow a
+// stream synchronisation.  The systems are processed in chunks of at most AC_CHUNK_BYTES of solution (16 n bytes each; at least one system),
+// so the device output buffers -- allocated on first use, kept by the handle, released in cadnip_destroy -- stay bounded however large B F is.
+#define AC_CHUNK_BYTES ((size_t)64 << 20)
+int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, const double* bac_host, int32_t wpb, double* x_host,
+                    double* berr_host, int32_t* flags_host, int32_t* info) {
+  if (!h || n_freq <= 0 || !omega || !bac_host || !x_host || !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
+  const size_t B = h->B, n = h->n, F = n_freq, S = B * F;
+  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * n)));
+  const AcPlan plan = ac_lu_plan(h, (long)std::min(S, chunk), wpb);
+  if (plan.wpb <= 0) return CADNIP_BADARG;                    // invalid wpb, or the work arrays do not fit LDS: nothing is launched
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  TRY(ac_lu_prepare(h));
+  AcState& A = h->ac;
+  if (!A.d_bac) TRY(dev_alloc(&A.d_bac, B * n * 2));
+  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
+  if (A.cap_sys < chunk) {
+    void* old[] = {A.d_x, A.d_berr, A.d_flags};
+    for (void* p : old) if (p) (void)hipFree(p);
+    A.d_x = nullptr; A.d_berr = nullptr; A.d_flags = nullptr; A.cap_sys = 0;
+    TRY(dev_alloc(&A.d_x, chunk * n * 2)); TRY(dev_alloc(&A.d_berr, chunk)); TRY(dev_alloc(&A.d_flags, chunk));
+    A.cap_sys = chunk;
+  }
+  HIP_TRY(hipMemcpy(A.d_bac, bac_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
+  for (size_t s0 = 0; s0 < S; s0 += chunk) {
+    const size_t ns = std::min(chunk, S - s0);
+    TRY(launch_ac_lu(h, plan, n_freq, (long)s0, (int)ns, gmin));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(berr_host + s0, A.d_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags_host + s0, A.d_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  info[0] = plan.wpb; info[1] = (int)plan.shmem; info[2] = (int)S; info[3] = (int)((S / chunk) * ((chunk + plan.wpb - 1) / plan.wpb) + ((S % chunk) + plan.wpb - 1) / plan.wpb);
+  return CADNIP_OK;
+}
+
 int cadnip_lu_stats(CadnipHandle* h, int32_t* nnz_lu, int32_t* n_terms, int32_t* n_levels, int32_t* n_fwd, int32_t* n_bwd) {
   if (!h || !h->analyzed) return CADNIP_NOTREADY;
   if (nnz_lu) *nnz_lu = h->lu.nnz_lu;
@@ -870,6 +917,7 @@ int upload_lu(CadnipHandle* h) {
   TRY(dev_alloc(&h->d_LU, (size_t)h->B * P.nnz_lu));
   h->analyzed = true;
   h->f2.dirty = true;
+  h->ac.dirty = true;
   return CADNIP_OK;
 }
 }  // namespace cadnip

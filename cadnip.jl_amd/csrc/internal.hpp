@@ -132,6 +132,17 @@ struct FusedState {
   void release();             // frees every device buffer; the next use builds everything again
 };
 
+// AC sweep (ac_lu.hip, cadnip_ac_solve): device buffers allocated on first use, and the pivot lists of the complex factorisation -- the rows
+// whose diagonal is final after the load (list 0) / after factor level l (list l + 1); ~row marks a constant-1 pivot (LUProgram::unit)
+struct AcState {
+  bool dirty = true;                       // the LU program changed: the pivot lists are built again
+  int *d_piv_rows = nullptr, *d_piv_lev_ptr = nullptr;
+  unsigned char* d_nodiag = nullptr;       // [n] 1 = a voltage node whose diagonal is not in the pattern: its gmin lives in the residuals only
+  double *d_bac = nullptr, *d_omega = nullptr, *d_x = nullptr, *d_berr = nullptr;
+  int* d_flags = nullptr;
+  size_t cap_freq = 0, cap_sys = 0;        // frequencies d_omega holds, systems the output buffers hold
+};
+
 }  // namespace cadnip
 
 struct CadnipHandle {
@@ -182,6 +193,7 @@ struct CadnipHandle {
   cadnip::LULeaves leaves;    // charge / limit ranges of the unknown layout [V | I | q | lim]
   bool va_ext = false;        // the circuit uses an external generated model (va_generated_ext.hpp): not compiled into the fused kernel
   cadnip::FusedState f2;      // the LDS-resident kernels' tables, step lists and buffers (fused2.hip, lu_f2.hip)
+  cadnip::AcState ac;         // AC sweep: pivot lists and transfer buffers (ac_lu.hip; released with the handle's other buffers in cadnip_destroy)
   // driver state (allocated lazily)
   struct Driver* drv = nullptr;
   // profiling
@@ -222,6 +234,13 @@ int launch_solve(CadnipHandle* h, const double* d_rhs, double* d_x);
 int launch_factor_solve(CadnipHandle* h, bool fuse_jacobian, const double* d_rhs, double* d_x, int kernel = CADNIP_LUK_AUTO, int* info = nullptr,
                         bool dry = false);
 int upload_lu(CadnipHandle* h);
+// ac_lu.hip: the launch plan of k_ac_lu<W> for n_sys systems -- wpb_req 0: the plan's choice (CADNIP_AC_WPB overrides it), else 1 / 2 / 4 / 8.
+// wpb 0: an invalid request, or the work arrays of wpb_req (of one, for 0) systems exceed LDS_BUDGET
+struct AcPlan { int wpb = 0; size_t shmem = 0; };
+AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req);
+int ac_lu_prepare(CadnipHandle* h);        // the pivot lists of the current LU program, on demand
+// systems [s0, s0 + n_sys) of the B x n_freq grid (s = b * n_freq + f) into h->ac.d_x / d_berr / d_flags from index 0
+int launch_ac_lu(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

@@ -1,4 +1,4 @@
-// lds_layout.hpp -- THE map of the dynamic LDS block of every LDS-resident kernel (k_fused2, k_fteam, k_lu_*).  The kernels take their
+// lds_layout.hpp -- THE map of the dynamic LDS block of every LDS-resident kernel (k_fused2, k_fteam, k_lu_*, k_ac_lu).  The kernels take their
 // pointers from it and the launchers their `shmem`: nobody else adds up table, descriptor or work-array words.  Plain C++ behind the
 // __host__ __device__ markers (tests/test_lds_layout.py compiles it with the host compiler).
 //
@@ -61,6 +61,18 @@ template <class P> LDS_HD LdsLu<P> lds_lu(P base, int tab_len, int desc_len, int
   L.desc = base + tab_len / 2;
   L.W = L.desc + desc_len + (size_t)w * L.per;
   L.end = L.desc + desc_len + (size_t)waves * L.per;
+  return L;
+}
+// AC kernel k_ac_lu<W>: W x [ complex L\U factors (nnz_lu) | x: rhs / solution (n) | r: residual (n) | y: correction, the solves' work
+// vector (n) ], every value an interleaved (re, im) pair of doubles -- 16 (nnz_lu + 3 n) bytes per system, each region on 16 bytes.  No
+// tables: the index arrays are read from global memory.  Regions of system w of the workgroup
+template <class P> struct LdsAc { P lu, x, r, y, end; int per; };   // per: doubles of one system
+template <class P> LDS_HD LdsAc<P> lds_ac(P base, int nnz_lu, int n, int w, int wpb) {
+  LdsAc<P> L;
+  L.per = 2 * (nnz_lu + 3 * n);
+  L.lu = base + (size_t)w * L.per;
+  L.x = L.lu + 2 * (size_t)nnz_lu; L.r = L.x + 2 * (size_t)n; L.y = L.r + 2 * (size_t)n;
+  L.end = base + (size_t)wpb * L.per;
   return L;
 }
 template <class L> LDS_HD size_t lds_bytes(const L& l) { return (size_t)l.end * 8; }   // of a layout taken from base (size_t)0

@@ -21,7 +21,7 @@ STATUS_NAMES = {0: "CADNIP_OK", 1: "CADNIP_BADARG", 2: "CADNIP_SINGULAR", 3: "CA
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free",
@@ -344,6 +344,30 @@ class Handle:
         _check(fn(self.h, _dp(uu), _dp(dd), None if g is None else _dp(g), None if tt is None else _dp(tt), C.c_int32(1 if refresh else 0),
                   _dp(delta), _dp(nrm), None if resid is None else _dp(resid)), "cadnip_newton_step_fused" if fused else "cadnip_newton_step")
         return (delta, nrm, resid) if want_resid else (delta, nrm)
+
+    def lu_order(self):
+        """(rperm, cperm) of the handle's current pivot order: pivot k uses original row rperm[k] and column cperm[k]."""
+        rp, cp = np.zeros(self.st.n, dtype=np.int32), np.zeros(self.st.n, dtype=np.int32)
+        _check(self.lib.cadnip_lu_order(self.h, _ip(rp), _ip(cp)), "cadnip_lu_order")
+        return rp, cp
+
+    def ac_solve(self, omega, gmin, b_ac, wpb=0):
+        """cadnip_ac_solve: x[b, f] = (G[b] + gmin on the node diagonals + j omega[f] C[b])^-1 b_ac[b] on the G / C of the last rebuild, with
+        the handle's pivot order -- B x F complex sparse systems in one batched kernel (csrc/ac_lu.hip).  ``omega`` [F] angular frequencies,
+        ``b_ac`` [B, n] complex (or [n], broadcast), ``wpb`` systems per workgroup (0: the launch plan's choice).  Returns (x complex128
+        [B, F, n], berr [B, F], flags [B, F], info) with berr the componentwise backward error of x, flags bit 0 a zero / non-finite pivot or a
+        non-finite solution, and info = {wpb, lds_bytes, systems, workgroups}.  An empty grid launches nothing.  A circuit whose work arrays
+        exceed LDS, or an invalid ``wpb``, raises CadnipError(CADNIP_BADARG)."""
+        om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
+        B, n, F = self.B, self.st.n, om.size
+        if F == 0:
+            return np.zeros((B, 0, n), dtype=complex), np.zeros((B, 0)), np.zeros((B, 0), dtype=np.int32), dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(b_ac, dtype=np.complex128), (B, n)))
+        x = np.empty((B, F, n), dtype=np.complex128)
+        berr, flags, info = np.empty((B, F)), np.zeros((B, F), dtype=np.int32), np.zeros(4, dtype=np.int32)
+        _check(self.lib.cadnip_ac_solve(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), b.ctypes.data_as(_D), C.c_int32(int(wpb)),
+                                        x.ctypes.data_as(_D), _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_solve")
+        return x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
 
     def lu_stats(self):
         v = [C.c_int32() for _ in range(5)]

@@ -149,6 +149,23 @@ function solve!(x::Vector{Float64}, ws::GPUEvalWorkspace, rhs::Vector{Float64})
     return x
 end
 
+# AC sweep (ac!, src/ac.jl:113-170) on the G / C of the last fast_rebuild!: x[:, f, b] = (G + gmin on the node diagonals + im omega[f] C) \ b_ac[:, b]
+# for every instance b and frequency f in one batched kernel.  Julia's column-major ComplexF64 arrays of size (n, F, B) / (n, B) are the C
+# layout [B][F][n][2] / [B][n][2].  Returns (x, berr, flags): rows with flags != 0 or a large backward error are the caller's to solve again.
+function ac_solve(ws::GPUEvalWorkspace, omega::Vector{Float64}, b_ac::Matrix{ComplexF64}; gmin=1e-12, wpb=0)
+    n, B, F = size(b_ac, 1), size(b_ac, 2), length(omega)
+    x = Array{ComplexF64}(undef, n, F, B); berr = Matrix{Float64}(undef, F, B); flags = Matrix{Int32}(undef, F, B); info = zeros(Int32, 4)
+    check(ccall((:cadnip_ac_solve, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Ptr{ComplexF64}, Int32, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                ws.handle, F, omega, gmin, b_ac, wpb, x, berr, flags, info), "cadnip_ac_solve")
+    return x, berr, flags
+end
+# the handle's pivot order (0-based): pivot k uses row rperm[k], column cperm[k]
+function lu_order(ws::GPUEvalWorkspace, n::Integer)
+    rperm = Vector{Int32}(undef, n); cperm = Vector{Int32}(undef, n)
+    check(ccall((:cadnip_lu_order, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), ws.handle, rperm, cperm), "cadnip_lu_order")
+    return rperm, cperm
+end
+
 # One Newton iteration in one ccall (cadnip_newton_step): resid = C du + G u - b, [J = G + gamma C refactored when `refresh`,] delta = J^-1 resid.
 # For a hand-written Newton loop around the library (the shape of _dc_pcnr_newton, src/mna/solve.jl:599-698, on the DAE residual) and for an
 # integrator whose nonlinear solver can be replaced: five entry points and five synchronisations become one.  Returns ||resid||_2.

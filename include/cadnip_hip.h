@@ -225,6 +225,22 @@ int cadnip_newton_step(CadnipHandle* h, const double* u_host, const double* du_h
 int cadnip_newton_step_fused(CadnipHandle* h, const double* u_host, const double* du_host, const double* gamma_host, const double* t_host, int32_t refresh,
                              double* delta_host, double* resid_norm_host, double* resid_host);
 int cadnip_lu_stats(CadnipHandle* h, int32_t* nnz_lu, int32_t* n_terms, int32_t* n_levels, int32_t* n_fwd_levels, int32_t* n_bwd_levels);
+/* the handle's current pivot order: pivot k uses original row rperm[k] and column cperm[k] ([n] each); CADNIP_NOTREADY before an analysis */
+int cadnip_lu_order(CadnipHandle* h, int32_t* rperm, int32_t* cperm);
+
+/* ---- AC sweep == the frequency loop of ac!, src/ac.jl:113-170 (there: one dense (G + jw C) \ b_ac per frequency) -----------------
+ * x[b][f] = (G[b] + gmin on the voltage-node diagonals + j omega[f] C[b])^-1 b_ac[b] on the G / C of the last cadnip_rebuild and the handle's
+ * current pivot order: B * n_freq independent complex sparse systems, one wave each (csrc/ac_lu.hip), factorisation, solve, one step of
+ * iterative refinement and the componentwise backward error berr = max_i |b - A x|_i / (|A| |x| + |b|)_i of the returned x.
+ * gmin of a node whose diagonal is not in the pattern enters the residuals (refinement, berr) and not the factors.
+ * Complex values are interleaved (re, im) doubles.  flags bit 0: zero / non-finite pivot or non-finite solution of that system (reported,
+ * never raised: the call still returns CADNIP_OK).  wpb: systems per workgroup, 0 = the launch plan's choice, else 1, 2, 4 or 8.
+ * info: W that ran, LDS bytes of a workgroup, systems, workgroups.  CADNIP_BADARG -- and nothing launched -- without an analysis, with
+ * n_freq <= 0, an invalid wpb, or when the work arrays of W systems, 16 (nnz(L+U) + 3 n) bytes each, exceed the 160 KB of LDS.  Large
+ * sweeps run in chunks of at most 64 MiB of solution, so the handle's output buffers stay bounded. */
+int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega /* [F] */, double gmin, const double* bac_host /* [B][n][2] */,
+                    int32_t wpb, double* x_host /* [B][F][n][2] */, double* berr_host /* [B][F] */, int32_t* flags_host /* [B][F] */,
+                    int32_t* info /* [4] */);
 
 /* ---- host drivers (Newton loop + step controller; stand-in for IDA / _dc_pcnr_newton) ----
  * The loops run on the host and launch the kernels above on the handle's stream; the
