@@ -219,9 +219,8 @@ void cadnip_destroy(CadnipHandle* h) {
   h->f2.release();
   for (auto& g : h->step_graph) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (auto& b : h->blocks) {
-    void* bp[] = {b.d_nodes, b.d_ipar, b.d_par, b.d_sp_tptr, b.d_sp_info, b.d_sp_rec, b.d_cache, b.d_sp_rowoff,
-                  b.sp_gen.tptr, b.sp_gen.info, b.sp_gen.rec, b.sp_gen.rowoff, b.sp_plain.tptr, b.sp_plain.info, b.sp_plain.rec, b.sp_plain.rowoff};
-    for (void* p : bp) if (p) (void)hipFree(p);
+    for (void* p : {(void*)b.d_nodes, (void*)b.d_ipar, (void*)b.d_par, (void*)b.d_cache}) if (p) (void)hipFree(p);
+    for (auto& P : b.plan) for (void* p : {(void*)P.tptr, (void*)P.info, (void*)P.rec, (void*)P.rowoff}) if (p) (void)hipFree(p);
   }
   if (h->h_pinned) (void)hipHostFree(h->h_pinned);
   if (h->h_stage) (void)hipHostFree(h->h_stage);

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "../../include/cadnip_hip.h"
+#include "stamp_plan.hpp"   // StampShape
 // rows of the derived sp_mos1 parameter card (devices.hpp: enum M1_*) that cadnip_set_params inspects
 #define CADNIP_MOS1_PAR_OXCAP 8
 #define CADNIP_MOS1_PAR_GD 30
@@ -85,18 +86,12 @@ struct DeviceBlock {
   bool mos1_plain = false;   // sp_mos1 block: every instance has gd = gs = OxideCap = 0 (set by cadnip_set_params)
   int* d_ipar = nullptr;
   double* d_par = nullptr;   // [B][n_par][count]
-  // reduction plan of the stamping kernel (stamp_csr.hip): devices per tile, tiles per instance, and per tile the targets
-  // (CSR entries of G / C, rows of b) it contributes to with the LDS offsets of their contributions in COO order
-  int sp_cs = 0, sp_chunks = 0, sp_n_targets = 0, sp_levels = 1, sp_scratch = 0;
-  struct Target { int chunk; unsigned word; std::vector<unsigned short> offs; };
-  std::vector<Target> sp_targets;            // build-time only
-  int *d_sp_tptr = nullptr, *d_sp_info = nullptr; uint4* d_sp_rec = nullptr;
-  // sp_mos1 blocks carry two plans -- the lane-pair path (mos1_plain: the rows of the external d / g / s terminals and the d / s columns
-  // are structural zeros there) stages fewer rows -- and the launch picks the one that matches the parameters in force
-  struct PlanSet { int n_targets = 0, levels = 1, scratch = 0, rows = 0; int *tptr = nullptr, *info = nullptr; uint4* rec = nullptr; unsigned short* rowoff = nullptr; };
-  PlanSet sp_gen, sp_plain;
-  int sp_rows = 0;                           // staged rows of a tile: the slots some target reads (+ one trash row for the rest); see build_stamp_plan
-  unsigned short* d_sp_rowoff = nullptr;     // [n_g + n_c + n_b] word offset of every slot's row inside a tile
+  // the stamping kernel's plan (stamp_plan.hpp; uploaded by stamp_csr.hip: build_stamp_plan): devices per tile, tiles per instance, and the
+  // tables in device memory.  plan[0]: the general plan; plan[1]: the lane-pair plan of an sp_mos1 block (mos1_plain: fewer live rows),
+  // empty for every other type -- the launch picks the one that matches the parameters in force
+  int sp_cs = 0, sp_chunks = 0;
+  struct PlanSet { StampShape shape; int *tptr = nullptr, *info = nullptr; uint4* rec = nullptr; unsigned short* rowoff = nullptr; };
+  PlanSet plan[2];
 };
 
 struct ProfEntry { const char* name; double ms = 0; int64_t calls = 0; };

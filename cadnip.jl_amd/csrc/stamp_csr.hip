@@ -21,10 +21,12 @@
 // is accumulated with a global fp64 atomic, on a word that k_stamp_prep has pre-set when no earlier kernel stores it.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <algorithm>
 #include <vector>
 #include "stamp_csr_kernel.hpp"   // CsrStampArgs, LdsOut, k_stamp_csr<TYPE, EXT>
+#include "stamp_plan.hpp"         // the plan the kernel follows and its launch geometry (host only)
 
 namespace cadnip {
 
@@ -45,254 +47,43 @@ __global__ void __launch_bounds__(256) k_stamp_prep(PrepArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
-// host: the reduction plan, built once per structure (cadnip_create)
+// host: the plan (stamp_plan.hpp), built and uploaded once per structure (cadnip_create)
 // ------------------------------------------------------------------------------------------
-template <class T> static int upload_vec(T** p, const std::vector<T>& v) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
+static_assert(sizeof(StampRec) == sizeof(uint4) && offsetof(StampRec, x) == offsetof(uint4, x) && offsetof(StampRec, y) == offsetof(uint4, y) &&
+              offsetof(StampRec, z) == offsetof(uint4, z) && offsetof(StampRec, w) == offsetof(uint4, w), "a record is one uint4 of the kernel");
+
+template <class D, class T> static int upload_vec(D** p, const std::vector<T>& v) {
+  static_assert(sizeof(D) == sizeof(T), "element types of the same layout");
   HIP_TRY(hipMalloc((void**)p, std::max<size_t>(v.size(), 1) * sizeof(T)));
   if (!v.empty()) HIP_TRY(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return CADNIP_OK;
 }
 
-static int build_plan_variant(CadnipHandle* h, const CadnipStructure* s, bool plain) {
-  const int n = h->n, nnz = h->nnz;
-  // slot -> (block, k, dev) per array; blocks own disjoint slot ranges
-  struct Owner { int blk, k, dev; };
-  auto owners = [&](int which, int total) {
-    std::vector<Owner> o((size_t)total, Owner{-1, 0, 0});
-    for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
-      const DeviceBlock& b = h->blocks[bi];
-      if (b.count == 0) continue;
-      const int base = which == 0 ? b.g_base : which == 1 ? b.c_base : b.b_base, nk = which == 0 ? b.n_g : which == 1 ? b.n_c : b.n_b;
-      for (int k = 0; k < nk; ++k) for (int d = 0; d < b.count; ++d) o[(size_t)base + (size_t)k * b.count + d] = Owner{(int)bi, k, d};
-    }
-    return o;
-  };
-  // tile geometry per block
-  for (auto& b : h->blocks) {
-    if (b.count == 0) continue;
-    const int nslots = b.n_g + b.n_c + b.n_b;
-    int cs = b.type == CADNIP_DEV_MOS1 ? 32 : 64;                       // sp_mos1: room for two lanes per device
-    if (b.type == CADNIP_DEV_VA && b.va_tl) cs = 64 / b.va_tl;           // external models: 16 or 32 direction lanes per device (va_runtime.hpp)
-    while (cs > 1 && (size_t)cs * nslots * 8 > 96 * 1024) cs >>= 1;     // big generated models: smaller chunks
-    if ((size_t)cs * nslots > 65535) return CADNIP_BADARG;              // 16-bit staging offsets
-    if (b.count <= cs) { b.sp_cs = b.count; b.sp_chunks = 1; }
-    else { b.sp_cs = cs; b.sp_chunks = (b.count + cs - 1) / cs; }
-    b.sp_targets.clear();
-  }
-  // contributions of every target, in COO order, tagged with (block, chunk)
-  struct Contrib { int blk, chunk; unsigned short off; };
-  const int* ptrs[3] = {s->g_ptr, s->c_ptr, s->b_ptr};
-  const int* slots[3] = {s->g_slots, s->c_slots, s->b_slots};
-  const int n_tgt[3] = {nnz, nnz, n};
-  const int totals[3] = {h->ns_g, h->ns_c, h->ns_b};
-  // Rows of a tile.  A tile stages [row][device]; only the slots that some target reads need a row of their own (a stamp into a
-  // ground row / column has no target, nor has the unused form -- charge state or linear -- of a reactive branch): they are packed,
-  // every other slot writes into one shared trash row, and a slot whose value is structurally zero is read from the tile's zero
-  // word.  Fewer rows = less LDS per wave = more waves per CU: this kernel's duration follows its occupancy.
-  const unsigned short ROW_ZERO = 0xFFFEu, ROW_NONE = 0xFFFFu;
-  std::vector<std::vector<unsigned short>> rowmap(h->blocks.size());
-  for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
-    const DeviceBlock& b = h->blocks[bi];
-    rowmap[bi].assign((size_t)(b.n_g + b.n_c + b.n_b), ROW_NONE);
-  }
-  auto packs = [](const DeviceBlock& b) { return b.type == CADNIP_DEV_MOS1 || b.type == CADNIP_DEV_VA; };   // (stamp_csr_kernel.hpp: REMAP)
-  for (int arr = 0; arr < 3; ++arr) {
-    const std::vector<Owner> own = owners(arr, totals[arr]);
-    for (int e = 0; e < n_tgt[arr]; ++e)
-      for (int p = ptrs[arr][e]; p < ptrs[arr][e + 1]; ++p) {
-        const Owner& o = own[(size_t)slots[arr][p]];
-        if (o.blk < 0) return CADNIP_BADARG;
-        const DeviceBlock& b = h->blocks[o.blk];
-        rowmap[o.blk][(size_t)(o.k + (arr == 0 ? 0 : arr == 1 ? b.n_g : b.n_g + b.n_c))] = 0;      // live
-      }
-  }
+static StampBlock stamp_block_of(const DeviceBlock& b) { return StampBlock{b.type, b.count, b.n_g, b.n_c, b.n_b, b.g_base, b.c_base, b.b_base, b.va_tl}; }
+
+// (every pointer lands in the handle as soon as it is allocated: cadnip_destroy releases a handle whose build failed half way)
+int build_stamp_plan(CadnipHandle* h, const CadnipStructure* s) {
+  std::vector<StampBlock> blocks;
+  for (const DeviceBlock& b : h->blocks) blocks.push_back(stamp_block_of(b));
+  StampPlans plans;
+  TRY_RC(stamp_plan_build(*s, blocks, plans));
   for (size_t bi = 0; bi < h->blocks.size(); ++bi) {
     DeviceBlock& b = h->blocks[bi];
-    if (b.count == 0) continue;
-    if (b.type == CADNIP_DEV_MOS1)                      // devices.hpp: the charge rows' d/dV_d and d/dV_s entries (gq[1], gq[3]) and their linear
-      for (int r = 0; r < 4; ++r)                       // form (dq[0], dq[2]) are zeros whatever the parameters
-        for (int k : {48 + 7 * r + 1, 48 + 7 * r + 3, b.n_g + 4 + 6 * r, b.n_g + 4 + 6 * r + 2})
-          if (rowmap[bi][(size_t)k] != ROW_NONE) rowmap[bi][(size_t)k] = ROW_ZERO;
-    if (b.type == CADNIP_DEV_MOS1 && plain) {           // the lane-pair path (stamp_mos1_pair; gd = gs = OxideCap = 0): the KCL rows of the external
-      auto zero = [&](int k) { if (rowmap[bi][(size_t)k] != ROW_NONE) rowmap[bi][(size_t)k] = ROW_ZERO; };   // d, g, s terminals carry nothing ...
-      for (int k = 12; k < 12 + 18; ++k) zero(k);
-      for (int br = 3; br < 6; ++br) { zero(12 + 6 * br); zero(12 + 6 * br + 2); }      // ... and no row has an entry in the d / s columns
-      for (int k = 0; k < 3; ++k) zero(b.n_g + b.n_c + k);                               // b of rows d, g, s
-    }
-    if (!packs(b)) {                                    // one row per slot, no table
-      for (size_t k = 0; k < rowmap[bi].size(); ++k) rowmap[bi][k] = (unsigned short)k;
-      b.sp_rows = (int)rowmap[bi].size();
-      if (b.d_sp_rowoff) { (void)hipFree(b.d_sp_rowoff); b.d_sp_rowoff = nullptr; }
-      continue;
-    }
-    int rows = 0;
-    for (auto& r : rowmap[bi]) if (r == 0) r = (unsigned short)rows++;
-    b.sp_rows = rows + 1;                               // + the trash row
-    if ((size_t)b.sp_rows * b.sp_cs > 65000) return CADNIP_BADARG;   // 16-bit staging offsets
-    std::vector<unsigned short> ro(rowmap[bi].size());
-    for (size_t k = 0; k < ro.size(); ++k) ro[k] = (unsigned short)((rowmap[bi][k] >= ROW_ZERO ? rows : rowmap[bi][k]) * b.sp_cs);
-    int rc = upload_vec(&b.d_sp_rowoff, ro);
-    if (rc) return rc;
-  }
-  const unsigned OFF_ZERO = 0xFFFFu;                    // operand that reads the tile's zero word (patched below, like an unused operand slot)
-  std::vector<unsigned> prep, prep_orphan;   // atomically accumulated words nobody stores first | unstamped node diagonals
-  std::vector<char> is_diag((size_t)nnz, 0);
-  for (int i = 0; i < s->n_nodes; ++i) if (s->diag_nz[i] >= 0 && s->diag_nz[i] < nnz) is_diag[s->diag_nz[i]] = 1;
-  std::vector<Contrib> cl;
-  std::vector<int> order;
-  for (int arr = 0; arr < 3; ++arr) {
-    const std::vector<Owner> own = owners(arr, totals[arr]);
-    for (int e = 0; e < n_tgt[arr]; ++e) {
-      cl.clear();
-      for (int p = ptrs[arr][e]; p < ptrs[arr][e + 1]; ++p) {
-        const Owner& o = own[(size_t)slots[arr][p]];
-        if (o.blk < 0) return CADNIP_BADARG;                            // a gather list names a slot no block owns
-        const DeviceBlock& b = h->blocks[o.blk];
-        const int kk = o.k + (arr == 0 ? 0 : arr == 1 ? b.n_g : b.n_g + b.n_c);
-        const unsigned short row = rowmap[o.blk][(size_t)kk];
-        cl.push_back(Contrib{o.blk, o.dev / b.sp_cs, row == ROW_ZERO ? (unsigned short)OFF_ZERO : (unsigned short)(row * b.sp_cs + o.dev % b.sp_cs)});
-      }
-      if (cl.empty()) {
-        // a G entry nobody stamps stays zero for ever -- unless it is a node diagonal, which carries gshunt
-        if (arr == 0 && is_diag[e]) prep_orphan.push_back((unsigned)e);
-        continue;
-      }
-      // group by tile (block, chunk) in launch order; inside a tile the COO order is kept
-      order.resize(cl.size());
-      for (size_t i = 0; i < cl.size(); ++i) order[i] = (int)i;
-      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cl[x].blk != cl[y].blk ? cl[x].blk < cl[y].blk : cl[x].chunk < cl[y].chunk; });
-      const int first_blk = cl[order[0]].blk;
-      for (size_t i = 0; i < order.size();) {
-        const int blk = cl[order[i]].blk, chunk = cl[order[i]].chunk;
-        size_t j = i;
-        DeviceBlock::Target t;
-        t.chunk = chunk;
-        while (j < order.size() && cl[order[j]].blk == blk && cl[order[j]].chunk == chunk) t.offs.push_back(cl[order[j++]].off);
-        // does another tile of the same kernel contribute too?
-        const bool shared_in_kernel = (i > 0 && cl[order[i - 1]].blk == blk) || (j < order.size() && cl[order[j]].blk == blk);
-        const int mode = shared_in_kernel ? TGT_ATOMIC : (blk == first_blk ? TGT_STORE : TGT_RMW);
-        if (mode == TGT_ATOMIC && blk == first_blk && i == 0) prep.push_back(((unsigned)arr << 28) | (unsigned)e);   // nobody stores it first
-        t.word = ((unsigned)mode << 30) | ((unsigned)arr << 28) | (unsigned)e;
-        h->blocks[blk].sp_targets.push_back(std::move(t));
-        i = j;
-      }
+    b.sp_cs = plans.block[bi].tiling.cs; b.sp_chunks = plans.block[bi].tiling.chunks;
+    for (int v = 0; v < 2; ++v) {
+      const StampPlan& P = plans.block[bi].plan[v];
+      if (P.empty()) continue;
+      DeviceBlock::PlanSet& D = b.plan[v];
+      D.shape = P;
+      TRY_RC(upload_vec(&D.tptr, P.tptr));
+      TRY_RC(upload_vec(&D.info, P.info));
+      TRY_RC(upload_vec(&D.rec, P.rec));
+      if (!P.rowoff.empty()) TRY_RC(upload_vec(&D.rowoff, P.rowoff));
     }
   }
-  // per block: targets grouped by chunk (stable: array, then CSR position), uploaded as flat arrays
-  for (auto& b : h->blocks) {
-    if (b.count == 0) continue;
-    std::stable_sort(b.sp_targets.begin(), b.sp_targets.end(), [](const DeviceBlock::Target& x, const DeviceBlock::Target& y) { return x.chunk < y.chunk; });
-    // record = {destination word, count | off0 << 16, off1 | off2 << 16, off3 | off4 << 16}: up to five operands inline.
-    // A target with more contributions becomes a 5-ary tree: level-0 records sum consecutive runs of five staged words into
-    // scratch words of the tile, the next level combines five of those, ... until one record is left, which carries the
-    // target's real destination.  Records are grouped per chunk and level.
-    const int stage_words = b.sp_rows * b.sp_cs;
-    struct Rec { int chunk, level, cls; uint4 r; };
-    auto cls_of = [](unsigned word) { const unsigned md = word >> 30, arr = (word >> 28) & 3u; return md == TGT_PARTIAL ? 3 : md == TGT_STORE ? (int)arr : 4; };
-    std::vector<Rec> recs;
-    std::vector<int> scratch_used(b.sp_chunks, 0);
-    int n_levels = 1;
-    // (the zero word's offset is known only after the scratch words are counted: unused operand slots are patched below)
-    const unsigned UNUSED = 0xFFFFu;
-    auto pack = [&](unsigned word, const unsigned* o, unsigned cnt) {
-      uint4 r; unsigned v[5] = {UNUSED, UNUSED, UNUSED, UNUSED, UNUSED};
-      for (unsigned i = 0; i < cnt; ++i) v[i] = o[i];
-      r.x = word; r.y = cnt | (v[0] << 16); r.z = v[1] | (v[2] << 16); r.w = v[3] | (v[4] << 16);
-      return r;
-    };
-    for (auto& t : b.sp_targets) {
-      std::vector<unsigned> cur(t.offs.begin(), t.offs.end());
-      int level = 0;
-      while (cur.size() > 5) {
-        std::vector<unsigned> next;
-        for (size_t i = 0; i < cur.size(); i += 5) {
-          const unsigned cnt = (unsigned)std::min<size_t>(5, cur.size() - i);
-          if (cnt == 1) { next.push_back(cur[i]); continue; }             // a lone tail word moves up as it is
-          const unsigned so = (unsigned)(stage_words + scratch_used[t.chunk]++);
-          recs.push_back(Rec{t.chunk, level, 3, pack(((unsigned)TGT_PARTIAL << 30) | so, &cur[i], cnt)});
-          next.push_back(so);
-        }
-        cur.swap(next);
-        ++level;
-      }
-      recs.push_back(Rec{t.chunk, level, cls_of(t.word), pack(t.word, cur.data(), (unsigned)cur.size())});
-      n_levels = std::max(n_levels, level + 1);
-    }
-    int n_scratch = 0;
-    for (int c = 0; c < b.sp_chunks; ++c) n_scratch = std::max(n_scratch, scratch_used[c]);
-    n_scratch += 1;                                                         // + the tile's zero word (its last word)
-    if ((stage_words + n_scratch) & 1) n_scratch += 1;                      // tiles stay 16-byte aligned (zeroing uses 16-byte stores)
-    if ((size_t)stage_words + n_scratch >= 65535) return CADNIP_BADARG;
-    {
-      const unsigned zero_off = (unsigned)(stage_words + n_scratch - 1);
-      auto fix = [&](unsigned half) { return half == UNUSED ? zero_off : half; };
-      for (auto& rc_ : recs) {
-        uint4& r = rc_.r;
-        r.y = (r.y & 0xFFFFu) | (fix(r.y >> 16) << 16);
-        r.z = fix(r.z & 0xFFFFu) | (fix(r.z >> 16) << 16);
-        r.w = fix(r.w & 0xFFFFu) | (fix(r.w >> 16) << 16);
-      }
-    }
-    std::stable_sort(recs.begin(), recs.end(), [](const Rec& x, const Rec& y) { return x.chunk != y.chunk ? x.chunk < y.chunk : x.level != y.level ? x.level < y.level : x.cls < y.cls; });
-    // steps: runs of STEP_W records (two per lane), every step within one (level, class); a short last step of a group is
-    // padded with count-0 records that sum the zero word and write nothing
-    std::vector<int> sptr(b.sp_chunks + 1, 0), sinfo;
-    std::vector<uint4> rec;
-    {
-      const unsigned zo = (unsigned)(stage_words + n_scratch - 1);
-      uint4 padrec; padrec.x = 0; padrec.y = 0u | (zo << 16); padrec.z = zo | (zo << 16); padrec.w = zo | (zo << 16);
-      size_t k = 0;
-      for (int c = 0; c < b.sp_chunks; ++c) {
-        sptr[c] = (int)sinfo.size();
-        for (int l = 0; l < n_levels; ++l) {
-          bool first_of_level = l > 0;
-          for (int cls = 0; cls < N_CLS; ++cls) {
-            size_t k1 = k;
-            while (k1 < recs.size() && recs[k1].chunk == c && recs[k1].level == l && recs[k1].cls == cls) ++k1;
-            for (size_t p = k; p < k1; p += STEP_W) {
-              sinfo.push_back(cls | (first_of_level ? 0x100 : 0));
-              first_of_level = false;
-              for (size_t j = p; j < p + STEP_W; ++j) rec.push_back(j < k1 ? recs[j].r : padrec);
-            }
-            k = k1;
-          }
-          if (first_of_level) sinfo.push_back(5 | 0x100), rec.insert(rec.end(), STEP_W, padrec);   // an empty level still fences
-        }
-      }
-      sptr[b.sp_chunks] = (int)sinfo.size();
-    }
-    b.sp_n_targets = (int)rec.size();
-    b.sp_levels = n_levels; b.sp_scratch = n_scratch;
-    int rc;
-    if ((rc = upload_vec(&b.d_sp_tptr, sptr))) return rc;
-    if ((rc = upload_vec(&b.d_sp_info, sinfo))) return rc;
-    if ((rc = upload_vec(&b.d_sp_rec, rec))) return rc;
-    b.sp_targets.clear(); b.sp_targets.shrink_to_fit();
-  }
-  h->n_prep_atomic = (int)prep.size();
-  prep.insert(prep.end(), prep_orphan.begin(), prep_orphan.end());
-  h->n_prep = (int)prep.size();
-  if (h->n_prep) { int rc = upload_vec(&h->d_prep, prep); if (rc) return rc; }
-  return CADNIP_OK;
-}
-
-int build_stamp_plan(CadnipHandle* h, const CadnipStructure* s) {
-  auto take = [](DeviceBlock& b) {
-    DeviceBlock::PlanSet p;
-    p.n_targets = b.sp_n_targets; p.levels = b.sp_levels; p.scratch = b.sp_scratch; p.rows = b.sp_rows;
-    p.tptr = b.d_sp_tptr; p.info = b.d_sp_info; p.rec = b.d_sp_rec; p.rowoff = b.d_sp_rowoff;
-    b.d_sp_tptr = nullptr; b.d_sp_info = nullptr; b.d_sp_rec = nullptr; b.d_sp_rowoff = nullptr;
-    return p;
-  };
-  bool any_mos1 = false;
-  for (auto& b : h->blocks) any_mos1 = any_mos1 || (b.type == CADNIP_DEV_MOS1 && b.count > 0);
-  int rc = build_plan_variant(h, s, false);
-  if (rc || !any_mos1) return rc;
-  for (auto& b : h->blocks) if (b.type == CADNIP_DEV_MOS1 && b.count > 0) b.sp_gen = take(b);
-  rc = build_plan_variant(h, s, true);
-  if (rc) return rc;
-  for (auto& b : h->blocks) if (b.type == CADNIP_DEV_MOS1 && b.count > 0) b.sp_plain = take(b);
+  h->n_prep_atomic = plans.n_prep_atomic;
+  h->n_prep = (int)plans.prep.size();
+  if (h->n_prep) TRY_RC(upload_vec(&h->d_prep, plans.prep));
   return CADNIP_OK;
 }
 
@@ -325,34 +116,23 @@ template <int TYPE>
 static int launch_stamp_csr_pass(CadnipHandle* h, DeviceBlock& b, bool dump_only) {
   const int nslots = b.n_g + b.n_c + b.n_b;
   const bool pair = TYPE == CADNIP_DEV_MOS1 && b.mos1_plain;
-  const int lpd = pair ? 2 : (TYPE == CADNIP_DEV_VA && b.va_tl) ? b.va_tl : 1;
-  DeviceBlock::PlanSet P;                              // the plan in force
-  if (TYPE == CADNIP_DEV_MOS1) P = b.mos1_plain ? b.sp_plain : b.sp_gen;
-  else { P.levels = b.sp_levels; P.scratch = b.sp_scratch; P.rows = b.sp_rows; P.tptr = b.d_sp_tptr; P.info = b.d_sp_info; P.rec = b.d_sp_rec; P.rowoff = b.d_sp_rowoff; }
-  const int rows = dump_only ? nslots : P.rows;        // the read-out pass stages every slot in a row of its own
-  int ipw = 1;
-  if (b.sp_chunks == 1) ipw = std::min(8, std::max(1, 64 / (b.count * lpd)));   // (a wave reduces its instances one after the other: few per wave)
-  const size_t tile_words = (size_t)rows * b.sp_cs + P.scratch;
-  while (ipw > 1 && (size_t)ipw * tile_words * 8 > 64 * 1024) --ipw;
-  const int u_lds = (size_t)ipw * h->n * 8 <= 16 * 1024 ? 1 : 0;
+  const DeviceBlock::PlanSet& P = b.plan[pair ? 1 : 0];   // the plan in force
   static const size_t lds_pad = getenv("CADNIP_SC_PAD") ? (size_t)atol(getenv("CADNIP_SC_PAD")) : 0;        // experiments: occupancy as a function of the LDS request
-  // tiles (staged rows + tree scratch), per-instance scalars, u, the slots' row offsets
-  const size_t shmem = ((size_t)ipw * tile_words + 3 * (size_t)ipw + (u_lds ? (size_t)ipw * h->n : 0)) * 8 + (((size_t)nslots * 2 + 7) & ~(size_t)7) + lds_pad;
+  const StampGeom g = stamp_geometry(stamp_block_of(b), StampTiling{b.sp_cs, b.sp_chunks}, P.shape, h->B, h->n, pair, dump_only, lds_pad);
   CsrStampArgs a{b.d_nodes, b.d_ipar, b.d_par, h->d_wave, h->d_u, h->d_t, h->d_active, h->d_cold, h->d_G, h->d_C, h->d_b, h->d_limit_w, h->d_nonfinite,
                  h->d_diag_flag, h->d_gshunt, h->d_srcfact, P.tptr, P.info, P.rec,
-                 h->B, b.count, h->n, h->nnz, b.n_par, b.n_g, b.n_c, b.n_b, b.sp_cs, b.sp_chunks, ipw, lpd, h->spec.mode, h->initjct,
-                 (TYPE == CADNIP_DEV_MOS1 || TYPE == CADNIP_DEV_VA) ? 1 : 0, P.levels, P.scratch, u_lds,
+                 h->B, b.count, h->n, h->nnz, b.n_par, b.n_g, b.n_c, b.n_b, b.sp_cs, b.sp_chunks, g.ipw, g.lpd, h->spec.mode, h->initjct,
+                 stamp_packs(TYPE) ? 1 : 0, P.shape.levels, P.shape.scratch, g.u_lds,
                  b.d_cache, b.n_cache, dump_only ? h->d_dump : nullptr, h->ns, b.g_base, h->ns_g + b.c_base, h->ns_g + h->ns_c + b.b_base,
-                 dump_only ? nullptr : P.rowoff, rows, dump_only ? 1 : 0};
-  const unsigned grid = (unsigned)b.sp_chunks * (unsigned)((h->B + ipw - 1) / ipw);
+                 dump_only ? nullptr : P.rowoff, g.rows, dump_only ? 1 : 0};
   if (getenv("CADNIP_SC_DEBUG")) fprintf(stderr, "[cadnip stamp] type %d count %d cs %d chunks %d ipw %d lpd %d slots %d rows %d scratch %d tile_words %zu shmem %zu grid %u levels %d u_lds %d%s\n",
-                                         TYPE, b.count, b.sp_cs, b.sp_chunks, ipw, lpd, nslots, rows, P.scratch, tile_words, shmem, grid, P.levels, u_lds, dump_only ? " (read-out pass)" : "");
+                                         TYPE, b.count, b.sp_cs, b.sp_chunks, g.ipw, g.lpd, nslots, g.rows, P.shape.scratch, g.tile_words, g.shmem, g.grid, P.shape.levels, g.u_lds, dump_only ? " (read-out pass)" : "");
   if (TYPE == CADNIP_DEV_VA && b.va_tl) {           // external model: its own kernel (va_ext/<module>.hip)
     const int ext = b.va_model - CADNIP_VA_NBUILTIN;
     if (ext < 0 || ext >= CADNIP_VA_NEXT) return CADNIP_BADARG;
-    return VA_EXT_STAMP[ext](a, grid, shmem, h->stream);
+    return VA_EXT_STAMP[ext](a, g.grid, g.shmem, h->stream);
   }
-  return launch_stamp_kernel<TYPE>(a, grid, shmem, h->stream);
+  return launch_stamp_kernel<TYPE>(a, g.grid, g.shmem, h->stream);
 }
 
 // The stamping pass of one block; with the operating-point read-out armed (cadnip_get_contributions), a second pass that stages every
@@ -364,18 +144,26 @@ static int launch_stamp_csr_t(CadnipHandle* h, DeviceBlock& b) {
   return rc;
 }
 
+// device type -> its profile name and the launcher of its kernel instantiation, in the order of CadnipDeviceType
+struct StampType { int type; const char* prof; int (*launch)(CadnipHandle*, DeviceBlock&); };
+#define ROW(T, NAME) {T, NAME, launch_stamp_csr_t<T>}
+static const StampType STAMP_TYPES[] = {
+    ROW(CADNIP_DEV_RESISTOR, "stamp_resistor"), ROW(CADNIP_DEV_CAPACITOR, "stamp_capacitor"), ROW(CADNIP_DEV_INDUCTOR, "stamp_inductor"),
+    ROW(CADNIP_DEV_VSOURCE, "stamp_vsource"), ROW(CADNIP_DEV_ISOURCE, "stamp_isource"), ROW(CADNIP_DEV_VCVS, "stamp_vcvs"), ROW(CADNIP_DEV_VCCS, "stamp_vccs"),
+    ROW(CADNIP_DEV_CCVS, "stamp_ccvs"), ROW(CADNIP_DEV_CCCS, "stamp_cccs"), ROW(CADNIP_DEV_DIODE, "stamp_diode"), ROW(CADNIP_DEV_DIODECAP, "stamp_diodecap"),
+    ROW(CADNIP_DEV_SIMPLEMOS, "stamp_simplemos"), ROW(CADNIP_DEV_MOS1, "stamp_mos1"), ROW(CADNIP_DEV_BVSOURCE, "stamp_bvsource"),
+    ROW(CADNIP_DEV_BISOURCE, "stamp_bisource"), ROW(CADNIP_DEV_VA, "stamp_va")};
+#undef ROW
+static_assert(sizeof(STAMP_TYPES) / sizeof(STAMP_TYPES[0]) == CADNIP_DEV_NTYPES, "one row per device type");
+static const StampType* stamp_type(int type) {
+  return type >= 0 && type < CADNIP_DEV_NTYPES && STAMP_TYPES[type].type == type ? &STAMP_TYPES[type] : nullptr;
+}
+
 // one stamping kernel alone (bench.py times it back to back for the stamp-kernel roofline line)
 int launch_stamp_block(CadnipHandle* h, int block) {
   if (block < 0 || block >= (int)h->blocks.size() || h->blocks[block].count == 0) return CADNIP_BADARG;
-  DeviceBlock& blk = h->blocks[block];
-  switch (blk.type) {
-#define CASE(T) case T: return launch_stamp_csr_t<T>(h, blk);
-    CASE(CADNIP_DEV_RESISTOR) CASE(CADNIP_DEV_CAPACITOR) CASE(CADNIP_DEV_INDUCTOR) CASE(CADNIP_DEV_VSOURCE) CASE(CADNIP_DEV_ISOURCE)
-    CASE(CADNIP_DEV_VCVS) CASE(CADNIP_DEV_VCCS) CASE(CADNIP_DEV_CCVS) CASE(CADNIP_DEV_CCCS) CASE(CADNIP_DEV_DIODE) CASE(CADNIP_DEV_DIODECAP)
-    CASE(CADNIP_DEV_SIMPLEMOS) CASE(CADNIP_DEV_MOS1) CASE(CADNIP_DEV_BVSOURCE) CASE(CADNIP_DEV_BISOURCE) CASE(CADNIP_DEV_VA)
-#undef CASE
-  }
-  return CADNIP_BADARG;
+  const StampType* t = stamp_type(h->blocks[block].type);
+  return t ? t->launch(h, h->blocks[block]) : CADNIP_BADARG;
 }
 
 int launch_rebuild(CadnipHandle* h) {
@@ -391,20 +179,10 @@ int launch_rebuild(CadnipHandle* h) {
   }
   for (auto& blk : h->blocks) {
     if (blk.count == 0) continue;
-    int rc = CADNIP_OK;
-    switch (blk.type) {
-#define CASE(T, NAME) case T: { ProfScope ps(h, NAME); rc = launch_stamp_csr_t<T>(h, blk); } break;
-      CASE(CADNIP_DEV_RESISTOR, "stamp_resistor") CASE(CADNIP_DEV_CAPACITOR, "stamp_capacitor")
-      CASE(CADNIP_DEV_INDUCTOR, "stamp_inductor") CASE(CADNIP_DEV_VSOURCE, "stamp_vsource")
-      CASE(CADNIP_DEV_ISOURCE, "stamp_isource") CASE(CADNIP_DEV_VCVS, "stamp_vcvs") CASE(CADNIP_DEV_VCCS, "stamp_vccs")
-      CASE(CADNIP_DEV_CCVS, "stamp_ccvs") CASE(CADNIP_DEV_CCCS, "stamp_cccs") CASE(CADNIP_DEV_DIODE, "stamp_diode")
-      CASE(CADNIP_DEV_DIODECAP, "stamp_diodecap") CASE(CADNIP_DEV_SIMPLEMOS, "stamp_simplemos")
-      CASE(CADNIP_DEV_MOS1, "stamp_mos1") CASE(CADNIP_DEV_BVSOURCE, "stamp_bvsource") CASE(CADNIP_DEV_BISOURCE, "stamp_bisource")
-      CASE(CADNIP_DEV_VA, "stamp_va")
-#undef CASE
-      default: return CADNIP_BADARG;
-    }
-    if (rc) return rc;
+    const StampType* t = stamp_type(blk.type);
+    if (!t) return CADNIP_BADARG;
+    ProfScope ps(h, t->prof);
+    TRY_RC(t->launch(h, blk));
   }
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;

@@ -5,13 +5,10 @@
 #include <type_traits>
 #include "devices.hpp"
 #include "internal.hpp"
+#include "stamp_plan.hpp"   // the record encoding: TGT_*, N_CLS, STEP_W, the bits of a target word and of a step-info word
 #include "tran_ctrl.hpp"   // CADNIP_WAVE_SYNC
 
 namespace cadnip {
-
-#define N_CLS 5   // record classes of the reduction (k_stamp_csr); 5 = padding step
-enum { TGT_STORE = 0, TGT_RMW = 1, TGT_ATOMIC = 2, TGT_PARTIAL = 3 };   // bits 30-31 of a target word; bits 28-29: 0 G, 1 C, 2 b; bits 0-27: index
-                                                                       // (TGT_PARTIAL: index = LDS scratch word of the tile, relative to the tile)
 
 // LDS staging writer: slot (k, dev) of this lane's instance tile; same interface as SlotOut (devices.hpp)
 // REMAP: the block's plan packs its rows (sp_mos1 and the generated models: many slots, many of them without a target); the small device types
@@ -73,7 +70,6 @@ static __device__ unsigned long long g_sc_sum[8], g_sc_cnt;
 #define SC_POINT(id) do {} while (0)
 #endif
 
-#define STEP_W 128   // records per reduction step (two per lane)
 #define PIPE 8       // steps whose records are in flight / in registers
 
 // EXT: void for the built-in device types; for a generated external model (va_ext/<module>.hip) a struct with

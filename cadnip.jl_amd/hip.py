@@ -162,6 +162,44 @@ LU_KERNELS = ("auto", "steps4", "mw4", "f2s", "f2", "plain")
 MODE_NAMES = ("dcop", "tran", "tranop")
 
 
+def structure_c(st: Structure):
+    """The CadnipStructure of ``st`` (include/cadnip_hip.h) and the arrays it points into, which the caller keeps alive as long as
+    the struct is in use.  Loads no library: the host-only tests feed the same struct to code compiled with the host compiler."""
+    keep = []
+    blocks = (DeviceBlockC * max(1, len(st.blocks)))()
+    for k, blk in enumerate(st.blocks):
+        nodes = np.ascontiguousarray(blk.nodes, dtype=np.int32)
+        ipar = np.ascontiguousarray(blk.ipar, dtype=np.int32)
+        keep += [nodes, ipar]
+        b = blocks[k]
+        b.type, b.count = type_id(blk.type), blk.count
+        b.n_nodes, b.nodes = nodes.shape[0], _ip(nodes)
+        b.n_ipar, b.ipar = ipar.shape[0], _ip(ipar)
+        b.n_par = blk.n_par
+        b.g_base, b.c_base, b.b_base = blk.g_base, blk.c_base, blk.b_base
+        b.n_g, b.n_c, b.n_b = blk.n_g, blk.n_c, blk.n_b
+    s = StructureC()
+    s.n, s.n_nodes, s.n_currents, s.n_charges, s.n_limits = st.n, st.n_nodes, st.n_currents, st.n_charges, st.n_limits
+    s.nnz = st.nnz
+    arrs = {}
+    for nm in ("rowptr", "colidx", "to_ref_nz", "g_ptr", "g_slots", "c_ptr", "c_slots", "b_ptr", "b_slots", "diag_nz"):
+        a = np.ascontiguousarray(getattr(st, nm), dtype=np.int32)
+        if a.size == 0:
+            a = np.zeros(1, dtype=np.int32)
+        arrs[nm] = a
+        setattr(s, nm, _ip(a))
+    wd = np.ascontiguousarray(st.wave_data, dtype=np.float64)
+    wdp = wd if wd.size else np.zeros(1)
+    li = np.ascontiguousarray(st.limit_init, dtype=np.float64)
+    lip = li if li.size else np.zeros(1)
+    keep += [arrs, wdp, lip, blocks]
+    s.n_blocks, s.blocks = len(st.blocks), blocks
+    s.n_wave_data, s.wave_data = wd.size, _dp(wdp)
+    s.ns_g, s.ns_c, s.ns_b = st.ns_g, st.ns_c, st.ns_b
+    s.limit_init = _dp(lip)
+    return s, keep
+
+
 class Handle:
     """One (structure, GPU) handle with ``B`` resident sweep instances."""
 
@@ -169,38 +207,7 @@ class Handle:
         self.lib = load_library()
         self.st = st
         self.B = int(B)
-        self._keep = []
-        blocks = (DeviceBlockC * max(1, len(st.blocks)))()
-        for k, blk in enumerate(st.blocks):
-            nodes = np.ascontiguousarray(blk.nodes, dtype=np.int32)
-            ipar = np.ascontiguousarray(blk.ipar, dtype=np.int32)
-            self._keep += [nodes, ipar]
-            b = blocks[k]
-            b.type, b.count = type_id(blk.type), blk.count
-            b.n_nodes, b.nodes = nodes.shape[0], _ip(nodes)
-            b.n_ipar, b.ipar = ipar.shape[0], _ip(ipar)
-            b.n_par = blk.n_par
-            b.g_base, b.c_base, b.b_base = blk.g_base, blk.c_base, blk.b_base
-            b.n_g, b.n_c, b.n_b = blk.n_g, blk.n_c, blk.n_b
-        s = StructureC()
-        s.n, s.n_nodes, s.n_currents, s.n_charges, s.n_limits = st.n, st.n_nodes, st.n_currents, st.n_charges, st.n_limits
-        s.nnz = st.nnz
-        arrs = {}
-        for nm in ("rowptr", "colidx", "to_ref_nz", "g_ptr", "g_slots", "c_ptr", "c_slots", "b_ptr", "b_slots", "diag_nz"):
-            a = np.ascontiguousarray(getattr(st, nm), dtype=np.int32)
-            if a.size == 0:
-                a = np.zeros(1, dtype=np.int32)
-            arrs[nm] = a
-            setattr(s, nm, _ip(a))
-        wd = np.ascontiguousarray(st.wave_data, dtype=np.float64)
-        wdp = wd if wd.size else np.zeros(1)
-        li = np.ascontiguousarray(st.limit_init, dtype=np.float64)
-        lip = li if li.size else np.zeros(1)
-        self._keep += [arrs, wdp, lip, blocks]
-        s.n_blocks, s.blocks = len(st.blocks), blocks
-        s.n_wave_data, s.wave_data = wd.size, _dp(wdp)
-        s.ns_g, s.ns_c, s.ns_b = st.ns_g, st.ns_c, st.ns_b
-        s.limit_init = _dp(lip)
+        s, self._keep = structure_c(st)
         self.h = C.c_void_p()
         _check(self.lib.cadnip_create(C.byref(s), C.c_int32(self.B), C.c_int32(device), C.byref(self.h)), "cadnip_create")
         self.spec = dict(mode="tran", gmin=1e-12, gshunt=0.0, srcFact=1.0)
