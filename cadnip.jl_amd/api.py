@@ -706,6 +706,7 @@ class NoiseSol:
     def __init__(self, freqs, output, onoise, contributions, temp, input, gain, inoise):
         self.freqs, self.output, self.onoise, self.contributions = freqs, output, onoise, contributions
         self.temp, self.input, self.gain, self.inoise = temp, input, gain, inoise
+        self.stats = {}          # noise(..., solver="gpu" | "auto"): what the batched GPU sweep did (``noise_solve_gpu``); empty on the host path
 
     def __getitem__(self, name):
         if name == "onoise":
@@ -813,12 +814,8 @@ def noise_sources(st, circuit, params, u, temp_c=27.0, gmin=1e-12):
     return out
 
 
-def noise_solve(st, G, C, sources, output, freqs, input=None, temp_c=27.0):
-    """noise.jl:150-188 on dense G (gmin already on the voltage-node diagonals) and C: one adjoint solve per frequency,
-    S_out(f) = sum_k |x_adj[p_k] - x_adj[n_k]|^2 S_k(f); the same adjoint gives the gain from the input source's branch row."""
-    freqs = np.asarray(freqs, dtype=float)
-    if freqs.size == 0:
-        raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
+def noise_indices(st, output, input=None):
+    """(out_idx, in_idx or None): the output unknown and the branch row of the input source, with noise!'s own errors"""
     names = list(st.node_names) + list(st.current_names)
     if output in ("gnd", "0"):
         raise KeyError("noise: the output cannot be ground")
@@ -831,6 +828,19 @@ def noise_solve(st, G, C, sources, output, freqs, input=None, temp_c=27.0):
         if not cand:
             raise KeyError("noise: input source %s is not an independent voltage source (no current variable I_%s)" % (input, input))
         in_idx = st.n_nodes + st.current_names.index(cand[0])
+    return out_idx, in_idx
+
+
+def noise_solve(st, G, C, sources, output, freqs, input=None, temp_c=27.0, adjoint=None):
+    """noise.jl:150-188 on dense G (gmin already on the voltage-node diagonals) and C: one adjoint solve per frequency,
+    S_out(f) = sum_k |x_adj[p_k] - x_adj[n_k]|^2 S_k(f); the same adjoint gives the gain from the input source's branch row.
+    ``adjoint``: None -- the dense solve here -- or (index, H): the probe differences H[f, index[(p, n)]] = x_adj[p] - x_adj[n] of this
+    point, solved elsewhere (``noise_solve_gpu``) for every source's (p, n) and for (in_idx, -1); the weighting and the sums are the same
+    statements in the same source order either way."""
+    freqs = np.asarray(freqs, dtype=float)
+    if freqs.size == 0:
+        raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
+    out_idx, in_idx = noise_indices(st, output, input)
     e_out = np.zeros(st.n, dtype=complex)
     e_out[out_idx] = 1.0
     onoise = np.zeros(len(freqs))
@@ -838,42 +848,149 @@ def noise_solve(st, G, C, sources, output, freqs, input=None, temp_c=27.0):
     gain = np.zeros(len(freqs), dtype=complex) if input is not None else np.zeros(0, dtype=complex)
     inoise = np.zeros(len(freqs)) if input is not None else np.zeros(0)
     for fi, f in enumerate(freqs):
-        x_adj = np.linalg.solve((1j * 2.0 * np.pi * f * C + G).T, e_out)
+        if adjoint is None:
+            x_adj = np.linalg.solve((1j * 2.0 * np.pi * f * C + G).T, e_out)
         for s in sources:
-            Hk = (x_adj[s[0]] if s[0] >= 0 else 0.0) - (x_adj[s[1]] if s[1] >= 0 else 0.0)
+            if adjoint is None:
+                Hk = (x_adj[s[0]] if s[0] >= 0 else 0.0) - (x_adj[s[1]] if s[1] >= 0 else 0.0)
+            else:
+                Hk = adjoint[1][fi, adjoint[0][(s[0], s[1])]]
             c = abs(Hk) ** 2 * noise_psd(s, temp_c, f)
             onoise[fi] += c
             contributions[s[5]][fi] += c
         if input is not None:
-            H = x_adj[in_idx]
+            H = x_adj[in_idx] if adjoint is None else adjoint[1][fi, adjoint[0][(in_idx, -1)]]
             gain[fi] = H
             inoise[fi] = np.inf if H == 0 else onoise[fi] / abs(H) ** 2
     return NoiseSol(freqs, output, onoise, contributions, temp_c, input, gain, inoise)
 
 
-def noise(target, output, freqs, input=None, gmin=1e-12, device=0):
+# The adjoint sweep's gate, as AC_BERR_MAX above and measured the same way on the TRANSPOSED systems: 16 x the largest componentwise backward
+# error np.linalg.solve(A.T, e_out) -- the host path's solve -- leaves over the noise test systems (tests/ac_ref.py CASES on the CPU port's
+# G, C at the DC points, e_out at the output nodes of tests/noise_ref.py), and not below 64 eps.
+# The measurement gave 1.45e-15 (linear_zoo at 1 Hz; the flip-flop 6.8e-16, the Butterworth filter 8.0e-16, the inverter 1.2e-16), held
+# here rounded up to two digits: a gate of 2.4e-14.  Unlike the plain systems' b_ac, e_out at an output node leaves no row whose terms all
+# vanish, so the dense solve's componentwise figure stays near eps and the gate is a real one; the static-order adjoint solve measures at most
+# 2.1e-16 on the same systems.  tests/test_lu_transpose_cpu.py repeats the measurement.  DESIGN.md section 6.
+NOISE_BERR_MEASURED = 1.5e-15
+NOISE_BERR_MAX = max(16 * NOISE_BERR_MEASURED, 64 * float(np.finfo(np.float64).eps))
+
+
+def noise_probe_pairs(source_lists, in_idx=None):
+    """The probe pairs of a structure class: the distinct (p, n) over all its points' sources in order of first appearance, plus
+    (in_idx, -1) for the gain.  Returns (pairs [K, 2] int32, {(p, n): k})."""
+    index = {}
+    for srcs in source_lists:
+        for s in srcs:
+            index.setdefault((int(s[0]), int(s[1])), len(index))
+    if in_idx is not None:
+        index.setdefault((int(in_idx), -1), len(index))
+    return np.array(list(index), dtype=np.int32).reshape(-1, 2), index
+
+
+def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, input=None, temps=27.0, gmin=1e-12, solver="gpu", stats=None):
+    """The adjoint sweep of one structure class on the GPU, reachable without ``noise_sources``: ``h`` (a hip.Handle holding the restamp at the
+    DC points; ``G_ref`` / ``C_ref`` [B, nnz] are its get_GCb) re-analyses its pivot order on ``ac_pivot_sample`` and solves all points x all
+    frequencies in ONE ``ac_adjoint`` call for the class's probe pairs; ``Gd`` / ``Cd`` (dense, gmin on the node diagonals) and
+    ``source_lists`` are per point.  A system whose flag is set or whose backward error exceeds NOISE_BERR_MAX is solved again by the host's
+    dense adjoint solve.  The PSD weighting and the sums are ``noise_solve``'s.  Returns one NoiseSol per point; ``stats`` (shared by the call)
+    is updated as by ``ac_gpu_sweep``.  A circuit that does not fit the launch plan raises with solver="gpu"; with "auto" the points are
+    solved on the host and stats["fallback"] says why."""
+    from . import hip
+    freqs = np.asarray(freqs, dtype=float)
+    if freqs.size == 0:
+        raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
+    if stats is None:
+        stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    B, F = len(Gd), freqs.size
+    temps = np.broadcast_to(np.asarray(temps, dtype=float), (B,))
+    out_idx, in_idx = noise_indices(st, output, input)
+    omegas = 2.0 * np.pi * freqs
+    pairs, index = noise_probe_pairs(source_lists, in_idx)
+    host = lambda k, adj=None: noise_solve(st, Gd[k], Cd[k], source_lists[k], output, freqs, input, float(temps[k]), adjoint=adj)
+    if len(pairs) == 0:                                  # no source and no input: nothing to probe, the sums are empty
+        sols = [host(k) for k in range(B)]
+        stats["host_systems"] += B * F
+    else:
+        to_ref = np.asarray(st.to_ref_nz)
+        sample_ref = np.empty(st.nnz)
+        sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+        h.analyze_values(sample_ref)
+        e_out = np.zeros(st.n, dtype=complex)
+        e_out[out_idx] = 1.0
+        try:
+            H, _, berr, flags, info = h.ac_adjoint(omegas, gmin, e_out, pairs)
+        except hip.CadnipError as e:
+            if solver == "auto" and e.code == hip.BADARG:
+                stats["host_systems"] += B * F
+                stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
+                sols = [host(k) for k in range(B)]
+                for s in sols:
+                    s.stats = stats
+                return sols
+            raise
+        redo = (flags != 0) | ~(berr <= NOISE_BERR_MAX)
+        H = np.array(H)
+        pp, nn = pairs[:, 0], pairs[:, 1]
+        for k, f in zip(*np.nonzero(redo)):
+            x_adj = np.linalg.solve((1j * omegas[f] * Cd[k] + Gd[k]).T, e_out)
+            H[k, f] = np.where(pp >= 0, x_adj[pp], 0.0) - np.where(nn >= 0, x_adj[nn], 0.0)
+        sols = [host(k, (index, H[k])) for k in range(B)]
+        kept = berr[~redo]
+        stats["gpu_systems"] += int((~redo).sum())
+        stats["host_systems"] += int(redo.sum())
+        stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
+        stats["wpb"] = info["wpb"]
+    for s in sols:
+        s.stats = stats
+    return sols
+
+
+def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"):
     """noise!(circuit, output; freqs, input, gmin) -- src/noise.jl:118-190.  As for ``ac``: the DC operating point and the restamp at it run on the
-    GPU; the sources are collected on the host at that point (noise_sources) and the adjoint sweep is the reference's own dense solve."""
+    GPU; the sources are collected on the host at that point (noise_sources) and the adjoint sweep is the reference's own dense solve.
+    A CircuitSweep returns one NoiseSol per point (one resident batch per structure class).
+    ``solver``: "host" (default) as above; "gpu" solves the adjoint systems of every point on the device as well -- points x frequencies
+    transposed complex sparse systems in one batched kernel per structure class (``noise_solve_gpu``), for the probe pairs the class's
+    sources need -- while the PSD weighting stays in numpy; ``ns.stats`` = {"gpu_systems", "host_systems", "max_berr", "wpb"} of the call.
+    "gpu" raises for a circuit too large for the kernel, "auto" takes the host path for it and says so in ``stats["fallback"]``."""
     import scipy.sparse as sp
+    if solver not in ("host", "gpu", "auto"):
+        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
     if len(freqs) == 0:
         raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
-    mc = MNACircuit(target.circuit, target.params, MNASpec(temp=target.spec.temp, mode="dcop", gmin=target.spec.gmin))
-    sim = BatchSimulator(mc, None, device)
-    try:
-        st = sim.st
-        u, conv, _ = sim.dc()
-        if not np.all(conv):
-            raise RuntimeError("noise: the DC operating point did not converge")
-        sim.h.rebuild(u, 0.0)
-        G, C, _, _ = sim.h.get_GCb()
-        dense = lambda nz: sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
-        Gd, Cd = dense(G[0]), dense(C[0])
-        Gd[np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
-        p0 = {kk: float(v[0]) for kk, v in sim.params.items()}
-        srcs = noise_sources(st, mc.circuit, p0, u[0], mc.spec.temp, mc.spec.gmin)
-        return noise_solve(st, Gd, Cd, srcs, output, freqs, input, mc.spec.temp)
-    finally:
-        sim.close()
+    sweep = isinstance(target, CircuitSweep)
+    mc0 = target.circuit if sweep else target
+    mc = MNACircuit(mc0.circuit, mc0.params, MNASpec(temp=mc0.spec.temp, mode="dcop", gmin=mc0.spec.gmin))
+    pts = target.points() if sweep else [{}]
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    sols = [None] * len(pts)
+    for idx, st in structure_classes(mc, pts) if sweep else [([0], None)]:
+        sim = BatchSimulator(mc, [pts[i] for i in idx] if sweep else None, device, st=st)
+        try:
+            st = sim.st
+            u, conv, _ = sim.dc()
+            if not np.all(conv):
+                raise RuntimeError("noise: the DC operating point did not converge" + (" for %d point(s)" % int((~conv).sum()) if sweep else ""))
+            sim.h.rebuild(u, 0.0)
+            G, C, _, _ = sim.h.get_GCb()
+            dense = lambda nz: sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
+            Gd, Cd, srcs, temps = [], [], [], []
+            for k, i in enumerate(idx):
+                Gd.append(dense(G[k])), Cd.append(dense(C[k]))
+                Gd[k][np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
+                p_k = {kk: float(v[k]) for kk, v in sim.params.items()}
+                temps.append(float(pts[i].get("temp", mc.spec.temp)))
+                srcs.append(noise_sources(st, mc.circuit, p_k, u[k], temps[k], mc.spec.gmin))
+            if solver == "host":
+                got = [noise_solve(st, Gd[k], Cd[k], srcs[k], output, freqs, input, temps[k]) for k in range(len(idx))]
+            else:
+                got = noise_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, output, freqs, input, temps, gmin, solver, stats)
+            for k, i in enumerate(idx):
+                sols[i] = got[k]
+        finally:
+            sim.close()
+    return SweepResult(pts, sols) if sweep else sols[0]
 
 
 def tran(target, tspan, abstol=1e-10, reltol=1e-8, saveat=None, device=0, **kw):

@@ -23,6 +23,7 @@
 #include "internal.hpp"
 #include "tran_ctrl.hpp"
 #include "lds_layout.hpp"
+#include "lu_transpose.hpp"
 
 namespace cadnip {
 
@@ -51,26 +52,19 @@ __device__ __forceinline__ double2 crecip(double2 p) {
 }
 __device__ __forceinline__ double cabs2(double2 a) { return hypot(a.x, a.y); }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu(AcArgs a) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = a.n;
-  const int ls = blockIdx.x * W + w;                           // system of this wave inside the launch
-  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
-  const LdsAc<double*> L = lds_ac((double*)sm, a.nnz_lu, n, w, W);
-  double2 *lu = (double2*)L.lu, *x = (double2*)L.x, *r = (double2*)L.r, *y = (double2*)L.y;
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
-  const double om = a.omega[fi], gmin = a.gmin;
-  auto entry = [&](int e) { return make_double2(G[e] + (a.diag_flag[e] ? gmin : 0.0), om * C[e]); };   // A at CSR position e
+// A at CSR position e of instance-local G / C
+__device__ __forceinline__ double2 ac_entry(const AcArgs& a, const double* G, const double* C, double om, int e) {
+  return make_double2(G[e] + (a.diag_flag[e] ? a.gmin : 0.0), om * C[e]);
+}
+
+// Steps 1 and 2 of both kernels -- load A into lu, factor in place -- so that k_ac_lu and k_ac_adj hold the same doubles by construction.
+// Returns 1 in the lanes that met a zero / non-finite pivot.
+__device__ __forceinline__ int ac_load_factor(const AcArgs& a, double2* lu, const double* G, const double* C, double om, int lane) {
   int bad = 0;
   // ---- 1. load
   for (int p = lane; p < a.nnz_lu; p += 64) lu[p] = make_double2(0.0, 0.0);
   CADNIP_WAVE_SYNC();
-  for (int e = lane; e < a.nnz; e += 64) lu[a.load_dst[e]] = entry(e);
+  for (int e = lane; e < a.nnz; e += 64) lu[a.load_dst[e]] = ac_entry(a, G, C, om, e);
   CADNIP_WAVE_SYNC();
   // ---- 2. factor; the pivots of list l are final before level l runs (list 0: after the load)
   auto pivots = [&](int l) {
@@ -97,6 +91,25 @@ __global__ void __launch_bounds__(64 * W) k_ac_lu(AcArgs a) {
     CADNIP_WAVE_SYNC();
     pivots(lev + 1);
   }
+  return bad;
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu(AcArgs a) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = a.n;
+  const int ls = blockIdx.x * W + w;                           // system of this wave inside the launch
+  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  const LdsAc<double*> L = lds_ac((double*)sm, a.nnz_lu, n, w, W);
+  double2 *lu = (double2*)L.lu, *x = (double2*)L.x, *r = (double2*)L.r, *y = (double2*)L.y;
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
+  const double om = a.omega[fi], gmin = a.gmin;
+  auto entry = [&](int e) { return ac_entry(a, G, C, om, e); };   // A at CSR position e
+  int bad = ac_load_factor(a, lu, G, C, om, lane);
   // ---- 3. / 4. y := A^-1 y through the factors (y in pivot-row order on entry, pivot-column order on return)
   auto solve = [&]() {
     for (int lev = 0; lev < a.n_fwd_lev; ++lev) {
@@ -173,6 +186,122 @@ __global__ void __launch_bounds__(64 * W) k_ac_lu(AcArgs a) {
   if (lane == 0) { a.berr[ls] = nan ? __builtin_nan("") : worst; a.flags[ls] = bad ? 1 : 0; }
 }
 
+// ---- the adjoint kernel: A^T x = c with the same factors (noise.jl:150-188: one adjoint solve per frequency serves every noise source) --------
+// Steps 1 and 2 as k_ac_lu (ac_load_factor).  Then, through the tables of lu_transpose.hpp (M = A[rperm][:, cperm] = L U, so M^T = U^T L^T and
+// the permutations swap roles):
+//   3. y[j] = c[cperm[j]];  U^T z = y forward, L^T w = z backward, both a gather per unknown over its COLUMN of L\U, level by level, in place
+//      in y;  x[rperm[i]] = w[i].  The diagonal word holds 1 / pivot (1 for constant-1 pivots),
+//   4. one refinement step with r = c - A^T x from G and C in HBM over the column view of the CSR pattern; gmin sits on diagonals, so the
+//      diag_flag entries and the `nodiag` nodes carry it exactly as in the plain residual,
+//   5. the componentwise backward error max_j |r_j| / (|A^T| |x| + |c|)_j, 0 / 0 = 0, a NaN stays,
+//   6. stores: h[k] = x[p_k] - x[n_k] for the K probe pairs of the call (-1: ground, contributes 0), lanes striding over K; berr; the flag
+//      (bit 0 as k_ac_lu); x itself when the caller asked for it.
+// Everything is a gather and every multiply-add an explicit fma: no atomics, no workgroup barrier, the W instantiations compute the same doubles.
+struct AcAdjArgs {
+  AcArgs a;                                 // a.bac: c [B][n]; a.x: x out (null: not wanted); a.berr / a.flags: this kernel's outputs
+  const int *t_colptr, *t_pos, *t_row, *t_diag, *ut_rows, *ut_lev_ptr, *lt_rows, *lt_lev_ptr, *a_colptr, *a_row, *a_pos;
+  const int* pairs; double* h;
+  int n_ut_lev, n_lt_lev, n_pairs;
+};
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj(AcAdjArgs t) {
+  extern __shared__ double sm[];
+  const AcArgs& a = t.a;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = a.n;
+  const int ls = blockIdx.x * W + w;
+  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  const LdsAc<double*> L = lds_ac((double*)sm, a.nnz_lu, n, w, W);
+  double2 *lu = (double2*)L.lu, *x = (double2*)L.x, *r = (double2*)L.r, *y = (double2*)L.y;
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double2* c = (const double2*)a.bac + (size_t)inst * n;
+  const double om = a.omega[fi], gmin = a.gmin;
+  int bad = ac_load_factor(a, lu, G, C, om, lane);
+  // ---- 3. / 4. y := M^-T y (y in pivot-column order on entry, pivot-row order on return)
+  auto solve = [&]() {
+    for (int lev = 0; lev < t.n_ut_lev; ++lev) {
+      const int r1 = t.ut_lev_ptr[lev + 1];
+      for (int q = t.ut_lev_ptr[lev] + lane; q < r1; q += 64) {
+        const int j = t.ut_rows[q], p0 = t.t_colptr[j], pd = p0 + t.t_diag[j];
+        double2 acc = y[j];
+        for (int p = p0; p < pd; ++p) acc = cmsub(acc, lu[t.t_pos[p]], y[t.t_row[p]]);
+        y[j] = cmul(acc, lu[t.t_pos[pd]]);                      // the diagonal word holds 1 / pivot
+      }
+      CADNIP_WAVE_SYNC();
+    }
+    for (int lev = 0; lev < t.n_lt_lev; ++lev) {
+      const int r1 = t.lt_lev_ptr[lev + 1];
+      for (int q = t.lt_lev_ptr[lev] + lane; q < r1; q += 64) {
+        const int j = t.lt_rows[q], p1 = t.t_colptr[j + 1];
+        double2 acc = y[j];
+        for (int p = t.t_colptr[j] + t.t_diag[j] + 1; p < p1; ++p) acc = cmsub(acc, lu[t.t_pos[p]], y[t.t_row[p]]);
+        y[j] = acc;
+      }
+      CADNIP_WAVE_SYNC();
+    }
+  };
+  // r = c - A^T x, one column of A per lane; with DEN the backward error of the wave's columns is returned
+  auto residual = [&](auto den_tag) -> double {
+    constexpr bool DEN = decltype(den_tag)::value;
+    double worst = 0.0;
+    for (int j = lane; j < n; j += 64) {
+      const double2 cj = c[j];
+      double2 acc = cj;
+      double den = DEN ? cabs2(cj) : 0.0;
+      const int p1 = t.a_colptr[j + 1];
+      for (int p = t.a_colptr[j]; p < p1; ++p) {
+        const double2 av = ac_entry(a, G, C, om, t.a_pos[p]), xv = x[t.a_row[p]];
+        acc = cmsub(acc, av, xv);
+        if (DEN) den = fma(cabs2(av), cabs2(xv), den);
+      }
+      if (a.nodiag[j]) {                                        // gmin of a node diagonal outside the pattern
+        const double2 xv = x[j];
+        acc = cmsub(acc, make_double2(gmin, 0.0), xv);
+        if (DEN) den = fma(gmin, cabs2(xv), den);
+      }
+      r[j] = acc;
+      if (DEN) {
+        const double num = cabs2(acc);
+        const double q = num == 0.0 ? 0.0 : num / den;
+        worst = (q > worst || q != q) ? q : worst;              // a NaN stays
+      }
+    }
+    CADNIP_WAVE_SYNC();
+    return worst;
+  };
+  for (int j = lane; j < n; j += 64) y[j] = c[a.cperm[j]];
+  CADNIP_WAVE_SYNC();
+  solve();
+  for (int i = lane; i < n; i += 64) x[a.rperm[i]] = y[i];
+  CADNIP_WAVE_SYNC();
+  (void)residual(std::false_type());
+  for (int j = lane; j < n; j += 64) y[j] = r[a.cperm[j]];
+  CADNIP_WAVE_SYNC();
+  solve();
+  for (int i = lane; i < n; i += 64) { const int k = a.rperm[i]; const double2 xv = x[k], dv = y[i]; x[k] = make_double2(xv.x + dv.x, xv.y + dv.y); }
+  CADNIP_WAVE_SYNC();
+  // ---- 5. backward error
+  double worst = residual(std::true_type());
+  int nan = worst != worst;
+  if (nan) worst = 0.0;
+  for (int off = 32; off >= 1; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
+  nan = wave_any(nan);
+  // ---- 6. store
+  double2* xo = a.x ? (double2*)a.x + (size_t)ls * n : nullptr;
+  for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
+  double2* ho = (double2*)t.h + (size_t)ls * t.n_pairs;
+  for (int k = lane; k < t.n_pairs; k += 64) {
+    const int p = t.pairs[2 * k], q = t.pairs[2 * k + 1];
+    const double2 xp = p >= 0 ? x[p] : make_double2(0.0, 0.0), xn = q >= 0 ? x[q] : make_double2(0.0, 0.0);
+    ho[k] = make_double2(xp.x - xn.x, xp.y - xn.y);
+  }
+  bad = wave_any(bad);
+  if (lane == 0) { a.berr[ls] = nan ? __builtin_nan("") : worst; a.flags[ls] = bad ? 1 : 0; }
+}
+
 // The launch plan -- the one place that sizes the LDS block and picks W, and the only reader of CADNIP_AC_WPB.  A compute unit holds
 // min(32 waves, LDS_BUDGET / block) workgroups' worth of systems: the plan takes the W with the most resident systems (ties: the largest),
 // then halves it while the launch would not put a workgroup on half of the 256 compute units.
@@ -207,9 +336,24 @@ template <class T> int ac_upload(T** p, const std::vector<T>& v) {
 }
 }  // namespace
 
-int ac_lu_prepare(CadnipHandle* h) {
+// the transposed-solve tables of the current LU program (lu_transpose.hpp) into AcState
+static int ac_adjoint_tables(CadnipHandle* h) {
+  AcState& A = h->ac;
+  LUTranspose T;
+  lu_transpose_build(h->lu, h->h_rowptr, h->h_colidx, T);
+  TRY_RC(ac_upload(&A.d_t_colptr, T.t_colptr)); TRY_RC(ac_upload(&A.d_t_pos, T.t_pos)); TRY_RC(ac_upload(&A.d_t_row, T.t_row));
+  TRY_RC(ac_upload(&A.d_t_diag, T.t_diag)); TRY_RC(ac_upload(&A.d_ut_rows, T.ut_rows)); TRY_RC(ac_upload(&A.d_ut_lev_ptr, T.ut_lev_ptr));
+  TRY_RC(ac_upload(&A.d_lt_rows, T.lt_rows)); TRY_RC(ac_upload(&A.d_lt_lev_ptr, T.lt_lev_ptr));
+  TRY_RC(ac_upload(&A.d_a_colptr, T.a_colptr)); TRY_RC(ac_upload(&A.d_a_row, T.a_row)); TRY_RC(ac_upload(&A.d_a_pos, T.a_pos));
+  A.n_ut_lev = (int)T.ut_lev_ptr.size() - 1; A.n_lt_lev = (int)T.lt_lev_ptr.size() - 1;
+  A.adj_ready = true;
+  return CADNIP_OK;
+}
+
+int ac_lu_prepare(CadnipHandle* h, bool adjoint) {
   if (!h->analyzed) return CADNIP_NOTREADY;
-  if (!h->ac.dirty) return CADNIP_OK;
+  if (!h->ac.dirty) return adjoint && !h->ac.adj_ready ? ac_adjoint_tables(h) : CADNIP_OK;
+  h->ac.adj_ready = false;                                     // tables of the previous program
   const LUProgram& P = h->lu;
   const int n_lev = (int)P.lev_ptr.size() - 1;
   // the factor level that computes each position (-1: final as loaded); a diagonal is only ever read as a pivot, by entries of later levels
@@ -231,12 +375,11 @@ int ac_lu_prepare(CadnipHandle* h) {
   TRY_RC(ac_upload(&h->ac.d_piv_rows, rows));
   TRY_RC(ac_upload(&h->ac.d_piv_lev_ptr, ptr));
   h->ac.dirty = false;
-  return CADNIP_OK;
+  return adjoint ? ac_adjoint_tables(h) : CADNIP_OK;
 }
 
-int launch_ac_lu(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin) {
-  if (p.wpb <= 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
-  ProfScope ps(h, "ac_lu");
+// the arguments both kernels share; the output pointers are the plain sweep's
+static AcArgs ac_args(CadnipHandle* h, int n_freq, long s0, int n_sys, double gmin) {
   const LUProgram& P = h->lu;
   AcArgs a;
   a.G = h->d_G; a.C = h->d_C; a.omega = h->ac.d_omega; a.bac = h->ac.d_bac; a.diag_flag = h->d_diag_flag; a.nodiag = h->ac.d_nodiag; a.gmin = gmin;
@@ -249,8 +392,32 @@ int launch_ac_lu(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sy
   a.n = h->n; a.nnz = h->nnz; a.nnz_lu = P.nnz_lu; a.n_lev = (int)P.lev_ptr.size() - 1;
   a.n_fwd_lev = (int)P.fwd_lev_ptr.size() - 1; a.n_bwd_lev = (int)P.bwd_lev_ptr.size() - 1;
   a.n_freq = n_freq; a.n_sys = n_sys; a.s0 = s0;
+  return a;
+}
+
+int launch_ac_lu(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin) {
+  if (p.wpb <= 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
+  ProfScope ps(h, "ac_lu");
+  const AcArgs a = ac_args(h, n_freq, s0, n_sys, gmin);
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
   TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, a); }));
+  HIP_TRY(hipGetLastError());
+  return CADNIP_OK;
+}
+
+int launch_ac_adjoint(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x) {
+  AcState& A = h->ac;
+  if (p.wpb <= 0 || n_sys <= 0 || n_pairs <= 0 || A.dirty || !A.adj_ready) return CADNIP_BADARG;
+  ProfScope ps(h, "ac_adj");
+  AcAdjArgs t;
+  t.a = ac_args(h, n_freq, s0, n_sys, gmin);
+  t.a.x = want_x ? A.d_adj_x : nullptr; t.a.berr = A.d_adj_berr; t.a.flags = A.d_adj_flags;
+  t.t_colptr = A.d_t_colptr; t.t_pos = A.d_t_pos; t.t_row = A.d_t_row; t.t_diag = A.d_t_diag;
+  t.ut_rows = A.d_ut_rows; t.ut_lev_ptr = A.d_ut_lev_ptr; t.lt_rows = A.d_lt_rows; t.lt_lev_ptr = A.d_lt_lev_ptr;
+  t.a_colptr = A.d_a_colptr; t.a_row = A.d_a_row; t.a_pos = A.d_a_pos;
+  t.pairs = A.d_pairs; t.h = A.d_h; t.n_ut_lev = A.n_ut_lev; t.n_lt_lev = A.n_lt_lev; t.n_pairs = n_pairs;
+  const int grid = (n_sys + p.wpb - 1) / p.wpb;
+  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "internal.hpp"
+#include "lu_transpose.hpp"
 #include "va_generated.hpp"   // CADNIP_VA_SHAPES: the generated Verilog-A modules this library was built with
 
 using namespace cadnip;
@@ -216,6 +217,7 @@ void cadnip_destroy(CadnipHandle* h) {
                   h->d_cperm, h->d_fwd_rows, h->d_fwd_lev_ptr, h->d_bwd_rows, h->d_bwd_lev_ptr,
                   h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_bac, h->ac.d_omega, h->ac.d_x, h->ac.d_berr, h->ac.d_flags};
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  h->ac.each_adjoint_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->f2.release();
   for (auto& g : h->step_graph) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (auto& b : h->blocks) {
@@ -478,9 +480,20 @@ int cadnip_analyze_values(CadnipHandle* h, const double* J_csr_host) {
   return upload_lu(h);
 }
 
-struct CadnipHostLU { cadnip::LUProgram p; };
+struct CadnipHostLU { cadnip::LUProgram p; std::vector<int> rowptr, colidx; cadnip::LUTranspose t; bool has_t = false; };
 static const std::vector<int>* host_lu_array(const CadnipHostLU* lu, int which) {
   const cadnip::LUProgram& P = lu->p;
+  if (which >= CADNIP_LUT_COLPTR) {                            // the transposed-solve tables: after cadnip_host_lu_transpose only
+    const cadnip::LUTranspose& T = lu->t;
+    if (!lu->has_t) return nullptr;
+    switch (which) {
+      case CADNIP_LUT_COLPTR: return &T.t_colptr; case CADNIP_LUT_POS: return &T.t_pos; case CADNIP_LUT_ROW: return &T.t_row;
+      case CADNIP_LUT_DIAG: return &T.t_diag; case CADNIP_LUT_UT_ROWS: return &T.ut_rows; case CADNIP_LUT_UT_LEV_PTR: return &T.ut_lev_ptr;
+      case CADNIP_LUT_LT_ROWS: return &T.lt_rows; case CADNIP_LUT_LT_LEV_PTR: return &T.lt_lev_ptr; case CADNIP_LUT_A_COLPTR: return &T.a_colptr;
+      case CADNIP_LUT_A_ROW: return &T.a_row; case CADNIP_LUT_A_POS: return &T.a_pos;
+    }
+    return nullptr;
+  }
   switch (which) {
     case CADNIP_LU_RPERM: return &P.rperm; case CADNIP_LU_CPERM: return &P.cperm; case CADNIP_LU_ROWPTR: return &P.lu_rowptr;
     case CADNIP_LU_COL: return &P.lu_col; case CADNIP_LU_DIAG: return &P.lu_diag; case CADNIP_LU_LOAD_SRC: return &P.load_src;
@@ -504,7 +517,13 @@ int cadnip_host_lu_analyze_leaves(int32_t n, const int32_t* rowptr, const int32_
   cadnip::LULeaves lv; lv.q_begin = q_begin; lv.lim_begin = lim_begin; lv.unit_ok = unit_ok; lv.first = getenv("CADNIP_LU_LEAF_FIRST") != nullptr;
   int rc = lu_analyze(n, rp, ci, v, pivot_tol, sample != 0, lu->p, err, q_begin >= 0 ? &lv : nullptr);
   if (rc) { delete lu; return rc; }
+  lu->rowptr = rp; lu->colidx = ci;
   *out = lu;
+  return CADNIP_OK;
+}
+int cadnip_host_lu_transpose(CadnipHostLU* lu) {
+  if (!lu) return CADNIP_BADARG;
+  if (!lu->has_t) { cadnip::lu_transpose_build(lu->p, lu->rowptr, lu->colidx, lu->t); lu->has_t = true; }
   return CADNIP_OK;
 }
 int32_t cadnip_host_lu_size(const CadnipHostLU* lu, int32_t which) { auto* v = lu ? host_lu_array(lu, which) : nullptr; return v ? (int32_t)v->size() : -1; }
@@ -774,6 +793,51 @@ int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega, double
     HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(berr_host + s0, A.d_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0, A.d_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  info[0] = plan.wpb; info[1] = (int)plan.shmem; info[2] = (int)S; info[3] = (int)((S / chunk) * ((chunk + plan.wpb - 1) / plan.wpb) + ((S % chunk) + plan.wpb - 1) / plan.wpb);
+  return CADNIP_OK;
+}
+
+// The adjoint sweep x[b][f] = (A[b][f])^-T c[b] with A as above, and of it the probe differences h[b][f][k] = x[p_k] - x[n_k]: S = B n_freq
+// systems through k_ac_adj (ac_lu.hip), which factors exactly as k_ac_lu does and solves through the transposed tables.  Same rules as
+// cadnip_ac_solve; a system's device output is 16 (K + n [x wanted]) bytes.  Buffers live in AcState.
+int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, const double* c_host, int32_t n_pairs, const int32_t* pairs,
+                      int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
+  if (!h || n_freq <= 0 || !omega || !c_host || n_pairs < 1 || !pairs || !h_host || !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
+  const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_pairs;
+  for (size_t k = 0; k < 2 * K; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
+  const bool want_x = x_host != nullptr;
+  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * (K + (want_x ? n : 0)))));
+  const AcPlan plan = ac_lu_plan(h, (long)std::min(S, chunk), wpb);
+  if (plan.wpb <= 0) return CADNIP_BADARG;                    // invalid wpb, or the work arrays do not fit LDS: nothing is launched
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  TRY(ac_lu_prepare(h, true));
+  AcState& A = h->ac;
+  if (!A.d_bac) TRY(dev_alloc(&A.d_bac, B * n * 2));
+  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
+  if (A.cap_pairs < K || A.cap_adj_sys < chunk) {             // d_h is [systems][pairs]: either growing reallocates it
+    const size_t ck = std::max(A.cap_pairs, K), cs = std::max(A.cap_adj_sys, chunk);
+    void* old[] = {A.d_pairs, A.d_h, A.d_adj_berr, A.d_adj_flags};
+    for (void* p : old) if (p) (void)hipFree(p);
+    A.d_pairs = nullptr; A.d_h = nullptr; A.d_adj_berr = nullptr; A.d_adj_flags = nullptr; A.cap_pairs = 0; A.cap_adj_sys = 0;
+    TRY(dev_alloc(&A.d_pairs, ck * 2)); TRY(dev_alloc(&A.d_h, cs * ck * 2)); TRY(dev_alloc(&A.d_adj_berr, cs)); TRY(dev_alloc(&A.d_adj_flags, cs));
+    A.cap_pairs = ck; A.cap_adj_sys = cs;
+  }
+  if (want_x && A.cap_adj_x < chunk) {
+    if (A.d_adj_x) { (void)hipFree(A.d_adj_x); A.d_adj_x = nullptr; }
+    A.cap_adj_x = 0; TRY(dev_alloc(&A.d_adj_x, chunk * n * 2)); A.cap_adj_x = chunk;
+  }
+  HIP_TRY(hipMemcpy(A.d_bac, c_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_pairs, pairs, K * 2 * sizeof(int), hipMemcpyHostToDevice));
+  for (size_t s0 = 0; s0 < S; s0 += chunk) {
+    const size_t ns = std::min(chunk, S - s0);
+    TRY(launch_ac_adjoint(h, plan, n_freq, (long)s0, (int)ns, gmin, n_pairs, want_x));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h_host + s0 * K * 2, A.d_h, ns * K * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_adj_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(berr_host + s0, A.d_adj_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags_host + s0, A.d_adj_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
   }
   info[0] = plan.wpb; info[1] = (int)plan.shmem; info[2] = (int)S; info[3] = (int)((S / chunk) * ((chunk + plan.wpb - 1) / plan.wpb) + ((S % chunk) + plan.wpb - 1) / plan.wpb);
   return CADNIP_OK;

@@ -136,6 +136,22 @@ struct AcState {
   double *d_bac = nullptr, *d_omega = nullptr, *d_x = nullptr, *d_berr = nullptr;
   int* d_flags = nullptr;
   size_t cap_freq = 0, cap_sys = 0;        // frequencies d_omega holds, systems the output buffers hold
+  // adjoint sweep (k_ac_adj, cadnip_ac_adjoint): the transposed-solve tables of the LU program (lu_transpose.hpp), built with the pivot
+  // lists under `dirty` but only once the adjoint path is asked for (`adj_ready`), and its own transfer buffers
+  bool adj_ready = false;
+  int *d_t_colptr = nullptr, *d_t_pos = nullptr, *d_t_row = nullptr, *d_t_diag = nullptr;
+  int *d_ut_rows = nullptr, *d_ut_lev_ptr = nullptr, *d_lt_rows = nullptr, *d_lt_lev_ptr = nullptr;
+  int *d_a_colptr = nullptr, *d_a_row = nullptr, *d_a_pos = nullptr;
+  int n_ut_lev = 0, n_lt_lev = 0;
+  int* d_pairs = nullptr;                  // [K][2] probe pairs of the call
+  double *d_h = nullptr, *d_adj_x = nullptr, *d_adj_berr = nullptr;
+  int* d_adj_flags = nullptr;
+  size_t cap_pairs = 0, cap_adj_sys = 0, cap_adj_x = 0;   // pairs d_pairs and a system of d_h hold, systems of the outputs, systems of d_adj_x
+  template <class F> void each_adjoint_buffer(F f) {
+    f((void**)&d_t_colptr); f((void**)&d_t_pos); f((void**)&d_t_row); f((void**)&d_t_diag); f((void**)&d_ut_rows); f((void**)&d_ut_lev_ptr);
+    f((void**)&d_lt_rows); f((void**)&d_lt_lev_ptr); f((void**)&d_a_colptr); f((void**)&d_a_row); f((void**)&d_a_pos); f((void**)&d_pairs);
+    f((void**)&d_h); f((void**)&d_adj_x); f((void**)&d_adj_berr); f((void**)&d_adj_flags);
+  }
 };
 
 }  // namespace cadnip
@@ -233,9 +249,13 @@ int upload_lu(CadnipHandle* h);
 // wpb 0: an invalid request, or the work arrays of wpb_req (of one, for 0) systems exceed LDS_BUDGET
 struct AcPlan { int wpb = 0; size_t shmem = 0; };
 AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req);
-int ac_lu_prepare(CadnipHandle* h);        // the pivot lists of the current LU program, on demand
+// the pivot lists of the current LU program, on demand; adjoint: the transposed-solve tables (lu_transpose.hpp) as well
+int ac_lu_prepare(CadnipHandle* h, bool adjoint = false);
 // systems [s0, s0 + n_sys) of the B x n_freq grid (s = b * n_freq + f) into h->ac.d_x / d_berr / d_flags from index 0
 int launch_ac_lu(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin);
+// ... of A^T x = c (c in h->ac.d_bac) through k_ac_adj: h[k] = x[p_k] - x[n_k] for the n_pairs pairs of h->ac.d_pairs into h->ac.d_h, berr and
+// flags into d_adj_berr / d_adj_flags, x into d_adj_x with want_x -- all from index 0
+int launch_ac_adjoint(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

@@ -21,10 +21,10 @@ STATUS_NAMES = {0: "CADNIP_OK", 1: "CADNIP_BADARG", 2: "CADNIP_SINGULAR", 3: "CA
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
-    "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free",
+    "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
     "cadnip_host_f2_build", "cadnip_host_f2_size", "cadnip_host_f2_get", "cadnip_host_f2_free", "cadnip_host_f2_team_steps", "cadnip_host_f2_steps",
 ]
 
@@ -376,6 +376,27 @@ class Handle:
                                         x.ctypes.data_as(_D), _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_solve")
         return x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
 
+    def ac_adjoint(self, omega, gmin, c, pairs, wpb=0, want_x=False):
+        """cadnip_ac_adjoint: x[b, f] solves A^T x = c[b] with A = G[b] + gmin on the node diagonals + j omega[f] C[b] as ``ac_solve`` -- same pivot
+        order, same factors, the solves run transposed (csrc/ac_lu.hip: k_ac_adj).  ``c`` [B, n] complex (or [n], broadcast), ``pairs`` [K, 2]
+        unknown indices (-1 = ground).  Returns (h complex128 [B, F, K] with h[..., k] = x[p_k] - x[n_k], x [B, F, n] or None without
+        ``want_x``, berr [B, F], flags [B, F], info) -- berr, flags and info as ``ac_solve``.  An empty grid launches nothing.  No pairs, a pair
+        index outside [-1, n), a circuit beyond LDS or an invalid ``wpb`` raise CadnipError(CADNIP_BADARG)."""
+        om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
+        pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        B, n, F, K = self.B, self.st.n, om.size, pr.shape[0]
+        if F == 0:
+            return (np.zeros((B, 0, K), dtype=complex), np.zeros((B, 0, n), dtype=complex) if want_x else None, np.zeros((B, 0)),
+                    np.zeros((B, 0), dtype=np.int32), dict(wpb=0, lds_bytes=0, systems=0, workgroups=0))
+        cc = np.ascontiguousarray(np.broadcast_to(np.asarray(c, dtype=np.complex128), (B, n)))
+        hh = np.empty((B, F, K), dtype=np.complex128)
+        x = np.empty((B, F, n), dtype=np.complex128) if want_x else None
+        berr, flags, info = np.empty((B, F)), np.zeros((B, F), dtype=np.int32), np.zeros(4, dtype=np.int32)
+        _check(self.lib.cadnip_ac_adjoint(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), cc.ctypes.data_as(_D), C.c_int32(K),
+                                          _ip(pr) if K else None, C.c_int32(int(wpb)), hh.ctypes.data_as(_D), None if x is None else x.ctypes.data_as(_D),
+                                          _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_adjoint")
+        return hh, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+
     def lu_stats(self):
         v = [C.c_int32() for _ in range(5)]
         _check(self.lib.cadnip_lu_stats(self.h, *[C.byref(x) for x in v]), "cadnip_lu_stats")
@@ -467,6 +488,9 @@ def _stats(st):
 
 LU_ARRAYS = ("rperm", "cperm", "rowptr", "col", "diag", "load_src", "load_dst", "ent_pos", "ent_diag", "ent_ptr",
              "term_a", "term_b", "lev_ptr", "fwd_rows", "fwd_lev_ptr", "bwd_rows", "bwd_lev_ptr")
+# host_lu_analyze(..., transpose=True): the transposed-solve tables (csrc/lu_transpose.hpp), CADNIP_LUT_COLPTR onwards
+LUT_ARRAYS = ("t_colptr", "t_pos", "t_row", "t_diag", "ut_rows", "ut_lev_ptr", "lt_rows", "lt_lev_ptr", "a_colptr", "a_row", "a_pos")
+LUT_FIRST = 32
 
 
 F2_ARRAYS = (("posW", np.int32), ("lanes", np.uint64), ("passes", np.uint64), ("terms", np.uint32), ("meta", np.int32))
@@ -482,16 +506,17 @@ def leaves_of(st):
     return q0, l0, ok
 
 
-def host_lu_analyze(n, rowptr, colidx, vals, pivot_tol=1e-3, sample=False, f2_nc=None, leaves=None, order=None):
+def host_lu_analyze(n, rowptr, colidx, vals, pivot_tol=1e-3, sample=False, f2_nc=None, leaves=None, order=None, transpose=False):
     """Host-only symbolic phase (no GPU needed): returns the LU program as a dict of int32 arrays.  ``leaves``: ``leaves_of(st)`` for
     the pivot order of a handle (device-local unknowns first), None for the plain Markowitz search.  ``order``: "klu" | "markowitz" forces
     the ordering (csrc/symbolic.cpp: default Markowitz up to 4 096 unknowns, KLU's block triangular form + minimum degree beyond);
-    ``out["n_blocks"]`` = diagonal blocks found (0 with the Markowitz search)."""
+    ``out["n_blocks"]`` = diagonal blocks found (0 with the Markowitz search).  ``transpose``: also the tables of the transposed solve
+    through the same factors (``LUT_ARRAYS``: the column view of L\\U, the level schedules of U^T and L^T, the column view of the pattern)."""
     if order is not None:
         prev = os.environ.get("CADNIP_LU_ORDER")
         os.environ["CADNIP_LU_ORDER"] = order
         try:
-            return host_lu_analyze(n, rowptr, colidx, vals, pivot_tol, sample, f2_nc, leaves)
+            return host_lu_analyze(n, rowptr, colidx, vals, pivot_tol, sample, f2_nc, leaves, transpose=transpose)
         finally:
             if prev is None:
                 os.environ.pop("CADNIP_LU_ORDER", None)
@@ -519,6 +544,13 @@ def host_lu_analyze(n, rowptr, colidx, vals, pivot_tol=1e-3, sample=False, f2_nc
             out[nm] = a[:sz]
         lib.cadnip_host_lu_blocks.restype = C.c_int32
         out["n_blocks"] = int(lib.cadnip_host_lu_blocks(p))
+        if transpose:
+            _check(lib.cadnip_host_lu_transpose(p), "cadnip_host_lu_transpose")
+            for k, nm in enumerate(LUT_ARRAYS):
+                sz = lib.cadnip_host_lu_size(p, C.c_int32(LUT_FIRST + k))
+                a = np.zeros(max(sz, 1), dtype=np.int32)
+                _check(lib.cadnip_host_lu_get(p, C.c_int32(LUT_FIRST + k), _ip(a)), "cadnip_host_lu_get")
+                out[nm] = a[:sz]
         if f2_nc is not None:
             ts = (C.c_int32 * 4)()
             out["team_steps"] = {}

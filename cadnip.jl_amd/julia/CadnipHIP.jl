@@ -159,6 +159,15 @@ function ac_solve(ws::GPUEvalWorkspace, omega::Vector{Float64}, b_ac::Matrix{Com
                 ws.handle, F, omega, gmin, b_ac, wpb, x, berr, flags, info), "cadnip_ac_solve")
     return x, berr, flags
 end
+# Adjoint sweep (noise!, src/noise.jl:150-188): transpose(G + gmin on the node diagonals + im omega[f] C) \ c[:, b] with the same factors, and of
+# it h[k, f, b] = x[p_k] - x[n_k] for the 0-based probe pairs pairs[:, k] = (p_k, n_k), -1 = ground.  Returns (h, berr, flags).
+function ac_adjoint(ws::GPUEvalWorkspace, omega::Vector{Float64}, c::Matrix{ComplexF64}, pairs::Matrix{Int32}; gmin=1e-12, wpb=0)
+    B, F, K = size(c, 2), length(omega), size(pairs, 2)
+    h = Array{ComplexF64}(undef, K, F, B); berr = Matrix{Float64}(undef, F, B); flags = Matrix{Int32}(undef, F, B); info = zeros(Int32, 4)
+    check(ccall((:cadnip_ac_adjoint, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Ptr{ComplexF64}, Int32, Ptr{Int32}, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                ws.handle, F, omega, gmin, c, K, pairs, wpb, h, C_NULL, berr, flags, info), "cadnip_ac_adjoint")
+    return h, berr, flags
+end
 # the handle's pivot order (0-based): pivot k uses row rperm[k], column cperm[k]
 function lu_order(ws::GPUEvalWorkspace, n::Integer)
     rperm = Vector{Int32}(undef, n); cperm = Vector{Int32}(undef, n)

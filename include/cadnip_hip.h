@@ -241,6 +241,16 @@ int cadnip_lu_order(CadnipHandle* h, int32_t* rperm, int32_t* cperm);
 int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega /* [F] */, double gmin, const double* bac_host /* [B][n][2] */,
                     int32_t wpb, double* x_host /* [B][F][n][2] */, double* berr_host /* [B][F] */, int32_t* flags_host /* [B][F] */,
                     int32_t* info /* [4] */);
+/* The adjoint sweep of noise!, src/noise.jl:150-188 (there: one dense transpose(G + jw C) \ e_out per frequency): x[b][f] solves
+ * A^T x = c[b] with the same A, pivot order and factors as cadnip_ac_solve -- the triangular solves and the residual run over columns
+ * (csrc/lu_transpose.hpp) -- with one refinement step and berr = max_j |c - A^T x|_j / (|A^T| |x| + |c|)_j.  Returned are the n_pairs probe
+ * differences h[b][f][k] = x[p_k] - x[n_k] (pairs[k] = {p_k, n_k}; -1 = ground, which contributes 0) and, with x_host non-NULL, x itself.
+ * flags, wpb, info and the chunking (here 16 (n_pairs + n [x wanted]) bytes of device output per system) as cadnip_ac_solve.
+ * CADNIP_BADARG -- and nothing launched -- also with n_pairs < 1 or a pair index outside [-1, n). */
+int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega /* [F] */, double gmin, const double* c_host /* [B][n][2] */,
+                      int32_t n_pairs, const int32_t* pairs /* [K][2], -1 = ground */, int32_t wpb, double* h_host /* [B][F][K][2] */,
+                      double* x_host /* [B][F][n][2] or NULL */, double* berr_host /* [B][F] */, int32_t* flags_host /* [B][F] */,
+                      int32_t* info /* [4] */);
 
 /* ---- host drivers (Newton loop + step controller; stand-in for IDA / _dc_pcnr_newton) ----
  * The loops run on the host and launch the kernels above on the handle's stream; the
@@ -362,6 +372,12 @@ int32_t cadnip_host_lu_size(const CadnipHostLU* lu, int32_t which);
 int32_t cadnip_host_lu_blocks(const CadnipHostLU* lu);   /* diagonal blocks of the block triangular form when KLU's ordering was used (csrc/klu_order.cpp), 0 = Markowitz search */
 int cadnip_host_lu_get(const CadnipHostLU* lu, int32_t which, int32_t* dst);
 void cadnip_host_lu_free(CadnipHostLU* lu);
+/* The tables of the TRANSPOSED solve through the same factors (csrc/lu_transpose.hpp; the adjoint kernel k_ac_adj follows them): built by
+ * this call, then read with cadnip_host_lu_size / _get under the indices below.  COLPTR / POS / ROW / DIAG: the column view of L\U;
+ * UT_* / LT_*: the level schedules of U^T z = y (forward) and L^T w = z (backward); A_*: the column view of the CSR pattern. */
+typedef enum { CADNIP_LUT_COLPTR = 32, CADNIP_LUT_POS, CADNIP_LUT_ROW, CADNIP_LUT_DIAG, CADNIP_LUT_UT_ROWS, CADNIP_LUT_UT_LEV_PTR,
+               CADNIP_LUT_LT_ROWS, CADNIP_LUT_LT_LEV_PTR, CADNIP_LUT_A_COLPTR, CADNIP_LUT_A_ROW, CADNIP_LUT_A_POS } CadnipLUTArray;
+int cadnip_host_lu_transpose(CadnipHostLU* lu);
 
 /* The fused kernel's linear-solve program for core size nc (0, 8, 12 or 16; csrc/f2_program.cpp), built from a host LU:
  * arrays POSW (int32: LU pattern position -> work-array offset), LANES / PASSES (uint64 descriptors), TERMS (uint32) and
