@@ -610,14 +610,43 @@ def ac_pivot_sample(st, G_csr, C_csr, omegas, gmin):
     return s
 
 
-def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats):
+AC_MEMORIES = ("lds", "hbm", "auto")
+
+
+def _ac_memory(memory):
+    if memory not in AC_MEMORIES:
+        raise ValueError("memory must be 'lds', 'hbm' or 'auto'")
+    return memory
+
+
+class _ac_memory_of:
+    """``with _ac_memory_of(h, memory)``: the handle's AC memory setting for one sweep.  "lds" -- the default -- makes no call of its own: the
+    sweep is call for call what it was, under the setting of a new handle; "hbm" / "auto" are set for the block and LDS restored after it."""
+
+    def __init__(self, h, memory):
+        self.h, self.memory = h, memory
+
+    def __enter__(self):
+        if self.memory != "lds":
+            self.h.ac_set_memory(self.memory)
+
+    def __exit__(self, *exc):
+        if self.memory != "lds":
+            self.h.ac_set_memory("lds")
+
+
+def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory="lds"):
     """The frequency sweep of one structure class on the GPU: ``h`` (a hip.Handle holding the restamp at the DC points) re-analyses its
     pivot order on ``ac_pivot_sample`` and solves all points x all frequencies in ONE ``ac_solve`` call; every ACSol of ``sols`` gets the
     rows of its point into its cache under the key ``tuple(omegas)``.  A system whose flag is set or whose backward error exceeds
     AC_BERR_MAX is solved again by the host's dense solve, which replaces the GPU row.  ``stats`` (shared by the call) is updated:
     gpu_systems / host_systems, max_berr over the accepted GPU rows, wpb.  A circuit that does not fit the launch plan raises with
-    solver="gpu"; with "auto" nothing is cached -- the sols solve on the host on demand -- and stats["fallback"] says why."""
+    solver="gpu"; with "auto" nothing is cached -- the sols solve on the host on demand -- and stats["fallback"] says why.
+    ``memory``: where the kernel keeps a system's work arrays (hip.Handle.ac_set_memory) -- "lds" (the default; DESIGN section 9 has
+    the figures and leaves another default to a later change): circuits beyond the LDS budget are refused as above; "hbm": a workspace in device memory, so
+    such a circuit is solved on the GPU; "auto": LDS where the circuit fits, else HBM.  stats["memory"] is what the launch used."""
     from . import hip
+    _ac_memory(memory)
     omegas = np.asarray(omegas, dtype=float)
     B, F = len(sols), omegas.size
     key = tuple(omegas)
@@ -630,7 +659,9 @@ def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats):
     sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
     h.analyze_values(sample_ref)
     try:
-        x, berr, flags, info = h.ac_solve(omegas, gmin, np.array([s.b_ac for s in sols]))
+        with _ac_memory_of(h, memory):
+            x, berr, flags, info = h.ac_solve(omegas, gmin, np.array([s.b_ac for s in sols]))
+            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
     except hip.CadnipError as e:
         if solver == "auto" and e.code == hip.BADARG:
             stats["host_systems"] += B * F
@@ -648,9 +679,10 @@ def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats):
     stats["host_systems"] += int(redo.sum())
     stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
     stats["wpb"] = info["wpb"]
+    stats["memory"] = used
 
 
-def ac(target, freqs=(), gmin=1e-12, device=0, solver="host"):
+def ac(target, freqs=(), gmin=1e-12, device=0, solver="host", memory="lds"):
     """ac!(circuit, freqs; gmin) -- src/ac.jl:113-170.  The DC operating point and the restamp at it run on the GPU (cadnip_dc_run,
     cadnip_rebuild: the linearisation IS the stamping); G gets ``gmin`` on the voltage-node diagonals (assemble_G(ctx; gshunt=gmin),
     ac.jl:127).  The frequency sweep is the reference's own dense ``(jw C + G)^-1 b_ac`` on the host: n is a circuit's size, not a
@@ -658,11 +690,15 @@ def ac(target, freqs=(), gmin=1e-12, device=0, solver="host"):
     ``solver``: "host" (default) as above; "gpu" solves the grid of every point on the device as well -- points x frequencies complex
     sparse systems in one batched kernel per structure class (``ac_gpu_sweep``) -- and fills the ACSols' caches for the grid, so ``sol[name]``,
     ``magnitude_db`` and ``phase_deg`` read GPU results while ``freqresp`` at other frequencies still solves on the host; ``sol.stats`` =
-    {"gpu_systems", "host_systems", "max_berr", "wpb"} of the call.  "gpu" raises for a circuit too large for the kernel, "auto" takes the
-    host path for it and says so in ``stats``."""
+    {"gpu_systems", "host_systems", "max_berr", "wpb", "memory"} of the call.  "gpu" raises for a circuit too large for the kernel, "auto"
+    takes the host path for it and says so in ``stats``.
+    ``memory`` (ignored with solver="host"): "lds" (default) keeps a system's work arrays in LDS -- "too large" is then 160 KB; "hbm" keeps
+    them in device memory and "auto" does so where LDS refuses, so such a circuit is solved on the GPU (``ac_gpu_sweep``).  The default
+    stays "lds": DESIGN section 9 has the measured figures and leaves making "auto" the default to a later change."""
     import scipy.sparse as sp
     if solver not in ("host", "gpu", "auto"):
         raise ValueError("solver must be 'host', 'gpu' or 'auto'")
+    _ac_memory(memory)
     stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
     sweep = isinstance(target, CircuitSweep)
     mc0 = target.circuit if sweep else target
@@ -685,7 +721,7 @@ def ac(target, freqs=(), gmin=1e-12, device=0, solver="host"):
                 p_i = {kk: float(v[k]) for kk, v in sim.params.items()}
                 sols[i] = ACSol(st, Gd, Cd, rhs_ac(st, mc.circuit, p_i), u[k].copy(), freqs)
             if solver != "host":
-                ac_gpu_sweep(sim.h, st, [sols[i] for i in idx], G, C, 2.0 * np.pi * np.asarray(freqs, dtype=float), gmin, solver, stats)
+                ac_gpu_sweep(sim.h, st, [sols[i] for i in idx], G, C, 2.0 * np.pi * np.asarray(freqs, dtype=float), gmin, solver, stats, memory)
         finally:
             sim.close()
     if solver != "host":
@@ -888,15 +924,19 @@ def noise_probe_pairs(source_lists, in_idx=None):
     return np.array(list(index), dtype=np.int32).reshape(-1, 2), index
 
 
-def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, input=None, temps=27.0, gmin=1e-12, solver="gpu", stats=None):
+def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, input=None, temps=27.0, gmin=1e-12, solver="gpu", stats=None,
+                    memory="lds"):
     """The adjoint sweep of one structure class on the GPU, reachable without ``noise_sources``: ``h`` (a hip.Handle holding the restamp at the
     DC points; ``G_ref`` / ``C_ref`` [B, nnz] are its get_GCb) re-analyses its pivot order on ``ac_pivot_sample`` and solves all points x all
     frequencies in ONE ``ac_adjoint`` call for the class's probe pairs; ``Gd`` / ``Cd`` (dense, gmin on the node diagonals) and
     ``source_lists`` are per point.  A system whose flag is set or whose backward error exceeds NOISE_BERR_MAX is solved again by the host's
     dense adjoint solve.  The PSD weighting and the sums are ``noise_solve``'s.  Returns one NoiseSol per point; ``stats`` (shared by the call)
     is updated as by ``ac_gpu_sweep``.  A circuit that does not fit the launch plan raises with solver="gpu"; with "auto" the points are
-    solved on the host and stats["fallback"] says why."""
+    solved on the host and stats["fallback"] says why.  ``memory``: "lds" (the default; DESIGN section 9 has the figures and leaves
+    another default to a later change), "hbm" or "auto", as for ``ac_gpu_sweep``: with the latter two a circuit beyond the LDS budget is solved on the GPU;
+    stats["memory"] is what the launch used."""
     from . import hip
+    _ac_memory(memory)
     freqs = np.asarray(freqs, dtype=float)
     if freqs.size == 0:
         raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
@@ -919,7 +959,9 @@ def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, in
         e_out = np.zeros(st.n, dtype=complex)
         e_out[out_idx] = 1.0
         try:
-            H, _, berr, flags, info = h.ac_adjoint(omegas, gmin, e_out, pairs)
+            with _ac_memory_of(h, memory):
+                H, _, berr, flags, info = h.ac_adjoint(omegas, gmin, e_out, pairs)
+                used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
         except hip.CadnipError as e:
             if solver == "auto" and e.code == hip.BADARG:
                 stats["host_systems"] += B * F
@@ -941,22 +983,27 @@ def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, in
         stats["host_systems"] += int(redo.sum())
         stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
         stats["wpb"] = info["wpb"]
+        stats["memory"] = used
     for s in sols:
         s.stats = stats
     return sols
 
 
-def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"):
+def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host", memory="lds"):
     """noise!(circuit, output; freqs, input, gmin) -- src/noise.jl:118-190.  As for ``ac``: the DC operating point and the restamp at it run on the
     GPU; the sources are collected on the host at that point (noise_sources) and the adjoint sweep is the reference's own dense solve.
     A CircuitSweep returns one NoiseSol per point (one resident batch per structure class).
     ``solver``: "host" (default) as above; "gpu" solves the adjoint systems of every point on the device as well -- points x frequencies
     transposed complex sparse systems in one batched kernel per structure class (``noise_solve_gpu``), for the probe pairs the class's
     sources need -- while the PSD weighting stays in numpy; ``ns.stats`` = {"gpu_systems", "host_systems", "max_berr", "wpb"} of the call.
-    "gpu" raises for a circuit too large for the kernel, "auto" takes the host path for it and says so in ``stats["fallback"]``."""
+    "gpu" raises for a circuit too large for the kernel, "auto" takes the host path for it and says so in ``stats["fallback"]``.
+    ``memory`` (ignored with solver="host"): "lds" (default), "hbm" or "auto" as for ``ac`` -- with "hbm" / "auto" a circuit beyond the
+    160 KB of LDS is solved on the GPU; ``stats["memory"]`` says which ran.  The default stays "lds": DESIGN section 9 has the measured
+    figures and leaves making "auto" the default to a later change."""
     import scipy.sparse as sp
     if solver not in ("host", "gpu", "auto"):
         raise ValueError("solver must be 'host', 'gpu' or 'auto'")
+    _ac_memory(memory)
     if len(freqs) == 0:
         raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
     sweep = isinstance(target, CircuitSweep)
@@ -985,7 +1032,7 @@ def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"
             if solver == "host":
                 got = [noise_solve(st, Gd[k], Cd[k], srcs[k], output, freqs, input, temps[k]) for k in range(len(idx))]
             else:
-                got = noise_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, output, freqs, input, temps, gmin, solver, stats)
+                got = noise_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, output, freqs, input, temps, gmin, solver, stats, memory)
             for k, i in enumerate(idx):
                 sols[i] = got[k]
         finally:

@@ -15,6 +15,8 @@
 //   5. recomputes r and the componentwise backward error max_i |r_i| / (|A| |x| + |b|)_i, 0 / 0 = 0 (tests/lu_ref.py with complex moduli),
 //   6. stores x (interleaved re, im), berr and the flag (bit 0: zero / non-finite pivot or non-finite solution -- a flag, never a trap).
 // Every multiply-add is an explicit fma: the W instantiations compute the same doubles.
+// k_ac_lu_hbm / k_ac_adj_hbm (cadnip_ac_set_memory) run the same steps -- the same __device__ functions -- with the work arrays in a per-wave
+// workspace in global memory, for circuits beyond the LDS budget: persistent waves, planned by ac_hbm_plan.hpp.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -24,6 +26,7 @@
 #include "tran_ctrl.hpp"
 #include "lds_layout.hpp"
 #include "lu_transpose.hpp"
+#include "ac_hbm_plan.hpp"
 
 namespace cadnip {
 
@@ -57,15 +60,35 @@ __device__ __forceinline__ double2 ac_entry(const AcArgs& a, const double* G, co
   return make_double2(G[e] + (a.diag_flag[e] ? a.gmin : 0.0), om * C[e]);
 }
 
-// Steps 1 and 2 of both kernels -- load A into lu, factor in place -- so that k_ac_lu and k_ac_adj hold the same doubles by construction.
+// How the lanes of a wave order their accesses to the work arrays between two steps: a level's lanes read words that OTHER lanes of the wave
+// stored in an earlier level.  The steps below are generic in it, so the LDS and the HBM kernels run the same statements on the same doubles.
+struct AcInLds {                                               // work arrays in LDS: the wave-scope fence of every LDS-resident kernel
+  static __device__ __forceinline__ void sync() { CADNIP_WAVE_SYNC(); }
+};
+// Work arrays in global memory: the fence the fused kernel uses for words "read back by other lanes of this wave" (fused2_kernel.hpp:
+// history_to_memory), then the wave barrier.  Why workgroup scope suffices on gfx950, from the memory model (LLVM AMDGPU: scopes are
+// inclusive, gfx942 code sequences): a wave's workspace is written and read by the lanes of that ONE wave and by nobody else -- no other
+// wave, no other workgroup, not the host (which reads x / berr / flags after the kernel's end, a system-scope release of its own).  Writer
+// and reader therefore always sit in the same workgroup, the smallest named scope that is guaranteed to contain both, and a release-acquire
+// fence at that scope orders the accesses of any two threads inside it.  What it costs: the release half waits for the wave's outstanding
+// stores (vmcnt(0)) -- they have gone through the compute unit's write-through vector L1 -- before a later load issues; the acquire half
+// needs no cache invalidate, because the waves of a workgroup (we never build threadgroup-split code) share that one L1, and a wave
+// trivially shares it with itself.  A wider scope would add L1 invalidates / L2 write-backs for readers that do not exist.  For the
+// compiler the fence pins every global access to its side and forbids keeping a loaded word in a register across it.
+struct AcInHbm {
+  static __device__ __forceinline__ void sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
+};
+
+// Steps 1 and 2 of every kernel -- load A into lu, factor in place -- so that k_ac_lu and k_ac_adj hold the same doubles by construction.
 // Returns 1 in the lanes that met a zero / non-finite pivot.
+template <class M>
 __device__ __forceinline__ int ac_load_factor(const AcArgs& a, double2* lu, const double* G, const double* C, double om, int lane) {
   int bad = 0;
   // ---- 1. load
   for (int p = lane; p < a.nnz_lu; p += 64) lu[p] = make_double2(0.0, 0.0);
-  CADNIP_WAVE_SYNC();
+  M::sync();
   for (int e = lane; e < a.nnz; e += 64) lu[a.load_dst[e]] = ac_entry(a, G, C, om, e);
-  CADNIP_WAVE_SYNC();
+  M::sync();
   // ---- 2. factor; the pivots of list l are final before level l runs (list 0: after the load)
   auto pivots = [&](int l) {
     const int k1 = a.piv_lev_ptr[l + 1];
@@ -76,7 +99,7 @@ __device__ __forceinline__ int ac_load_factor(const AcArgs& a, double2* lu, cons
       if ((pv.x == 0.0 && pv.y == 0.0) || !isfinite(pv.x) || !isfinite(pv.y)) bad = 1;
       lu[dp] = crecip(pv);
     }
-    CADNIP_WAVE_SYNC();
+    M::sync();
   };
   pivots(0);
   for (int lev = 0; lev < a.n_lev; ++lev) {
@@ -88,102 +111,139 @@ __device__ __forceinline__ int ac_load_factor(const AcArgs& a, double2* lu, cons
       if (dg >= 0) acc = cmul(acc, lu[dg]);
       lu[pos] = acc;
     }
-    CADNIP_WAVE_SYNC();
+    M::sync();
     pivots(lev + 1);
   }
   return bad;
 }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu(AcArgs a) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = a.n;
-  const int ls = blockIdx.x * W + w;                           // system of this wave inside the launch
-  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
-  const LdsAc<double*> L = lds_ac((double*)sm, a.nnz_lu, n, w, W);
-  double2 *lu = (double2*)L.lu, *x = (double2*)L.x, *r = (double2*)L.r, *y = (double2*)L.y;
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
-  const double om = a.omega[fi], gmin = a.gmin;
-  auto entry = [&](int e) { return ac_entry(a, G, C, om, e); };   // A at CSR position e
-  int bad = ac_load_factor(a, lu, G, C, om, lane);
-  // ---- 3. / 4. y := A^-1 y through the factors (y in pivot-row order on entry, pivot-column order on return)
-  auto solve = [&]() {
-    for (int lev = 0; lev < a.n_fwd_lev; ++lev) {
-      const int r1 = a.fwd_lev_ptr[lev + 1];
-      for (int q = a.fwd_lev_ptr[lev] + lane; q < r1; q += 64) {
-        const int i = a.fwd_rows[q], p1 = a.lu_diag[i];
-        double2 acc = y[i];
-        for (int p = a.lu_rowptr[i]; p < p1; ++p) acc = cmsub(acc, lu[p], y[a.lu_col[p]]);
-        y[i] = acc;
-      }
-      CADNIP_WAVE_SYNC();
+// the work arrays of one system (lds_layout.hpp: lds_ac), in LDS or in the wave's workspace in global memory
+struct AcWork { double2 *lu, *x, *r, *y; };
+__device__ __forceinline__ AcWork ac_work(const LdsAc<double*>& L) { return AcWork{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y}; }
+
+// ---- 3. / 4. y := A^-1 y through the factors (y in pivot-row order on entry, pivot-column order on return)
+template <class M>
+__device__ __forceinline__ void ac_solve(const AcArgs& a, const double2* lu, double2* y, int lane) {
+  for (int lev = 0; lev < a.n_fwd_lev; ++lev) {
+    const int r1 = a.fwd_lev_ptr[lev + 1];
+    for (int q = a.fwd_lev_ptr[lev] + lane; q < r1; q += 64) {
+      const int i = a.fwd_rows[q], p1 = a.lu_diag[i];
+      double2 acc = y[i];
+      for (int p = a.lu_rowptr[i]; p < p1; ++p) acc = cmsub(acc, lu[p], y[a.lu_col[p]]);
+      y[i] = acc;
     }
-    for (int lev = 0; lev < a.n_bwd_lev; ++lev) {
-      const int r1 = a.bwd_lev_ptr[lev + 1];
-      for (int q = a.bwd_lev_ptr[lev] + lane; q < r1; q += 64) {
-        const int i = a.bwd_rows[q], dp = a.lu_diag[i], p1 = a.lu_rowptr[i + 1];
-        double2 acc = y[i];
-        for (int p = dp + 1; p < p1; ++p) acc = cmsub(acc, lu[p], y[a.lu_col[p]]);
-        y[i] = cmul(acc, lu[dp]);                               // the diagonal word holds 1 / pivot
-      }
-      CADNIP_WAVE_SYNC();
+    M::sync();
+  }
+  for (int lev = 0; lev < a.n_bwd_lev; ++lev) {
+    const int r1 = a.bwd_lev_ptr[lev + 1];
+    for (int q = a.bwd_lev_ptr[lev] + lane; q < r1; q += 64) {
+      const int i = a.bwd_rows[q], dp = a.lu_diag[i], p1 = a.lu_rowptr[i + 1];
+      double2 acc = y[i];
+      for (int p = dp + 1; p < p1; ++p) acc = cmsub(acc, lu[p], y[a.lu_col[p]]);
+      y[i] = cmul(acc, lu[dp]);                               // the diagonal word holds 1 / pivot
     }
-  };
-  // r = b - A x, one row per lane; with DEN the backward error of the wave's rows is returned
-  auto residual = [&](auto den_tag) -> double {
-    constexpr bool DEN = decltype(den_tag)::value;
-    double worst = 0.0;
-    for (int i = lane; i < n; i += 64) {
-      const double2 bi = bac[i];
-      double2 acc = bi;
-      double den = DEN ? cabs2(bi) : 0.0;
-      const int p1 = a.rowptr[i + 1];
-      for (int p = a.rowptr[i]; p < p1; ++p) {
-        const double2 av = entry(p), xv = x[a.colidx[p]];
-        acc = cmsub(acc, av, xv);
-        if (DEN) den = fma(cabs2(av), cabs2(xv), den);
-      }
-      if (a.nodiag[i]) {                                        // gmin of a node diagonal outside the pattern
-        const double2 xv = x[i];
-        acc = cmsub(acc, make_double2(gmin, 0.0), xv);
-        if (DEN) den = fma(gmin, cabs2(xv), den);
-      }
-      r[i] = acc;
-      if (DEN) {
-        const double num = cabs2(acc);
-        const double q = num == 0.0 ? 0.0 : num / den;
-        worst = (q > worst || q != q) ? q : worst;              // a NaN stays
-      }
+    M::sync();
+  }
+}
+
+// r = b - A x, one row per lane; with DEN the backward error of the wave's rows is returned
+template <class M, bool DEN>
+__device__ __forceinline__ double ac_residual(const AcArgs& a, const double* G, const double* C, double om, const double2* bac, const double2* x,
+                                              double2* r, int lane) {
+  const double gmin = a.gmin;
+  double worst = 0.0;
+  for (int i = lane; i < a.n; i += 64) {
+    const double2 bi = bac[i];
+    double2 acc = bi;
+    double den = DEN ? cabs2(bi) : 0.0;
+    const int p1 = a.rowptr[i + 1];
+    for (int p = a.rowptr[i]; p < p1; ++p) {
+      const double2 av = ac_entry(a, G, C, om, p), xv = x[a.colidx[p]];
+      acc = cmsub(acc, av, xv);
+      if (DEN) den = fma(cabs2(av), cabs2(xv), den);
     }
-    CADNIP_WAVE_SYNC();
-    return worst;
-  };
-  for (int i = lane; i < n; i += 64) y[i] = bac[a.rperm[i]];
-  CADNIP_WAVE_SYNC();
-  solve();
-  for (int i = lane; i < n; i += 64) x[a.cperm[i]] = y[i];
-  CADNIP_WAVE_SYNC();
-  (void)residual(std::false_type());
-  for (int i = lane; i < n; i += 64) y[i] = r[a.rperm[i]];
-  CADNIP_WAVE_SYNC();
-  solve();
-  for (int i = lane; i < n; i += 64) { const int j = a.cperm[i]; const double2 xv = x[j], dv = y[i]; x[j] = make_double2(xv.x + dv.x, xv.y + dv.y); }
-  CADNIP_WAVE_SYNC();
-  // ---- 5. backward error
-  double worst = residual(std::true_type());
+    if (a.nodiag[i]) {                                        // gmin of a node diagonal outside the pattern
+      const double2 xv = x[i];
+      acc = cmsub(acc, make_double2(gmin, 0.0), xv);
+      if (DEN) den = fma(gmin, cabs2(xv), den);
+    }
+    r[i] = acc;
+    if (DEN) {
+      const double num = cabs2(acc);
+      const double q = num == 0.0 ? 0.0 : num / den;
+      worst = (q > worst || q != q) ? q : worst;              // a NaN stays
+    }
+  }
+  M::sync();
+  return worst;
+}
+
+// the backward error of the wave from its lanes' figures, and the system's two status words: berr (a NaN stays a NaN) and the flag
+__device__ __forceinline__ void ac_store_status(const AcArgs& a, int ls, double worst, int bad, int lane) {
   int nan = worst != worst;
   if (nan) worst = 0.0;
   for (int off = 32; off >= 1; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
   nan = wave_any(nan);
+  bad = wave_any(bad);
+  if (lane == 0) { a.berr[ls] = nan ? __builtin_nan("") : worst; a.flags[ls] = bad ? 1 : 0; }
+}
+
+// Steps 1 to 6 for system ls of the launch, by one wave, in the work arrays wk.  Everything a system leaves behind is in wk, and every word of
+// wk is written before it is read: lu by step 1, y / x / r by the full-length loops below -- a wave may run system after system in one wk
+template <class M>
+__device__ __forceinline__ void ac_lu_system(const AcArgs& a, int ls, const AcWork& wk, int lane) {
+  const int n = a.n;
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
+  const double om = a.omega[fi];
+  int bad = ac_load_factor<M>(a, lu, G, C, om, lane);
+  for (int i = lane; i < n; i += 64) y[i] = bac[a.rperm[i]];
+  M::sync();
+  ac_solve<M>(a, lu, y, lane);
+  for (int i = lane; i < n; i += 64) x[a.cperm[i]] = y[i];
+  M::sync();
+  (void)ac_residual<M, false>(a, G, C, om, bac, x, r, lane);
+  for (int i = lane; i < n; i += 64) y[i] = r[a.rperm[i]];
+  M::sync();
+  ac_solve<M>(a, lu, y, lane);
+  for (int i = lane; i < n; i += 64) { const int j = a.cperm[i]; const double2 xv = x[j], dv = y[i]; x[j] = make_double2(xv.x + dv.x, xv.y + dv.y); }
+  M::sync();
+  // ---- 5. backward error
+  const double worst = ac_residual<M, true>(a, G, C, om, bac, x, r, lane);
   // ---- 6. store
   double2* xo = (double2*)a.x + (size_t)ls * n;
   for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; xo[i] = v; }
-  bad = wave_any(bad);
-  if (lane == 0) { a.berr[ls] = nan ? __builtin_nan("") : worst; a.flags[ls] = bad ? 1 : 0; }
+  ac_store_status(a, ls, worst, bad, lane);
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu(AcArgs a) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;                           // system of this wave inside the launch
+  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
+  ac_lu_system<AcInLds>(a, ls, ac_work(lds_ac((double*)sm, a.nnz_lu, a.n, w, W)), lane);
+}
+
+// The HBM-resident variants: the same steps with the work arrays in the wave's workspace in global memory (ac_hbm_plan.hpp).  Persistent
+// waves: wave g of n_waves handles systems g, g + n_waves, ... of the launch in its one workspace -- region g of lds_ac's layout over
+// `work`, contiguous per wave, so a level's lanes touch neighbouring words.  The loop bound is the only tail handling: a wave beyond
+// n_waves (the last workgroup when wpb does not divide n_waves) has no workspace and no system.  No workgroup barrier.
+struct AcHbmArgs { double* work; int n_waves; };
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu_hbm(AcArgs a, AcHbmArgs m) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? a.n_sys : 0;
+  const AcWork wk = ac_work(lds_ac(m.work, a.nnz_lu, a.n, g, m.n_waves));     // size_t offsets (lds_layout.hpp)
+  for (int ls = g; ls < end; ls += m.n_waves) {
+    ac_lu_system<AcInHbm>(a, ls, wk, lane);
+    AcInHbm::sync();                                           // the last reads of x before the next system's words
+  }
 }
 
 // ---- the adjoint kernel: A^T x = c with the same factors (noise.jl:150-188: one adjoint solve per frequency serves every noise source) --------
@@ -204,91 +264,90 @@ struct AcAdjArgs {
   int n_ut_lev, n_lt_lev, n_pairs;
 };
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj(AcAdjArgs t) {
-  extern __shared__ double sm[];
+// ---- 3. / 4. y := M^-T y (y in pivot-column order on entry, pivot-row order on return)
+template <class M>
+__device__ __forceinline__ void ac_adj_solve(const AcAdjArgs& t, const double2* lu, double2* y, int lane) {
+  for (int lev = 0; lev < t.n_ut_lev; ++lev) {
+    const int r1 = t.ut_lev_ptr[lev + 1];
+    for (int q = t.ut_lev_ptr[lev] + lane; q < r1; q += 64) {
+      const int j = t.ut_rows[q], p0 = t.t_colptr[j], pd = p0 + t.t_diag[j];
+      double2 acc = y[j];
+      for (int p = p0; p < pd; ++p) acc = cmsub(acc, lu[t.t_pos[p]], y[t.t_row[p]]);
+      y[j] = cmul(acc, lu[t.t_pos[pd]]);                      // the diagonal word holds 1 / pivot
+    }
+    M::sync();
+  }
+  for (int lev = 0; lev < t.n_lt_lev; ++lev) {
+    const int r1 = t.lt_lev_ptr[lev + 1];
+    for (int q = t.lt_lev_ptr[lev] + lane; q < r1; q += 64) {
+      const int j = t.lt_rows[q], p1 = t.t_colptr[j + 1];
+      double2 acc = y[j];
+      for (int p = t.t_colptr[j] + t.t_diag[j] + 1; p < p1; ++p) acc = cmsub(acc, lu[t.t_pos[p]], y[t.t_row[p]]);
+      y[j] = acc;
+    }
+    M::sync();
+  }
+}
+
+// r = c - A^T x, one column of A per lane; with DEN the backward error of the wave's columns is returned
+template <class M, bool DEN>
+__device__ __forceinline__ double ac_adj_residual(const AcAdjArgs& t, const double* G, const double* C, double om, const double2* c, const double2* x,
+                                                  double2* r, int lane) {
   const AcArgs& a = t.a;
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = a.n;
-  const int ls = blockIdx.x * W + w;
-  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
+  const double gmin = a.gmin;
+  double worst = 0.0;
+  for (int j = lane; j < a.n; j += 64) {
+    const double2 cj = c[j];
+    double2 acc = cj;
+    double den = DEN ? cabs2(cj) : 0.0;
+    const int p1 = t.a_colptr[j + 1];
+    for (int p = t.a_colptr[j]; p < p1; ++p) {
+      const double2 av = ac_entry(a, G, C, om, t.a_pos[p]), xv = x[t.a_row[p]];
+      acc = cmsub(acc, av, xv);
+      if (DEN) den = fma(cabs2(av), cabs2(xv), den);
+    }
+    if (a.nodiag[j]) {                                        // gmin of a node diagonal outside the pattern
+      const double2 xv = x[j];
+      acc = cmsub(acc, make_double2(gmin, 0.0), xv);
+      if (DEN) den = fma(gmin, cabs2(xv), den);
+    }
+    r[j] = acc;
+    if (DEN) {
+      const double num = cabs2(acc);
+      const double q = num == 0.0 ? 0.0 : num / den;
+      worst = (q > worst || q != q) ? q : worst;              // a NaN stays
+    }
+  }
+  M::sync();
+  return worst;
+}
+
+// Steps 1 to 6 of the adjoint system ls of the launch; what ac_lu_system says about wk holds here word for word
+template <class M>
+__device__ __forceinline__ void ac_adj_system(const AcAdjArgs& t, int ls, const AcWork& wk, int lane) {
+  const AcArgs& a = t.a;
+  const int n = a.n;
   const long s = a.s0 + ls;
   const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
-  const LdsAc<double*> L = lds_ac((double*)sm, a.nnz_lu, n, w, W);
-  double2 *lu = (double2*)L.lu, *x = (double2*)L.x, *r = (double2*)L.r, *y = (double2*)L.y;
+  double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
   const double* G = a.G + (size_t)inst * a.nnz;
   const double* C = a.C + (size_t)inst * a.nnz;
   const double2* c = (const double2*)a.bac + (size_t)inst * n;
-  const double om = a.omega[fi], gmin = a.gmin;
-  int bad = ac_load_factor(a, lu, G, C, om, lane);
-  // ---- 3. / 4. y := M^-T y (y in pivot-column order on entry, pivot-row order on return)
-  auto solve = [&]() {
-    for (int lev = 0; lev < t.n_ut_lev; ++lev) {
-      const int r1 = t.ut_lev_ptr[lev + 1];
-      for (int q = t.ut_lev_ptr[lev] + lane; q < r1; q += 64) {
-        const int j = t.ut_rows[q], p0 = t.t_colptr[j], pd = p0 + t.t_diag[j];
-        double2 acc = y[j];
-        for (int p = p0; p < pd; ++p) acc = cmsub(acc, lu[t.t_pos[p]], y[t.t_row[p]]);
-        y[j] = cmul(acc, lu[t.t_pos[pd]]);                      // the diagonal word holds 1 / pivot
-      }
-      CADNIP_WAVE_SYNC();
-    }
-    for (int lev = 0; lev < t.n_lt_lev; ++lev) {
-      const int r1 = t.lt_lev_ptr[lev + 1];
-      for (int q = t.lt_lev_ptr[lev] + lane; q < r1; q += 64) {
-        const int j = t.lt_rows[q], p1 = t.t_colptr[j + 1];
-        double2 acc = y[j];
-        for (int p = t.t_colptr[j] + t.t_diag[j] + 1; p < p1; ++p) acc = cmsub(acc, lu[t.t_pos[p]], y[t.t_row[p]]);
-        y[j] = acc;
-      }
-      CADNIP_WAVE_SYNC();
-    }
-  };
-  // r = c - A^T x, one column of A per lane; with DEN the backward error of the wave's columns is returned
-  auto residual = [&](auto den_tag) -> double {
-    constexpr bool DEN = decltype(den_tag)::value;
-    double worst = 0.0;
-    for (int j = lane; j < n; j += 64) {
-      const double2 cj = c[j];
-      double2 acc = cj;
-      double den = DEN ? cabs2(cj) : 0.0;
-      const int p1 = t.a_colptr[j + 1];
-      for (int p = t.a_colptr[j]; p < p1; ++p) {
-        const double2 av = ac_entry(a, G, C, om, t.a_pos[p]), xv = x[t.a_row[p]];
-        acc = cmsub(acc, av, xv);
-        if (DEN) den = fma(cabs2(av), cabs2(xv), den);
-      }
-      if (a.nodiag[j]) {                                        // gmin of a node diagonal outside the pattern
-        const double2 xv = x[j];
-        acc = cmsub(acc, make_double2(gmin, 0.0), xv);
-        if (DEN) den = fma(gmin, cabs2(xv), den);
-      }
-      r[j] = acc;
-      if (DEN) {
-        const double num = cabs2(acc);
-        const double q = num == 0.0 ? 0.0 : num / den;
-        worst = (q > worst || q != q) ? q : worst;              // a NaN stays
-      }
-    }
-    CADNIP_WAVE_SYNC();
-    return worst;
-  };
+  const double om = a.omega[fi];
+  int bad = ac_load_factor<M>(a, lu, G, C, om, lane);
   for (int j = lane; j < n; j += 64) y[j] = c[a.cperm[j]];
-  CADNIP_WAVE_SYNC();
-  solve();
+  M::sync();
+  ac_adj_solve<M>(t, lu, y, lane);
   for (int i = lane; i < n; i += 64) x[a.rperm[i]] = y[i];
-  CADNIP_WAVE_SYNC();
-  (void)residual(std::false_type());
+  M::sync();
+  (void)ac_adj_residual<M, false>(t, G, C, om, c, x, r, lane);
   for (int j = lane; j < n; j += 64) y[j] = r[a.cperm[j]];
-  CADNIP_WAVE_SYNC();
-  solve();
+  M::sync();
+  ac_adj_solve<M>(t, lu, y, lane);
   for (int i = lane; i < n; i += 64) { const int k = a.rperm[i]; const double2 xv = x[k], dv = y[i]; x[k] = make_double2(xv.x + dv.x, xv.y + dv.y); }
-  CADNIP_WAVE_SYNC();
+  M::sync();
   // ---- 5. backward error
-  double worst = residual(std::true_type());
-  int nan = worst != worst;
-  if (nan) worst = 0.0;
-  for (int off = 32; off >= 1; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
-  nan = wave_any(nan);
+  const double worst = ac_adj_residual<M, true>(t, G, C, om, c, x, r, lane);
   // ---- 6. store
   double2* xo = a.x ? (double2*)a.x + (size_t)ls * n : nullptr;
   for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
@@ -298,8 +357,27 @@ __global__ void __launch_bounds__(64 * W) k_ac_adj(AcAdjArgs t) {
     const double2 xp = p >= 0 ? x[p] : make_double2(0.0, 0.0), xn = q >= 0 ? x[q] : make_double2(0.0, 0.0);
     ho[k] = make_double2(xp.x - xn.x, xp.y - xn.y);
   }
-  bad = wave_any(bad);
-  if (lane == 0) { a.berr[ls] = nan ? __builtin_nan("") : worst; a.flags[ls] = bad ? 1 : 0; }
+  ac_store_status(a, ls, worst, bad, lane);
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj(AcAdjArgs t) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= t.a.n_sys) return;                                 // the tail workgroup: no workgroup barrier anywhere below
+  ac_adj_system<AcInLds>(t, ls, ac_work(lds_ac((double*)sm, t.a.nnz_lu, t.a.n, w, W)), lane);
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj_hbm(AcAdjArgs t, AcHbmArgs m) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
+  const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
+  for (int ls = g; ls < end; ls += m.n_waves) {
+    ac_adj_system<AcInHbm>(t, ls, wk, lane);
+    AcInHbm::sync();
+  }
 }
 
 // The launch plan -- the one place that sizes the LDS block and picks W, and the only reader of CADNIP_AC_WPB.  A compute unit holds
@@ -325,6 +403,38 @@ AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req) {
   while (best > 1 && n_sys < 128L * best) best >>= 1;
   AcPlan p; p.wpb = best; p.shmem = bytes(best);
   return p;
+}
+
+// Where the work arrays of a call live (cadnip_ac_set_memory) and the plan of that home: LDS -- ac_lu_plan alone, as ever; HBM -- the plan of
+// ac_hbm_plan.hpp on this device's compute units; AUTO -- LDS when ac_lu_plan accepts the circuit, else HBM.  memory < 0: refused
+AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req) {
+  AcLaunch L;
+  AcState& A = h->ac;
+  if (!h->analyzed || n_sys <= 0) return L;
+  if (A.memory != CADNIP_AC_HBM) {
+    L.lds = ac_lu_plan(h, n_sys, wpb_req);
+    if (L.lds.wpb > 0) { L.memory = CADNIP_AC_LDS; return L; }
+    if (A.memory == CADNIP_AC_LDS) return L;
+  }
+  if (A.n_cu <= 0) {
+    int cu = 0;
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cu = 0;
+    A.n_cu = cu > 0 ? cu : 256;
+  }
+  L.hbm = ac_hbm_plan(h->lu.nnz_lu, h->n, n_sys, wpb_req, A.max_waves, A.n_cu);
+  if (L.hbm.wpb > 0) L.memory = CADNIP_AC_HBM;
+  return L;
+}
+
+// the waves' workspace, grown like the other AC buffers: kept by the handle, released with it
+static int ac_work_reserve(CadnipHandle* h, size_t bytes) {
+  AcState& A = h->ac;
+  if (A.cap_work >= bytes) return CADNIP_OK;
+  if (A.d_work) { (void)hipFree(A.d_work); A.d_work = nullptr; }
+  A.cap_work = 0;
+  HIP_TRY(hipMalloc((void**)&A.d_work, bytes));
+  A.cap_work = bytes;
+  return CADNIP_OK;
 }
 
 namespace {
@@ -395,20 +505,31 @@ static AcArgs ac_args(CadnipHandle* h, int n_freq, long s0, int n_sys, double gm
   return a;
 }
 
-int launch_ac_lu(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin) {
-  if (p.wpb <= 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
-  ProfScope ps(h, "ac_lu");
+int launch_ac_lu(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin) {
+  if (L.memory < 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
   const AcArgs a = ac_args(h, n_freq, s0, n_sys, gmin);
+  if (L.memory == CADNIP_AC_HBM) {
+    const AcHbmPlan& p = L.hbm;
+    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
+    TRY_RC(ac_work_reserve(h, p.work_bytes));
+    ProfScope ps(h, "ac_lu_hbm");
+    const AcHbmArgs m{h->ac.d_work, p.n_waves};
+    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
+    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, a, m); return CADNIP_OK; }));
+    HIP_TRY(hipGetLastError());
+    return CADNIP_OK;
+  }
+  const AcPlan& p = L.lds;
+  ProfScope ps(h, "ac_lu");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
   TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, a); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }
 
-int launch_ac_adjoint(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x) {
+int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x) {
   AcState& A = h->ac;
-  if (p.wpb <= 0 || n_sys <= 0 || n_pairs <= 0 || A.dirty || !A.adj_ready) return CADNIP_BADARG;
-  ProfScope ps(h, "ac_adj");
+  if (L.memory < 0 || n_sys <= 0 || n_pairs <= 0 || A.dirty || !A.adj_ready) return CADNIP_BADARG;
   AcAdjArgs t;
   t.a = ac_args(h, n_freq, s0, n_sys, gmin);
   t.a.x = want_x ? A.d_adj_x : nullptr; t.a.berr = A.d_adj_berr; t.a.flags = A.d_adj_flags;
@@ -416,6 +537,19 @@ int launch_ac_adjoint(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int
   t.ut_rows = A.d_ut_rows; t.ut_lev_ptr = A.d_ut_lev_ptr; t.lt_rows = A.d_lt_rows; t.lt_lev_ptr = A.d_lt_lev_ptr;
   t.a_colptr = A.d_a_colptr; t.a_row = A.d_a_row; t.a_pos = A.d_a_pos;
   t.pairs = A.d_pairs; t.h = A.d_h; t.n_ut_lev = A.n_ut_lev; t.n_lt_lev = A.n_lt_lev; t.n_pairs = n_pairs;
+  if (L.memory == CADNIP_AC_HBM) {
+    const AcHbmPlan& p = L.hbm;
+    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
+    TRY_RC(ac_work_reserve(h, p.work_bytes));
+    ProfScope ps(h, "ac_adj_hbm");
+    const AcHbmArgs m{A.d_work, p.n_waves};
+    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
+    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m); return CADNIP_OK; }));
+    HIP_TRY(hipGetLastError());
+    return CADNIP_OK;
+  }
+  const AcPlan& p = L.lds;
+  ProfScope ps(h, "ac_adj");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
   TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
   HIP_TRY(hipGetLastError());

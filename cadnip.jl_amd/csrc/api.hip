@@ -215,7 +215,7 @@ void cadnip_destroy(CadnipHandle* h) {
                   h->d_resid, h->d_delta, h->d_limit_w, h->d_LU, h->d_tmp, h->d_flags, h->d_active, h->d_nonfinite, h->d_gshunt, h->d_srcfact, h->d_cold, h->d_load_src, h->d_load_dst, h->d_ent_pos,
                   h->d_ent_diag, h->d_ent_ptr, h->d_term_a, h->d_term_b, h->d_lev_ptr, h->d_lu_rowptr, h->d_lu_col, h->d_lu_diag, h->d_rperm,
                   h->d_cperm, h->d_fwd_rows, h->d_fwd_lev_ptr, h->d_bwd_rows, h->d_bwd_lev_ptr,
-                  h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_bac, h->ac.d_omega, h->ac.d_x, h->ac.d_berr, h->ac.d_flags};
+                  h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_bac, h->ac.d_omega, h->ac.d_x, h->ac.d_berr, h->ac.d_flags, h->ac.d_work};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   h->ac.each_adjoint_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->f2.release();
@@ -760,6 +760,28 @@ int cadnip_lu_order(CadnipHandle* h, int32_t* rperm, int32_t* cperm) {
   return CADNIP_OK;
 }
 
+// info [4] of the two sweeps (W that ran, LDS bytes of a workgroup, systems, workgroups launched) and the record cadnip_ac_plan_info reads;
+// `plan`: of the full chunks, `tail`: of the last, shorter one
+static void ac_report(CadnipHandle* h, const AcLaunch& plan, const AcLaunch& tail, size_t S, size_t chunk, int32_t* info) {
+  const bool hbm = plan.memory == CADNIP_AC_HBM;
+  info[0] = plan.wpb(); info[1] = hbm ? 0 : (int)plan.lds.shmem; info[2] = (int)S;
+  info[3] = (int)((S / chunk) * plan.workgroups((long)chunk) + (S % chunk ? tail.workgroups((long)(S % chunk)) : 0));
+  int64_t* last = h->ac.last;
+  last[0] = plan.memory; last[1] = hbm ? plan.hbm.n_waves : 0; last[2] = hbm ? (int64_t)plan.hbm.work_bytes : 0; last[3] = info[1];
+}
+
+int cadnip_ac_set_memory(CadnipHandle* h, int32_t mode, int32_t max_waves) {
+  if (!h || (mode != CADNIP_AC_LDS && mode != CADNIP_AC_HBM && mode != CADNIP_AC_AUTO) || max_waves < 0) return CADNIP_BADARG;
+  h->ac.memory = mode; h->ac.max_waves = max_waves;
+  return CADNIP_OK;
+}
+
+int cadnip_ac_plan_info(CadnipHandle* h, int64_t out[4]) {
+  if (!h || !out) return CADNIP_BADARG;
+  for (int i = 0; i < 4; ++i) out[i] = h->ac.last[i];
+  return CADNIP_OK;
+}
+
 // The AC sweep x[b][f] = (G[b] + gmin [node diagonals] + j omega[f] C[b])^-1 b_ac[b] on the G / C of the last cadnip_rebuild, with the handle's
 // pivot order: S = B n_freq systems through k_ac_lu (ac_lu.hip).  Uploads are blocking copies at entry (the stream is idle), downloads follow a
 // stream synchronisation.  The systems are processed in chunks of at most AC_CHUNK_BYTES of solution (16 n bytes each; at least one system),
@@ -770,8 +792,9 @@ int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega, double
   if (!h || n_freq <= 0 || !omega || !bac_host || !x_host || !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
   const size_t B = h->B, n = h->n, F = n_freq, S = B * F;
   const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * n)));
-  const AcPlan plan = ac_lu_plan(h, (long)std::min(S, chunk), wpb);
-  if (plan.wpb <= 0) return CADNIP_BADARG;                    // invalid wpb, or the work arrays do not fit LDS: nothing is launched
+  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb);             // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
+  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb) : plan;
+  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
   HIP_TRY(hipStreamSynchronize(h->stream));
   TRY(ac_lu_prepare(h));
   AcState& A = h->ac;
@@ -788,13 +811,13 @@ int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega, double
   HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
   for (size_t s0 = 0; s0 < S; s0 += chunk) {
     const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_lu(h, plan, n_freq, (long)s0, (int)ns, gmin));
+    TRY(launch_ac_lu(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(berr_host + s0, A.d_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0, A.d_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
   }
-  info[0] = plan.wpb; info[1] = (int)plan.shmem; info[2] = (int)S; info[3] = (int)((S / chunk) * ((chunk + plan.wpb - 1) / plan.wpb) + ((S % chunk) + plan.wpb - 1) / plan.wpb);
+  ac_report(h, plan, tail, S, chunk, info);
   return CADNIP_OK;
 }
 
@@ -808,8 +831,9 @@ int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, doub
   for (size_t k = 0; k < 2 * K; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
   const bool want_x = x_host != nullptr;
   const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * (K + (want_x ? n : 0)))));
-  const AcPlan plan = ac_lu_plan(h, (long)std::min(S, chunk), wpb);
-  if (plan.wpb <= 0) return CADNIP_BADARG;                    // invalid wpb, or the work arrays do not fit LDS: nothing is launched
+  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb);             // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
+  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb) : plan;
+  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
   HIP_TRY(hipStreamSynchronize(h->stream));
   TRY(ac_lu_prepare(h, true));
   AcState& A = h->ac;
@@ -832,14 +856,14 @@ int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, doub
   HIP_TRY(hipMemcpy(A.d_pairs, pairs, K * 2 * sizeof(int), hipMemcpyHostToDevice));
   for (size_t s0 = 0; s0 < S; s0 += chunk) {
     const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_adjoint(h, plan, n_freq, (long)s0, (int)ns, gmin, n_pairs, want_x));
+    TRY(launch_ac_adjoint(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin, n_pairs, want_x));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(h_host + s0 * K * 2, A.d_h, ns * K * 2 * sizeof(double), hipMemcpyDeviceToHost));
     if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_adj_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(berr_host + s0, A.d_adj_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0, A.d_adj_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
   }
-  info[0] = plan.wpb; info[1] = (int)plan.shmem; info[2] = (int)S; info[3] = (int)((S / chunk) * ((chunk + plan.wpb - 1) / plan.wpb) + ((S % chunk) + plan.wpb - 1) / plan.wpb);
+  ac_report(h, plan, tail, S, chunk, info);
   return CADNIP_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/cadnip_hip.h"
 #include "stamp_plan.hpp"   // StampShape
+#include "ac_hbm_plan.hpp"  // AcHbmPlan
 // rows of the derived sp_mos1 parameter card (devices.hpp: enum M1_*) that cadnip_set_params inspects
 #define CADNIP_MOS1_PAR_OXCAP 8
 #define CADNIP_MOS1_PAR_GD 30
@@ -147,6 +148,12 @@ struct AcState {
   double *d_h = nullptr, *d_adj_x = nullptr, *d_adj_berr = nullptr;
   int* d_adj_flags = nullptr;
   size_t cap_pairs = 0, cap_adj_sys = 0, cap_adj_x = 0;   // pairs d_pairs and a system of d_h hold, systems of the outputs, systems of d_adj_x
+  // HBM-resident variant (k_ac_lu_hbm / k_ac_adj_hbm; cadnip_ac_set_memory, ac_hbm_plan.hpp): the setting, the persistent waves' workspace
+  // (grown on demand like the buffers above, released with the handle) and what the last AC / adjoint call ran (cadnip_ac_plan_info)
+  int memory = CADNIP_AC_LDS, max_waves = 0;
+  double* d_work = nullptr; size_t cap_work = 0;   // cap_work: bytes
+  int n_cu = 0;                                    // compute units of the device (queried by the first HBM plan)
+  int64_t last[4] = {CADNIP_AC_LDS, 0, 0, 0};      // memory, n_waves, work_bytes, lds_bytes
   template <class F> void each_adjoint_buffer(F f) {
     f((void**)&d_t_colptr); f((void**)&d_t_pos); f((void**)&d_t_row); f((void**)&d_t_diag); f((void**)&d_ut_rows); f((void**)&d_ut_lev_ptr);
     f((void**)&d_lt_rows); f((void**)&d_lt_lev_ptr); f((void**)&d_a_colptr); f((void**)&d_a_row); f((void**)&d_a_pos); f((void**)&d_pairs);
@@ -249,13 +256,21 @@ int upload_lu(CadnipHandle* h);
 // wpb 0: an invalid request, or the work arrays of wpb_req (of one, for 0) systems exceed LDS_BUDGET
 struct AcPlan { int wpb = 0; size_t shmem = 0; };
 AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req);
+// the home of a call's work arrays under the handle's setting (h->ac.memory) and its plan: memory CADNIP_AC_LDS -> lds, CADNIP_AC_HBM -> hbm
+// (ac_hbm_plan.hpp, on the device's compute units and h->ac.max_waves); -1: refused -- an invalid wpb, or the circuit fits neither
+struct AcLaunch {
+  int memory = -1; AcPlan lds; AcHbmPlan hbm;
+  int wpb() const { return memory == CADNIP_AC_HBM ? hbm.wpb : lds.wpb; }
+  int workgroups(long n_sys) const { return memory == CADNIP_AC_HBM ? (hbm.n_waves + hbm.wpb - 1) / hbm.wpb : (int)((n_sys + lds.wpb - 1) / lds.wpb); }
+};
+AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req);
 // the pivot lists of the current LU program, on demand; adjoint: the transposed-solve tables (lu_transpose.hpp) as well
 int ac_lu_prepare(CadnipHandle* h, bool adjoint = false);
 // systems [s0, s0 + n_sys) of the B x n_freq grid (s = b * n_freq + f) into h->ac.d_x / d_berr / d_flags from index 0
-int launch_ac_lu(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin);
+int launch_ac_lu(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin);
 // ... of A^T x = c (c in h->ac.d_bac) through k_ac_adj: h[k] = x[p_k] - x[n_k] for the n_pairs pairs of h->ac.d_pairs into h->ac.d_h, berr and
 // flags into d_adj_berr / d_adj_flags, x into d_adj_x with want_x -- all from index 0
-int launch_ac_adjoint(CadnipHandle* h, const AcPlan& p, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x);
+int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

@@ -17,11 +17,13 @@ OK, BADARG, SINGULAR, NONFINITE, HIPERROR, NOTREADY, NOCONV = range(7)
 STATUS_NAMES = {0: "CADNIP_OK", 1: "CADNIP_BADARG", 2: "CADNIP_SINGULAR", 3: "CADNIP_NONFINITE",
                 4: "CADNIP_HIPERROR", 5: "CADNIP_NOTREADY", 6: "CADNIP_NOCONV"}
 
+AC_MEMORY = {"lds": 0, "hbm": 1, "auto": 2}     # CADNIP_AC_LDS / _HBM / _AUTO (Handle.ac_set_memory)
+
 # every symbol declared in include/cadnip_hip.h
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
@@ -364,7 +366,7 @@ class Handle:
         ``b_ac`` [B, n] complex (or [n], broadcast), ``wpb`` systems per workgroup (0: the launch plan's choice).  Returns (x complex128
         [B, F, n], berr [B, F], flags [B, F], info) with berr the componentwise backward error of x, flags bit 0 a zero / non-finite pivot or a
         non-finite solution, and info = {wpb, lds_bytes, systems, workgroups}.  An empty grid launches nothing.  A circuit whose work arrays
-        exceed LDS, or an invalid ``wpb``, raises CadnipError(CADNIP_BADARG)."""
+        exceed LDS (under the default memory: ``ac_set_memory``), or an invalid ``wpb``, raises CadnipError(CADNIP_BADARG)."""
         om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
         B, n, F = self.B, self.st.n, om.size
         if F == 0:
@@ -396,6 +398,21 @@ class Handle:
                                           _ip(pr) if K else None, C.c_int32(int(wpb)), hh.ctypes.data_as(_D), None if x is None else x.ctypes.data_as(_D),
                                           _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_adjoint")
         return hh, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+
+    def ac_set_memory(self, mode="lds", max_waves=0):
+        """cadnip_ac_set_memory: where ``ac_solve`` / ``ac_adjoint`` keep a system's work arrays from now on.  "lds" (the default of a new handle):
+        in LDS, every call as without the setting; "hbm": in a workspace in device memory, by persistent waves (k_ac_lu_hbm / k_ac_adj_hbm:
+        the same doubles; ``wpb`` is then waves per workgroup, 0 = 4, and info["lds_bytes"] is 0); "auto": LDS when its launch plan accepts the
+        circuit, else HBM.  ``max_waves`` > 0 caps the waves (= workspaces) of a launch, 0: the plan's choice (csrc/ac_hbm_plan.hpp).  An
+        unknown mode or a negative ``max_waves`` raises CadnipError(CADNIP_BADARG) and leaves the setting as it was."""
+        code = AC_MEMORY.get(mode, -1) if isinstance(mode, str) else int(mode)
+        _check(self.lib.cadnip_ac_set_memory(self.h, C.c_int32(code), C.c_int32(int(max_waves))), "cadnip_ac_set_memory")
+
+    def ac_plan_info(self):
+        """cadnip_ac_plan_info: {memory ("lds" / "hbm"), n_waves, work_bytes, lds_bytes} of the last ``ac_solve`` / ``ac_adjoint`` call that launched."""
+        out = (C.c_int64 * 4)()
+        _check(self.lib.cadnip_ac_plan_info(self.h, out), "cadnip_ac_plan_info")
+        return dict(memory={v: k for k, v in AC_MEMORY.items()}[int(out[0])], n_waves=int(out[1]), work_bytes=int(out[2]), lds_bytes=int(out[3]))
 
     def lu_stats(self):
         v = [C.c_int32() for _ in range(5)]

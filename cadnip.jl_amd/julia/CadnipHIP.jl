@@ -168,6 +168,17 @@ function ac_adjoint(ws::GPUEvalWorkspace, omega::Vector{Float64}, c::Matrix{Comp
                 ws.handle, F, omega, gmin, c, K, pairs, wpb, h, C_NULL, berr, flags, info), "cadnip_ac_adjoint")
     return h, berr, flags
 end
+# Where ac_solve / ac_adjoint keep a system's work arrays from now on: :lds (the default: in LDS, refused beyond 160 KB), :hbm (a workspace in
+# device memory, persistent waves, the same doubles) or :auto (LDS when its launch plan accepts the circuit, else HBM); max_waves > 0 caps the
+# waves of a launch.  ac_plan_info: (memory, n_waves, work_bytes, lds_bytes) of the last sweep that launched.
+const AC_MEMORY = Dict(:lds => Int32(0), :hbm => Int32(1), :auto => Int32(2))
+ac_set_memory!(ws::GPUEvalWorkspace, mode::Symbol=:lds; max_waves=0) =
+    check(ccall((:cadnip_ac_set_memory, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), ws.handle, get(AC_MEMORY, mode, Int32(-1)), max_waves), "cadnip_ac_set_memory")
+function ac_plan_info(ws::GPUEvalWorkspace)
+    out = zeros(Int64, 4)
+    check(ccall((:cadnip_ac_plan_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), ws.handle, out), "cadnip_ac_plan_info")
+    return (memory = out[1] == 1 ? :hbm : :lds, n_waves = out[2], work_bytes = out[3], lds_bytes = out[4])
+end
 # the handle's pivot order (0-based): pivot k uses row rperm[k], column cperm[k]
 function lu_order(ws::GPUEvalWorkspace, n::Integer)
     rperm = Vector{Int32}(undef, n); cperm = Vector{Int32}(undef, n)

@@ -252,6 +252,24 @@ int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega /* [F
                       double* x_host /* [B][F][n][2] or NULL */, double* berr_host /* [B][F] */, int32_t* flags_host /* [B][F] */,
                       int32_t* info /* [4] */);
 
+/* Where the AC and adjoint sweeps keep a system's work arrays -- a handle setting, LDS by default: every call exactly as without it.
+ *   CADNIP_AC_LDS   in LDS (k_ac_lu / k_ac_adj): one wave per system, refused beyond 160 KB as described above,
+ *   CADNIP_AC_HBM   in a workspace in device memory (k_ac_lu_hbm / k_ac_adj_hbm): the same arithmetic -- bit-identical results where both
+ *                   apply -- by persistent waves; wave g of n_waves handles systems g, g + n_waves, ... of a launch in its one workspace
+ *                   of 16 (nnz(L+U) + 3 n) bytes, so the handle's footprint is bounded (csrc/ac_hbm_plan.hpp: n_waves = min(systems,
+ *                   compute units x k), k the largest of 8, 4, 2, 1 that keeps the workspace within 256 MiB),
+ *   CADNIP_AC_AUTO  LDS when its launch plan accepts the circuit (and the wpb asked for), else HBM.
+ * max_waves > 0 replaces compute units x k; 0: the plan's choice.  Under HBM, wpb is waves per workgroup (0: 4), info[1] (LDS bytes) is 0 and
+ * info[3] the workgroups launched; a system whose own workspace exceeds 256 MiB is CADNIP_BADARG.  An unknown mode or max_waves < 0 is
+ * CADNIP_BADARG and leaves the setting as it was. */
+#define CADNIP_AC_LDS 0
+#define CADNIP_AC_HBM 1
+#define CADNIP_AC_AUTO 2
+int cadnip_ac_set_memory(CadnipHandle* h, int32_t mode, int32_t max_waves);
+/* of the last cadnip_ac_solve / cadnip_ac_adjoint call that launched: the memory used (CADNIP_AC_LDS / CADNIP_AC_HBM), n_waves and work_bytes of
+ * its largest launch (0 under LDS), LDS bytes of a workgroup (0 under HBM) */
+int cadnip_ac_plan_info(CadnipHandle* h, int64_t out[4]);
+
 /* ---- host drivers (Newton loop + step controller; stand-in for IDA / _dc_pcnr_newton) ----
  * The loops run on the host and launch the kernels above on the handle's stream; the
  * per-instance convergence / step decisions are evaluated on the device (one lane-group
