@@ -682,7 +682,117 @@ def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory=
     stats["memory"] = used
 
 
-def ac(target, freqs=(), gmin=1e-12, device=0, solver="host", memory="lds"):
+def _ac_target(target):
+    """(sweep?, the circuit in dcop mode, the sweep points) of an AC-family call"""
+    sweep = isinstance(target, CircuitSweep)
+    mc0 = target.circuit if sweep else target
+    mc = MNACircuit(mc0.circuit, mc0.params, MNASpec(temp=mc0.spec.temp, mode="dcop", gmin=mc0.spec.gmin))
+    return sweep, mc, target.points() if sweep else [{}]
+
+
+def _ac_classes(sweep, mc, pts, gmin, device, what):
+    """The linearisation ``ac`` and ``network`` share, one structure class at a time: a resident batch per class, its DC operating points, the
+    restamp at them, and per point the dense G (``gmin`` on the voltage-node diagonals) and C.  Yields (sim, st, idx, G, C, lin) with G / C the
+    handle's get_GCb ([B, nnz]) and lin = [(point index, G dense, C dense, point parameters, DC solution)]; the batch is closed when the
+    consumer moves on -- or closes the generator."""
+    import scipy.sparse as sp
+    for idx, st in structure_classes(mc, pts) if sweep else [(list(range(1)), None)]:
+        sim = BatchSimulator(mc, [pts[i] for i in idx] if sweep else None, device, st=st)
+        try:
+            st = sim.st
+            u, conv, _ = sim.dc()
+            if not np.all(conv):
+                raise RuntimeError("%s: the DC operating point did not converge for %d point(s)" % (what, int((~conv).sum())))
+            sim.h.rebuild(u, 0.0)
+            G, C, _, _ = sim.h.get_GCb()
+            lin = []
+            for k, i in enumerate(idx):
+                dense = lambda nz: sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
+                Gd, Cd = dense(G[k]), dense(C[k])
+                Gd[np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
+                lin.append((i, Gd, Cd, {kk: float(v[k]) for kk, v in sim.params.items()}, u[k].copy()))
+            yield sim, st, idx, G, C, lin
+        finally:
+            sim.close()
+
+
+def source_rhs(st, circuit, name):
+    """The excitation of ONE independent source at unit magnitude, whatever its ``ac`` value: a V source's branch row gets 1, an I source puts
+    +1 into p and -1 into n (as ``rhs_ac``).  The name is matched as ``noise(..., input=)`` matches it (as written, then in lower case)."""
+    d = next((d for d in circuit.devices if d.type in ("V", "I") and d.name == name), None) or \
+        next((d for d in circuit.devices if d.type in ("V", "I") and d.name.lower() == name.lower()), None)
+    if d is None:
+        raise ValueError("%s is not an independent source of the circuit" % name)
+    b = np.zeros(st.n, dtype=complex)
+    if d.type == "V":
+        b[port_rows(st, [d.name])[0]] = 1.0
+    else:
+        for nm, sgn in ((d.nodes[0], 1.0), (d.nodes[1], -1.0)):
+            if nm not in ("0", "gnd", "gnd!"):
+                b[st.index_of(nm)] += sgn
+    return b
+
+
+def port_rows(st, ports):
+    """The branch rows I_<V> of the voltage sources named in ``ports``, resolved as ``noise_indices`` resolves ``input``; ValueError for a name
+    that is not an independent voltage source."""
+    rows = []
+    for nm in ports:
+        cand = [c for c in ("I_" + nm, "I_" + nm.lower()) if c in st.current_names]
+        if not cand:
+            raise ValueError("network: port %s is not an independent voltage source (no current variable I_%s)" % (nm, nm))
+        rows.append(st.n_nodes + st.current_names.index(cand[0]))
+    if len(set(rows)) != len(rows):
+        raise ValueError("network: a port is named twice")
+    return rows
+
+
+def ac_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, rhs, pairs, want_x, solver, stats, memory="lds"):
+    """K excitations per point against ONE factorisation per (point, frequency), on the GPU: ``h`` (holding the restamp at the DC points)
+    re-analyses its pivot order on ``ac_pivot_sample`` -- as ``ac_gpu_sweep`` -- and solves points x frequencies x the K columns of ``rhs``
+    ([K, n]) in ONE ``ac_solve_multi`` call.  Returns (h [B, F, K, P] for the probe ``pairs`` or None, x [B, F, K, n] or None without
+    ``want_x``).  The gate is ``ac_gpu_sweep``'s, per column: a column whose flag is set or whose backward error exceeds AC_BERR_MAX is solved
+    again by the host's dense solve on ``Gd`` / ``Cd`` (per point; gmin on the node diagonals).  ``stats`` counts columns as systems.  A
+    circuit the memory home refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why."""
+    from . import hip
+    _ac_memory(memory)
+    omegas = np.asarray(omegas, dtype=float)
+    rhs = np.asarray(rhs, dtype=complex)
+    B, F, K = len(Gd), omegas.size, rhs.shape[0]
+    stats["rhs"] = K
+    to_ref = np.asarray(st.to_ref_nz)
+    sample_ref = np.empty(st.nnz)
+    sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+    h.analyze_values(sample_ref)
+    try:
+        with _ac_memory_of(h, memory):
+            hh, x, berr, flags, info = h.ac_solve_multi(omegas, gmin, rhs, pairs, 0, want_x)
+            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
+    except hip.CadnipError as e:
+        if solver == "auto" and e.code == hip.BADARG:
+            stats["host_systems"] += B * F * K
+            stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
+            return None
+        raise
+    redo = (flags != 0) | ~(berr <= AC_BERR_MAX)
+    if redo.any():
+        pr = None if hh is None else np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        for b, f, k in zip(*np.nonzero(redo)):
+            xh = np.linalg.solve(Gd[b] + 1j * omegas[f] * Cd[b], rhs[k])
+            if x is not None:
+                x[b, f, k] = xh
+            if hh is not None:
+                hh[b, f, k] = np.where(pr[:, 0] >= 0, xh[pr[:, 0]], 0.0) - np.where(pr[:, 1] >= 0, xh[pr[:, 1]], 0.0)
+    kept = berr[~redo]
+    stats["gpu_systems"] += int((~redo).sum())
+    stats["host_systems"] += int(redo.sum())
+    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
+    stats["wpb"] = info["wpb"]
+    stats["memory"] = used
+    return hh, x
+
+
+def ac(target, freqs=(), gmin=1e-12, device=0, solver="host", memory="lds", sources=None):
     """ac!(circuit, freqs; gmin) -- src/ac.jl:113-170.  The DC operating point and the restamp at it run on the GPU (cadnip_dc_run,
     cadnip_rebuild: the linearisation IS the stamping); G gets ``gmin`` on the voltage-node diagonals (assemble_G(ctx; gshunt=gmin),
     ac.jl:127).  The frequency sweep is the reference's own dense ``(jw C + G)^-1 b_ac`` on the host: n is a circuit's size, not a
@@ -694,36 +804,130 @@ def ac(target, freqs=(), gmin=1e-12, device=0, solver="host", memory="lds"):
     takes the host path for it and says so in ``stats``.
     ``memory`` (ignored with solver="host"): "lds" (default) keeps a system's work arrays in LDS -- "too large" is then 160 KB; "hbm" keeps
     them in device memory and "auto" does so where LDS refuses, so such a circuit is solved on the GPU (``ac_gpu_sweep``).  The default
-    stays "lds": DESIGN section 9 has the measured figures and leaves making "auto" the default to a later change."""
-    import scipy.sparse as sp
+    stays "lds": DESIGN section 9 has the measured figures and leaves making "auto" the default to a later change.
+    ``sources`` (default None: the call is exactly what it is without the keyword): a list of names of independent sources.  The result is
+    then, per point, a dict name -> ACSol whose excitation is that source ALONE at unit magnitude (``source_rhs``; the circuit's ``ac=``
+    values are ignored): the separate responses from one DC solve and one restamp, and with a GPU solver from one factorisation per (point,
+    frequency) serving all of them (``ac_multi_gpu_sweep``; ``stats`` then counts columns as systems and has "rhs": the number of sources)."""
+    from contextlib import closing
     if solver not in ("host", "gpu", "auto"):
         raise ValueError("solver must be 'host', 'gpu' or 'auto'")
     _ac_memory(memory)
     stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
-    sweep = isinstance(target, CircuitSweep)
-    mc0 = target.circuit if sweep else target
-    mc = MNACircuit(mc0.circuit, mc0.params, MNASpec(temp=mc0.spec.temp, mode="dcop", gmin=mc0.spec.gmin))
-    pts = target.points() if sweep else [{}]
+    sweep, mc, pts = _ac_target(target)
     sols = [None] * len(pts)
-    for idx, st in structure_classes(mc, pts) if sweep else [(list(range(1)), None)]:
-        sim = BatchSimulator(mc, [pts[i] for i in idx] if sweep else None, device, st=st)
-        try:
-            st = sim.st
-            u, conv, _ = sim.dc()
-            if not np.all(conv):
-                raise RuntimeError("ac: the DC operating point did not converge for %d point(s)" % int((~conv).sum()))
-            sim.h.rebuild(u, 0.0)
-            G, C, _, _ = sim.h.get_GCb()
-            for k, i in enumerate(idx):
-                dense = lambda nz: sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
-                Gd, Cd = dense(G[k]), dense(C[k])
-                Gd[np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
-                p_i = {kk: float(v[k]) for kk, v in sim.params.items()}
-                sols[i] = ACSol(st, Gd, Cd, rhs_ac(st, mc.circuit, p_i), u[k].copy(), freqs)
-            if solver != "host":
-                ac_gpu_sweep(sim.h, st, [sols[i] for i in idx], G, C, 2.0 * np.pi * np.asarray(freqs, dtype=float), gmin, solver, stats, memory)
-        finally:
-            sim.close()
+    omegas = 2.0 * np.pi * np.asarray(freqs, dtype=float)
+    with closing(_ac_classes(sweep, mc, pts, gmin, device, "ac")) as classes:
+        for sim, st, idx, G, C, lin in classes:
+            if sources is None:
+                for i, Gd, Cd, p_i, u_i in lin:
+                    sols[i] = ACSol(st, Gd, Cd, rhs_ac(st, mc.circuit, p_i), u_i, freqs)
+                if solver != "host":
+                    ac_gpu_sweep(sim.h, st, [sols[i] for i in idx], G, C, omegas, gmin, solver, stats, memory)
+                continue
+            rhs = np.array([source_rhs(st, mc.circuit, nm) for nm in sources]).reshape(len(sources), st.n)
+            for i, Gd, Cd, p_i, u_i in lin:
+                sols[i] = {nm: ACSol(st, Gd, Cd, rhs[j], u_i, freqs) for j, nm in enumerate(sources)}
+            if solver != "host" and omegas.size and len(sources):
+                got = ac_multi_gpu_sweep(sim.h, st, [l[1] for l in lin], [l[2] for l in lin], G, C, omegas, gmin, rhs, None, True, solver, stats, memory)
+                if got is not None:
+                    for k, i in enumerate(idx):
+                        for j, nm in enumerate(sources):
+                            sols[i][nm]._cache[tuple(omegas)] = np.array(got[1][k, :, j])
+    if solver != "host":
+        for s in sols:
+            for a in (s.values() if isinstance(s, dict) else [s]):
+                a.stats = stats
+    return SweepResult(pts, sols) if sweep else sols[0]
+
+
+class NetworkSol:
+    """``network``'s result: the N-port admittance matrix of a circuit linearised at its DC point, over a grid in hertz.  ``y`` [F, P, P]
+    complex with y[f, i, j] the current INTO port i per volt at port j, the other ports shorted; ``z`` = inv(y) per frequency (a singular y
+    raises numpy's LinAlgError -- from ``z`` only); ``s`` the scattering matrix for the reference impedances ``z0`` (a scalar, or one real
+    value per port): (I - z0 y)(I + z0 y)^-1, and with unequal impedances the power-wave form F (I - Z0 y)(I + Z0 y)^-1 F^-1 with
+    Z0 = diag(z0), F = diag(1 / (2 sqrt(z0_i))).  ``s_db(i, j)`` is 20 log10 |s[:, i, j]| (ports by index or by name).  ``dc_x`` is the DC
+    solution, ``stats`` what a GPU solver did (as ``ACSol.stats``, columns counted as systems, plus "rhs")."""
+
+    def __init__(self, freqs, ports, y, z0=50.0, dc_x=None):
+        self.freqs, self.ports, self.dc_x = np.asarray(freqs, dtype=float), list(ports), dc_x
+        P = len(self.ports)
+        self.y = np.ascontiguousarray(np.asarray(y, dtype=complex).reshape(len(self.freqs), P, P))
+        z = np.asarray(z0, dtype=float)
+        if z.ndim > 1 or (z.ndim == 1 and z.size != P) or not np.all(z > 0):
+            raise ValueError("z0 must be a positive scalar or one positive value per port")
+        self.z0 = float(z) if z.ndim == 0 else z.copy()
+        self.stats = {}
+
+    @property
+    def z(self):
+        return np.linalg.inv(self.y)
+
+    @property
+    def s(self):
+        P = len(self.ports)
+        z0 = np.broadcast_to(np.asarray(self.z0, dtype=float), (P,))
+        eye, zy = np.eye(P), z0[:, None] * self.y                    # Z0 y
+        s = (eye - zy) @ np.linalg.inv(eye + zy)
+        f = 1.0 / (2.0 * np.sqrt(z0))
+        return s if np.all(z0 == z0[0]) else (f[:, None] * s) / f[None, :]
+
+    def _port(self, i):
+        return self.ports.index(i) if isinstance(i, str) else int(i)
+
+    def s_db(self, i, j):
+        return 20.0 * np.log10(np.abs(self.s[:, self._port(i), self._port(j)]))
+
+
+def network_solve(st, G, C, ports, freqs, z0=50.0, dc_x=None):
+    """The host path of ``network`` on dense G (gmin already on the voltage-node diagonals) and C: per frequency ONE dense LU serves the P
+    columns -- column j has 1 on the branch row of port j's source and 0 elsewhere -- and y[f, i, j] = -x_j[I_<Vi>]: a V source's branch
+    current flows from + through the source to -, so the current into the port from outside is its negative."""
+    freqs = np.asarray(freqs, dtype=float)
+    rows = port_rows(st, ports)
+    E = np.zeros((st.n, len(rows)), dtype=complex)
+    E[rows, np.arange(len(rows))] = 1.0
+    y = np.zeros((len(freqs), len(rows), len(rows)), dtype=complex)
+    for fi, f in enumerate(freqs):
+        y[fi] = -np.linalg.solve(G + 1j * 2.0 * np.pi * f * C, E)[rows]
+    return NetworkSol(freqs, ports, y, z0, dc_x)
+
+
+def network(target, ports, freqs, z0=50.0, gmin=1e-12, device=0, solver="host", memory="lds"):
+    """The N-port small-signal parameters of a circuit (SPICE's .net / .sp): ``ports`` names P independent voltage sources, port i is its
+    source's (+, -) node pair.  The circuit is linearised at its DC point exactly as by ``ac`` (the same code); column j of the admittance
+    matrix is the response to 1 V on port j's source with every other port AC-shorted by its own source -- the ``ac=`` values of the circuit
+    are ignored.  Returns a NetworkSol (``y``, ``z``, ``s``, ``s_db``), or for a CircuitSweep a SweepResult of them.  A port that is not an
+    independent voltage source raises ValueError.
+    ``solver``: "host" (default) -- dense solves, one LU per frequency serving all P columns (``network_solve``); "gpu" -- one
+    ``ac_solve_multi`` call per structure class: each (point, frequency) system is factored once on the device for its P columns, and only
+    the P x P port currents per system come back (``ac_multi_gpu_sweep``: the gate of ``ac_gpu_sweep`` per column, a rejected column is solved
+    again on the host); "auto" -- as "gpu", with the host path for a circuit the memory home refuses.  ``memory`` as for ``ac``.
+    ``stats`` = {"gpu_systems", "host_systems", "max_berr", "wpb", "memory", "rhs"} with columns counted as systems."""
+    from contextlib import closing
+    if solver not in ("host", "gpu", "auto"):
+        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
+    _ac_memory(memory)
+    ports = list(ports)
+    freqs = np.asarray(freqs, dtype=float)
+    omegas = 2.0 * np.pi * freqs
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    sweep, mc, pts = _ac_target(target)
+    sols = [None] * len(pts)
+    with closing(_ac_classes(sweep, mc, pts, gmin, device, "network")) as classes:
+        for sim, st, idx, G, C, lin in classes:
+            rows = port_rows(st, ports)
+            got = None
+            if solver != "host" and freqs.size and rows:
+                rhs = np.zeros((len(rows), st.n), dtype=complex)
+                rhs[np.arange(len(rows)), rows] = 1.0
+                got = ac_multi_gpu_sweep(sim.h, st, [l[1] for l in lin], [l[2] for l in lin], G, C, omegas, gmin, rhs, [(r, -1) for r in rows], False,
+                                         solver, stats, memory)
+            for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin):
+                if got is None:
+                    sols[i] = network_solve(st, Gd, Cd, ports, freqs, z0, u_i)
+                else:
+                    sols[i] = NetworkSol(freqs, ports, -np.swapaxes(got[0][k], 1, 2), z0, u_i)      # h[f, column j, port i] -> y[f, i, j]
     if solver != "host":
         for s in sols:
             s.stats = stats

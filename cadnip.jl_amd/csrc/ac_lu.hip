@@ -17,6 +17,7 @@
 // Every multiply-add is an explicit fma: the W instantiations compute the same doubles.
 // k_ac_lu_hbm / k_ac_adj_hbm (cadnip_ac_set_memory) run the same steps -- the same __device__ functions -- with the work arrays in a per-wave
 // workspace in global memory, for circuits beyond the LDS budget: persistent waves, planned by ac_hbm_plan.hpp.
+// k_ac_lu_multi / k_ac_lu_multi_hbm (cadnip_ac_solve_multi) run steps 1 and 2 once per system and steps 3 to 6 for each of K right-hand sides.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -380,6 +381,80 @@ __global__ void __launch_bounds__(64 * W) k_ac_adj_hbm(AcAdjArgs t, AcHbmArgs m)
   }
 }
 
+// ---- the multi-column kernel: A x_k = b_k for the K right-hand sides of an instance against ONE factorisation per system (cadnip_ac_solve_multi:
+// the columns of a network's Y matrix, the responses to several sources) -------------------------------------------------------------------------
+// Steps 1 and 2 once per system (ac_load_factor).  Then, per column k = 0 .. K-1, steps 3 to 5 of ac_lu_system word for word -- the same
+// statements on the same doubles, in the same x / r / y, so column k holds what k_ac_lu gives with b_k as its b_ac -- and the stores of step 6:
+// x when the caller asked for it, the probe differences h[j] = x[p_j] - x[n_j] (pairs as k_ac_adj: -1 = ground, contributes 0), berr, the flag
+// (bit 0: a zero / non-finite pivot of the system -- in all its K columns -- or a non-finite solution of THIS column).  Every word of x, r
+// and y is written before it is read inside a column, as in ac_lu_system, so a column leaves nothing to the next one; the M::sync() that ends
+// a column puts its last reads of x (the stores) before the next column's writes.  No atomics, no workgroup barrier.
+struct AcMultiArgs {
+  AcArgs a;                                 // a.x: x out [systems][K][n] (null: not wanted); a.berr / a.flags: [systems][K]; a.bac is not read
+  const double* rhs; long rhs_stride;       // b [B][K][n] complex; complex words from one instance to the next (K n)
+  const int* pairs; double* h;              // [n_pairs][2]; h out [systems][K][n_pairs] complex
+  int n_rhs, n_pairs;
+};
+
+template <class M>
+__device__ __forceinline__ void ac_multi_system(const AcMultiArgs& t, int ls, const AcWork& wk, int lane) {
+  const AcArgs& a = t.a;
+  const int n = a.n;
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double om = a.omega[fi];
+  const int bad_pivot = ac_load_factor<M>(a, lu, G, C, om, lane);
+  for (int k = 0; k < t.n_rhs; ++k) {
+    const double2* bac = (const double2*)t.rhs + (size_t)inst * t.rhs_stride + (size_t)k * n;
+    const size_t lk = (size_t)ls * t.n_rhs + k;               // (system, column) of the launch: within int (api.hip bounds a launch's output)
+    int bad = bad_pivot;
+    for (int i = lane; i < n; i += 64) y[i] = bac[a.rperm[i]];
+    M::sync();
+    ac_solve<M>(a, lu, y, lane);
+    for (int i = lane; i < n; i += 64) x[a.cperm[i]] = y[i];
+    M::sync();
+    (void)ac_residual<M, false>(a, G, C, om, bac, x, r, lane);
+    for (int i = lane; i < n; i += 64) y[i] = r[a.rperm[i]];
+    M::sync();
+    ac_solve<M>(a, lu, y, lane);
+    for (int i = lane; i < n; i += 64) { const int j = a.cperm[i]; const double2 xv = x[j], dv = y[i]; x[j] = make_double2(xv.x + dv.x, xv.y + dv.y); }
+    M::sync();
+    // ---- 5. backward error
+    const double worst = ac_residual<M, true>(a, G, C, om, bac, x, r, lane);
+    // ---- 6. store
+    double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
+    for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
+    double2* ho = (double2*)t.h + lk * t.n_pairs;
+    for (int j = lane; j < t.n_pairs; j += 64) {
+      const int p = t.pairs[2 * j], q = t.pairs[2 * j + 1];
+      const double2 xp = p >= 0 ? x[p] : make_double2(0.0, 0.0), xn = q >= 0 ? x[q] : make_double2(0.0, 0.0);
+      ho[j] = make_double2(xp.x - xn.x, xp.y - xn.y);
+    }
+    ac_store_status(a, (int)lk, worst, bad, lane);
+    M::sync();                                                 // the last reads of this column's x before the next column's (next system's) words
+  }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu_multi(AcMultiArgs t) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= t.a.n_sys) return;                                 // the tail workgroup: no workgroup barrier anywhere below
+  ac_multi_system<AcInLds>(t, ls, ac_work(lds_ac((double*)sm, t.a.nnz_lu, t.a.n, w, W)), lane);
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu_multi_hbm(AcMultiArgs t, AcHbmArgs m) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
+  const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
+  for (int ls = g; ls < end; ls += m.n_waves) ac_multi_system<AcInHbm>(t, ls, wk, lane);   // a system's last column ends in the fence the next one needs
+}
+
 // The launch plan -- the one place that sizes the LDS block and picks W, and the only reader of CADNIP_AC_WPB.  A compute unit holds
 // min(32 waves, LDS_BUDGET / block) workgroups' worth of systems: the plan takes the W with the most resident systems (ties: the largest),
 // then halves it while the launch would not put a workgroup on half of the 256 compute units.
@@ -552,6 +627,33 @@ int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, i
   ProfScope ps(h, "ac_adj");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
   TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
+  HIP_TRY(hipGetLastError());
+  return CADNIP_OK;
+}
+
+int launch_ac_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x) {
+  AcState& A = h->ac;
+  if (L.memory < 0 || n_sys <= 0 || n_rhs < 1 || n_pairs < 0 || (n_pairs == 0 && !want_x) || A.dirty) return CADNIP_BADARG;
+  AcMultiArgs t;
+  t.a = ac_args(h, n_freq, s0, n_sys, gmin);
+  t.a.bac = nullptr; t.a.x = want_x ? A.d_multi_x : nullptr; t.a.berr = A.d_multi_berr; t.a.flags = A.d_multi_flags;
+  t.rhs = A.d_multi_rhs; t.rhs_stride = (long)n_rhs * h->n;
+  t.pairs = A.d_multi_pairs; t.h = A.d_multi_h; t.n_rhs = n_rhs; t.n_pairs = n_pairs;
+  if (L.memory == CADNIP_AC_HBM) {
+    const AcHbmPlan& p = L.hbm;
+    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
+    TRY_RC(ac_work_reserve(h, p.work_bytes));
+    ProfScope ps(h, "ac_lu_multi_hbm");
+    const AcHbmArgs m{A.d_work, p.n_waves};
+    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
+    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_multi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m); return CADNIP_OK; }));
+    HIP_TRY(hipGetLastError());
+    return CADNIP_OK;
+  }
+  const AcPlan& p = L.lds;
+  ProfScope ps(h, "ac_lu_multi");
+  const int grid = (n_sys + p.wpb - 1) / p.wpb;
+  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }

@@ -218,6 +218,7 @@ void cadnip_destroy(CadnipHandle* h) {
                   h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_bac, h->ac.d_omega, h->ac.d_x, h->ac.d_berr, h->ac.d_flags, h->ac.d_work};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   h->ac.each_adjoint_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
+  h->ac.each_multi_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->f2.release();
   for (auto& g : h->step_graph) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (auto& b : h->blocks) {
@@ -862,6 +863,58 @@ int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, doub
     if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_adj_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(berr_host + s0, A.d_adj_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0, A.d_adj_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  ac_report(h, plan, tail, S, chunk, info);
+  return CADNIP_OK;
+}
+
+// The multi-column sweep x[b][f][k] = (A[b][f])^-1 b[b][k] with A as above: S = B n_freq systems through k_ac_lu_multi (ac_lu.hip), which factors
+// each system once, exactly as k_ac_lu does, and runs the solve, the refinement and the backward error per column.  Same rules as
+// cadnip_ac_solve; a system's device output is 16 K (n_pairs + n [x wanted]) bytes.  Buffers live in AcState.
+int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* b_host, int32_t n_pairs,
+                          const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
+  if (!h || n_freq <= 0 || !omega || n_rhs < 1 || !b_host || n_pairs < 0 || (n_pairs > 0 && (!pairs || !h_host)) || (n_pairs == 0 && !x_host) ||
+      !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
+  const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_rhs, P = n_pairs;
+  for (size_t k = 0; k < 2 * P; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
+  const bool want_x = x_host != nullptr;
+  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * K * (P + (want_x ? n : 0)))));
+  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb);             // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
+  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb) : plan;
+  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  TRY(ac_lu_prepare(h));
+  AcState& A = h->ac;
+  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
+  auto grow = [](auto** p, size_t* cap, size_t need, size_t words) {       // one buffer to `need` units of `words` elements
+    if (*cap >= need) return (int)CADNIP_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    *cap = 0;
+    TRY(dev_alloc(p, need * words));
+    *cap = need;
+    return (int)CADNIP_OK;
+  };
+  TRY(grow(&A.d_multi_rhs, &A.cap_multi_rhs, B * K * n, 2));
+  if (P) { TRY(grow(&A.d_multi_pairs, &A.cap_multi_pairs, P, 2)); TRY(grow(&A.d_multi_h, &A.cap_multi_h, chunk * K * P, 2)); }
+  if (want_x) TRY(grow(&A.d_multi_x, &A.cap_multi_x, chunk * K * n, 2));
+  if (A.cap_multi_cols < chunk * K) {                           // berr and flags: one capacity
+    if (A.d_multi_berr) { (void)hipFree(A.d_multi_berr); A.d_multi_berr = nullptr; }
+    if (A.d_multi_flags) { (void)hipFree(A.d_multi_flags); A.d_multi_flags = nullptr; }
+    A.cap_multi_cols = 0;
+    TRY(dev_alloc(&A.d_multi_berr, chunk * K)); TRY(dev_alloc(&A.d_multi_flags, chunk * K));
+    A.cap_multi_cols = chunk * K;
+  }
+  HIP_TRY(hipMemcpy(A.d_multi_rhs, b_host, B * K * n * 2 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
+  if (P) HIP_TRY(hipMemcpy(A.d_multi_pairs, pairs, P * 2 * sizeof(int), hipMemcpyHostToDevice));
+  for (size_t s0 = 0; s0 < S; s0 += chunk) {
+    const size_t ns = std::min(chunk, S - s0);
+    TRY(launch_ac_multi(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin, n_rhs, n_pairs, want_x));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (P) HIP_TRY(hipMemcpy(h_host + s0 * K * P * 2, A.d_multi_h, ns * K * P * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * K * n * 2, A.d_multi_x, ns * K * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(berr_host + s0 * K, A.d_multi_berr, ns * K * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags_host + s0 * K, A.d_multi_flags, ns * K * sizeof(int), hipMemcpyDeviceToHost));
   }
   ac_report(h, plan, tail, S, chunk, info);
   return CADNIP_OK;

@@ -148,6 +148,13 @@ struct AcState {
   double *d_h = nullptr, *d_adj_x = nullptr, *d_adj_berr = nullptr;
   int* d_adj_flags = nullptr;
   size_t cap_pairs = 0, cap_adj_sys = 0, cap_adj_x = 0;   // pairs d_pairs and a system of d_h hold, systems of the outputs, systems of d_adj_x
+  // multi-column sweep (k_ac_lu_multi, cadnip_ac_solve_multi): its own transfer buffers, each grown on demand to the capacity beside it
+  double *d_multi_rhs = nullptr, *d_multi_h = nullptr, *d_multi_x = nullptr, *d_multi_berr = nullptr;   // [B][K][n], [S][K][pairs], [S][K][n] complex; [S][K]
+  int *d_multi_pairs = nullptr, *d_multi_flags = nullptr;                                              // [pairs][2]; [S][K]
+  size_t cap_multi_rhs = 0, cap_multi_h = 0, cap_multi_x = 0, cap_multi_pairs = 0, cap_multi_cols = 0; // complex words, complex words, complex words, pairs, (system, column)s
+  template <class F> void each_multi_buffer(F f) {
+    f((void**)&d_multi_rhs); f((void**)&d_multi_h); f((void**)&d_multi_x); f((void**)&d_multi_berr); f((void**)&d_multi_pairs); f((void**)&d_multi_flags);
+  }
   // HBM-resident variant (k_ac_lu_hbm / k_ac_adj_hbm; cadnip_ac_set_memory, ac_hbm_plan.hpp): the setting, the persistent waves' workspace
   // (grown on demand like the buffers above, released with the handle) and what the last AC / adjoint call ran (cadnip_ac_plan_info)
   int memory = CADNIP_AC_LDS, max_waves = 0;
@@ -271,6 +278,9 @@ int launch_ac_lu(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_
 // ... of A^T x = c (c in h->ac.d_bac) through k_ac_adj: h[k] = x[p_k] - x[n_k] for the n_pairs pairs of h->ac.d_pairs into h->ac.d_h, berr and
 // flags into d_adj_berr / d_adj_flags, x into d_adj_x with want_x -- all from index 0
 int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x);
+// ... of A x_k = b_k for the n_rhs columns per instance in h->ac.d_multi_rhs through k_ac_lu_multi (one factorisation per system): per (system,
+// column) the n_pairs probe differences into d_multi_h, x into d_multi_x with want_x, berr and flags into d_multi_berr / d_multi_flags
+int launch_ac_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

@@ -23,7 +23,7 @@ AC_MEMORY = {"lds": 0, "hbm": 1, "auto": 2}     # CADNIP_AC_LDS / _HBM / _AUTO (
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
@@ -397,6 +397,37 @@ class Handle:
         _check(self.lib.cadnip_ac_adjoint(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), cc.ctypes.data_as(_D), C.c_int32(K),
                                           _ip(pr) if K else None, C.c_int32(int(wpb)), hh.ctypes.data_as(_D), None if x is None else x.ctypes.data_as(_D),
                                           _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_adjoint")
+        return hh, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+
+    def ac_solve_multi(self, omega, gmin, b, pairs=None, wpb=0, want_x=True, x_out=None):
+        """cadnip_ac_solve_multi: x[b, f, k] = A[b, f]^-1 b[b, k] for K right-hand sides per instance against ONE factorisation per system, A and
+        the pivot order as ``ac_solve`` (csrc/ac_lu.hip: k_ac_lu_multi) -- column k is bit-identical to ``ac_solve(omega, gmin, b[:, k])``.
+        ``b`` [B, K, n] complex (or [K, n], broadcast), ``pairs`` [P, 2] unknown indices (-1 = ground) or None.  Returns (h complex128
+        [B, F, K, P] with h[..., j] = x[p_j] - x[n_j], or None without pairs; x [B, F, K, n], or None without ``want_x``; berr [B, F, K];
+        flags [B, F, K]; info) -- berr, flags (per column; a bad pivot flags all K columns of its system) and info as ``ac_solve``.  An empty
+        grid launches nothing.  ``x_out``: a C-contiguous complex128 array [B, F, K, n] to receive x (and be returned) instead of a new one -- a
+        caller that sweeps repeatedly spares the first touch of a fresh array, which above 32 MiB costs more than the sweep (DESIGN section 9);
+        it implies ``want_x``.  No column, neither pairs nor x, a pair index outside [-1, n), a circuit the memory setting refuses or an
+        invalid ``wpb`` raise CadnipError(CADNIP_BADARG)."""
+        om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
+        bb = np.asarray(b, dtype=np.complex128)
+        B, n, F = self.B, self.st.n, om.size
+        if bb.ndim < 2 or bb.shape[-1] != n:
+            raise ValueError("b must be [K, n] or [B, K, n]")
+        K = bb.shape[-2]
+        bb = np.ascontiguousarray(np.broadcast_to(bb, (B, K, n)))
+        pr = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        P = 0 if pr is None else pr.shape[0]
+        hh = np.empty((B, F, K, P), dtype=np.complex128) if P else None
+        if x_out is not None and (not isinstance(x_out, np.ndarray) or x_out.dtype != np.complex128 or x_out.shape != (B, F, K, n) or not x_out.flags.c_contiguous):
+            raise ValueError("x_out must be a C-contiguous complex128 array of shape [B, F, K, n]")
+        x = x_out if x_out is not None else np.empty((B, F, K, n), dtype=np.complex128) if want_x else None
+        berr, flags, info = np.empty((B, F, K)), np.zeros((B, F, K), dtype=np.int32), np.zeros(4, dtype=np.int32)
+        if F == 0:
+            return hh, x, berr, flags, dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
+        _check(self.lib.cadnip_ac_solve_multi(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), C.c_int32(K), bb.ctypes.data_as(_D), C.c_int32(P),
+                                              _ip(pr) if P else None, C.c_int32(int(wpb)), None if hh is None else hh.ctypes.data_as(_D),
+                                              None if x is None else x.ctypes.data_as(_D), _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_solve_multi")
         return hh, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
 
     def ac_set_memory(self, mode="lds", max_waves=0):

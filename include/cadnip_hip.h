@@ -251,6 +251,19 @@ int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega /* [F
                       int32_t n_pairs, const int32_t* pairs /* [K][2], -1 = ground */, int32_t wpb, double* h_host /* [B][F][K][2] */,
                       double* x_host /* [B][F][n][2] or NULL */, double* berr_host /* [B][F] */, int32_t* flags_host /* [B][F] */,
                       int32_t* info /* [4] */);
+/* Many right-hand sides per factorisation (the columns of a network's Y matrix, the responses to several sources; SPICE's .net / .tf):
+ * x[b][f][k] = A^-1 b[b][k] for the n_rhs columns of instance b, with the same A, pivot order and factors as cadnip_ac_solve.  Each of the
+ * B * n_freq systems is factored ONCE by its wave (csrc/ac_lu.hip: k_ac_lu_multi); the solve, the refinement step and the backward error then
+ * run per column, statement for statement as in cadnip_ac_solve: column k is bit-identical to that call with b[.][k] as its bac_host.
+ * Returned per (b, f, k): the n_pairs probe differences h = x[p_j] - x[n_j] (pairs as cadnip_ac_adjoint; n_pairs may be 0), x itself with
+ * x_host non-NULL, berr, and flags -- bit 0: a zero / non-finite pivot of system (b, f), set in all its columns, or a non-finite solution of
+ * that column.  wpb, info, cadnip_ac_set_memory and cadnip_ac_plan_info as cadnip_ac_solve; chunks of at most 64 MiB of device output,
+ * 16 n_rhs (n_pairs + n [x wanted]) bytes per system (a single system beyond that runs as a chunk of one).  CADNIP_BADARG -- and nothing
+ * launched -- also with n_rhs < 1, n_pairs < 0, n_pairs == 0 without x_host (nothing to return) or a pair index outside [-1, n). */
+int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega /* [F] */, double gmin, int32_t n_rhs,
+                          const double* b_host /* [B][K][n][2] */, int32_t n_pairs, const int32_t* pairs /* [n_pairs][2], -1 = ground */,
+                          int32_t wpb, double* h_host /* [B][F][K][n_pairs][2] */, double* x_host /* [B][F][K][n][2] or NULL */,
+                          double* berr_host /* [B][F][K] */, int32_t* flags_host /* [B][F][K] */, int32_t* info /* [4] */);
 
 /* Where the AC and adjoint sweeps keep a system's work arrays -- a handle setting, LDS by default: every call exactly as without it.
  *   CADNIP_AC_LDS   in LDS (k_ac_lu / k_ac_adj): one wave per system, refused beyond 160 KB as described above,
