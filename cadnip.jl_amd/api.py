@@ -1203,7 +1203,11 @@ def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"
     "gpu" raises for a circuit too large for the kernel, "auto" takes the host path for it and says so in ``stats["fallback"]``.
     ``memory`` (ignored with solver="host"): "lds" (default), "hbm" or "auto" as for ``ac`` -- with "hbm" / "auto" a circuit beyond the
     160 KB of LDS is solved on the GPU; ``stats["memory"]`` says which ran.  The default stays "lds": DESIGN section 9 has the measured
-    figures and leaves making "auto" the default to a later change."""
+    figures and leaves making "auto" the default to a later change.
+    ``output`` as a list of names (a string is exactly the call above): the result is then, per point, a dict name -> NoiseSol from one DC solve
+    and one restamp; the host path runs ``noise_solve`` once per output, a GPU solver makes ONE ``ac_adjoint_multi`` call per structure class
+    -- one factorisation per (point, frequency) serving every output (``noise_multi_solve_gpu``; ``stats`` then counts columns as systems and
+    has "rhs": the number of outputs).  Each NoiseSol equals the single-output call's to the bit."""
     import scipy.sparse as sp
     if solver not in ("host", "gpu", "auto"):
         raise ValueError("solver must be 'host', 'gpu' or 'auto'")
@@ -1216,6 +1220,9 @@ def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"
     pts = target.points() if sweep else [{}]
     stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
     sols = [None] * len(pts)
+    outputs = None if isinstance(output, str) else list(output)
+    if outputs is not None and (not outputs or len(set(outputs)) != len(outputs)):
+        raise ValueError("noise: output as a list needs at least one name, each once")
     for idx, st in structure_classes(mc, pts) if sweep else [([0], None)]:
         sim = BatchSimulator(mc, [pts[i] for i in idx] if sweep else None, device, st=st)
         try:
@@ -1233,7 +1240,12 @@ def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"
                 p_k = {kk: float(v[k]) for kk, v in sim.params.items()}
                 temps.append(float(pts[i].get("temp", mc.spec.temp)))
                 srcs.append(noise_sources(st, mc.circuit, p_k, u[k], temps[k], mc.spec.gmin))
-            if solver == "host":
+            if not isinstance(output, str):
+                if solver == "host":
+                    got = [{o: noise_solve(st, Gd[k], Cd[k], srcs[k], o, freqs, input, temps[k]) for o in outputs} for k in range(len(idx))]
+                else:
+                    got = noise_multi_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, outputs, freqs, input, temps, gmin, solver, stats, memory)
+            elif solver == "host":
                 got = [noise_solve(st, Gd[k], Cd[k], srcs[k], output, freqs, input, temps[k]) for k in range(len(idx))]
             else:
                 got = noise_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, output, freqs, input, temps, gmin, solver, stats, memory)
@@ -1241,6 +1253,259 @@ def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"
                 sols[i] = got[k]
         finally:
             sim.close()
+    return SweepResult(pts, sols) if sweep else sols[0]
+
+
+def adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, cols, pairs, solver, stats, memory="lds"):
+    """K adjoint right-hand sides per point against ONE factorisation per (point, frequency), on the GPU -- the transposed counterpart of
+    ``ac_multi_gpu_sweep``: ``h`` re-analyses its pivot order on ``ac_pivot_sample`` and solves A^T x = cols[k] for points x frequencies x the
+    K columns of ``cols`` ([K, n]) in ONE ``ac_adjoint_multi`` call.  Returns the probe differences H [B, F, K, P] for ``pairs``.  The gate is
+    ``noise_solve_gpu``'s, per column: a column whose flag is set or whose backward error exceeds NOISE_BERR_MAX is solved again by the host's
+    dense adjoint solve on ``Gd`` / ``Cd``.  ``stats`` counts columns as systems and carries "rhs" and "memory".  A circuit the memory home
+    refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why."""
+    from . import hip
+    _ac_memory(memory)
+    omegas = np.asarray(omegas, dtype=float)
+    cols = np.asarray(cols, dtype=complex)
+    B, F, K = len(Gd), omegas.size, cols.shape[0]
+    stats["rhs"] = K
+    to_ref = np.asarray(st.to_ref_nz)
+    sample_ref = np.empty(st.nnz)
+    sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+    h.analyze_values(sample_ref)
+    try:
+        with _ac_memory_of(h, memory):
+            H, _, berr, flags, info = h.ac_adjoint_multi(omegas, gmin, cols, pairs)
+            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
+    except hip.CadnipError as e:
+        if solver == "auto" and e.code == hip.BADARG:
+            stats["host_systems"] += B * F * K
+            stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
+            return None
+        raise
+    redo = (flags != 0) | ~(berr <= NOISE_BERR_MAX)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    pp, nn = pr[:, 0], pr[:, 1]
+    for b, f, k in zip(*np.nonzero(redo)):
+        x_adj = np.linalg.solve((1j * omegas[f] * Cd[b] + Gd[b]).T, cols[k])
+        H[b, f, k] = np.where(pp >= 0, x_adj[pp], 0.0) - np.where(nn >= 0, x_adj[nn], 0.0)
+    kept = berr[~redo]
+    stats["gpu_systems"] += int((~redo).sum())
+    stats["host_systems"] += int(redo.sum())
+    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
+    stats["wpb"] = info["wpb"]
+    stats["memory"] = used
+    return H
+
+
+def noise_multi_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, outputs, freqs, input=None, temps=27.0, gmin=1e-12, solver="gpu", stats=None,
+                          memory="lds"):
+    """``noise_solve_gpu`` for several outputs: column j of ONE ``ac_adjoint_multi`` call is e_out of ``outputs[j]``, the probe pairs are those of
+    the single-output call (``noise_probe_pairs``), and the weighting is ``noise_solve``'s per output.  Returns one dict output -> NoiseSol per
+    point; the kernel's columns are bit-identical to the single-column kernel's, so each NoiseSol equals ``noise_solve_gpu``'s for that output."""
+    freqs = np.asarray(freqs, dtype=float)
+    if freqs.size == 0:
+        raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
+    if stats is None:
+        stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    B, F, K = len(Gd), freqs.size, len(outputs)
+    temps = np.broadcast_to(np.asarray(temps, dtype=float), (B,))
+    idxs = [noise_indices(st, o, input) for o in outputs]
+    pairs, index = noise_probe_pairs(source_lists, idxs[0][1])
+    host = lambda k, o, adj=None: noise_solve(st, Gd[k], Cd[k], source_lists[k], o, freqs, input, float(temps[k]), adjoint=adj)
+    H = None
+    stats["rhs"] = K
+    if len(pairs):
+        cols = np.zeros((K, st.n), dtype=complex)
+        cols[np.arange(K), [i[0] for i in idxs]] = 1.0
+        H = adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, 2.0 * np.pi * freqs, gmin, cols, pairs, solver, stats, memory)
+    else:                                                # no source and no input: nothing to probe, the sums are empty
+        stats["host_systems"] += B * F * K
+    sols = [{o: host(k, o, None if H is None else (index, H[k, :, j])) for j, o in enumerate(outputs)} for k in range(B)]
+    for d in sols:
+        for s in d.values():
+            s.stats = stats
+    return sols
+
+
+# ---- the noise of N-ports (SPICE's .net with .noise; Spectre's sp with donoise=yes) -------------------------------------------------------
+T0 = 290.0            # K: the standard source temperature of a noise figure (IEEE)
+
+
+class NetworkNoiseSol(NetworkSol):
+    """``network_noise``'s result: a NetworkSol (``y``, ``z``, ``s``, ``s_db``) with the noise of the same ports.  ``cy`` [F, P, P] is the
+    one-sided correlation matrix of the ports' short-circuit noise currents in A^2 / Hz (Hermitian, positive semidefinite),
+    ``cy_by_source`` {source name: [F, P, P]} its parts (their sum is ``cy``), ``temp`` the circuit temperature in degrees Celsius.
+    For a two-port -- port 0 the input, port 1 the output -- the noise parameters against T0 = 290 K, all linear ratios unless named ``_db``:
+    ``ca`` [F, 2, 2] the chain-form correlation matrix of the input-referred noise voltage and current (M cy M^H, M = [[0, B], [1, D]],
+    B = -1 / y21, D = -y11 / y21), ``rn`` = ca00 / (4 k T0) in ohms, ``yopt`` the optimum source admittance, ``gamma_opt`` its reflection
+    coefficient for z0 of port 0, ``nfmin``, ``nf(zs)`` the noise factor for a source impedance ``zs`` (default: z0 of port 0; a scalar or
+    one value per frequency), ``nf_db`` / ``nfmin_db``.  With another number of ports these raise ValueError.  Where y21 == 0 the chain form
+    does not exist: the figures are inf / nan there."""
+
+    def __init__(self, freqs, ports, y, cy, cy_by_source, temp, z0=50.0, dc_x=None):
+        super().__init__(freqs, ports, y, z0, dc_x)
+        self.cy, self.cy_by_source, self.temp = cy, cy_by_source, temp
+
+    def _two_port(self):
+        if len(self.ports) != 2:
+            raise ValueError("the noise parameters (ca, rn, yopt, gamma_opt, nfmin, nf) are those of a two-port; this network has %d port(s)" % len(self.ports))
+
+    @property
+    def ca(self):
+        self._two_port()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            y11, y21 = self.y[:, 0, 0], self.y[:, 1, 0]
+            M = np.zeros((len(self.freqs), 2, 2), dtype=complex)
+            M[:, 0, 1], M[:, 1, 0], M[:, 1, 1] = -1.0 / y21, 1.0, -y11 / y21
+            return M @ self.cy @ np.conj(np.swapaxes(M, 1, 2))
+
+    @property
+    def rn(self):
+        return self.ca[:, 0, 0].real / (4.0 * K_BOLTZMANN * T0)
+
+    @property
+    def yopt(self):
+        ca = self.ca
+        with np.errstate(divide="ignore", invalid="ignore"):
+            b = ca[:, 0, 1].imag / ca[:, 0, 0].real
+            return np.sqrt(np.maximum(ca[:, 1, 1].real / ca[:, 0, 0].real - b * b, 0.0)) + 1j * b      # ca is positive semidefinite: below 0 is rounding
+
+    @property
+    def gamma_opt(self):
+        y0 = 1.0 / float(np.broadcast_to(np.asarray(self.z0, dtype=float), (2,))[0])
+        yo = self.yopt
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (y0 - yo) / (y0 + yo)
+
+    @property
+    def nfmin(self):
+        ca = self.ca
+        with np.errstate(invalid="ignore"):
+            return 1.0 + (ca[:, 0, 1].real + ca[:, 0, 0].real * self.yopt.real) / (2.0 * K_BOLTZMANN * T0)
+
+    def nf(self, zs=None):
+        ca = self.ca
+        if zs is None:
+            zs = float(np.broadcast_to(np.asarray(self.z0, dtype=float), (2,))[0])
+        zs = np.broadcast_to(np.asarray(zs, dtype=complex), (len(self.freqs),))
+        z = np.stack([np.ones(len(self.freqs), dtype=complex), np.conj(zs)], axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 1.0 + np.einsum("fi,fij,fj->f", np.conj(z), ca, z).real / (4.0 * K_BOLTZMANN * T0 * zs.real)
+
+    def nf_db(self, zs=None):
+        return 10.0 * np.log10(self.nf(zs))
+
+    @property
+    def nfmin_db(self):
+        return 10.0 * np.log10(self.nfmin)
+
+
+def network_noise_pairs(rows, source_lists):
+    """The probe pairs of a structure class's network noise: ``noise_probe_pairs`` of its sources -- the transfers T[i, s] -- and (row_j, -1)
+    for the port rows -- the admittances.  Returns (pairs [K, 2] int32, {(p, n): k})."""
+    _, index = noise_probe_pairs(source_lists)
+    for r in rows:
+        index.setdefault((int(r), -1), len(index))
+    return np.array(list(index), dtype=np.int32).reshape(-1, 2), index
+
+
+def network_noise_solve(st, G, C, sources, ports, freqs, z0=50.0, temp_c=27.0, dc_x=None, adjoint=None):
+    """The host path of ``network_noise`` on dense G (gmin already on the voltage-node diagonals) and C: per frequency ONE dense LU of A^T serves
+    the P adjoint columns -- column i solves A^T l_i = e_row_i with row_i the branch row of port i's source.  From them y[f, i, j] = -l_i[row_j]
+    and the transfer of noise source s to the short-circuit current of port i, T[i, s] = l_i[p_s] - l_i[n_s];
+    cy[f] = sum_s S_s(f) T[:, s] T[:, s]^H with S_s = noise_psd(s, temp_c, f).
+    ``adjoint``: None -- the dense solve here -- or (index, H): the probe differences H[f, i, index[(p, n)]] = l_i[p] - l_i[n] of this point,
+    solved elsewhere (``network_noise_gpu``) for every source's (p, n) and for (row_j, -1); the weighting and the sums are the same
+    statements in the same source order either way."""
+    freqs = np.asarray(freqs, dtype=float)
+    rows = port_rows(st, ports)
+    P = len(rows)
+    if adjoint is None:
+        pairs, index = network_noise_pairs(rows, [sources])
+        pp, nn = pairs[:, 0].astype(np.int64)[:, None], pairs[:, 1].astype(np.int64)[:, None]
+        E = np.zeros((st.n, P), dtype=complex)
+        E[rows, np.arange(P)] = 1.0
+    else:
+        index = adjoint[0]
+    at_rows = [index[(r, -1)] for r in rows]
+    y = np.zeros((len(freqs), P, P), dtype=complex)
+    cy = np.zeros((len(freqs), P, P), dtype=complex)
+    by_source = {s[5]: np.zeros((len(freqs), P, P), dtype=complex) for s in sources}
+    for fi, f in enumerate(freqs):
+        if adjoint is None:
+            lam = np.linalg.solve((1j * 2.0 * np.pi * f * C + G).T, E)                       # [n, P]: column i is l_i
+            Hf = (np.where(pp >= 0, lam[pp[:, 0]], 0.0) - np.where(nn >= 0, lam[nn[:, 0]], 0.0)).T
+        else:
+            Hf = adjoint[1][fi]                                                              # [P, pairs]
+        y[fi] = -Hf[:, at_rows]
+        for s in sources:
+            T = Hf[:, index[(s[0], s[1])]]
+            c = noise_psd(s, temp_c, f) * np.outer(T, np.conj(T))
+            cy[fi] += c
+            by_source[s[5]][fi] += c
+    return NetworkNoiseSol(freqs, ports, y, cy, by_source, temp_c, z0, dc_x)
+
+
+def network_noise_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, ports, freqs, z0=50.0, temps=27.0, gmin=1e-12, solver="gpu", stats=None,
+                      memory="lds", dc_x=None):
+    """The P adjoint columns of one structure class on the GPU, shaped like ``noise_solve_gpu``: ``h`` (holding the restamp at the DC points)
+    solves all points x frequencies x ports in ONE ``ac_adjoint_multi`` call (``adjoint_multi_gpu_sweep``: one factorisation per (point,
+    frequency), the gate NOISE_BERR_MAX per column, a rejected column solved again by the host's dense adjoint solve) for the class's probe
+    pairs (``network_noise_pairs``); the PSD weighting is ``network_noise_solve``'s.  Returns one NetworkNoiseSol per point (``dc_x``: their
+    DC solutions, per point).  A circuit the memory home refuses raises with solver="gpu"; with "auto" the points are solved on the host."""
+    _ac_memory(memory)
+    freqs = np.asarray(freqs, dtype=float)
+    if stats is None:
+        stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    B = len(Gd)
+    temps = np.broadcast_to(np.asarray(temps, dtype=float), (B,))
+    rows = port_rows(st, ports)
+    pairs, index = network_noise_pairs(rows, source_lists)
+    H = None
+    if freqs.size and rows:
+        cols = np.zeros((len(rows), st.n), dtype=complex)
+        cols[np.arange(len(rows)), rows] = 1.0
+        H = adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, 2.0 * np.pi * freqs, gmin, cols, pairs, solver, stats, memory)
+    sols = [network_noise_solve(st, Gd[k], Cd[k], source_lists[k], ports, freqs, z0, float(temps[k]), None if dc_x is None else dc_x[k],
+                                None if H is None else (index, H[k])) for k in range(B)]
+    for s in sols:
+        s.stats = stats
+    return sols
+
+
+def network_noise(target, ports, freqs, z0=50.0, gmin=1e-12, device=0, solver="host", memory="lds"):
+    """The noise of an N-port beside its small-signal parameters (SPICE's .net with .noise): ``ports`` as for ``network``, the linearisation as
+    for ``ac`` (the same code), the noise sources per point as for ``noise`` (``noise_sources`` at the point's temperature).  Returns a
+    NetworkNoiseSol -- ``y`` / ``z`` / ``s`` as ``network``'s, ``cy`` the correlation matrix of the ports' short-circuit noise currents and,
+    for a two-port, ``nfmin``, ``rn``, ``yopt`` / ``gamma_opt`` and ``nf(zs)`` -- or for a CircuitSweep a SweepResult of them.  All of it comes
+    from P adjoint solves per frequency: A^T l_i = e_row_i for the branch row of port i's source.  A port that is not an independent voltage
+    source raises ValueError.
+    ``solver``: "host" (default) -- one dense LU of A^T per frequency serving the P columns (``network_noise_solve``); "gpu" -- one
+    ``ac_adjoint_multi`` call per structure class, each (point, frequency) system factored once on the device for its P columns
+    (``network_noise_gpu``); "auto" -- as "gpu", with the host path for a circuit the memory home refuses.  ``memory`` as for ``ac``.
+    ``stats`` = {"gpu_systems", "host_systems", "max_berr", "wpb", "memory", "rhs"} with columns counted as systems."""
+    from contextlib import closing
+    if solver not in ("host", "gpu", "auto"):
+        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
+    _ac_memory(memory)
+    ports = list(ports)
+    freqs = np.asarray(freqs, dtype=float)
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    sweep, mc, pts = _ac_target(target)
+    sols = [None] * len(pts)
+    with closing(_ac_classes(sweep, mc, pts, gmin, device, "network_noise")) as classes:
+        for sim, st, idx, G, C, lin in classes:
+            port_rows(st, ports)
+            temps = [float(pts[i].get("temp", mc.spec.temp)) for i in idx]
+            srcs = [noise_sources(st, mc.circuit, p_i, u_i, temps[k], mc.spec.gmin) for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin)]
+            if solver == "host":
+                got = [network_noise_solve(st, Gd, Cd, srcs[k], ports, freqs, z0, temps[k], u_i) for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin)]
+            else:
+                got = network_noise_gpu(sim.h, st, G, C, [l[1] for l in lin], [l[2] for l in lin], srcs, ports, freqs, z0, temps, gmin, solver,
+                                        stats, memory, [l[4] for l in lin])
+            for k, i in enumerate(idx):
+                sols[i] = got[k]
     return SweepResult(pts, sols) if sweep else sols[0]
 
 

@@ -17,7 +17,8 @@
 // Every multiply-add is an explicit fma: the W instantiations compute the same doubles.
 // k_ac_lu_hbm / k_ac_adj_hbm (cadnip_ac_set_memory) run the same steps -- the same __device__ functions -- with the work arrays in a per-wave
 // workspace in global memory, for circuits beyond the LDS budget: persistent waves, planned by ac_hbm_plan.hpp.
-// k_ac_lu_multi / k_ac_lu_multi_hbm (cadnip_ac_solve_multi) run steps 1 and 2 once per system and steps 3 to 6 for each of K right-hand sides.
+// k_ac_lu_multi / k_ac_lu_multi_hbm (cadnip_ac_solve_multi) run steps 1 and 2 once per system and steps 3 to 6 for each of K right-hand sides;
+// k_ac_adj_multi / k_ac_adj_multi_hbm (cadnip_ac_adjoint_multi) do the same for K adjoint right-hand sides.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -323,19 +324,16 @@ __device__ __forceinline__ double ac_adj_residual(const AcAdjArgs& t, const doub
   return worst;
 }
 
-// Steps 1 to 6 of the adjoint system ls of the launch; what ac_lu_system says about wk holds here word for word
+// Steps 3 to 6 of ONE adjoint column: A^T x = c through the factors in lu, the refinement step, the backward error and the stores of
+// (system, column) lk of the launch -- h, berr, the flag, x when asked for.  `bad`: what ac_load_factor returned for the system.  Shared by
+// k_ac_adj (one column per system, lk = ls) and k_ac_adj_multi: the same statements on the same doubles in the same x / r / y.  Every word of
+// x, r and y is written before it is read, so a column leaves nothing to the next one
 template <class M>
-__device__ __forceinline__ void ac_adj_system(const AcAdjArgs& t, int ls, const AcWork& wk, int lane) {
+__device__ __forceinline__ void ac_adj_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c,
+                                              size_t lk, int bad, int lane) {
   const AcArgs& a = t.a;
   const int n = a.n;
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
   double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double2* c = (const double2*)a.bac + (size_t)inst * n;
-  const double om = a.omega[fi];
-  int bad = ac_load_factor<M>(a, lu, G, C, om, lane);
   for (int j = lane; j < n; j += 64) y[j] = c[a.cperm[j]];
   M::sync();
   ac_adj_solve<M>(t, lu, y, lane);
@@ -350,15 +348,29 @@ __device__ __forceinline__ void ac_adj_system(const AcAdjArgs& t, int ls, const 
   // ---- 5. backward error
   const double worst = ac_adj_residual<M, true>(t, G, C, om, c, x, r, lane);
   // ---- 6. store
-  double2* xo = a.x ? (double2*)a.x + (size_t)ls * n : nullptr;
+  double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
   for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
-  double2* ho = (double2*)t.h + (size_t)ls * t.n_pairs;
+  double2* ho = (double2*)t.h + lk * t.n_pairs;
   for (int k = lane; k < t.n_pairs; k += 64) {
     const int p = t.pairs[2 * k], q = t.pairs[2 * k + 1];
     const double2 xp = p >= 0 ? x[p] : make_double2(0.0, 0.0), xn = q >= 0 ? x[q] : make_double2(0.0, 0.0);
     ho[k] = make_double2(xp.x - xn.x, xp.y - xn.y);
   }
-  ac_store_status(a, ls, worst, bad, lane);
+  ac_store_status(a, (int)lk, worst, bad, lane);
+}
+
+// Steps 1 to 6 of the adjoint system ls of the launch; what ac_lu_system says about wk holds here word for word
+template <class M>
+__device__ __forceinline__ void ac_adj_system(const AcAdjArgs& t, int ls, const AcWork& wk, int lane) {
+  const AcArgs& a = t.a;
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double2* c = (const double2*)a.bac + (size_t)inst * a.n;
+  const double om = a.omega[fi];
+  const int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
+  ac_adj_column<M>(t, wk, G, C, om, c, (size_t)ls, bad, lane);
 }
 
 template <int W>
@@ -453,6 +465,52 @@ __global__ void __launch_bounds__(64 * W) k_ac_lu_multi_hbm(AcMultiArgs t, AcHbm
   const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
   const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
   for (int ls = g; ls < end; ls += m.n_waves) ac_multi_system<AcInHbm>(t, ls, wk, lane);   // a system's last column ends in the fence the next one needs
+}
+
+// ---- the multi-column adjoint kernel: A^T x_k = c_k for the K columns of an instance against ONE factorisation per system (cadnip_ac_adjoint_multi:
+// the noise of several outputs, the noise correlation matrix of an N-port) ------------------------------------------------------------------------
+// Steps 1 and 2 once per system (ac_load_factor).  Then, per column k = 0 .. K-1, ac_adj_column -- the very function k_ac_adj runs, so column k
+// holds what k_ac_adj gives with c_k as its c -- with the stores indexed by (system, column) as in ac_multi_system.  Flag bit 0: a zero /
+// non-finite pivot of the system -- in all its K columns -- or a non-finite solution of THIS column.  The M::sync() that ends a column puts its
+// last reads of x (the stores) before the next column's writes.  No atomics, no workgroup barrier.
+struct AcAdjMultiArgs {
+  AcAdjArgs t;                              // t.a.x: x out [systems][K][n] (null: not wanted); t.h: [systems][K][n_pairs]; t.a.berr / t.a.flags: [systems][K]; t.a.bac is not read
+  const double* rhs; long rhs_stride;       // c [B][K][n] complex; complex words from one instance to the next (K n)
+  int n_rhs;
+};
+
+template <class M>
+__device__ __forceinline__ void ac_adj_multi_system(const AcAdjMultiArgs& u, int ls, const AcWork& wk, int lane) {
+  const AcArgs& a = u.t.a;
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double om = a.omega[fi];
+  const int bad_pivot = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
+  for (int k = 0; k < u.n_rhs; ++k) {
+    const double2* c = (const double2*)u.rhs + (size_t)inst * u.rhs_stride + (size_t)k * a.n;
+    const size_t lk = (size_t)ls * u.n_rhs + k;               // (system, column) of the launch: within int (api.hip bounds a launch's output)
+    ac_adj_column<M>(u.t, wk, G, C, om, c, lk, bad_pivot, lane);
+    M::sync();                                                 // the last reads of this column's x before the next column's (next system's) words
+  }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj_multi(AcAdjMultiArgs u) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= u.t.a.n_sys) return;                               // the tail workgroup: no workgroup barrier anywhere below
+  ac_adj_multi_system<AcInLds>(u, ls, ac_work(lds_ac((double*)sm, u.t.a.nnz_lu, u.t.a.n, w, W)), lane);
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj_multi_hbm(AcAdjMultiArgs u, AcHbmArgs m) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.t.a.n_sys : 0;
+  const AcWork wk = ac_work(lds_ac(m.work, u.t.a.nnz_lu, u.t.a.n, g, m.n_waves));
+  for (int ls = g; ls < end; ls += m.n_waves) ac_adj_multi_system<AcInHbm>(u, ls, wk, lane);   // a system's last column ends in the fence the next one needs
 }
 
 // The launch plan -- the one place that sizes the LDS block and picks W, and the only reader of CADNIP_AC_WPB.  A compute unit holds
@@ -602,16 +660,24 @@ int launch_ac_lu(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_
   return CADNIP_OK;
 }
 
-int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x) {
+// the transposed-solve tables and the adjoint's output pointers over ac_args
+static AcAdjArgs ac_adj_args(CadnipHandle* h, int n_freq, long s0, int n_sys, double gmin) {
   AcState& A = h->ac;
-  if (L.memory < 0 || n_sys <= 0 || n_pairs <= 0 || A.dirty || !A.adj_ready) return CADNIP_BADARG;
   AcAdjArgs t;
   t.a = ac_args(h, n_freq, s0, n_sys, gmin);
-  t.a.x = want_x ? A.d_adj_x : nullptr; t.a.berr = A.d_adj_berr; t.a.flags = A.d_adj_flags;
   t.t_colptr = A.d_t_colptr; t.t_pos = A.d_t_pos; t.t_row = A.d_t_row; t.t_diag = A.d_t_diag;
   t.ut_rows = A.d_ut_rows; t.ut_lev_ptr = A.d_ut_lev_ptr; t.lt_rows = A.d_lt_rows; t.lt_lev_ptr = A.d_lt_lev_ptr;
   t.a_colptr = A.d_a_colptr; t.a_row = A.d_a_row; t.a_pos = A.d_a_pos;
-  t.pairs = A.d_pairs; t.h = A.d_h; t.n_ut_lev = A.n_ut_lev; t.n_lt_lev = A.n_lt_lev; t.n_pairs = n_pairs;
+  t.n_ut_lev = A.n_ut_lev; t.n_lt_lev = A.n_lt_lev;
+  return t;
+}
+
+int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x) {
+  AcState& A = h->ac;
+  if (L.memory < 0 || n_sys <= 0 || n_pairs <= 0 || A.dirty || !A.adj_ready) return CADNIP_BADARG;
+  AcAdjArgs t = ac_adj_args(h, n_freq, s0, n_sys, gmin);
+  t.a.x = want_x ? A.d_adj_x : nullptr; t.a.berr = A.d_adj_berr; t.a.flags = A.d_adj_flags;
+  t.pairs = A.d_pairs; t.h = A.d_h; t.n_pairs = n_pairs;
   if (L.memory == CADNIP_AC_HBM) {
     const AcHbmPlan& p = L.hbm;
     if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
@@ -654,6 +720,33 @@ int launch_ac_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int
   ProfScope ps(h, "ac_lu_multi");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
   TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
+  HIP_TRY(hipGetLastError());
+  return CADNIP_OK;
+}
+
+int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x) {
+  AcState& A = h->ac;
+  if (L.memory < 0 || n_sys <= 0 || n_rhs < 1 || n_pairs < 0 || (n_pairs == 0 && !want_x) || A.dirty || !A.adj_ready) return CADNIP_BADARG;
+  AcAdjMultiArgs u;
+  u.t = ac_adj_args(h, n_freq, s0, n_sys, gmin);
+  u.t.a.bac = nullptr; u.t.a.x = want_x ? A.d_multi_x : nullptr; u.t.a.berr = A.d_multi_berr; u.t.a.flags = A.d_multi_flags;
+  u.t.pairs = A.d_multi_pairs; u.t.h = A.d_multi_h; u.t.n_pairs = n_pairs;
+  u.rhs = A.d_multi_rhs; u.rhs_stride = (long)n_rhs * h->n; u.n_rhs = n_rhs;
+  if (L.memory == CADNIP_AC_HBM) {
+    const AcHbmPlan& p = L.hbm;
+    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
+    TRY_RC(ac_work_reserve(h, p.work_bytes));
+    ProfScope ps(h, "ac_adj_multi_hbm");
+    const AcHbmArgs m{A.d_work, p.n_waves};
+    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
+    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_multi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, m); return CADNIP_OK; }));
+    HIP_TRY(hipGetLastError());
+    return CADNIP_OK;
+  }
+  const AcPlan& p = L.lds;
+  ProfScope ps(h, "ac_adj_multi");
+  const int grid = (n_sys + p.wpb - 1) / p.wpb;
+  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }

@@ -871,8 +871,9 @@ int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, doub
 // The multi-column sweep x[b][f][k] = (A[b][f])^-1 b[b][k] with A as above: S = B n_freq systems through k_ac_lu_multi (ac_lu.hip), which factors
 // each system once, exactly as k_ac_lu does, and runs the solve, the refinement and the backward error per column.  Same rules as
 // cadnip_ac_solve; a system's device output is 16 K (n_pairs + n [x wanted]) bytes.  Buffers live in AcState.
-int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* b_host, int32_t n_pairs,
-                          const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
+// cadnip_ac_adjoint_multi is the same call on A^T: x[b][f][k] = (A[b][f])^-T c[b][k] through k_ac_adj_multi, with the transposed tables built on first use.
+static int ac_multi_call(CadnipHandle* h, bool adjoint, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* b_host, int32_t n_pairs,
+                         const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || n_rhs < 1 || !b_host || n_pairs < 0 || (n_pairs > 0 && (!pairs || !h_host)) || (n_pairs == 0 && !x_host) ||
       !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
   const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_rhs, P = n_pairs;
@@ -883,7 +884,7 @@ int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega, 
   const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb) : plan;
   if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
   HIP_TRY(hipStreamSynchronize(h->stream));
-  TRY(ac_lu_prepare(h));
+  TRY(ac_lu_prepare(h, adjoint));
   AcState& A = h->ac;
   if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
   auto grow = [](auto** p, size_t* cap, size_t need, size_t words) {       // one buffer to `need` units of `words` elements
@@ -909,7 +910,7 @@ int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega, 
   if (P) HIP_TRY(hipMemcpy(A.d_multi_pairs, pairs, P * 2 * sizeof(int), hipMemcpyHostToDevice));
   for (size_t s0 = 0; s0 < S; s0 += chunk) {
     const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_multi(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin, n_rhs, n_pairs, want_x));
+    TRY((adjoint ? launch_ac_adjoint_multi : launch_ac_multi)(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin, n_rhs, n_pairs, want_x));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (P) HIP_TRY(hipMemcpy(h_host + s0 * K * P * 2, A.d_multi_h, ns * K * P * 2 * sizeof(double), hipMemcpyDeviceToHost));
     if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * K * n * 2, A.d_multi_x, ns * K * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
@@ -918,6 +919,16 @@ int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega, 
   }
   ac_report(h, plan, tail, S, chunk, info);
   return CADNIP_OK;
+}
+
+int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* b_host, int32_t n_pairs,
+                          const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
+  return ac_multi_call(h, false, n_freq, omega, gmin, n_rhs, b_host, n_pairs, pairs, wpb, h_host, x_host, berr_host, flags_host, info);
+}
+
+int cadnip_ac_adjoint_multi(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* c_host, int32_t n_pairs,
+                            const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
+  return ac_multi_call(h, true, n_freq, omega, gmin, n_rhs, c_host, n_pairs, pairs, wpb, h_host, x_host, berr_host, flags_host, info);
 }
 
 int cadnip_lu_stats(CadnipHandle* h, int32_t* nnz_lu, int32_t* n_terms, int32_t* n_levels, int32_t* n_fwd, int32_t* n_bwd) {

@@ -148,7 +148,8 @@ struct AcState {
   double *d_h = nullptr, *d_adj_x = nullptr, *d_adj_berr = nullptr;
   int* d_adj_flags = nullptr;
   size_t cap_pairs = 0, cap_adj_sys = 0, cap_adj_x = 0;   // pairs d_pairs and a system of d_h hold, systems of the outputs, systems of d_adj_x
-  // multi-column sweep (k_ac_lu_multi, cadnip_ac_solve_multi): its own transfer buffers, each grown on demand to the capacity beside it
+  // multi-column sweeps (k_ac_lu_multi, cadnip_ac_solve_multi; k_ac_adj_multi, cadnip_ac_adjoint_multi -- the same shapes, one set serves both):
+  // their own transfer buffers, each grown on demand to the capacity beside it
   double *d_multi_rhs = nullptr, *d_multi_h = nullptr, *d_multi_x = nullptr, *d_multi_berr = nullptr;   // [B][K][n], [S][K][pairs], [S][K][n] complex; [S][K]
   int *d_multi_pairs = nullptr, *d_multi_flags = nullptr;                                              // [pairs][2]; [S][K]
   size_t cap_multi_rhs = 0, cap_multi_h = 0, cap_multi_x = 0, cap_multi_pairs = 0, cap_multi_cols = 0; // complex words, complex words, complex words, pairs, (system, column)s
@@ -281,6 +282,9 @@ int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, i
 // ... of A x_k = b_k for the n_rhs columns per instance in h->ac.d_multi_rhs through k_ac_lu_multi (one factorisation per system): per (system,
 // column) the n_pairs probe differences into d_multi_h, x into d_multi_x with want_x, berr and flags into d_multi_berr / d_multi_flags
 int launch_ac_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x);
+// ... of A^T x_k = c_k for the n_rhs columns per instance in h->ac.d_multi_rhs through k_ac_adj_multi (one factorisation per system; needs
+// ac_lu_prepare(h, true)): the outputs as launch_ac_multi, in the same buffers
+int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

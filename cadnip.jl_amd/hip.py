@@ -23,7 +23,7 @@ AC_MEMORY = {"lds": 0, "hbm": 1, "auto": 2}     # CADNIP_AC_LDS / _HBM / _AUTO (
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
@@ -409,6 +409,18 @@ class Handle:
         caller that sweeps repeatedly spares the first touch of a fresh array, which above 32 MiB costs more than the sweep (DESIGN section 9);
         it implies ``want_x``.  No column, neither pairs nor x, a pair index outside [-1, n), a circuit the memory setting refuses or an
         invalid ``wpb`` raise CadnipError(CADNIP_BADARG)."""
+        return self._ac_multi("cadnip_ac_solve_multi", omega, gmin, b, pairs, wpb, want_x, x_out)
+
+    def ac_adjoint_multi(self, omega, gmin, c, pairs=None, wpb=0, want_x=False, x_out=None):
+        """cadnip_ac_adjoint_multi: x[b, f, k] solves A[b, f]^T x = c[b, k] for K right-hand sides per instance against ONE factorisation per
+        system, A, the pivot order and the transposed solves as ``ac_adjoint`` (csrc/ac_lu.hip: k_ac_adj_multi) -- column k is bit-identical
+        to ``ac_adjoint(omega, gmin, c[:, k], pairs)``.  ``c`` [B, K, n] complex (or [K, n], shared by all instances); everything else --
+        ``pairs``, ``x_out``, the returned (h [B, F, K, P] or None, x [B, F, K, n] or None, berr [B, F, K], flags [B, F, K], info) and what
+        raises -- as ``ac_solve_multi``, except that x is returned only when asked for."""
+        return self._ac_multi("cadnip_ac_adjoint_multi", omega, gmin, c, pairs, wpb, want_x, x_out)
+
+    def _ac_multi(self, entry, omega, gmin, b, pairs, wpb, want_x, x_out):
+        """the two multi-column entry points: one argument list, one layout"""
         om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
         bb = np.asarray(b, dtype=np.complex128)
         B, n, F = self.B, self.st.n, om.size
@@ -425,9 +437,9 @@ class Handle:
         berr, flags, info = np.empty((B, F, K)), np.zeros((B, F, K), dtype=np.int32), np.zeros(4, dtype=np.int32)
         if F == 0:
             return hh, x, berr, flags, dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
-        _check(self.lib.cadnip_ac_solve_multi(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), C.c_int32(K), bb.ctypes.data_as(_D), C.c_int32(P),
-                                              _ip(pr) if P else None, C.c_int32(int(wpb)), None if hh is None else hh.ctypes.data_as(_D),
-                                              None if x is None else x.ctypes.data_as(_D), _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_solve_multi")
+        _check(getattr(self.lib, entry)(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), C.c_int32(K), bb.ctypes.data_as(_D), C.c_int32(P),
+                                        _ip(pr) if P else None, C.c_int32(int(wpb)), None if hh is None else hh.ctypes.data_as(_D),
+                                        None if x is None else x.ctypes.data_as(_D), _dp(berr), _ip(flags), _ip(info)), entry)
         return hh, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
 
     def ac_set_memory(self, mode="lds", max_waves=0):

@@ -168,6 +168,15 @@ function ac_adjoint(ws::GPUEvalWorkspace, omega::Vector{Float64}, c::Matrix{Comp
                 ws.handle, F, omega, gmin, c, K, pairs, wpb, h, C_NULL, berr, flags, info), "cadnip_ac_adjoint")
     return h, berr, flags
 end
+# K adjoint right-hand sides per factorisation: c of size (n, K, B), and of every column's solution h[j, k, f, b] = x[p_j] - x[n_j] for the
+# 0-based probe pairs pairs[:, j].  Column k is bit-identical to ac_adjoint with c[:, k, :].  Returns (h, berr, flags), berr / flags of size (K, F, B).
+function ac_adjoint_multi(ws::GPUEvalWorkspace, omega::Vector{Float64}, c::Array{ComplexF64,3}, pairs::Matrix{Int32}; gmin=1e-12, wpb=0)
+    K, B, F, P = size(c, 2), size(c, 3), length(omega), size(pairs, 2)
+    h = Array{ComplexF64}(undef, P, K, F, B); berr = Array{Float64}(undef, K, F, B); flags = Array{Int32}(undef, K, F, B); info = zeros(Int32, 4)
+    check(ccall((:cadnip_ac_adjoint_multi, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Int32, Ptr{ComplexF64}, Int32, Ptr{Int32}, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                ws.handle, F, omega, gmin, K, c, P, pairs, wpb, h, C_NULL, berr, flags, info), "cadnip_ac_adjoint_multi")
+    return h, berr, flags
+end
 # Where ac_solve / ac_adjoint keep a system's work arrays from now on: :lds (the default: in LDS, refused beyond 160 KB), :hbm (a workspace in
 # device memory, persistent waves, the same doubles) or :auto (LDS when its launch plan accepts the circuit, else HBM); max_waves > 0 caps the
 # waves of a launch.  ac_plan_info: (memory, n_waves, work_bytes, lds_bytes) of the last sweep that launched.

@@ -264,6 +264,17 @@ int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega /
                           const double* b_host /* [B][K][n][2] */, int32_t n_pairs, const int32_t* pairs /* [n_pairs][2], -1 = ground */,
                           int32_t wpb, double* h_host /* [B][F][K][n_pairs][2] */, double* x_host /* [B][F][K][n][2] or NULL */,
                           double* berr_host /* [B][F][K] */, int32_t* flags_host /* [B][F][K] */, int32_t* info /* [4] */);
+/* Many adjoint right-hand sides per factorisation (the noise of several outputs, the noise correlation matrix of an N-port; SPICE's .net with
+ * .noise): x[b][f][k] solves A^T x = c[b][k] for the n_rhs columns of instance b, with the same A, pivot order and factors as cadnip_ac_adjoint.
+ * Each of the B * n_freq systems is factored ONCE by its wave (csrc/ac_lu.hip: k_ac_adj_multi); the transposed solve, the refinement step and
+ * the backward error then run per column in the very statements of cadnip_ac_adjoint: column k is bit-identical to that call with c[.][k] as
+ * its c_host -- h, x, berr and the flag, in LDS and in device memory, for every wpb.  Everything else -- what is returned per (b, f, k), the
+ * flags (a bad pivot of a system flags all its columns), wpb, info, cadnip_ac_set_memory, cadnip_ac_plan_info, the chunks of at most 64 MiB of
+ * device output with 16 n_rhs (n_pairs + n [x wanted]) bytes per system, and every CADNIP_BADARG -- exactly as cadnip_ac_solve_multi. */
+int cadnip_ac_adjoint_multi(CadnipHandle* h, int32_t n_freq, const double* omega /* [F] */, double gmin, int32_t n_rhs,
+                            const double* c_host /* [B][K][n][2] */, int32_t n_pairs, const int32_t* pairs /* [n_pairs][2], -1 = ground */,
+                            int32_t wpb, double* h_host /* [B][F][K][n_pairs][2] */, double* x_host /* [B][F][K][n][2] or NULL */,
+                            double* berr_host /* [B][F][K] */, int32_t* flags_host /* [B][F][K] */, int32_t* info /* [4] */);
 
 /* Where the AC and adjoint sweeps keep a system's work arrays -- a handle setting, LDS by default: every call exactly as without it.
  *   CADNIP_AC_LDS   in LDS (k_ac_lu / k_ac_adj): one wave per system, refused beyond 160 KB as described above,
