@@ -229,7 +229,7 @@ static int fused2_blocks(CadnipHandle* h) {
   return CADNIP_OK;
 }
 
-// The one place that decides what a fused launch runs, and the only reader of the diagnostic switches CADNIP_F2_NODIRECT / _TEAM / _WPB
+// The one place that decides what a fused launch runs, and the only reader of the diagnostic switches CADNIP_F2_NODIRECT / _TEAM / _WPB / _STEPS_PACKED
 // (CADNIP_F2_NC: f2_prepare, where the tables are built; CADNIP_F2_DEBUG prints the plan, launch_fused2).
 F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode) {
   F2Plan p;
@@ -288,7 +288,15 @@ F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode) {
   if (bytes(wpb) > LDS_BUDGET) return p;
   // resident workgroups only: the instances beyond them are handed out by the in-kernel queue as waves become free
   const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(LDS_BUDGET / bytes(wpb), (size_t)(32 / wpb)));
-  p.wpb = wpb; p.shmem = bytes(wpb); p.grid = std::min((h->B + wpb - 1) / wpb, S.n_cu * wg_per_cu); p.rc = CADNIP_OK;
+  // The step descriptors are staged pre-decoded (lds_layout.hpp: lds_step_predecode) when every word of a work array has a 16-bit byte
+  // offset and the flag bytes fit without costing a resident instance: neither wpb nor the workgroups per CU may change for them.  Otherwise,
+  // and under CADNIP_F2_STEPS_PACKED=1 (diagnostic, tests: the two decodes must agree to the bit), the kernel decodes the packed words.
+  size_t shmem = bytes(wpb);
+  if (p.steps && lds_steps_predec_ok(S.lu_words, h->n) && !getenv("CADNIP_F2_STEPS_PACKED")) {
+    const size_t pd = lds_bytes(lds_sweep((size_t)0, p.tab_len, lds_sweep_desc_words(p.steps->len, true), S.lu_words, h->n, 0, wpb));
+    if (pd <= LDS_BUDGET && (int)std::max<size_t>(1, std::min<size_t>(LDS_BUDGET / pd, (size_t)(32 / wpb))) == wg_per_cu) { p.step_predec = true; shmem = pd; }
+  }
+  p.wpb = wpb; p.shmem = shmem; p.grid = std::min((h->B + wpb - 1) / wpb, S.n_cu * wg_per_cu); p.rc = CADNIP_OK;
   return p;
 }
 
@@ -307,6 +315,7 @@ static int launch_fused2(CadnipHandle* h, const TranArgs& t, int rounds, const F
   f.n = h->n; f.nnz = h->nnz; f.nnz_lu = S.lu_words;
   f.n_pre = S.n_pre; f.n_post = S.n_post; f.nc = S.nc; f.dn0 = S.dn0; f.n_fwd = S.n_fwd;
   if (p.steps) { f.team_desc = p.steps->d; f.team_desc_len = p.steps->len; f.ts_pre = p.steps->n_steps[0]; f.ts_post = p.steps->n_steps[1]; f.ts_fwd = p.steps->n_steps[2]; }
+  f.step_predec = p.step_predec ? 1 : 0;
   f.step_refresh = step ? step->refresh : 0; f.step_resid = step ? step->resid : nullptr; f.step_norm = step ? step->norm : nullptr;
   f.step_reps = step ? step->reps : 1; f.step_skip = step ? step->skip : 0;
   if (p.keep_factors) {       // the kept factors of instances that are not resident live in HBM
@@ -332,8 +341,8 @@ static int launch_fused2(CadnipHandle* h, const TranArgs& t, int rounds, const F
     if (step) TRY_RC(fteam_launch_step(std::min(h->B, S.n_cu), p.shmem, h->stream, f));   // (one workgroup per CU, whatever p.grid allows)
     else TRY_RC(fteam_launch(p.nw, p.grid, p.shmem, h->stream, f));
   } else {
-    const size_t tab_b = (size_t)p.tab_len / 2 * 8, desc_b = (size_t)f.team_desc_len * 8;
-    if (debug) fprintf(stderr, "[cadnip f2] B %d n_cu %d wpb %d grid %d shmem %zu (tables %zu, steps %zu, per instance %zu) rounds %d nc %d passes %d+%d steps %d+%d / %d variant %d\n", h->B, S.n_cu, p.wpb, p.grid, p.shmem, tab_b, desc_b, (p.shmem - tab_b - desc_b) / p.wpb, rounds, S.nc, S.n_pre, S.n_post, f.ts_pre, f.ts_post, f.ts_fwd, p.var);
+    const size_t tab_b = (size_t)p.tab_len / 2 * 8, desc_b = (size_t)lds_sweep_desc_words(f.team_desc_len, p.step_predec) * 8;
+    if (debug) fprintf(stderr, "[cadnip f2] B %d n_cu %d wpb %d grid %d shmem %zu (tables %zu, steps %zu, per instance %zu) rounds %d nc %d passes %d+%d steps %d+%d / %d (%s) variant %d\n", h->B, S.n_cu, p.wpb, p.grid, p.shmem, tab_b, desc_b, (p.shmem - tab_b - desc_b) / p.wpb, rounds, S.nc, S.n_pre, S.n_post, f.ts_pre, f.ts_post, f.ts_fwd, p.step_predec ? "pre-decoded" : "packed", p.var);
     TRY_RC(p.var == 0 ? f2_launch_variant<0>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
          : p.var == 1 ? f2_launch_variant<1>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
                       : f2_launch_variant<2>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f));

@@ -53,6 +53,7 @@ struct F2Args {
   double* lufac;                    // [B][nnz_lu] kept factors of the instances that are not resident (between launches / while queued)
   const unsigned long long* team_desc; int team_desc_len;   // team kernel (fused_team_kernel.hpp): step descriptors of the linear solve (f2_program.cpp: f2_build_team)
   int ts_pre, ts_post, ts_fwd;      // ... steps of the pre-core, post-core and forward-only lists
+  int step_predec;                  // sweep kernel, lean variant: 1 = the descriptors are staged pre-decoded (lds_layout.hpp: lds_step_predecode; fused2.hip: fused2_plan decides)
   int par_words;                    // team kernel: doubles of the LDS-staged sp_mos1 parameter rows (F2Block::lds_par)
   int step_refresh; double *step_resid, *step_norm;   // team kernel, STEP mode (cadnip_newton_step_fused): refactor or use f.lufac; optional outputs
   int step_reps, step_skip;         // STEP mode, measurement only (cadnip_debug_step_time): repeat the same iteration, leave phases out (1 stamping, 2 combine, 4 linear-solve steps, 8 dense core)
@@ -345,12 +346,27 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   const TranArgs& a = f.t;
   const unsigned* tab = (const unsigned*)sm;
   // lean variant: the linear solve as straight-line steps (f2_program.cpp: f2_build_steps), their 16-byte lane descriptors staged behind the tables
-  const LdsSweep<double*> L = lds_sweep((double*)sm, f.tab_len, LEAN ? f.team_desc_len : 0, f.nnz_lu, n, w, WPB);
+  // ... as the host packs them, or pre-decoded on the way in (lds_layout.hpp: lds_step_predecode; one flag byte per lane and step behind them)
+  const bool predec = LEAN && f.step_predec;
+  const LdsSweep<double*> L = lds_sweep((double*)sm, f.tab_len, LEAN ? lds_sweep_desc_words(f.team_desc_len, predec) : 0, f.nnz_lu, n, w, WPB);
   const uint4* tdesc = (const uint4*)L.desc;
+  const unsigned char* tflag = (const unsigned char*)(L.desc + (LEAN ? f.team_desc_len : 0));
   if constexpr (LEAN) {
-    const uint2* src = (const uint2*)f.team_desc;
-    uint2* dst = (uint2*)L.desc;
-    for (int i = tid; i < f.team_desc_len; i += 64 * WPB) dst[i] = src[i];
+    if (predec) {
+      const uint4* src = (const uint4*)f.team_desc;
+      uint4* dst = (uint4*)L.desc;
+      unsigned char* fl = (unsigned char*)(L.desc + f.team_desc_len);
+      for (int i = tid; i < f.team_desc_len / 2; i += 64 * WPB) {     // (64 * WPB is a multiple of 64: entry i belongs to lane i & 63 = lane0)
+        const uint4 d = src[i];
+        const StepPredec p = lds_step_predecode(d.x, d.y, d.z, d.w, (unsigned)(f.nnz_lu + n + lane0));
+        dst[i] = make_uint4(p.x, p.y, p.z, p.w);
+        fl[i] = (unsigned char)p.flags;
+      }
+    } else {
+      const uint2* src = (const uint2*)f.team_desc;
+      uint2* dst = (uint2*)L.desc;
+      for (int i = tid; i < f.team_desc_len; i += 64 * WPB) dst[i] = src[i];
+    }
   }
   __syncthreads();
   const int nW = L.nW;                                    // LU | rhs | trash : zeroed every round
@@ -751,9 +767,48 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
       }
       CADNIP_WAVE_SYNC();
     };
+    // ... and from the pre-decoded descriptors (lds_layout.hpp: lds_step_predecode): the same reads, the same arithmetic in the same order,
+    // the same words written by the group leaders -- but an operand address is W's byte address plus a 16-bit half of the descriptor, the
+    // lane-group tests compare the lane's flag byte with a constant, and every lane stores to its entry (a non-leader's is its trash word,
+    // which is also what it reads as acc0: its result was and is discarded)
+    auto run_steps_pd = [&](const int s_first, const int s_count) {
+      if (s_count <= 0) return;
+      const uint4* dp = tdesc + (size_t)s_first * 64 + lane;
+      const unsigned char* fp = tflag + (size_t)s_first * 64 + lane;
+      char* const Wb = (char*)W;
+      uint4 D = dp[0];
+      unsigned F = fp[0];
+      for (int si = 0; si < s_count; ++si) {
+        double* const pp = (double*)(Wb + (D.x & 0xFFFFu));
+        const double piv = *(const double*)(Wb + (D.x >> 16));
+        const double a0v = *(const double*)(Wb + (D.y & 0xFFFFu)), b0v = *(const double*)(Wb + (D.y >> 16));
+        const double a1v = *(const double*)(Wb + (D.z & 0xFFFFu)), b1v = *(const double*)(Wb + (D.z >> 16));
+        const double a2v = *(const double*)(Wb + (D.w & 0xFFFFu)), b2v = *(const double*)(Wb + (D.w >> 16));
+        const double acc0 = *pp;
+        const uint4 Dn = dp[(size_t)(si + 1) * 64];
+        const unsigned Fn = fp[(size_t)(si + 1) * 64];
+        const unsigned fs = __builtin_amdgcn_readfirstlane(F), maxlg = fs & 7u;
+        double part = fma(a2v, b2v, fma(a1v, b1v, a0v * b0v));
+        if (maxlg >= 1) { const double o = dpp_f64<0xB1>(part); part += F >= 16u ? o : 0.0; }
+        if (maxlg >= 2) { const double o = dpp_f64<0x4E>(part); part += F >= 32u ? o : 0.0; }
+        if (maxlg >= 3) { const double o = dpp_f64<0x141>(part); part += F >= 48u ? o : 0.0; }
+        if (maxlg >= 4) { const double o = dpp_f64<0x140>(part); part += F >= 64u ? o : 0.0; }
+        double acc = acc0 - part;
+        if (fs & 8u) {
+          if (piv == 0.0 || !isfinite(piv)) bad = 1;        // (lanes and entries without a division read the constant 1.0)
+          acc = fast_div(acc, piv);
+        }
+        *pp = acc;
+        D = Dn; F = Fn;
+      }
+      CADNIP_WAVE_SYNC();
+    };
+    auto solve_steps = [&](const int s_first, const int s_count) {
+      if (predec) run_steps_pd(s_first, s_count); else run_steps(s_first, s_count);
+    };
     if constexpr (LEAN) {
-      if (refresh) run_steps(0, f.ts_pre);
-      else run_steps(f.ts_pre + f.ts_post, f.ts_fwd);       // kept factors: the forward substitution alone
+      // refactor + forward substitution, or on kept factors the forward substitution alone
+      solve_steps(refresh ? 0 : f.ts_pre + f.ts_post, refresh ? f.ts_pre : f.ts_fwd);
     } else {
       if (refresh) run_passes(0, f.n_pre);
       else run_passes(f.n_pre + f.n_post, f.n_fwd);
@@ -773,7 +828,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
       CADNIP_WAVE_SYNC();
     }
     CADNIP_TRACE_POINT(5);
-    if constexpr (LEAN) run_steps(f.ts_pre, f.ts_post); else run_passes(f.n_pre, f.n_post);
+    if constexpr (LEAN) solve_steps(f.ts_pre, f.ts_post); else run_passes(f.n_pre, f.n_post);
     CADNIP_TRACE_POINT(3);
     // ---- Newton update + step controller (registers / LDS; HBM only for history and outputs)
     if (DC) {

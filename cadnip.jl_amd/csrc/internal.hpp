@@ -313,6 +313,7 @@ struct F2Plan {
   int var = 0, wpb = 0, grid = 0; size_t shmem = 0;
   int tab_lo = 0, tab_len = 0;          // staged table range (32-bit words)
   const StepList* steps = nullptr;      // step descriptors staged behind it (null: the pass program of the full table)
+  bool step_predec = false;   // sweep kernel: the descriptors are staged pre-decoded, a flag byte per lane and step behind them (lds_layout.hpp)
   bool keep_factors = false;  // Newton mode 1 / single step: kept factors in HBM
 };
 F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode);

@@ -25,7 +25,30 @@ namespace cadnip {
 LDS_HD int lds_work_words(int lu_words, int n) { return lu_words + n + F2_TRASH; }
 #define LDS_CONSTS 2       // the step programs' constant words 0.0, 1.0 directly behind the trash words (f2_build_steps / f2_build_team)
 
-// sweep kernel k_fused2<WPB>: tables | step descriptors (lean variant) | WPB x [ W | consts | u | beta ]; W, u, beta: of instance w
+// ---- the sweep kernel's PRE-DECODED step descriptors.  f2_build_steps packs a lane's step as eight 15-bit WORD offsets into W with a flag in
+// every field's top bit (x: entry | pivot, y: a0 | b0, z: a1 | b1, w: a2 | b2; f2_program.cpp).  That format stays what the host builds and
+// what k_lu_f2s / k_lu_steps / k_fteam read; k_fused2 converts it once per launch, while it stages the descriptors, into eight 16-bit BYTE
+// offsets from the instance's W -- an operand address is one add of a 16-bit half -- with no flag among them:
+//   * a lane that does not lead its group gets its own trash word as its entry, so every lane stores to its entry unconditionally;
+//   * the lane's group width and the step's two uniform flags go to one byte per lane and step behind the descriptors:
+//     bits 4-6 log2 of the lane group's width, bit 3 "an entry of this step divides", bits 0-2 log2 of the step's widest group --
+//     `lg >= k` is `byte >= 16 k`, one compare against an inline constant.
+// Byte offsets need every word of W | consts below 8192: lds_steps_predec_ok; the launch plan (fused2.hip: fused2_plan) decides.
+struct StepPredec { unsigned x, y, z, w, flags; };
+LDS_HD StepPredec lds_step_predecode(unsigned x, unsigned y, unsigned z, unsigned w, unsigned trash_word) {
+  StepPredec r;
+  r.x = ((x & 0x8000u) ? (x & 0x7FFFu) : trash_word) << 3 | ((x >> 16) & 0x7FFFu) << 19;
+  r.y = (y & 0x7FFF7FFFu) << 3; r.z = (z & 0x7FFF7FFFu) << 3; r.w = (w & 0x7FFF7FFFu) << 3;
+  const unsigned lg = (x >> 31) | ((y >> 14) & 2u) | ((y >> 29) & 4u);
+  const unsigned maxlg = ((z >> 15) & 1u) | ((z >> 30) & 2u) | ((w >> 13) & 4u);
+  r.flags = lg << 4 | (w >> 31) << 3 | maxlg;
+  return r;
+}
+LDS_HD bool lds_steps_predec_ok(int lu_words, int n) { return lu_words + n + F2_TRASH + LDS_CONSTS <= 8192; }
+// 64-bit words of the descriptor area: desc_len as uploaded (two per lane and step), plus one flag byte per lane and step when pre-decoded
+LDS_HD int lds_sweep_desc_words(int desc_len, bool predec) { return desc_len + (predec ? desc_len / 16 : 0); }
+
+// sweep kernel k_fused2<WPB>: tables | step descriptors (lean variant; desc_len = lds_sweep_desc_words) | WPB x [ W | consts | u | beta ]; W, u, beta: of instance w
 template <class P> struct LdsSweep { P desc, W, u, beta, end; int nW, per; };   // nW, per: doubles of one work array / one instance
 template <class P> LDS_HD LdsSweep<P> lds_sweep(P base, int tab_len, int desc_len, int lu_words, int n, int w, int wpb) {
   LdsSweep<P> L;
