@@ -25,7 +25,7 @@ static __device__ int g_trace_wave;   // the traced wave of workgroup 0 (team ke
 __shared__ unsigned long long g_trace_last;
 // -DCADNIP_TRACE=1: the phase boundaries of a Newton round only (a point costs ~250 cycles: the fine points inside the device functions and
 // the update shift what they measure); -DCADNIP_TRACE=2: every point.
-#define CADNIP_TRACE_FINE(id) (((id) >= 8 && (id) <= 15) || (id) >= 20 || (id) == 0 || (id) == 2)
+#define CADNIP_TRACE_FINE(id) (((id) >= 8 && (id) <= 15) || (id) >= 18 || (id) == 0 || (id) == 2)
 #define CADNIP_TRACE_POINT(id)                                                                          \
   do {                                                                                                  \
     if ((CADNIP_TRACE + 0 >= 2 || !CADNIP_TRACE_FINE(id)) && blockIdx.x == 0 && (int)(threadIdx.x >> 6) == g_trace_wave) { \
@@ -35,12 +35,16 @@ __shared__ unsigned long long g_trace_last;
       }                                                                                                 \
     }                                                                                                   \
   } while (0)
+// makes the point behind it wait for `x` (a value still in flight from LDS or global memory): the compiler must have it in a register here
+#define CADNIP_TRACE_USE(x) asm volatile("" ::"v"(x))
 #elif defined(CADNIP_MARKS)
 // analysis build (tools/kernel_regs.sh ... -DCADNIP_MARKS): the trace points become comments in the assembly, so that the instructions of a
 // phase can be counted statically (tools/phase_instr.py)
 #define CADNIP_TRACE_POINT(id) asm volatile("; @@MARK " #id)
+#define CADNIP_TRACE_USE(x) do {} while (0)
 #else
 #define CADNIP_TRACE_POINT(id) do {} while (0)
+#define CADNIP_TRACE_USE(x) do {} while (0)
 #endif
 
 // swap a double between lanes 2j and 2j+1 (DPP quad_perm [1,0,3,2]); all lanes of the wave must be active
@@ -828,6 +832,11 @@ __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out&
   const double lambda = par_of(d, M1_LAMBDA), Beta = par_of(d, M1_BETA);
   const int vdep = Out::DIRECT ? d.ipar[d.dev] : 0;       // bit r: reactive branch r uses a charge unknown
   __builtin_amdgcn_sched_barrier(0);
+  // (trace build: the node and u reads have returned | the first parameter group has | what is left of the load section)
+  CADNIP_TRACE_USE(Vd); CADNIP_TRACE_USE(Vg); CADNIP_TRACE_USE(Vs); CADNIP_TRACE_USE(Vb); CADNIP_TRACE_USE(Vdi); CADNIP_TRACE_USE(Vsi);
+  CADNIP_TRACE_POINT(18);
+  CADNIP_TRACE_USE(type);
+  CADNIP_TRACE_POINT(19);
   CADNIP_TRACE_POINT(20);
   double w_gs, w_ds, w_bs, w_bd;
   m1_limit(d, u, type, vt, tPhi, tVbi, gamma, Vg, Vb, Vdi, Vsi, l0, l1, l2, l3, w_gs, w_ds, w_bs, w_bd);

@@ -201,6 +201,7 @@ static int fused2_blocks(CadnipHandle* h) {
     auto first_of = [&](int ta, int tb) { for (int i = 0; i < nb; ++i) if (hb[i].type == ta || hb[i].type == tb) return i; return -1; };
     S.rc_blk = first_of(CADNIP_DEV_CAPACITOR, CADNIP_DEV_RESISTOR);
     S.src_blk = first_of(CADNIP_DEV_VSOURCE, CADNIP_DEV_ISOURCE);
+    S.src_count = S.src_blk >= 0 ? hb[S.src_blk].count : 0;
     S.lean = true;
     for (int i = 0; i < nb; ++i) {
       const int ty = hb[i].type;
@@ -229,8 +230,11 @@ static int fused2_blocks(CadnipHandle* h) {
   return CADNIP_OK;
 }
 
-// The one place that decides what a fused launch runs, and the only reader of the diagnostic switches CADNIP_F2_NODIRECT / _TEAM / _WPB / _STEPS_PACKED
+// The one place that decides what a fused launch runs, and the only reader of the diagnostic switches CADNIP_F2_NODIRECT / _TEAM / _WPB / _STEPS_PACKED /
+// _SRC_CACHE
 // (CADNIP_F2_NC: f2_prepare, where the tables are built; CADNIP_F2_DEBUG prints the plan, launch_fused2).
+static bool env_is_zero(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }
+
 F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode) {
   F2Plan p;
   FusedState& S = h->f2;
@@ -296,6 +300,16 @@ F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode) {
     const size_t pd = lds_bytes(lds_sweep((size_t)0, p.tab_len, lds_sweep_desc_words(p.steps->len, true), S.lu_words, h->n, 0, wpb));
     if (pd <= LDS_BUDGET && (int)std::max<size_t>(1, std::min<size_t>(LDS_BUDGET / pd, (size_t)(32 / wpb))) == wg_per_cu) { p.step_predec = true; shmem = pd; }
   }
+  // Transient launches of the direct-residual variants keep the segment each pinned source is on in LDS (src_cache.hpp), under the same rule: the
+  // region may cost neither a wave per workgroup (wpb stands as chosen above) nor a workgroup per CU.  Otherwise, and under CADNIP_F2_SRC_CACHE=0
+  // (diagnostic, tests: bit-identical results either way), every new time point evaluates its sources from global memory as before.
+  if (mode == F2_TRAN && direct && S.src_blk >= 0 && !env_is_zero("CADNIP_F2_SRC_CACHE")) {
+    const int sw = src_cache_words(S.src_count), dw = p.steps ? lds_sweep_desc_words(p.steps->len, p.step_predec) : 0;
+    if (src_cache_fits(p.tab_len, dw, S.lu_words, h->n, wpb, sw)) {
+      p.src_words = sw;
+      shmem = lds_bytes(lds_sweep((size_t)0, p.tab_len, dw, S.lu_words, h->n, 0, wpb, sw));
+    }
+  }
   p.wpb = wpb; p.shmem = shmem; p.grid = std::min((h->B + wpb - 1) / wpb, S.n_cu * wg_per_cu); p.rc = CADNIP_OK;
   return p;
 }
@@ -316,6 +330,7 @@ static int launch_fused2(CadnipHandle* h, const TranArgs& t, int rounds, const F
   f.n_pre = S.n_pre; f.n_post = S.n_post; f.nc = S.nc; f.dn0 = S.dn0; f.n_fwd = S.n_fwd;
   if (p.steps) { f.team_desc = p.steps->d; f.team_desc_len = p.steps->len; f.ts_pre = p.steps->n_steps[0]; f.ts_post = p.steps->n_steps[1]; f.ts_fwd = p.steps->n_steps[2]; }
   f.step_predec = p.step_predec ? 1 : 0;
+  f.src_words = p.src_words;
   f.step_refresh = step ? step->refresh : 0; f.step_resid = step ? step->resid : nullptr; f.step_norm = step ? step->norm : nullptr;
   f.step_reps = step ? step->reps : 1; f.step_skip = step ? step->skip : 0;
   if (p.keep_factors) {       // the kept factors of instances that are not resident live in HBM
@@ -342,7 +357,7 @@ static int launch_fused2(CadnipHandle* h, const TranArgs& t, int rounds, const F
     else TRY_RC(fteam_launch(p.nw, p.grid, p.shmem, h->stream, f));
   } else {
     const size_t tab_b = (size_t)p.tab_len / 2 * 8, desc_b = (size_t)lds_sweep_desc_words(f.team_desc_len, p.step_predec) * 8;
-    if (debug) fprintf(stderr, "[cadnip f2] B %d n_cu %d wpb %d grid %d shmem %zu (tables %zu, steps %zu, per instance %zu) rounds %d nc %d passes %d+%d steps %d+%d / %d (%s) variant %d\n", h->B, S.n_cu, p.wpb, p.grid, p.shmem, tab_b, desc_b, (p.shmem - tab_b - desc_b) / p.wpb, rounds, S.nc, S.n_pre, S.n_post, f.ts_pre, f.ts_post, f.ts_fwd, p.step_predec ? "pre-decoded" : "packed", p.var);
+    if (debug) fprintf(stderr, "[cadnip f2] B %d n_cu %d wpb %d grid %d shmem %zu (tables %zu, steps %zu, per instance %zu) rounds %d nc %d passes %d+%d steps %d+%d / %d (%s) variant %d src-cache %d\n", h->B, S.n_cu, p.wpb, p.grid, p.shmem, tab_b, desc_b, (p.shmem - tab_b - desc_b) / p.wpb, rounds, S.nc, S.n_pre, S.n_post, f.ts_pre, f.ts_post, f.ts_fwd, p.step_predec ? "pre-decoded" : "packed", p.var, p.src_words);
     TRY_RC(p.var == 0 ? f2_launch_variant<0>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
          : p.var == 1 ? f2_launch_variant<1>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
                       : f2_launch_variant<2>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f));

@@ -7,6 +7,7 @@
 #include "internal.hpp"
 #include "tran_ctrl.hpp"
 #include "lds_layout.hpp"
+#include "src_cache.hpp"
 
 namespace cadnip {
 
@@ -54,6 +55,7 @@ struct F2Args {
   const unsigned long long* team_desc; int team_desc_len;   // team kernel (fused_team_kernel.hpp): step descriptors of the linear solve (f2_program.cpp: f2_build_team)
   int ts_pre, ts_post, ts_fwd;      // ... steps of the pre-core, post-core and forward-only lists
   int step_predec;                  // sweep kernel, lean variant: 1 = the descriptors are staged pre-decoded (lds_layout.hpp: lds_step_predecode; fused2.hip: fused2_plan decides)
+  int src_words;                    // sweep kernel, direct-residual variants, transient: doubles of an instance's source segment cache (src_cache.hpp; lds_layout.hpp: lds_sweep), 0 = none
   int par_words;                    // team kernel: doubles of the LDS-staged sp_mos1 parameter rows (F2Block::lds_par)
   int step_refresh; double *step_resid, *step_norm;   // team kernel, STEP mode (cadnip_newton_step_fused): refactor or use f.lufac; optional outputs
   int step_reps, step_skip;         // STEP mode, measurement only (cadnip_debug_step_time): repeat the same iteration, leave phases out (1 stamping, 2 combine, 4 linear-solve steps, 8 dense core)
@@ -348,7 +350,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   // lean variant: the linear solve as straight-line steps (f2_program.cpp: f2_build_steps), their 16-byte lane descriptors staged behind the tables
   // ... as the host packs them, or pre-decoded on the way in (lds_layout.hpp: lds_step_predecode; one flag byte per lane and step behind them)
   const bool predec = LEAN && f.step_predec;
-  const LdsSweep<double*> L = lds_sweep((double*)sm, f.tab_len, LEAN ? lds_sweep_desc_words(f.team_desc_len, predec) : 0, f.nnz_lu, n, w, WPB);
+  const LdsSweep<double*> L = lds_sweep((double*)sm, f.tab_len, LEAN ? lds_sweep_desc_words(f.team_desc_len, predec) : 0, f.nnz_lu, n, w, WPB, f.src_words);
   const uint4* tdesc = (const uint4*)L.desc;
   const unsigned char* tflag = (const unsigned char*)(L.desc + (LEAN ? f.team_desc_len : 0));
   if constexpr (LEAN) {
@@ -483,6 +485,17 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) { const int dev = lane0 + 64 * q; rc_val[q] = par[dev < B.count ? dev : 0]; }
   }
+  // source segment cache of this residence (src_cache.hpp; LDS behind beta): a DC source's entry answers every time point, every other
+  // source starts with an entry that cannot hit and caches the PWL segment its first evaluation finds
+  // (whether the launch has one is read from the kernarg segment where it is needed, like the pointers above: not one more scalar held, or spilled, across the round)
+  auto sc_on = [&]() -> bool { return !DC && DIRECT && kargs()->src_words > 0; };
+  if (sc_on()) {
+    const F2Block B = load_block(f.blk, f.src_blk);
+    const int cl = src_cache_lanes(B.count);
+    int ln = lane0;
+    asm volatile("" : "+v"(ln));                          // (an opaque copy, as in the round loop: the entry's address is formed here, not kept in a register from the kernel's entry on)
+    if (ln < cl) src_seg_store(L.src, cl, ln, src_seg_fill(B.ipar[ln], (B.par + (size_t)inst * B.n_par * B.count)[ln]));
+  }
   // values of the first independent-source block: functions of time only, kept over the Newton rounds of a time point
   double src_val = 0.0, src_t = 0.0;
   bool src_have = false;
@@ -542,14 +555,43 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
           atomicAdd(&W[rc_row[q] & 0xFFFFu], cur[q]); atomicAdd(&W[rc_row[q] >> 16], -cur[q]);
         }
       }
+      CADNIP_TRACE_POINT(14);
       if (f.src_blk >= 0) {
         if (DC || !src_have || tcur != src_t) {
-          const F2Block B = load_block(f.blk, f.src_blk);
-          const double* par = B.par + (size_t)inst * B.n_par * B.count;
-          LdsCtx d{nodes + B.nodes_off, B.ipar, par, f.wave, B.count, lane < B.count ? lane : 0, tcur, dmode, dinit};
-          src_val = source_value(d, par_of(d, 0), par_of(d, 1), &src_seg);
+          // a new time point: the lane's cached segment answers it from LDS when the time lies inside it ...
+          const int cl = src_cache_lanes(src_count);
+          const bool sc = sc_on();
+          int miss = 1;
+          double cv = 0.0;
+          if (sc) {
+            const SrcSeg e = src_seg_load((const double*)L.src, cl, lane < cl ? lane : 0);
+            miss = src_seg_hit(e, tcur) ? 0 : 1;
+            cv = src_seg_value(e, tcur);
+          }
+          // ... otherwise the evaluation from global memory, as without the cache -- by every lane of the wave (one instruction stream; a lane
+          // whose entry did answer gets the same value either way) -- and the segment the search found becomes the entry of a lane that missed
+          if (wave_any(miss)) {
+            const F2Block B = load_block(f.blk, f.src_blk);
+            const double* par = B.par + (size_t)inst * B.n_par * B.count;
+            LdsCtx d{nodes + B.nodes_off, B.ipar, par, f.wave, B.count, lane < B.count ? lane : 0, tcur, dmode, dinit};
+            src_val = source_value(d, par_of(d, 0), par_of(d, 1), &src_seg);
+          } else src_val = cv;
+          // (a rare path: what it needs is fetched again here, not held in scalar registers across the evaluation and its search loop)
+          if (sc_on() && miss && lane < cl) {
+            const F2ArgsK ka = kargs();
+            const F2Block B = load_block(ka->blk, ka->src_blk);
+            SrcSeg r = src_seg_never();
+            if (B.ipar[lane] == 1) {
+              const int len = B.ipar[2 * B.count + lane];
+              const double* wv = ka->wave + B.ipar[B.count + lane];
+              r = src_seg_refill(1, wv, wv + len, len, src_seg, (B.par + (size_t)inst * B.n_par * B.count)[B.count + lane]);
+            }
+            src_seg_store(L.src, cl, lane, r);
+          }
           src_t = tcur; src_have = true;
         }
+        CADNIP_TRACE_USE(src_val);
+        CADNIP_TRACE_POINT(15);
         if (src_type == CADNIP_DEV_VSOURCE) {
           // branch rows / columns +-1 (devices.hpp: branch4); KCL rows carry u[I], the branch row V(p) - V(n) - v
           const double ui = at(src_nd[1]), vd = at(src_nd[0] & 0xFFFFu) - at(src_nd[0] >> 16) - src_val;

@@ -118,6 +118,7 @@ struct FusedState {
   // device-block descriptors and what they decide (fused2.hip: fused2_blocks)
   void* d_blk = nullptr;
   int n_blk = 0, rc_blk = -1, src_blk = -1;   // first capacitor / resistor block, first independent-source block of the list
+  int src_count = 0;          // devices of block src_blk (the first 64 are pinned to lanes and may have their segment cached: src_cache.hpp)
   int par_words = 0;          // team kernel: doubles of the LDS-staged sp_mos1 parameter rows of one instance
   bool lean = false;          // only device types of the lean kernel variant
   // buffers of the launches
@@ -315,6 +316,7 @@ struct F2Plan {
   const StepList* steps = nullptr;      // step descriptors staged behind it (null: the pass program of the full table)
   bool step_predec = false;   // sweep kernel: the descriptors are staged pre-decoded, a flag byte per lane and step behind them (lds_layout.hpp)
   bool keep_factors = false;  // Newton mode 1 / single step: kept factors in HBM
+  int src_words = 0;          // sweep kernel: doubles of the per-instance source segment cache in LDS (src_cache.hpp), 0 = the launch runs without it
 };
 F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode);
 int launch_fused2_dc(CadnipHandle* h, const TranArgs& t, int rounds, double abstol, int maxiters, int use_pcnr, int mode, int initjct, int* d_dcstate);

@@ -48,15 +48,16 @@ LDS_HD bool lds_steps_predec_ok(int lu_words, int n) { return lu_words + n + F2_
 // 64-bit words of the descriptor area: desc_len as uploaded (two per lane and step), plus one flag byte per lane and step when pre-decoded
 LDS_HD int lds_sweep_desc_words(int desc_len, bool predec) { return desc_len + (predec ? desc_len / 16 : 0); }
 
-// sweep kernel k_fused2<WPB>: tables | step descriptors (lean variant; desc_len = lds_sweep_desc_words) | WPB x [ W | consts | u | beta ]; W, u, beta: of instance w
-template <class P> struct LdsSweep { P desc, W, u, beta, end; int nW, per; };   // nW, per: doubles of one work array / one instance
-template <class P> LDS_HD LdsSweep<P> lds_sweep(P base, int tab_len, int desc_len, int lu_words, int n, int w, int wpb) {
+// sweep kernel k_fused2<WPB>: tables | step descriptors (lean variant; desc_len = lds_sweep_desc_words) | WPB x [ W | consts | u | beta | src ]; W, u, beta,
+// src: of instance w.  src: the source segment cache (src_cache.hpp: src_cache_words doubles, an even number; 0 = the launch runs without it)
+template <class P> struct LdsSweep { P desc, W, u, beta, end; int nW, per; P src; };   // nW, per: doubles of one work array / one instance
+template <class P> LDS_HD LdsSweep<P> lds_sweep(P base, int tab_len, int desc_len, int lu_words, int n, int w, int wpb, int src_words = 0) {
   LdsSweep<P> L;
   L.nW = lds_work_words(lu_words, n);
-  L.per = L.nW + LDS_CONSTS + 2 * n;
+  L.per = L.nW + LDS_CONSTS + 2 * n + src_words;
   L.desc = base + tab_len / 2;
   L.W = L.desc + desc_len + (size_t)w * L.per;
-  L.u = L.W + L.nW + LDS_CONSTS; L.beta = L.u + n;
+  L.u = L.W + L.nW + LDS_CONSTS; L.beta = L.u + n; L.src = L.beta + n;
   L.end = L.desc + desc_len + (size_t)wpb * L.per;
   return L;
 }
