@@ -1509,6 +1509,230 @@ def network_noise(target, ports, freqs, z0=50.0, gmin=1e-12, device=0, solver="h
     return SweepResult(pts, sols) if sweep else sols[0]
 
 
+class SensSol:
+    """``sensitivity``'s result for one point: the response ``y`` [F] of the output over the grid ``freqs`` (hertz) and its derivatives ``dy``
+    [F, K] with respect to the K ``params`` (names; ``values`` their values at the point, "temp" in degrees Celsius; ``steps`` the
+    central-difference steps delta_k the stamps were differenced with).  ``dc_value`` is the output at the DC operating point and ``dc_dy``
+    [K] its derivative (u+[out] - u-[out]) / (2 delta), a by-product of the perturbed DC solves.  ``normalized(k)`` = p_k dy[:, k];
+    ``dmag(k)`` = d|y| / dp_k = Re(conj(y) dy) / |y|; ``dphase(k)`` = d arg(y) / dp_k = Im(dy / y) in radians (k: an index or a name).
+    ``stats``: what a GPU solver did, as ``ACSol.stats`` plus "params"; empty on the host path."""
+
+    def __init__(self, freqs, params, values, steps, y, dy, dc_value, dc_dy):
+        self.freqs, self.params = np.asarray(freqs, dtype=float), list(params)
+        self.values, self.steps = np.asarray(values, dtype=float), np.asarray(steps, dtype=float)
+        self.y, self.dy = np.asarray(y, dtype=complex), np.asarray(dy, dtype=complex)
+        self.dc_value, self.dc_dy = float(dc_value), np.asarray(dc_dy, dtype=float)
+        self.stats = {}
+
+    def _k(self, k):
+        return self.params.index(k) if isinstance(k, str) else int(k)
+
+    def normalized(self, k):
+        k = self._k(k)
+        return self.values[k] * self.dy[:, k]
+
+    def dmag(self, k):
+        return np.real(np.conj(self.y) * self.dy[:, self._k(k)]) / np.abs(self.y)
+
+    def dphase(self, k):
+        return np.imag(self.dy[:, self._k(k)] / self.y)
+
+
+def sens_output(st, output):
+    """(p, n) unknown indices (-1 = ground) of ``sensitivity``'s output: a name -- resolved as ``noise_indices`` resolves it -- against ground,
+    or a (p, n) pair of names of which one may be ground.  ValueError for anything that is not an unknown."""
+    names = [output] if isinstance(output, str) else list(output)
+    if len(names) not in (1, 2) or not all(isinstance(nm, str) for nm in names):
+        raise ValueError("sensitivity: output must be a name or a (p, n) pair of names")
+    idx = []
+    for nm in names:
+        try:
+            idx.append(-1 if len(names) == 2 and nm in ("gnd", "0") else noise_indices(st, nm)[0])
+        except KeyError as e:
+            raise ValueError("sensitivity: " + str(e.args[0])) from None
+    if len(idx) == 1:
+        idx.append(-1)
+    if idx[0] == idx[1]:
+        raise ValueError("sensitivity: the output pair names one unknown twice")
+    return idx[0], idx[1]
+
+
+def sensitivity_solve(st, Gd, Cd, b, dG, dC, db, out, omegas):
+    """The host path of ``sensitivity``, in dense numpy: with A = G + j w C (``Gd`` with gmin on the voltage-node diagonals, ``Cd``), A x = b and
+    the adjoint A^T lambda = e_p - e_n for ``out`` = (p, n) (-1 = ground),
+        y = x[p] - x[n],   dy/dp_k = lambda^T (db_k - (dG_k + j w dC_k) x)
+    per angular frequency of ``omegas`` -- one factorisation serving the response and all K derivatives.  ``dG`` / ``dC`` [K, n, n] are the
+    parameter derivatives of G and C (``sensitivity``: central differences of the stamps of perturbed points), ``db`` [K, n] that of the
+    excitation or None for zeros.  Returns (y [F], dy [F, K])."""
+    import scipy.linalg as sla
+    omegas = np.asarray(omegas, dtype=float).ravel()
+    dG, dC = np.asarray(dG, dtype=float), np.asarray(dC, dtype=float)
+    K, n = dG.shape[0], st.n
+    p, q = out
+    e = np.zeros(n, dtype=complex)
+    if p >= 0:
+        e[p] += 1.0
+    if q >= 0:
+        e[q] -= 1.0
+    b = np.asarray(b, dtype=complex)
+    y, dy = np.zeros(omegas.size, dtype=complex), np.zeros((omegas.size, K), dtype=complex)
+    for f, w in enumerate(omegas):
+        lu = sla.lu_factor(Gd + 1j * w * Cd)
+        x, lam = sla.lu_solve(lu, b), sla.lu_solve(lu, e, trans=1)
+        y[f] = e @ x
+        for k in range(K):
+            rhs = -((dG[k] + 1j * w * dC[k]) @ x)
+            if db is not None:
+                rhs = rhs + db[k]
+            dy[f, k] = lam @ rhs
+    return y, dy
+
+
+def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device=0, solver="host", memory="lds"):
+    """Small-signal sensitivities (SPICE's .SENS on an AC sweep): the response y of ``output`` over ``freqs`` (hertz) as ``ac`` gives it, and
+    dy/dp_k for every parameter of ``params`` -- names of circuit parameters, or "temp" -- from ONE factorisation per (point, frequency): with
+    the adjoint solve A^T lambda = e_out, dy/dp_k = lambda^T (db/dp_k - (dG/dp_k + j w dC/dp_k) x).  ``output``: a node or current name, or
+    a (p, n) pair of names (``sens_output``).  Returns a SensSol, or for a CircuitSweep a SweepResult of them.
+    The parameter derivatives of G, C and b are central differences of the STAMPS: every point expands to 1 + 2 K instances of one resident
+    batch -- the base, then p_k + delta_k, p_k - delta_k for each k -- with delta_k = rel_step |p_k| (rel_step when p_k == 0; rel_step
+    (T + 273.15) for "temp").  The bases are solved as ``ac`` solves them; the perturbed instances then start from their base's solution
+    (seeded as ``dc_continuation`` seeds points, so a multi-stable circuit stays on its branch), all must converge, and one restamp at
+    those points linearises everything, the moved operating point included.  The variants of a point must keep its structure: a step that
+    changes it (a series resistance leaving zero) raises ValueError naming the parameter.
+    ``solver``: "host" (default) -- ``sensitivity_solve`` in dense numpy; "gpu" -- one ``ac_sens`` call per structure class: the kernel
+    differences the perturbed instances' G and C in place on the device and returns K + 1 numbers per system (csrc/ac_lu.hip: k_ac_sens); a
+    system with a flag set, a forward backward error above AC_BERR_MAX or an adjoint one above NOISE_BERR_MAX is redone by the host path;
+    "auto" -- as "gpu", with the host path for a circuit the memory home refuses.  ``memory`` as for ``ac``.  ``stats`` =
+    {"gpu_systems", "host_systems", "max_berr", "wpb", "memory", "params"}.  Several outputs: call once per output."""
+    import scipy.sparse as sp
+    from . import hip
+    if solver not in ("host", "gpu", "auto"):
+        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
+    _ac_memory(memory)
+    params = [params] if isinstance(params, str) else list(params)
+    if not params or len(set(params)) != len(params):
+        raise ValueError("sensitivity: params needs at least one parameter name, each once")
+    freqs = np.asarray(freqs, dtype=float).ravel()
+    if freqs.size == 0:
+        raise ValueError("sensitivity(circuit, output, params, freqs) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
+    if not rel_step > 0:
+        raise ValueError("sensitivity: rel_step must be positive")
+    sweep, mc, pts = _ac_target(target)
+    for nm in params:
+        if nm != "temp" and nm not in mc.params:
+            raise ValueError("sensitivity: %s is not a parameter of the circuit (parameters: %s, or \"temp\")" % (nm, sorted(mc.params)))
+    K, omegas = len(params), 2.0 * np.pi * freqs
+    # the perturbed batch: point i -> instances i (1 + 2 K) + [0 | 1 + 2 k | 2 + 2 k] = base | p_k + delta | p_k - delta
+    per = 1 + 2 * K
+    values, steps, expanded = np.zeros((len(pts), K)), np.zeros((len(pts), K)), []
+    for i, pt in enumerate(pts):
+        expanded.append(dict(pt))
+        for k, nm in enumerate(params):
+            v = float(pt.get(nm, mc.spec.temp if nm == "temp" else mc.params.get(nm)))
+            d = rel_step * (v + 273.15) if nm == "temp" else rel_step * abs(v) if v != 0 else rel_step
+            values[i, k], steps[i, k] = v, d
+            for sgn in (1.0, -1.0):
+                q = dict(pt)
+                q[nm] = v + sgn * d
+                expanded.append(q)
+    cls_of = {}
+    classes = structure_classes(mc, expanded)
+    for ci, (members, st) in enumerate(classes):
+        for j in members:
+            cls_of[j] = ci
+    for i in range(len(pts)):
+        for k, nm in enumerate(params):
+            if cls_of[i * per + 1 + 2 * k] != cls_of[i * per] or cls_of[i * per + 2 + 2 * k] != cls_of[i * per]:
+                raise ValueError("sensitivity: a step of %g in %s at point %d changes the structure of the circuit (its unknowns or its pattern): "
+                                 "the derivative does not exist there" % (steps[i, k], nm, i))
+    outs = [sens_output(st, output) for _, st in classes]
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0, "params": K}
+    sols = [None] * len(pts)
+    for (members, st), out in zip(classes, outs):
+        bases = [j for j in members if j % per == 0]
+        if not bases:
+            continue
+        inst = {j: m for m, j in enumerate(j for b in bases for j in range(b, b + per))}      # expanded index -> instance of this batch
+        sim = BatchSimulator(mc, [expanded[j] for j in inst], device, st=st)
+        try:
+            B, NB = sim.B, len(bases)
+            base = np.array([inst[b] for b in bases], dtype=np.int32)
+            plus = np.array([[inst[b + 1 + 2 * k] for k in range(K)] for b in bases], dtype=np.int32)
+            minus = np.array([[inst[b + 2 + 2 * k] for k in range(K)] for b in bases], dtype=np.int32)
+            is_base = np.zeros(B, dtype=bool)
+            is_base[base] = True
+            u, conv, _ = sim.dc(participate=is_base)
+            if not np.all(conv[is_base]):
+                raise RuntimeError("sensitivity: the DC operating point did not converge for %d point(s)" % int((~conv[is_base]).sum()))
+            start = np.array(u)
+            start[~is_base] = np.repeat(u[base], 2 * K, axis=0)                                # every variant from its base's solution
+            uv, cv, _ = sim.dc(start, participate=~is_base, cold_start=True)
+            if not np.all(cv[~is_base]):
+                raise RuntimeError("sensitivity: the DC operating point of %d perturbed instance(s) did not converge" % int((~cv[~is_base]).sum()))
+            u[~is_base] = uv[~is_base]
+            sim.h.rebuild(u, 0.0)
+            G, C, _, _ = sim.h.get_GCb()
+            dense = lambda nz: sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
+            par_of = lambda m: {kk: float(v[m]) for kk, v in sim.params.items()}
+            scale = np.array([[1.0 / (2.0 * steps[b // per, k]) for k in range(K)] for b in bases])
+            bac = np.array([rhs_ac(st, mc.circuit, par_of(m)) for m in base])
+            db = np.array([[(rhs_ac(st, mc.circuit, par_of(plus[a, k])) - rhs_ac(st, mc.circuit, par_of(minus[a, k]))) * scale[a, k] for k in range(K)]
+                           for a in range(NB)])
+            if not db.any():
+                db = None
+            val = lambda m: (u[m, out[0]] if out[0] >= 0 else 0.0) - (u[m, out[1]] if out[1] >= 0 else 0.0)
+
+            def host(a):
+                Gd, Cd = dense(G[base[a]]), dense(C[base[a]])
+                Gd[np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
+                dG = np.array([(dense(G[plus[a, k]]) - dense(G[minus[a, k]])) * scale[a, k] for k in range(K)])
+                dC = np.array([(dense(C[plus[a, k]]) - dense(C[minus[a, k]])) * scale[a, k] for k in range(K)])
+                return lambda om: sensitivity_solve(st, Gd, Cd, bac[a], dG, dC, None if db is None else db[a], out, om)
+
+            got = None
+            if solver != "host":
+                to_ref = np.asarray(st.to_ref_nz)
+                sample_ref = np.empty(st.nnz)
+                sample_ref[to_ref] = ac_pivot_sample(st, G[:, to_ref], C[:, to_ref], omegas, gmin)
+                sim.h.analyze_values(sample_ref)
+                e = np.zeros(st.n, dtype=complex)
+                for j, sgn in zip(out, (1.0, -1.0)):
+                    if j >= 0:
+                        e[j] += sgn
+                try:
+                    with _ac_memory_of(sim.h, memory):
+                        y, s, _, berr, flags, info = sim.h.ac_sens(omegas, gmin, base, plus, minus, scale, bac, e, out, db)
+                        used = sim.h.ac_plan_info()["memory"] if memory != "lds" else "lds"
+                    redo = flags.any(axis=2) | ~(berr[:, :, 0] <= AC_BERR_MAX) | ~(berr[:, :, 1] <= NOISE_BERR_MAX)
+                    y, s = np.array(y), np.array(s)
+                    for a in np.flatnonzero(redo.any(axis=1)):
+                        ff = np.flatnonzero(redo[a])
+                        y[a, ff], s[a, ff] = host(a)(omegas[ff])
+                    kept = berr[~redo]
+                    stats["gpu_systems"] += int((~redo).sum())
+                    stats["host_systems"] += int(redo.sum())
+                    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
+                    stats["wpb"] = info["wpb"]
+                    stats["memory"] = used
+                    got = [(y[a], s[a]) for a in range(NB)]
+                except hip.CadnipError as err:
+                    if not (solver == "auto" and err.code == hip.BADARG):
+                        raise
+                    stats["host_systems"] += NB * omegas.size
+                    stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
+            if got is None:
+                got = [host(a)(omegas) for a in range(NB)]
+            for a, b in enumerate(bases):
+                i = b // per
+                dc_dy = np.array([(val(plus[a, k]) - val(minus[a, k])) * scale[a, k] for k in range(K)])
+                sols[i] = SensSol(freqs, params, values[i], steps[i], got[a][0], got[a][1], val(base[a]), dc_dy)
+                if solver != "host":
+                    sols[i].stats = stats
+        finally:
+            sim.close()
+    return SweepResult(pts, sols) if sweep else sols[0]
+
+
 def tran(target, tspan, abstol=1e-10, reltol=1e-8, saveat=None, device=0, **kw):
     """tran!(circuit, tspan) / tran!(cs::CircuitSweep, tspan) -- sweeps.jl:588-665, 692-707."""
     tspan = (float(tspan[0]), float(tspan[1]))

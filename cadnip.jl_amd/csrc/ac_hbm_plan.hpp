@@ -24,11 +24,14 @@ struct AcHbmPlan { int wpb = 0, n_waves = 0; size_t work_bytes = 0; };   // wpb 
 // bytes of one system's (= one wave's) workspace
 inline size_t ac_hbm_system_bytes(int nnz_lu, int n) { return 16 * ((size_t)nnz_lu + 3 * (size_t)n); }
 
-inline AcHbmPlan ac_hbm_plan(int nnz_lu, int n, long n_sys, int wpb_req, int max_waves, int n_cu) {
+// ... of k_ac_sens_hbm: a fourth complex n-vector (lds_layout.hpp: lds_ac_sens)
+inline size_t ac_sens_hbm_system_bytes(int nnz_lu, int n) { return 16 * ((size_t)nnz_lu + 4 * (size_t)n); }
+
+// the plan for workspaces of `per` bytes each
+inline AcHbmPlan ac_hbm_plan_bytes(size_t per, long n_sys, int wpb_req, int max_waves, int n_cu) {
   AcHbmPlan none, p;
-  if (nnz_lu <= 0 || n <= 0 || n_sys <= 0 || max_waves < 0 || n_cu <= 0) return none;
+  if (per == 0 || n_sys <= 0 || max_waves < 0 || n_cu <= 0) return none;
   if (wpb_req != 0 && wpb_req != 1 && wpb_req != 2 && wpb_req != 4 && wpb_req != 8) return none;
-  const size_t per = ac_hbm_system_bytes(nnz_lu, n);
   if (per > AC_WORK_BYTES) return none;
   size_t waves;
   if (max_waves > 0) waves = (size_t)max_waves;
@@ -43,6 +46,11 @@ inline AcHbmPlan ac_hbm_plan(int nnz_lu, int n, long n_sys, int wpb_req, int max
   p.n_waves = (int)waves;
   p.work_bytes = waves * per;
   return p;
+}
+
+inline AcHbmPlan ac_hbm_plan(int nnz_lu, int n, long n_sys, int wpb_req, int max_waves, int n_cu) {
+  if (nnz_lu <= 0 || n <= 0) return AcHbmPlan();
+  return ac_hbm_plan_bytes(ac_hbm_system_bytes(nnz_lu, n), n_sys, wpb_req, max_waves, n_cu);
 }
 
 }  // namespace cadnip

@@ -19,6 +19,8 @@
 // workspace in global memory, for circuits beyond the LDS budget: persistent waves, planned by ac_hbm_plan.hpp.
 // k_ac_lu_multi / k_ac_lu_multi_hbm (cadnip_ac_solve_multi) run steps 1 and 2 once per system and steps 3 to 6 for each of K right-hand sides;
 // k_ac_adj_multi / k_ac_adj_multi_hbm (cadnip_ac_adjoint_multi) do the same for K adjoint right-hand sides.
+// k_ac_sens / k_ac_sens_hbm (cadnip_ac_sens) run one forward and one adjoint column per system and, from the two solutions, K bilinear forms
+// over the stamps of perturbed instances: the response and its K parameter derivatives from one factorisation.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -190,19 +192,13 @@ __device__ __forceinline__ void ac_store_status(const AcArgs& a, int ls, double 
   if (lane == 0) { a.berr[ls] = nan ? __builtin_nan("") : worst; a.flags[ls] = bad ? 1 : 0; }
 }
 
-// Steps 1 to 6 for system ls of the launch, by one wave, in the work arrays wk.  Everything a system leaves behind is in wk, and every word of
-// wk is written before it is read: lu by step 1, y / x / r by the full-length loops below -- a wave may run system after system in one wk
+// Steps 3 to 5 of ONE column: A x = bac through the factors in lu, the refinement step and the backward error of the wave's rows (returned).
+// x is left in wk.x, visible to every lane.  Shared by k_ac_lu, k_ac_lu_multi and k_ac_sens: the same statements on the same doubles in the
+// same x / r / y.  Every word of x, r and y is written before it is read, so a column leaves nothing to the next one
 template <class M>
-__device__ __forceinline__ void ac_lu_system(const AcArgs& a, int ls, const AcWork& wk, int lane) {
+__device__ __forceinline__ double ac_lu_column(const AcArgs& a, const AcWork& wk, const double* G, const double* C, double om, const double2* bac, int lane) {
   const int n = a.n;
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
   double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
-  const double om = a.omega[fi];
-  int bad = ac_load_factor<M>(a, lu, G, C, om, lane);
   for (int i = lane; i < n; i += 64) y[i] = bac[a.rperm[i]];
   M::sync();
   ac_solve<M>(a, lu, y, lane);
@@ -215,7 +211,23 @@ __device__ __forceinline__ void ac_lu_system(const AcArgs& a, int ls, const AcWo
   for (int i = lane; i < n; i += 64) { const int j = a.cperm[i]; const double2 xv = x[j], dv = y[i]; x[j] = make_double2(xv.x + dv.x, xv.y + dv.y); }
   M::sync();
   // ---- 5. backward error
-  const double worst = ac_residual<M, true>(a, G, C, om, bac, x, r, lane);
+  return ac_residual<M, true>(a, G, C, om, bac, x, r, lane);
+}
+
+// Steps 1 to 6 for system ls of the launch, by one wave, in the work arrays wk.  Everything a system leaves behind is in wk, and every word of
+// wk is written before it is read: lu by step 1, y / x / r by the full-length loops of ac_lu_column -- a wave may run system after system in one wk
+template <class M>
+__device__ __forceinline__ void ac_lu_system(const AcArgs& a, int ls, const AcWork& wk, int lane) {
+  const int n = a.n;
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  const double2* x = wk.x;
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
+  const double om = a.omega[fi];
+  int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
+  const double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane);
   // ---- 6. store
   double2* xo = (double2*)a.x + (size_t)ls * n;
   for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; xo[i] = v; }
@@ -324,13 +336,13 @@ __device__ __forceinline__ double ac_adj_residual(const AcAdjArgs& t, const doub
   return worst;
 }
 
-// Steps 3 to 6 of ONE adjoint column: A^T x = c through the factors in lu, the refinement step, the backward error and the stores of
-// (system, column) lk of the launch -- h, berr, the flag, x when asked for.  `bad`: what ac_load_factor returned for the system.  Shared by
-// k_ac_adj (one column per system, lk = ls) and k_ac_adj_multi: the same statements on the same doubles in the same x / r / y.  Every word of
-// x, r and y is written before it is read, so a column leaves nothing to the next one
+// Steps 3 to 6 of ONE adjoint column: A^T x = c through the factors in lu, the refinement step, the backward error (ac_adj_solve_column: steps
+// 3 to 5, x left in wk.x, the backward error of the wave's columns returned) and the stores of (system, column) lk of the launch -- h, berr,
+// the flag, x when asked for.  `bad`: what ac_load_factor returned for the system.  Shared by k_ac_adj (one column per system, lk = ls),
+// k_ac_adj_multi and -- the solve -- k_ac_sens: the same statements on the same doubles in the same x / r / y.  Every word of x, r and y is
+// written before it is read, so a column leaves nothing to the next one
 template <class M>
-__device__ __forceinline__ void ac_adj_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c,
-                                              size_t lk, int bad, int lane) {
+__device__ __forceinline__ double ac_adj_solve_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c, int lane) {
   const AcArgs& a = t.a;
   const int n = a.n;
   double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
@@ -346,7 +358,16 @@ __device__ __forceinline__ void ac_adj_column(const AcAdjArgs& t, const AcWork& 
   for (int i = lane; i < n; i += 64) { const int k = a.rperm[i]; const double2 xv = x[k], dv = y[i]; x[k] = make_double2(xv.x + dv.x, xv.y + dv.y); }
   M::sync();
   // ---- 5. backward error
-  const double worst = ac_adj_residual<M, true>(t, G, C, om, c, x, r, lane);
+  return ac_adj_residual<M, true>(t, G, C, om, c, x, r, lane);
+}
+
+template <class M>
+__device__ __forceinline__ void ac_adj_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c,
+                                              size_t lk, int bad, int lane) {
+  const AcArgs& a = t.a;
+  const int n = a.n;
+  const double2* x = wk.x;
+  const double worst = ac_adj_solve_column<M>(t, wk, G, C, om, c, lane);
   // ---- 6. store
   double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
   for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
@@ -414,28 +435,16 @@ __device__ __forceinline__ void ac_multi_system(const AcMultiArgs& t, int ls, co
   const int n = a.n;
   const long s = a.s0 + ls;
   const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
-  double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
+  const double2* x = wk.x;
   const double* G = a.G + (size_t)inst * a.nnz;
   const double* C = a.C + (size_t)inst * a.nnz;
   const double om = a.omega[fi];
-  const int bad_pivot = ac_load_factor<M>(a, lu, G, C, om, lane);
+  const int bad_pivot = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
   for (int k = 0; k < t.n_rhs; ++k) {
     const double2* bac = (const double2*)t.rhs + (size_t)inst * t.rhs_stride + (size_t)k * n;
     const size_t lk = (size_t)ls * t.n_rhs + k;               // (system, column) of the launch: within int (api.hip bounds a launch's output)
     int bad = bad_pivot;
-    for (int i = lane; i < n; i += 64) y[i] = bac[a.rperm[i]];
-    M::sync();
-    ac_solve<M>(a, lu, y, lane);
-    for (int i = lane; i < n; i += 64) x[a.cperm[i]] = y[i];
-    M::sync();
-    (void)ac_residual<M, false>(a, G, C, om, bac, x, r, lane);
-    for (int i = lane; i < n; i += 64) y[i] = r[a.rperm[i]];
-    M::sync();
-    ac_solve<M>(a, lu, y, lane);
-    for (int i = lane; i < n; i += 64) { const int j = a.cperm[i]; const double2 xv = x[j], dv = y[i]; x[j] = make_double2(xv.x + dv.x, xv.y + dv.y); }
-    M::sync();
-    // ---- 5. backward error
-    const double worst = ac_residual<M, true>(a, G, C, om, bac, x, r, lane);
+    const double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane);
     // ---- 6. store
     double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
     for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
@@ -513,13 +522,127 @@ __global__ void __launch_bounds__(64 * W) k_ac_adj_multi_hbm(AcAdjMultiArgs u, A
   for (int ls = g; ls < end; ls += m.n_waves) ac_adj_multi_system<AcInHbm>(u, ls, wk, lane);   // a system's last column ends in the fence the next one needs
 }
 
+// ---- the sensitivity kernel: the response y = x[p] - x[n] of A x = b_ac and its derivatives with respect to K parameters from ONE factorisation
+// per system (cadnip_ac_sens; SPICE's .SENS on an AC sweep).  With the adjoint solution A^T lambda = c, c = e_p - e_n,
+//   dy/dp_k = lambda^T (db/dp_k - (dG/dp_k + j w dC/dp_k) x),
+// and the parameter derivatives of G and C are central differences of the stamps of two perturbed instances of the SAME resident batch.  A
+// system is (b, f) with b running over a LIST of base instances (u.base), not over the handle's instances.  The wave runs
+//   1. / 2.  ac_load_factor on the base instance's G and C,
+//   3.  the forward column (ac_lu_column: x is what k_ac_lu gives for that instance), copied into the fourth vector xf, which outlives
+//   4.  the adjoint column for c in the same x / r / y (ac_adj_solve_column: lambda is what k_ac_adj gives),
+//   5.  s_k = sum_i lambda_i db_k[i] - sum_e lambda[row(e)] ((G+[e] - G-[e]) + j w (C+[e] - C-[e])) scale[b][k] xf[col(e)], k = 0 .. K-1, with
+//       G+ / C+ the arrays of instance plus[b][k], G- / C- those of minus[b][k]: the differences are taken entry by entry from the handle's
+//       device arrays -- no derivative array exists anywhere.  gmin sits in both and cancels.  The lanes stride over i and over the entries
+//       (through the column view of the pattern, which carries an entry's row: a_row / a_pos of lu_transpose.hpp -- a fixed permutation of
+//       the CSR positions), keep one partial sum each, and wave_sum (tran_ctrl.hpp) adds the 64,
+//   6.  stores y, s[K], berr (forward, adjoint), one flag per column -- bit 0: zero / non-finite pivot or non-finite x or lambda of the SYSTEM,
+//       in all its columns; bit 1: non-finite s_k -- and x, lambda when the caller asked for them.
+// Every multiply-add is an explicit fma and the lane -> entry map does not depend on W or on where the work arrays live: the W instantiations
+// and the HBM variant compute the same doubles.  No atomics, no workgroup barrier.
+struct AcSensArgs {
+  AcAdjArgs t;                              // t.a.bac: b_ac [NB][n]; t.a.x: x, lambda out [systems][2][n] (null: not wanted); t.a.berr: [systems][2]; t.a.flags: [systems][K]
+  const int *base, *plus, *minus;           // [NB]; [NB][K]; [NB][K] instance indices
+  const double *scale, *db, *c;             // [NB][K]; [NB][K][n] complex (null: zeros); [n] complex
+  double *y, *s;                            // [systems] complex; [systems][K] complex
+  int n_par, p, q;                          // K; the output pair (-1: ground)
+};
+
+// acc + a b
+__device__ __forceinline__ double2 cmadd(double2 acc, double2 a, double2 b) {
+  return make_double2(fma(a.x, b.x, fma(-a.y, b.y, acc.x)), fma(a.x, b.y, fma(a.y, b.x, acc.y)));
+}
+
+// the wave's backward error from its lanes' figures (as ac_store_status: a NaN stays a NaN)
+__device__ __forceinline__ double ac_wave_berr(double worst) {
+  int nan = worst != worst;
+  if (nan) worst = 0.0;
+  for (int off = 32; off >= 1; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
+  return wave_any(nan) ? __builtin_nan("") : worst;
+}
+
+template <class M>
+__device__ __forceinline__ void ac_sens_system(const AcSensArgs& u, int ls, const AcWork& wk, double2* xf, int lane) {
+  const AcAdjArgs& t = u.t;
+  const AcArgs& a = t.a;
+  const int n = a.n, K = u.n_par;
+  const long s = a.s0 + ls;
+  const int bl = (int)(s / a.n_freq), fi = (int)(s - (long)bl * a.n_freq), inst = u.base[bl];
+  const double2* x = wk.x;
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double2* bac = (const double2*)a.bac + (size_t)bl * n;
+  const double2* c = (const double2*)u.c;
+  const double om = a.omega[fi];
+  int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
+  // ---- 3. the forward column; x goes to xf
+  const double berr_f = ac_wave_berr(ac_lu_column<M>(a, wk, G, C, om, bac, lane));
+  double2* xo = a.x ? (double2*)a.x + (size_t)ls * 2 * n : nullptr;
+  for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; xf[i] = v; if (xo) xo[i] = v; }
+  M::sync();                                                   // xf for every lane; the last reads of x before the adjoint column's words
+  // ---- 4. the adjoint column; lambda stays in x
+  const double berr_a = ac_wave_berr(ac_adj_solve_column<M>(t, wk, G, C, om, c, lane));
+  for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[n + i] = v; }
+  bad = wave_any(bad);
+  if (lane == 0) {
+    const double2 xp = u.p >= 0 ? xf[u.p] : make_double2(0.0, 0.0), xn = u.q >= 0 ? xf[u.q] : make_double2(0.0, 0.0);
+    ((double2*)u.y)[ls] = make_double2(xp.x - xn.x, xp.y - xn.y);
+    a.berr[2 * (size_t)ls] = berr_f; a.berr[2 * (size_t)ls + 1] = berr_a;
+  }
+  // ---- 5. / 6. the bilinear forms
+  for (int k = 0; k < K; ++k) {
+    const size_t bk = (size_t)bl * K + k, lk = (size_t)ls * K + k;   // lk: within int (api.hip bounds a launch's output)
+    const double *Gp = a.G + (size_t)u.plus[bk] * a.nnz, *Gm = a.G + (size_t)u.minus[bk] * a.nnz;
+    const double *Cp = a.C + (size_t)u.plus[bk] * a.nnz, *Cm = a.C + (size_t)u.minus[bk] * a.nnz;
+    const double sc = u.scale[bk];
+    double2 acc = make_double2(0.0, 0.0);
+    if (u.db) {
+      const double2* db = (const double2*)u.db + bk * n;
+      for (int i = lane; i < n; i += 64) acc = cmadd(acc, x[i], db[i]);
+    }
+    for (int q = lane; q < a.nnz; q += 64) {
+      const int e = t.a_pos[q];
+      const double2 dA = make_double2((Gp[e] - Gm[e]) * sc, (om * (Cp[e] - Cm[e])) * sc);
+      acc = cmsub(acc, x[t.a_row[q]], cmul(dA, xf[a.colidx[e]]));
+    }
+    const double re = wave_sum(acc.x), im = wave_sum(acc.y);
+    if (lane == 0) {
+      ((double2*)u.s)[lk] = make_double2(re, im);
+      a.flags[lk] = (bad ? 1 : 0) | ((!isfinite(re) || !isfinite(im)) ? 2 : 0);
+    }
+  }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_sens(AcSensArgs u) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= u.t.a.n_sys) return;                               // the tail workgroup: no workgroup barrier anywhere below
+  const LdsAcSens<double*> L = lds_ac_sens((double*)sm, u.t.a.nnz_lu, u.t.a.n, w, W);
+  ac_sens_system<AcInLds>(u, ls, AcWork{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y}, (double2*)L.xf, lane);
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_sens_hbm(AcSensArgs u, AcHbmArgs m) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.t.a.n_sys : 0;
+  const LdsAcSens<double*> L = lds_ac_sens(m.work, u.t.a.nnz_lu, u.t.a.n, g, m.n_waves);   // size_t offsets (lds_layout.hpp)
+  const AcWork wk{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y};
+  for (int ls = g; ls < end; ls += m.n_waves) {
+    ac_sens_system<AcInHbm>(u, ls, wk, (double2*)L.xf, lane);
+    AcInHbm::sync();                                           // the last reads of x and xf before the next system's words
+  }
+}
+
 // The launch plan -- the one place that sizes the LDS block and picks W, and the only reader of CADNIP_AC_WPB.  A compute unit holds
 // min(32 waves, LDS_BUDGET / block) workgroups' worth of systems: the plan takes the W with the most resident systems (ties: the largest),
 // then halves it while the launch would not put a workgroup on half of the 256 compute units.
-AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req) {
+AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req, bool sens) {
   AcPlan none;
   if (!h->analyzed || n_sys <= 0) return none;
-  auto bytes = [&](int wpb) { return lds_bytes(lds_ac((size_t)0, h->lu.nnz_lu, h->n, 0, wpb)); };
+  auto bytes = [&](int wpb) {
+    return sens ? lds_bytes(lds_ac_sens((size_t)0, h->lu.nnz_lu, h->n, 0, wpb)) : lds_bytes(lds_ac((size_t)0, h->lu.nnz_lu, h->n, 0, wpb));
+  };
   if (wpb_req == 0) if (const char* e = getenv("CADNIP_AC_WPB")) wpb_req = atoi(e);
   if (wpb_req != 0) {
     if ((wpb_req != 1 && wpb_req != 2 && wpb_req != 4 && wpb_req != 8) || bytes(wpb_req) > LDS_BUDGET) return none;
@@ -539,13 +662,14 @@ AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req) {
 }
 
 // Where the work arrays of a call live (cadnip_ac_set_memory) and the plan of that home: LDS -- ac_lu_plan alone, as ever; HBM -- the plan of
-// ac_hbm_plan.hpp on this device's compute units; AUTO -- LDS when ac_lu_plan accepts the circuit, else HBM.  memory < 0: refused
-AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req) {
+// ac_hbm_plan.hpp on this device's compute units; AUTO -- LDS when ac_lu_plan accepts the circuit, else HBM.  memory < 0: refused.
+// sens: the plan of k_ac_sens / k_ac_sens_hbm, whose systems keep a fourth n-vector
+AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req, bool sens) {
   AcLaunch L;
   AcState& A = h->ac;
   if (!h->analyzed || n_sys <= 0) return L;
   if (A.memory != CADNIP_AC_HBM) {
-    L.lds = ac_lu_plan(h, n_sys, wpb_req);
+    L.lds = ac_lu_plan(h, n_sys, wpb_req, sens);
     if (L.lds.wpb > 0) { L.memory = CADNIP_AC_LDS; return L; }
     if (A.memory == CADNIP_AC_LDS) return L;
   }
@@ -554,7 +678,8 @@ AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req) {
     if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cu = 0;
     A.n_cu = cu > 0 ? cu : 256;
   }
-  L.hbm = ac_hbm_plan(h->lu.nnz_lu, h->n, n_sys, wpb_req, A.max_waves, A.n_cu);
+  L.hbm = sens ? ac_hbm_plan_bytes(ac_sens_hbm_system_bytes(h->lu.nnz_lu, h->n), n_sys, wpb_req, A.max_waves, A.n_cu)
+               : ac_hbm_plan(h->lu.nnz_lu, h->n, n_sys, wpb_req, A.max_waves, A.n_cu);
   if (L.hbm.wpb > 0) L.memory = CADNIP_AC_HBM;
   return L;
 }
@@ -747,6 +872,35 @@ int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long
   ProfScope ps(h, "ac_adj_multi");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
   TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
+  HIP_TRY(hipGetLastError());
+  return CADNIP_OK;
+}
+
+int launch_ac_sens(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, bool db, const int* pair, bool want_x) {
+  AcState& A = h->ac;
+  if (L.memory < 0 || n_sys <= 0 || n_base < 1 || n_par < 1 || !pair || A.dirty || !A.adj_ready) return CADNIP_BADARG;
+  AcSensArgs u;
+  u.t = ac_adj_args(h, n_freq, s0, n_sys, gmin);
+  u.t.a.bac = A.d_sens_bac; u.t.a.x = want_x ? A.d_sens_x : nullptr; u.t.a.berr = A.d_sens_berr; u.t.a.flags = A.d_sens_flags;
+  u.t.pairs = nullptr; u.t.h = nullptr; u.t.n_pairs = 0;
+  u.base = A.d_sens_idx; u.plus = u.base + n_base; u.minus = u.plus + (size_t)n_base * n_par;
+  u.scale = A.d_sens_scale; u.db = db ? A.d_sens_db : nullptr; u.c = A.d_sens_c;
+  u.y = A.d_sens_y; u.s = A.d_sens_s; u.n_par = n_par; u.p = pair[0]; u.q = pair[1];
+  if (L.memory == CADNIP_AC_HBM) {
+    const AcHbmPlan& p = L.hbm;
+    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
+    TRY_RC(ac_work_reserve(h, p.work_bytes));
+    ProfScope ps(h, "ac_sens_hbm");
+    const AcHbmArgs m{A.d_work, p.n_waves};
+    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
+    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_sens_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, m); return CADNIP_OK; }));
+    HIP_TRY(hipGetLastError());
+    return CADNIP_OK;
+  }
+  const AcPlan& p = L.lds;
+  ProfScope ps(h, "ac_sens");
+  const int grid = (n_sys + p.wpb - 1) / p.wpb;
+  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_sens<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }

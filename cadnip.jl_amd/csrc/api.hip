@@ -219,6 +219,7 @@ void cadnip_destroy(CadnipHandle* h) {
   for (void* p : ptrs) if (p) (void)hipFree(p);
   h->ac.each_adjoint_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->ac.each_multi_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
+  h->ac.each_sens_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->f2.release();
   for (auto& g : h->step_graph) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (auto& b : h->blocks) {
@@ -929,6 +930,75 @@ int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega, 
 int cadnip_ac_adjoint_multi(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* c_host, int32_t n_pairs,
                             const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   return ac_multi_call(h, true, n_freq, omega, gmin, n_rhs, c_host, n_pairs, pairs, wpb, h_host, x_host, berr_host, flags_host, info);
+}
+
+// The sensitivity sweep: per (base instance b, frequency f) the response y = x[p] - x[n] of A x = b_ac and its derivatives with respect to n_par
+// parameters, s[k] = lambda^T (db[b][k] - (dG + j w dC) x) with A^T lambda = c and dG / dC the differences of the G / C of instances
+// plus[b][k] and minus[b][k] times scale[b][k] -- S = n_base n_freq systems through k_ac_sens (ac_lu.hip), one factorisation each.  Same rules
+// as cadnip_ac_solve; a system's device output is 16 (1 + K + 2 n [x wanted]) bytes.  Buffers live in AcState.
+int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_base, const int32_t* base, int32_t n_par, const int32_t* plus,
+                   const int32_t* minus, const double* scale, const double* bac_host, const double* db_host, const double* c_host, const int32_t* pair,
+                   int32_t wpb, double* y_host, double* s_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
+  if (!h || n_freq <= 0 || !omega || n_base < 1 || !base || n_par < 1 || !plus || !minus || !scale || !bac_host || !c_host || !pair || !y_host || !s_host ||
+      !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
+  const size_t B = h->B, n = h->n, F = n_freq, NB = n_base, K = n_par, S = NB * F;
+  for (size_t b = 0; b < NB; ++b) if (base[b] < 0 || base[b] >= (int32_t)B) return CADNIP_BADARG;
+  for (size_t k = 0; k < NB * K; ++k) if (plus[k] < 0 || plus[k] >= (int32_t)B || minus[k] < 0 || minus[k] >= (int32_t)B) return CADNIP_BADARG;
+  if (pair[0] < -1 || pair[0] >= (int32_t)n || pair[1] < -1 || pair[1] >= (int32_t)n || (pair[0] == -1 && pair[1] == -1)) return CADNIP_BADARG;
+  const bool want_x = x_host != nullptr, db = db_host != nullptr;
+  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * (1 + K + (want_x ? 2 * n : 0)))));
+  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb, true);       // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
+  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb, true) : plan;
+  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  TRY(ac_lu_prepare(h, true));
+  AcState& A = h->ac;
+  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
+  auto grow = [](auto** p, size_t* cap, size_t need, size_t words) {       // one buffer to `need` units of `words` elements
+    if (*cap >= need) return (int)CADNIP_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    *cap = 0;
+    TRY(dev_alloc(p, need * words));
+    *cap = need;
+    return (int)CADNIP_OK;
+  };
+  auto grow2 = [](auto** p, auto** q, size_t* cap, size_t need, size_t pw, size_t qw) {   // two buffers of one capacity
+    if (*cap >= need) return (int)CADNIP_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    if (*q) { (void)hipFree(*q); *q = nullptr; }
+    *cap = 0;
+    TRY(dev_alloc(p, need * pw)); TRY(dev_alloc(q, need * qw));
+    *cap = need;
+    return (int)CADNIP_OK;
+  };
+  if (!A.d_sens_c) TRY(dev_alloc(&A.d_sens_c, n * 2));
+  TRY(grow(&A.d_sens_idx, &A.cap_sens_idx, NB + 2 * NB * K, 1));
+  TRY(grow(&A.d_sens_scale, &A.cap_sens_scale, NB * K, 1));
+  TRY(grow(&A.d_sens_bac, &A.cap_sens_bac, NB * n, 2));
+  if (db) TRY(grow(&A.d_sens_db, &A.cap_sens_db, NB * K * n, 2));
+  TRY(grow2(&A.d_sens_y, &A.d_sens_berr, &A.cap_sens_sys, chunk, 2, 2));
+  TRY(grow2(&A.d_sens_s, &A.d_sens_flags, &A.cap_sens_cols, chunk * K, 2, 1));
+  if (want_x) TRY(grow(&A.d_sens_x, &A.cap_sens_x, chunk, 4 * n));
+  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_sens_idx, base, NB * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_sens_idx + NB, plus, NB * K * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_sens_idx + NB + NB * K, minus, NB * K * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_sens_scale, scale, NB * K * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_sens_bac, bac_host, NB * n * 2 * sizeof(double), hipMemcpyHostToDevice));
+  if (db) HIP_TRY(hipMemcpy(A.d_sens_db, db_host, NB * K * n * 2 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_sens_c, c_host, n * 2 * sizeof(double), hipMemcpyHostToDevice));
+  for (size_t s0 = 0; s0 < S; s0 += chunk) {
+    const size_t ns = std::min(chunk, S - s0);
+    TRY(launch_ac_sens(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin, n_base, n_par, db, pair, want_x));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(y_host + s0 * 2, A.d_sens_y, ns * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(s_host + s0 * K * 2, A.d_sens_s, ns * K * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * 4 * n, A.d_sens_x, ns * 4 * n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(berr_host + s0 * 2, A.d_sens_berr, ns * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags_host + s0 * K, A.d_sens_flags, ns * K * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  ac_report(h, plan, tail, S, chunk, info);
+  return CADNIP_OK;
 }
 
 int cadnip_lu_stats(CadnipHandle* h, int32_t* nnz_lu, int32_t* n_terms, int32_t* n_levels, int32_t* n_fwd, int32_t* n_bwd) {

@@ -157,6 +157,17 @@ struct AcState {
   template <class F> void each_multi_buffer(F f) {
     f((void**)&d_multi_rhs); f((void**)&d_multi_h); f((void**)&d_multi_x); f((void**)&d_multi_berr); f((void**)&d_multi_pairs); f((void**)&d_multi_flags);
   }
+  // sensitivity sweep (k_ac_sens, cadnip_ac_sens): its own transfer buffers, each grown on demand to the capacity beside it
+  int* d_sens_idx = nullptr;                                   // base [NB] | plus [NB][K] | minus [NB][K]
+  double *d_sens_scale = nullptr, *d_sens_bac = nullptr, *d_sens_db = nullptr, *d_sens_c = nullptr;   // [NB][K]; [NB][n], [NB][K][n], [n] complex
+  double *d_sens_y = nullptr, *d_sens_berr = nullptr, *d_sens_s = nullptr, *d_sens_x = nullptr;       // [S] complex, [S][2]; [S][K] complex; [S][2][n] complex
+  int* d_sens_flags = nullptr;                                 // [S][K]
+  size_t cap_sens_idx = 0, cap_sens_scale = 0, cap_sens_bac = 0, cap_sens_db = 0;   // ints, doubles, complex words, complex words
+  size_t cap_sens_sys = 0, cap_sens_cols = 0, cap_sens_x = 0;                       // systems (y, berr), (system, column)s (s, flags), systems of d_sens_x
+  template <class F> void each_sens_buffer(F f) {
+    f((void**)&d_sens_idx); f((void**)&d_sens_scale); f((void**)&d_sens_bac); f((void**)&d_sens_db); f((void**)&d_sens_c);
+    f((void**)&d_sens_y); f((void**)&d_sens_berr); f((void**)&d_sens_s); f((void**)&d_sens_x); f((void**)&d_sens_flags);
+  }
   // HBM-resident variant (k_ac_lu_hbm / k_ac_adj_hbm; cadnip_ac_set_memory, ac_hbm_plan.hpp): the setting, the persistent waves' workspace
   // (grown on demand like the buffers above, released with the handle) and what the last AC / adjoint call ran (cadnip_ac_plan_info)
   int memory = CADNIP_AC_LDS, max_waves = 0;
@@ -264,7 +275,7 @@ int upload_lu(CadnipHandle* h);
 // ac_lu.hip: the launch plan of k_ac_lu<W> for n_sys systems -- wpb_req 0: the plan's choice (CADNIP_AC_WPB overrides it), else 1 / 2 / 4 / 8.
 // wpb 0: an invalid request, or the work arrays of wpb_req (of one, for 0) systems exceed LDS_BUDGET
 struct AcPlan { int wpb = 0; size_t shmem = 0; };
-AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req);
+AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req, bool sens = false);   // sens: of k_ac_sens<W>, 16 (nnz(L+U) + 4 n) bytes per system
 // the home of a call's work arrays under the handle's setting (h->ac.memory) and its plan: memory CADNIP_AC_LDS -> lds, CADNIP_AC_HBM -> hbm
 // (ac_hbm_plan.hpp, on the device's compute units and h->ac.max_waves); -1: refused -- an invalid wpb, or the circuit fits neither
 struct AcLaunch {
@@ -272,7 +283,7 @@ struct AcLaunch {
   int wpb() const { return memory == CADNIP_AC_HBM ? hbm.wpb : lds.wpb; }
   int workgroups(long n_sys) const { return memory == CADNIP_AC_HBM ? (hbm.n_waves + hbm.wpb - 1) / hbm.wpb : (int)((n_sys + lds.wpb - 1) / lds.wpb); }
 };
-AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req);
+AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req, bool sens = false);
 // the pivot lists of the current LU program, on demand; adjoint: the transposed-solve tables (lu_transpose.hpp) as well
 int ac_lu_prepare(CadnipHandle* h, bool adjoint = false);
 // systems [s0, s0 + n_sys) of the B x n_freq grid (s = b * n_freq + f) into h->ac.d_x / d_berr / d_flags from index 0
@@ -286,6 +297,10 @@ int launch_ac_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int
 // ... of A^T x_k = c_k for the n_rhs columns per instance in h->ac.d_multi_rhs through k_ac_adj_multi (one factorisation per system; needs
 // ac_lu_prepare(h, true)): the outputs as launch_ac_multi, in the same buffers
 int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x);
+// systems [s0, s0 + n_sys) of the n_base x n_freq grid of cadnip_ac_sens (s = b * n_freq + f, b an index into the base list) through k_ac_sens
+// (needs ac_lu_prepare(h, true); p must come from ac_launch_plan(.., sens = true)): inputs and outputs in the d_sens_* buffers, outputs from
+// index 0; n_par columns, db: a db buffer was uploaded (else zeros), pair: the output pair
+int launch_ac_sens(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, bool db, const int* pair, bool want_x);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

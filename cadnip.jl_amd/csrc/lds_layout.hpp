@@ -99,6 +99,17 @@ template <class P> LDS_HD LdsAc<P> lds_ac(P base, int nnz_lu, int n, int w, int 
   L.end = base + (size_t)wpb * L.per;
   return L;
 }
+// Sensitivity kernel k_ac_sens<W>: lds_ac's regions in lds_ac's order, then xf (n): the forward solution, which has to outlive the adjoint
+// column that runs in x / r / y -- 16 (nnz_lu + 4 n) bytes per system
+template <class P> struct LdsAcSens { P lu, x, r, y, xf, end; int per; };   // per: doubles of one system
+template <class P> LDS_HD LdsAcSens<P> lds_ac_sens(P base, int nnz_lu, int n, int w, int wpb) {
+  LdsAcSens<P> L;
+  L.per = 2 * (nnz_lu + 4 * n);
+  L.lu = base + (size_t)w * L.per;
+  L.x = L.lu + 2 * (size_t)nnz_lu; L.r = L.x + 2 * (size_t)n; L.y = L.r + 2 * (size_t)n; L.xf = L.y + 2 * (size_t)n;
+  L.end = base + (size_t)wpb * L.per;
+  return L;
+}
 template <class L> LDS_HD size_t lds_bytes(const L& l) { return (size_t)l.end * 8; }   // of a layout taken from base (size_t)0
 
 #ifdef __HIPCC__

@@ -23,7 +23,7 @@ AC_MEMORY = {"lds": 0, "hbm": 1, "auto": 2}     # CADNIP_AC_LDS / _HBM / _AUTO (
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_sens", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
@@ -441,6 +441,47 @@ class Handle:
                                         _ip(pr) if P else None, C.c_int32(int(wpb)), None if hh is None else hh.ctypes.data_as(_D),
                                         None if x is None else x.ctypes.data_as(_D), _dp(berr), _ip(flags), _ip(info)), entry)
         return hh, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+
+    def ac_sens(self, omega, gmin, base, plus, minus, scale, b_ac, c, pair, db=None, wpb=0, want_x=False):
+        """cadnip_ac_sens: per (base instance, frequency) the response y = x[p] - x[n] of A x = b_ac and its derivatives with respect to K
+        parameters from ONE factorisation (csrc/ac_lu.hip: k_ac_sens): s[b, f, k] = lambda^T (db[b, k] - (dG + j omega[f] dC) x) with
+        A^T lambda = c, dG = (G[plus[b, k]] - G[minus[b, k]]) scale[b, k] and dC likewise, on the G / C of the last rebuild.  ``base`` [NB]
+        instance indices, ``plus`` / ``minus`` [NB, K] instance indices, ``scale`` [NB, K], ``b_ac`` [NB, n] complex (or [n], broadcast),
+        ``c`` [n] complex, ``pair`` (p, n) unknown indices (-1 = ground), ``db`` [NB, K, n] complex or None (zeros).  Returns (y complex128
+        [NB, F], s [NB, F, K], x [NB, F, 2, n] -- x and lambda -- or None without ``want_x``, berr [NB, F, 2] (forward, adjoint), flags
+        [NB, F, K] (bit 0: the system, bit 1: a non-finite s), info as ``ac_solve``).  x and lambda are bit-identical to ``ac_solve`` /
+        ``ac_adjoint`` on instance base[b].  An empty grid launches nothing.  Arrays of the wrong shape raise ValueError; no base, no parameter,
+        an instance index outside [0, B), a pair index outside [-1, n), the pair (-1, -1), a circuit the memory setting refuses or an invalid
+        ``wpb`` raise CadnipError(CADNIP_BADARG)."""
+        om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
+        bs = np.ascontiguousarray(np.asarray(base, dtype=np.int32).ravel())
+        pl, mi = np.ascontiguousarray(plus, dtype=np.int32), np.ascontiguousarray(minus, dtype=np.int32)
+        sc = np.ascontiguousarray(scale, dtype=np.float64)
+        n, F, NB = self.st.n, om.size, bs.size
+        if pl.ndim != 2 or pl.shape[0] != NB or mi.shape != pl.shape or sc.shape != pl.shape:
+            raise ValueError("plus, minus and scale must be [NB, K] for NB base instances")
+        K = pl.shape[1]
+        pr = np.ascontiguousarray(np.asarray(pair, dtype=np.int32).ravel())
+        cc = np.ascontiguousarray(np.asarray(c, dtype=np.complex128))
+        if pr.shape != (2,) or cc.shape != (n,):
+            raise ValueError("pair must be (p, n) and c an [n] column")
+        bb = np.asarray(b_ac, dtype=np.complex128)
+        if bb.shape not in ((n,), (NB, n)):
+            raise ValueError("b_ac must be [n] or [NB, n]")
+        bb = np.ascontiguousarray(np.broadcast_to(bb, (NB, n)))
+        dd = None if db is None else np.ascontiguousarray(db, dtype=np.complex128)
+        if dd is not None and dd.shape != (NB, K, n):
+            raise ValueError("db must be [NB, K, n]")
+        y, s = np.empty((NB, F), dtype=np.complex128), np.empty((NB, F, K), dtype=np.complex128)
+        x = np.empty((NB, F, 2, n), dtype=np.complex128) if want_x else None
+        berr, flags, info = np.empty((NB, F, 2)), np.zeros((NB, F, K), dtype=np.int32), np.zeros(4, dtype=np.int32)
+        if F == 0:
+            return y, s, x, berr, flags, dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
+        _check(self.lib.cadnip_ac_sens(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), C.c_int32(NB), _ip(bs), C.c_int32(K), _ip(pl), _ip(mi), _dp(sc),
+                                       bb.ctypes.data_as(_D), None if dd is None else dd.ctypes.data_as(_D), cc.ctypes.data_as(_D), _ip(pr),
+                                       C.c_int32(int(wpb)), y.ctypes.data_as(_D), s.ctypes.data_as(_D), None if x is None else x.ctypes.data_as(_D),
+                                       _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_sens")
+        return y, s, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
 
     def ac_set_memory(self, mode="lds", max_waves=0):
         """cadnip_ac_set_memory: where ``ac_solve`` / ``ac_adjoint`` keep a system's work arrays from now on.  "lds" (the default of a new handle):

@@ -275,6 +275,28 @@ int cadnip_ac_adjoint_multi(CadnipHandle* h, int32_t n_freq, const double* omega
                             const double* c_host /* [B][K][n][2] */, int32_t n_pairs, const int32_t* pairs /* [n_pairs][2], -1 = ground */,
                             int32_t wpb, double* h_host /* [B][F][K][n_pairs][2] */, double* x_host /* [B][F][K][n][2] or NULL */,
                             double* berr_host /* [B][F][K] */, int32_t* flags_host /* [B][F][K] */, int32_t* info /* [4] */);
+/* AC sensitivities (SPICE's .SENS on an AC sweep; the gradient of a sizing or yield loop): per system (b, f) -- b an index into the list
+ * `base` of n_base instances, NOT every instance of the handle -- the response y = x[p] - x[n] of A x = bac[b] (pair = {p, n}; -1 = ground)
+ * and its derivatives with respect to n_par parameters from ONE factorisation (csrc/ac_lu.hip: k_ac_sens):
+ *   s[b][f][k] = lambda^T (db[b][k] - (dG + j omega[f] dC) x),   A^T lambda = c,
+ * with dG = (G[plus[b][k]] - G[minus[b][k]]) scale[b][k] and dC likewise: the derivatives of G and C are differences of the stamps of
+ * perturbed instances that sit in the same handle (their G / C of the last cadnip_rebuild), taken entry by entry on the device; gmin
+ * cancels in them.  For a central difference p_k +- delta: scale = 1 / (2 delta), db = (b_ac(p_k + delta) - b_ac(p_k - delta)) / (2 delta);
+ * db_host NULL means zeros.  c is one [n] column for all systems, e_p - e_n for the derivative of y.  A, the pivot order, the factors, the
+ * solves, the refinement steps and the backward errors are those of cadnip_ac_solve and cadnip_ac_adjoint: x (hence y) and lambda are
+ * bit-identical to those calls on instance base[b].  berr: {forward, adjoint}.  flags, one word per (b, f, k): bit 0 a zero / non-finite
+ * pivot or a non-finite x or lambda of system (b, f), set in all its columns; bit 1 a non-finite s[b][f][k].  With x_host non-NULL x and
+ * lambda come back as well.  wpb, info, cadnip_ac_set_memory and cadnip_ac_plan_info as cadnip_ac_solve, except that a system keeps a
+ * fourth n-vector: 16 (nnz(L+U) + 4 n) bytes, in LDS and in a wave's workspace.  Chunks of at most 64 MiB of device output,
+ * 16 (1 + n_par + 2 n [x wanted]) bytes per system.  CADNIP_BADARG -- nothing launched, nothing written, no plan recorded -- without an
+ * analysis, with n_freq <= 0, n_base < 1, n_par < 1, an instance index outside [0, B), a pair index outside [-1, n), p == n == -1, an
+ * invalid wpb, or when the memory setting refuses the work arrays. */
+int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega /* [F] */, double gmin, int32_t n_base, const int32_t* base /* [NB] */,
+                   int32_t n_par, const int32_t* plus /* [NB][K] */, const int32_t* minus /* [NB][K] */, const double* scale /* [NB][K] */,
+                   const double* bac_host /* [NB][n][2] */, const double* db_host /* [NB][K][n][2] or NULL */, const double* c_host /* [n][2] */,
+                   const int32_t* pair /* [2], -1 = ground */, int32_t wpb, double* y_host /* [NB][F][2] */, double* s_host /* [NB][F][K][2] */,
+                   double* x_host /* [NB][F][2][n][2]: x, lambda; or NULL */, double* berr_host /* [NB][F][2] */,
+                   int32_t* flags_host /* [NB][F][K] */, int32_t* info /* [4] */);
 
 /* Where the AC and adjoint sweeps keep a system's work arrays -- a handle setting, LDS by default: every call exactly as without it.
  *   CADNIP_AC_LDS   in LDS (k_ac_lu / k_ac_adj): one wave per system, refused beyond 160 KB as described above,
