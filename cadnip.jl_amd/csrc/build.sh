@@ -24,4 +24,7 @@ if [ "${1:-}" = "--trace" ]; then
 else
   make -j"$JOBS"
   echo "built $(realpath ../libcadnip_hip.so)"
+  # the primitive probes (test infrastructure: csrc/probe/prim_probe.hip)
+  make probe
+  echo "built $(realpath ../libcadnip_probe.so)"
 fi

@@ -113,7 +113,11 @@ __device__ __forceinline__ double volt(const double* u, int node) { return node 
 // ------------------------------------------------------------------------------------------
 // `seg` (optional): the segment index i found by the previous call.  When t lies strictly inside that segment again
 // (time mostly advances in small steps) the search -- a chain of dependent memory reads -- is skipped; same result.
+// The waves are evaluated as the reference writes them, one rounding per operation: no fused multiply-add (the compiler's default would
+// contract y_lo + dt * slope), so that the value is the oracle's bit for bit (tests/test_gpu_primitives.py) and the same in every copy of
+// the expression (here twice, src_cache.hpp: src_seg_value).
 __device__ inline double pwl_at_time(const double* ts, const double* ys, int n, double t, int* seg = nullptr) {
+#pragma clang fp contract(off)
   if (seg) {
     const int i = *seg;
     if (i >= 2 && i <= n) {
@@ -139,6 +143,7 @@ __device__ inline double pwl_at_time(const double* ts, const double* ys, int n, 
 }
 
 __device__ inline double pulse_at_time(double v1, double v2, double td, double tr, double tf, double pw, double per, double t) {
+#pragma clang fp contract(off)
   if (t < td) return v1;
   double phase;
   if (per > 0) { phase = fmod(t - td, per); if (phase < 0) phase += per; } else phase = t - td;

@@ -41,6 +41,9 @@ LDS_HD SrcSeg src_seg_fill(int kind, double dc) {
 LDS_HD bool src_seg_hit(const SrcSeg& e, double t) { return e.t_lo < t && t < e.t_hi; }
 // value at a time the entry answers for: pwl_at_time's expression, then source_value's scale
 LDS_HD double src_seg_value(const SrcSeg& e, double t) {
+#ifdef __clang__
+#pragma clang fp contract(off)    // as pwl_at_time: one rounding per operation (the host test builds this header with -ffp-contract=off)
+#endif
   double v;
   if (e.y_lo == e.y_hi) v = e.y_hi;
   else v = e.y_lo + (t - e.t_lo) * ((e.y_hi - e.y_lo) / (e.t_hi - e.t_lo));

@@ -48,10 +48,13 @@ __device__ __forceinline__ double wave_sum(double v) {
 __device__ __forceinline__ int wave_any(int v) { return __any(v); }
 
 // a / b for finite, non-zero, normal-range b (pivots, positive error weights, step sizes): v_rcp_f64 + two Newton steps +
-// one residual correction; none of IEEE division's range scaling.  For normal-range operands and quotients it IS the correctly rounded
-// quotient -- bit for bit the result of `a / b` over 1.3e9 random pairs with exponents up to +-500 apart (tools/ubench/divcheck.hip) --
-// so the CPU port's plain divisions stay its exact counterpart.  One wave alone pays ~45 cycles for it, 117 for the compiler's IEEE
-// sequence (tools/ubench/lat.hip), and the controller's scalars are a chain of such divisions.
+// one residual correction; none of IEEE division's range scaling.  For 2^-1022 <= |b| <= 2^1022 (1 / b a normal number), |a| >= 2^-969 (the
+// residual a - b q a normal number) and a quotient in the normal range it IS the correctly rounded quotient -- bit for bit the result of
+// `a / b` over 1.3e9 random pairs with exponents up to +-500 apart (tools/ubench/divcheck.hip), and in the suite over 65536 of them and 1e5
+// pairs whose quotient lies within 2^-102 of a rounding midpoint (tests/test_gpu_primitives.py) -- so the CPU port's plain divisions stay
+// its exact counterpart.  Outside that range the quotient may be one ulp off; a = 0 gives a zero, with IEEE's sign except that -0 / b,
+// b > 0, gives +0; b = +-0, +-inf or NaN, or a non-finite a, never gives a finite number.  One wave alone pays ~45 cycles for it, 117 for the
+// compiler's IEEE sequence (tools/ubench/lat.hip), and the controller's scalars are a chain of such divisions.
 __device__ __forceinline__ double fast_div(double a, double b) {
   double r = __builtin_amdgcn_rcp(b);
   r = fma(fma(-b, r, 1.0), r, r);
@@ -62,8 +65,9 @@ __device__ __forceinline__ double fast_div(double a, double b) {
 
 // x^(-1/(ord+1)) for the step-size rule, ord = 1 or 2, x > 0 finite.  `pow` costs one wave ~870 cycles (tools/ubench/lat.hip) once per
 // accepted step.  Order 1: 1 / sqrt(x), both IEEE-exact.  Order 2: x = m 8^q with m in [0.5, 4), y ~ m^(-1/3) by four Newton steps
-// y <- y (4 - m y^3) / 3 from a linear start (relative error 1e-13: a step-size heuristic does not need the last bits, it needs the same
-// bits on both sides) -- written with single-rounding operations only (products, fma, exact frexp / ldexp), so that oracle/cpu_port.cpp's
+// y <- y (4 - m y^3) / 3 from a linear start (relative error up to 9.33e-8, reached at m -> 4-; the error after each step is 7.4e-2,
+// 1.0e-2, 2.2e-4, 9.3e-8: a step-size heuristic does not need the last bits, it needs the same bits on both sides, and a fifth step would
+// change every transient's step sequence) -- written with single-rounding operations only (products, fma, exact frexp / ldexp), so that oracle/cpu_port.cpp's
 // copy (step_root) returns the same double.
 __device__ __forceinline__ double step_root(double x, int ord) {
   if (ord == 1) return fast_div(1.0, sqrt(x));

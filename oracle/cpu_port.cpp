@@ -25,6 +25,8 @@ namespace {
 
 // x^(-1/(ord+1)) of the step-size rule: operation for operation the product's step_root (csrc/tran_ctrl.hpp) -- IEEE sqrt and division
 // for order 1; for order 2 exact frexp / ldexp, products and fused multiply-adds only, so that both sides get the same double.
+// Order 2 is four Newton steps from a linear start: relative error up to 9.33e-8 (at m -> 4-; errors per step 7.4e-2, 1.0e-2, 2.2e-4,
+// 9.3e-8), which a step-size heuristic tolerates.  A fifth step would change every transient's step sequence.
 static double step_root(double x, int ord) {
   if (ord == 1) return 1.0 / std::sqrt(x);
   if (ord == 3) return 1.0 / std::sqrt(std::sqrt(x));
@@ -71,7 +73,13 @@ struct Port {
 };
 
 // ---- waves (devices.jl:30-103,155-203) ---------------------------------------------------------
-double pwl(const double* ts, const double* ys, int n, double t) {
+// one rounding per operation, as the reference and the product's pwl_at_time / pulse_at_time: no fused multiply-add
+#if defined(__GNUC__) && !defined(__clang__)
+#define PORT_NO_FMA __attribute__((optimize("fp-contract=off")))
+#else
+#define PORT_NO_FMA
+#endif
+PORT_NO_FMA double pwl(const double* ts, const double* ys, int n, double t) {
   int i = (int)(std::lower_bound(ts, ts + n, t) - ts) + 1;
   if (i <= n && ts[i - 1] == t) i += 1;
   if (i <= 1) return ys[0];
@@ -80,7 +88,7 @@ double pwl(const double* ts, const double* ys, int n, double t) {
   if (ts[i - 1] == ts[i - 2]) return (ys[i - 2] + ys[i - 1]) / 2;
   return ys[i - 2] + (t - ts[i - 2]) * ((ys[i - 1] - ys[i - 2]) / (ts[i - 1] - ts[i - 2]));
 }
-double pulse(const double* w, double t) {
+PORT_NO_FMA double pulse(const double* w, double t) {
   double v1 = w[0], v2 = w[1], td = w[2], tr = w[3], tf = w[4], pw = w[5], per = w[6];
   if (t < td) return v1;
   double ph = per > 0 ? std::fmod(t - td, per) : t - td;
@@ -431,6 +439,9 @@ bool lu_solve_kept(Port& P, const double* rhs, double* x) {
 }  // namespace
 
 extern "C" {
+
+// the controller's step_root on its own (tests/test_gpu_primitives.py: the device's copy must return the same double)
+double cadnip_port_step_root(double x, int ord) { return step_root(x, ord); }
 
 void* port_create(int n, int n_nodes, int n_limits, int nnz, const int* rowptr, const int* colidx, int ns_g, int ns_c, int ns_b,
                   const int* g_ptr, const int* g_slots, const int* c_ptr, const int* c_slots, const int* b_ptr, const int* b_slots,

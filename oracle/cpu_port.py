@@ -52,7 +52,14 @@ def lib():
         _lib.port_set_spec.restype = None
         _lib.port_set_lu.restype = None
         _lib.port_rebuild.restype = None
+        _lib.cadnip_port_step_root.restype = C.c_double
+        _lib.cadnip_port_step_root.argtypes = [C.c_double, C.c_int32]
     return _lib
+
+
+def step_root(x, order):
+    """The port's copy of the controller's x^(-1/(order+1)) (csrc/tran_ctrl.hpp: step_root)."""
+    return float(lib().cadnip_port_step_root(float(x), int(order)))
 
 
 def _ia(a):

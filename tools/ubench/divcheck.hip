@@ -1,5 +1,7 @@
 // divcheck.hip -- is fast_div (tran_ctrl.hpp: v_rcp_f64 + two Newton steps + one residual correction) the correctly rounded quotient
 // for normal-range operands?  Compares it bit for bit with IEEE division over 2^28 random pairs drawn from several magnitude ranges.
+// This is the bulk run, by hand.  The gate is in the suite: tests/test_gpu_primitives.py (test_fast_div_*) runs the header's own fast_div over
+// random pairs, structured operands and 1e5 pairs next to a rounding midpoint, and pins where it stops being IEEE division.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdint.h>
