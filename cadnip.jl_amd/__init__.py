@@ -7,6 +7,7 @@ reference-shaped API (MNACircuit / dc / tran / CircuitSweep).  Device side: libc
 from .circuit import Circuit, Param, Device  # noqa: F401
 from .structure import discover, pack_params, expand_breakpoints, Structure  # noqa: F401
 from . import mos1_params, bsource, netlist  # noqa: F401
-from .api import network, NetworkSol, network_noise, NetworkNoiseSol  # noqa: F401
+from .api import network, NetworkSol, network_noise, NetworkNoiseSol, pz, PZSol, pz_solve, subsystem, poles_dense, zeros_dense  # noqa: F401
 
-__all__ = ["Circuit", "Param", "Device", "discover", "pack_params", "expand_breakpoints", "Structure", "network", "NetworkSol", "network_noise", "NetworkNoiseSol"]
+__all__ = ["Circuit", "Param", "Device", "discover", "pack_params", "expand_breakpoints", "Structure", "network", "NetworkSol", "network_noise", "NetworkNoiseSol", "pz", "PZSol", "pz_solve", "subsystem",
+           "poles_dense", "zeros_dense"]

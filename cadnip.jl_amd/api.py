@@ -1733,6 +1733,292 @@ def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device
     return SweepResult(pts, sols) if sweep else sols[0]
 
 
+def subsystem(ac, name):
+    """subsystem(ac, name) -- src/ac.jl:358-388: the single-output descriptor system E x' = A x + B u, y = C x + D u of an ACSol as the tuple
+    (A, E, B, C_row, D) = (-G, C, b_ac[:, None], e_name^T, 0) -- what a control-systems package takes.  Ground is not an unknown: ValueError."""
+    if name in ("0", "gnd", "gnd!"):
+        raise ValueError("subsystem: ground is not an unknown of the system")
+    try:
+        i = ac.st.index_of(name)
+    except KeyError as e:
+        raise ValueError("subsystem: " + str(e.args[0])) from None
+    c = np.zeros((1, ac.st.n))
+    c[0, i] = 1.0
+    return -np.asarray(ac.G, dtype=float), np.asarray(ac.C, dtype=float), np.asarray(ac.b_ac, dtype=complex)[:, None], c, np.zeros((1, 1))
+
+
+# A Ritz value theta of A^-1 C whose modulus is below PZ_THETA_TOL times the largest one belongs to the infinite eigenvalues of the pencil (the
+# null space of C: algebraic unknowns) and gives no pole.  Measured with the numpy port (tests/pz_ref.py) over the circuits of
+# tests/test_pz_cpu.py, on Krylov spaces that closed: the smallest genuine |theta| / max |theta| is 1.4e-2 (the eight-section ladder), the
+# largest spurious one 6.3e-16 -- the geometric middle of the gap (DESIGN section 9)
+PZ_THETA_TOL = 3e-9
+# A dense pencil's eigenvalue alpha / beta (both matrices scaled to unit norm) is infinite when |beta| <= PZ_INF_TOL |alpha|: QZ leaves the
+# infinite ones at |beta| of the order of the unit roundoff, and a finite pole 1e9 times beyond ||G|| / ||C|| is not one a circuit has
+PZ_INF_TOL = 1e-9
+# A Ritz pair is accepted as a pole when its residual estimate |h_{m+1,m}| |e_m^T y| / |theta| is at most this; after a breakdown the estimate is
+# 0.  The square root of the unit roundoff: a converged pair, to the first order at which the estimate means anything
+PZ_RESID_MAX = 1.5e-8
+# the relative perturbation of the probe row with which ``pz_solve`` tells the zeros of a reduced model from the images of its zeros at infinity:
+# those move by at least its square root (1e-5), a genuine zero is kept when it moves by less than a hundredth of that
+PZ_ZERO_PROBE = 1e-10
+# two accepted poles from different shifts closer than this (relative to the larger modulus) are one pole: the one with the smaller estimate stays
+PZ_MERGE_TOL = 1e-6
+
+
+def _finite_eigs(M0, M1):
+    """The finite s with det(M0 + s M1) = 0 through scipy.linalg.eig in homogeneous form, each matrix scaled to unit norm: an eigenvalue
+    alpha / beta is infinite when |beta| <= PZ_INF_TOL |alpha| there."""
+    import scipy.linalg as sla
+    M0, M1 = np.asarray(M0, dtype=complex), np.asarray(M1, dtype=complex)
+    n0, n1 = np.linalg.norm(M0), np.linalg.norm(M1)
+    if n0 == 0.0 or n1 == 0.0:
+        return np.zeros(0, dtype=complex)
+    ab = sla.eig(-M0 / n0, M1 / n1, right=False, homogeneous_eigvals=True)
+    keep = np.abs(ab[1]) > PZ_INF_TOL * np.abs(ab[0])
+    return ab[0][keep] / ab[1][keep] * (n0 / n1)
+
+
+def poles_dense(G, C):
+    """The finite generalized eigenvalues of (-G, C): every finite pole of (G + s C)^-1 -- the host path of ``pz`` and the tests' reference."""
+    return _finite_eigs(G, C)
+
+
+def zeros_dense(G, C, b, c):
+    """The finite transmission zeros of c^T (G + s C)^-1 b: the finite generalized eigenvalues of the bordered pencil [[G, -b], [c^T, 0]] +
+    s [[C, 0], [0, 0]]."""
+    n = len(b)
+    M0, M1 = np.zeros((n + 1, n + 1), dtype=complex), np.zeros((n + 1, n + 1), dtype=complex)
+    M0[:n, :n], M0[:n, n], M0[n, :n] = G, -np.asarray(b), np.asarray(c)
+    M1[:n, :n] = C
+    return _finite_eigs(M0, M1)
+
+
+def arnoldi_host(G, C, b, omega0, m, c, breakdown_tol=None):
+    """The host implementation of cadnip_ac_arnoldi's algorithm for one system, dense: A = G + j omega0 C, r = A^-1 b, m steps of K = A^-1 C
+    with two passes of modified Gram-Schmidt and the kernel's breakdown test.  ``c`` [P, n]: the probe rows.  Returns (H [m+1, m], beta,
+    m_eff, l [m, P]) as the kernel lays them out."""
+    import scipy.linalg as sla
+    from . import hip
+    tol = hip.AC_BREAKDOWN_TOL if breakdown_tol is None else breakdown_tol
+    n = len(b)
+    c = np.asarray(c, dtype=complex).reshape(-1, n)
+    H, l = np.zeros((m + 1, m), dtype=complex), np.zeros((m, c.shape[0]), dtype=complex)
+    lu = sla.lu_factor(np.asarray(G) + 1j * omega0 * np.asarray(C))
+    r = sla.lu_solve(lu, np.asarray(b, dtype=complex))
+    beta = float(np.linalg.norm(r))
+    if not (beta > 0.0 and np.isfinite(beta)):
+        return H, beta, 0, l
+    V = [r / beta]
+    l[0] = c @ V[0]
+    m_eff = m
+    for j in range(m):
+        w = sla.lu_solve(lu, np.asarray(C) @ V[j])
+        nu0 = np.linalg.norm(w)
+        for _ in range(2):
+            for i in range(j + 1):
+                h = np.vdot(V[i], w)
+                w = w - h * V[i]
+                H[i, j] += h
+        nu1 = np.linalg.norm(w)
+        if nu0 == 0.0 or nu1 <= tol * nu0:
+            m_eff = j + 1
+            break
+        H[j + 1, j] = nu1
+        V.append(w / nu1)
+        if j + 1 < m:
+            l[j + 1] = c @ V[j + 1]
+    return H, beta, m_eff, l
+
+
+class PZSol:
+    """``pz``'s result for one point.  ``poles`` / ``zeros``: complex, in rad/s; ``gain``: the transfer function at s = 0; ``pole_resid`` /
+    ``pole_shift``: per pole its residual estimate and the shift that found it (0 / nan on the dense host path); ``reduced(shift)`` ->
+    (H [m_eff, m_eff], beta, l [m_eff]) of that shift, from which T(s) = l^T (I + (s - j omega_0) H)^-1 beta e_1 (``transfer``, s in rad/s);
+    ``dc_x``: the DC solution; ``stats``: ``ACSol.stats``' keys plus "order", "shifts", "breakdowns".  A shift is named as the caller gave
+    it: an angular frequency to ``pz_solve``, hertz to ``pz`` (``shift_scale`` = 2 pi there)."""
+
+    def __init__(self, poles, zeros, gain, pole_resid, pole_shift, models, dc_x=None):
+        self.poles, self.zeros, self.gain = np.asarray(poles, dtype=complex), np.asarray(zeros, dtype=complex), complex(gain)
+        self.pole_resid, self.pole_shift = np.asarray(pole_resid, dtype=float), np.asarray(pole_shift, dtype=float)
+        self._models, self.dc_x, self.stats, self.shift_scale = dict(models), dc_x, {}, 1.0
+
+    def _in_hertz(self, shifts_hz, omegas):
+        name = {float(w): float(f) for f, w in zip(shifts_hz, omegas)}
+        self._models = {name[w]: v for w, v in self._models.items()}
+        self.pole_shift = np.array([name[float(w)] for w in self.pole_shift], dtype=float)
+        self.shift_scale = 2.0 * np.pi
+
+    def reduced(self, shift):
+        return self._models[float(shift)]
+
+    def transfer(self, s, shift=None):
+        key = float(shift) if shift is not None else min(self._models, key=abs)
+        H, beta, l = self._models[key]
+        w0 = key * self.shift_scale
+        e1 = np.zeros(H.shape[0], dtype=complex)
+        e1[0] = beta
+        return np.array([l @ np.linalg.solve(np.eye(H.shape[0]) + (sv - 1j * w0) * H, e1) for sv in np.atleast_1d(np.asarray(s, dtype=complex))])
+
+
+def pz_solve(st, G, C, b, out, shifts, order, arnoldi=None):
+    """The matrix-level worker of ``pz`` for one point: ``G`` (gmin on the node diagonals), ``C`` dense, ``b`` the excitation, ``out`` a (p, n)
+    pair of unknown indices (-1 = ground), ``shifts`` angular frequencies omega_0 of the shifts j omega_0, ``order`` the Arnoldi steps m (at most
+    n).  ``arnoldi(omega_0) -> (H, beta, m_eff, l)`` supplies the reduction of a shift (l [m, 1] for the one probe pair) and defaults to
+    ``arnoldi_host``.  Per shift: the Ritz values theta of H[:m_eff, :m_eff] give poles j omega_0 - 1 / theta with the residual estimate
+    |h_{m_eff+1, m_eff}| |e^T y| / |theta| (0 after a breakdown); theta below PZ_THETA_TOL max |theta| are the infinite eigenvalues and dropped;
+    poles whose estimate is at most PZ_RESID_MAX are accepted and merged across the shifts (PZ_MERGE_TOL).  Zeros: the finite eigenvalues of
+    the reduced pencil [[I + (s - s_0) H, -beta e_1], [l^T, 0]] of the first shift whose space closed (else of the first shift), beyond
+    1 / (PZ_THETA_TOL max |theta|) from the shift dropped.  The gain is the reduced model of the shift nearest 0 at s = 0 (exact for shift 0).
+    Returns (PZSol, breakdowns)."""
+    n = len(b)
+    m = min(int(order), n)
+    c = np.zeros(n, dtype=complex)
+    for j, sgn in zip(out, (1.0, -1.0)):
+        if j >= 0:
+            c[j] += sgn
+    if arnoldi is None:
+        arnoldi = lambda w0: arnoldi_host(G, C, b, w0, m, c[None])
+    cand, models, closed, breakdowns = [], {}, [], 0
+    for w0 in (float(w) for w in shifts):
+        H, beta, m_eff, l = arnoldi(w0)
+        m_eff = int(m_eff)
+        H, l = np.asarray(H), np.asarray(l).reshape(H.shape[1], -1)[:, 0]
+        Hm = H[:m_eff, :m_eff]
+        models[w0] = (Hm, float(beta), l[:m_eff])
+        if m_eff == 0:
+            continue
+        sub = abs(H[m_eff, m_eff - 1])
+        if sub == 0.0:
+            breakdowns += 1
+            closed.append(w0)
+        theta, Y = np.linalg.eig(Hm)
+        big = np.max(np.abs(theta))
+        for k in np.flatnonzero(np.abs(theta) > PZ_THETA_TOL * big):
+            y = Y[:, k] / np.linalg.norm(Y[:, k])
+            cand.append((1j * w0 - 1.0 / theta[k], sub * abs(y[-1]) / abs(theta[k]), w0))
+    poles = []
+    for p, res, w0 in sorted((c_ for c_ in cand if c_[1] <= PZ_RESID_MAX), key=lambda c_: c_[1]):
+        if not any(abs(p - q[0]) <= PZ_MERGE_TOL * max(abs(p), abs(q[0])) for q in poles):
+            poles.append((p, res, w0))
+    poles.sort(key=lambda q: (abs(q[0]), q[0].imag))
+    zeros, gain = np.zeros(0, dtype=complex), 0.0
+    live = [w for w in models if models[w][0].shape[0]]
+    if live:
+        wz = closed[0] if closed else live[0]
+        Hm, beta, l = models[wz]
+        k = Hm.shape[0]
+        def reduced_zeros(lv):
+            M0, M1 = np.zeros((k + 1, k + 1), dtype=complex), np.zeros((k + 1, k + 1), dtype=complex)
+            M0[:k, :k], M0[0, k], M0[k, :k] = np.eye(k), -beta, lv
+            M1[:k, :k] = Hm
+            return _finite_eigs(M0, M1)
+        sig = reduced_zeros(l)
+        big = np.max(np.abs(np.linalg.eigvals(Hm)))
+        sig = sig[np.abs(sig) * (PZ_THETA_TOL * big) < 1.0]
+        # a transfer function of relative degree k > 1 has a k-fold zero at infinity, which the reduced pencil returns as k values on a circle of
+        # radius eps^(-1/k) -- not large.  They are told apart by what makes them: a perturbation of relative size d moves them by d^(1/k), a
+        # genuine zero by d times its condition number
+        moved = reduced_zeros(l * (1.0 + PZ_ZERO_PROBE * (-1.0) ** np.arange(k)))
+        if sig.size:
+            near = np.min(np.abs(sig[:, None] - moved[None, :]), axis=1) if moved.size else np.full(sig.size, np.inf)
+            sig = sig[near <= np.sqrt(PZ_ZERO_PROBE) * 1e-2 * np.abs(sig)]
+        zeros = 1j * wz + sig
+        zeros = zeros[np.argsort(np.abs(zeros))]
+        wg = min(live, key=abs)
+        Hm, beta, l = models[wg]
+        e1 = np.zeros(Hm.shape[0], dtype=complex)
+        e1[0] = beta
+        gain = l @ np.linalg.solve(np.eye(Hm.shape[0]) - 1j * wg * Hm, e1)
+    sol = PZSol([q[0] for q in poles], zeros, gain, [q[1] for q in poles], [q[2] for q in poles], models)
+    return sol, breakdowns
+
+
+def pz_gpu_sweep(h, st, G_ref, C_ref, rhs, out, omegas, m, gmin, solver, stats, memory="lds"):
+    """The Arnoldi reductions of one structure class on the GPU: ``h`` (holding the restamp at the DC points) re-analyses its pivot order on
+    ``ac_pivot_sample`` over the shifts -- as ``ac_gpu_sweep`` -- and runs points x shifts systems of ``m`` steps in ONE ``ac_arnoldi`` call
+    with the probe pair ``out``.  Returns (H [B, S, m+1, m], beta, m_eff, l [B, S, m, 1], redo [B, S]) -- ``redo``: flag bit 0 or 1 set, or
+    a backward error above AC_BERR_MAX: the caller reduces that system on the host -- and updates ``stats`` as ``ac_gpu_sweep`` does.  A
+    circuit the memory home refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why."""
+    from . import hip
+    _ac_memory(memory)
+    omegas = np.asarray(omegas, dtype=float)
+    to_ref = np.asarray(st.to_ref_nz)
+    sample_ref = np.empty(st.nnz)
+    sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+    h.analyze_values(sample_ref)
+    try:
+        with _ac_memory_of(h, memory):
+            H, beta, meff, l, _, berr, flags, info = h.ac_arnoldi(omegas, gmin, rhs, m, [out])
+            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
+    except hip.CadnipError as err:
+        if not (solver == "auto" and err.code == hip.BADARG):
+            raise
+        stats["host_systems"] += len(rhs) * omegas.size
+        stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host Arnoldi"
+        return None
+    redo = ((flags & 3) != 0) | ~(berr <= AC_BERR_MAX)
+    kept = berr[~redo]
+    stats["gpu_systems"] += int((~redo).sum())
+    stats["host_systems"] += int(redo.sum())
+    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
+    stats["wpb"], stats["memory"] = info["wpb"], used
+    return H, beta, meff, l, redo
+
+
+def pz(target, output, input=None, shifts=(0.0,), order=16, gmin=1e-12, device=0, solver="host", memory="lds"):
+    """Pole-zero analysis of the circuit linearised at its DC operating point (SPICE's .pz; the poles / zeros one takes from the reference's
+    ``subsystem`` through a descriptor-systems package): the finite poles of (G + s C)^-1, the zeros and the DC gain of the transfer function
+    from ``input`` to ``output``.  ``output``: a name or a (p, n) pair (``sens_output``); ``input``: None -- the circuit's ``ac=`` excitation
+    (``rhs_ac``) -- or the name of an independent source (``source_rhs``).  A CircuitSweep returns one PZSol per point.
+    ``solver``: "host" (default) -- the dense pencils per point (``poles_dense``, ``zeros_dense``): EVERY finite pole, O(n^3) per point; "gpu" --
+    shift-invert Arnoldi of ``order`` steps at the ``shifts`` (hertz, on the imaginary axis): the pivot order is re-analysed on
+    ``ac_pivot_sample`` over the shift list and ONE ``ac_arnoldi`` call per structure class runs points x shifts systems
+    (csrc/ac_lu.hip: k_ac_arnoldi); ``pz_solve`` turns the reductions into the poles nearest the shifts that converged.  A system whose flag
+    bit 0 or 1 is set or whose backward error exceeds AC_BERR_MAX is reduced again by ``arnoldi_host`` and counted in ``stats``
+    ("host_systems").  "gpu" raises for a circuit the memory setting refuses; "auto" takes the host Arnoldi for it and says so in
+    ``stats["fallback"]``.  ``memory`` as ``ac``.  ``stats`` = ``ACSol.stats``' keys plus "order", "shifts", "breakdowns" (systems whose Krylov
+    space closed before ``order`` steps: their poles are exact)."""
+    from contextlib import closing
+    if solver not in ("host", "gpu", "auto"):
+        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
+    _ac_memory(memory)
+    omegas = 2.0 * np.pi * np.asarray(shifts, dtype=float).ravel()
+    if solver != "host" and (omegas.size == 0 or int(order) < 1):
+        raise ValueError("pz: at least one shift and one Arnoldi step")
+    sweep, mc, pts = _ac_target(target)
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0, "order": int(order), "shifts": int(omegas.size), "breakdowns": 0}
+    sols = [None] * len(pts)
+    with closing(_ac_classes(sweep, mc, pts, gmin, device, "pz")) as classes:
+        for sim, st, idx, G, C, lin in classes:
+            out = sens_output(st, output)
+            c = np.zeros(st.n, dtype=complex)
+            for j, sgn in zip(out, (1.0, -1.0)):
+                if j >= 0:
+                    c[j] += sgn
+            rhs = [rhs_ac(st, mc.circuit, p_i) if input is None else source_rhs(st, mc.circuit, input) for _, _, _, p_i, _ in lin]
+            if solver == "host":
+                for (i, Gd, Cd, p_i, u_i), b in zip(lin, rhs):
+                    sols[i] = PZSol(poles_dense(Gd, Cd), zeros_dense(Gd, Cd, b, c), c @ np.linalg.solve(Gd.astype(complex), b), [], [], {}, u_i)
+                    sols[i].pole_resid, sols[i].pole_shift = np.zeros(len(sols[i].poles)), np.full(len(sols[i].poles), np.nan)
+                continue
+            m = min(int(order), st.n)
+            got = pz_gpu_sweep(sim.h, st, G, C, np.array(rhs), out, omegas, m, gmin, solver, stats, memory)
+            for k, ((i, Gd, Cd, p_i, u_i), b) in enumerate(zip(lin, rhs)):
+                def arnoldi(w0, k=k, Gd=Gd, Cd=Cd, b=b):
+                    s = int(np.flatnonzero(omegas == w0)[0])
+                    if got is None or got[4][k, s]:
+                        return arnoldi_host(Gd, Cd, b, w0, m, c[None])
+                    return got[0][k, s], got[1][k, s], got[2][k, s], got[3][k, s]
+                sols[i], nb = pz_solve(st, Gd, Cd, b, out, omegas, m, arnoldi)
+                sols[i].dc_x = u_i
+                sols[i]._in_hertz(np.asarray(shifts, dtype=float).ravel(), omegas)
+                stats["breakdowns"] += nb
+    if solver != "host":
+        for s in sols:
+            s.stats = stats
+    return SweepResult(pts, sols) if sweep else sols[0]
+
+
 def tran(target, tspan, abstol=1e-10, reltol=1e-8, saveat=None, device=0, **kw):
     """tran!(circuit, tspan) / tran!(cs::CircuitSweep, tspan) -- sweeps.jl:588-665, 692-707."""
     tspan = (float(tspan[0]), float(tspan[1]))

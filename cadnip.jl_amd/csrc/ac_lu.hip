@@ -21,6 +21,8 @@
 // k_ac_adj_multi / k_ac_adj_multi_hbm (cadnip_ac_adjoint_multi) do the same for K adjoint right-hand sides.
 // k_ac_sens / k_ac_sens_hbm (cadnip_ac_sens) run one forward and one adjoint column per system and, from the two solutions, K bilinear forms
 // over the stamps of perturbed instances: the response and its K parameter derivatives from one factorisation.
+// k_ac_arnoldi / k_ac_arnoldi_hbm (cadnip_ac_arnoldi) factor at a shift j w_s and run m Arnoldi steps of A^-1 C there -- m + 1 columns with
+// the same factors, each right-hand side C times the previous solution, kept in the wave: the pole-zero analysis.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -634,6 +636,153 @@ __global__ void __launch_bounds__(64 * W) k_ac_sens_hbm(AcSensArgs u, AcHbmArgs 
   }
 }
 
+// ---- the Arnoldi kernel: an orthonormal basis of the Krylov space of K = A^-1 C started at A^-1 b_ac, A = G + gmin + j w_s C at the SHIFT
+// j w_s, from ONE factorisation per system (cadnip_ac_arnoldi: poles, zeros and a reduced model of the descriptor system (C, -G) -- the
+// eigenvalues theta of K are the poles p = j w_s - 1 / theta).  A system is (instance b, shift s).  The wave runs
+//   1. / 2.  ac_load_factor at w_s,
+//   3.  the start vector: x = A^-1 b_ac[b] by ac_lu_column (x is what k_ac_lu gives for (b, w_s)), beta = ||x||_2, v_0 = x / beta.  beta zero
+//       or non-finite: flag bit 1, m_eff = 0, no step,
+//   4.  for j = 0 .. m-1: t = C[b] v_j (CSR rows, real C times complex v_j, one row per lane, into the fourth vector); w = A^-1 t by
+//       ac_lu_column (solve, refinement, backward error, as every column of this file); nu_0 = ||w||_2; two passes of modified Gram-Schmidt
+//       against v_0 .. v_j, H[i][j] the sum of the two passes' <v_i, w> (v_i conjugated); nu_1 = ||w||_2.  nu_0 = 0 or nu_1 <= tol nu_0: the
+//       space has closed -- m_eff = j + 1, H[j+1][j] = 0, flag bit 2 (informational), the system is finished.  Else H[j+1][j] = nu_1 and
+//       v_{j+1} = w / nu_1; without a breakdown m_eff = m,
+//   5.  stores: H ((m+1) x m, zero beyond m_eff), beta, m_eff, the unconjugated probe projections l[j][p] = v_j[p_p] - v_j[n_p] (pairs as
+//       k_ac_adj, zero beyond m_eff), berr -- the worst of the m_eff + 1 columns, a NaN stays --, the flag (bit 0: zero / non-finite pivot or a
+//       non-finite word of H, beta or l; bits 1 and 2 as above), and the basis V ((m+1) x n; rows that hold no vector are zero).
+// Where the vectors live.  w is ac_lu_column's x and is orthogonalised and normalised IN PLACE there, so the current v_j sits in a work
+// array (LDS, or the wave's workspace) under the memory policy M, and everything that reads a vector ACROSS lanes -- the product C v_j
+// through colidx, the probe differences -- reads that copy, behind M::sync().  The basis itself does not fit LDS next to the factors
+// (16 (m+1) n bytes per system): it lives in global memory in both variants, in the launch's V buffer at the system's own index.  Its words are
+// accessed by index k = lane, lane + 64, ... only -- written when a vector is normalised, read back by the dot products and the updates of
+// the Gram-Schmidt passes -- so every lane reads only words it wrote itself: program order of one thread orders them, and the LDS kernel
+// needs no global-memory fence (the HBM kernel's fences belong to its work arrays, as everywhere in this file).  H and l are written by the
+// lane that read them (lane 0: the second pass adds to the word the first pass wrote) or once, at the end, where no vector was.
+// Reductions: per-lane partial sums over k = lane, lane + 64, ... in index order, explicit fma, then the xor butterfly of ac_store_status --
+// every lane holds the same double, whatever W and wherever the work arrays live.  No atomics, no workgroup barrier.
+struct AcArnArgs {
+  AcArgs a;                                 // a.bac: b_ac [B][n]; a.x is not used; a.berr / a.flags: [systems]
+  const int* pairs;                         // [n_pairs][2]
+  double *H, *beta, *l, *V;                 // [systems][m+1][m] complex; [systems]; [systems][m][n_pairs] complex; [systems][m+1][n] complex
+  int* meff;                                // [systems]
+  double tol; int m, n_pairs;
+};
+
+__device__ __forceinline__ double ac_wave_add(double v) {
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// ||x||_2 over the lane's words k = lane, lane + 64, ...
+__device__ __forceinline__ double ac_wave_norm(const double2* x, int n, int lane) {
+  double p = 0.0;
+  for (int k = lane; k < n; k += 64) { const double2 v = x[k]; p = fma(v.x, v.x, fma(v.y, v.y, p)); }
+  return sqrt(ac_wave_add(p));
+}
+
+template <class M>
+__device__ __forceinline__ void ac_arnoldi_system(const AcArnArgs& u, int ls, const AcWork& wk, double2* t, int lane) {
+  const AcArgs& a = u.a;
+  const int n = a.n, m = u.m, P = u.n_pairs;
+  const long s = a.s0 + ls;
+  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  double2* x = wk.x;
+  const double* G = a.G + (size_t)inst * a.nnz;
+  const double* C = a.C + (size_t)inst * a.nnz;
+  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
+  const double om = a.omega[fi];
+  double2* Ho = (double2*)u.H + (size_t)ls * (m + 1) * m;
+  double2* lo = (double2*)u.l + (size_t)ls * m * P;
+  double2* Vo = (double2*)u.V + (size_t)ls * (m + 1) * n;
+  int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
+  int flag = 0, meff = 0, nvec = 0;                              // nvec: rows of V that hold a vector
+  // v_j := x / nrm in x and in row j of V; its probe projections
+  auto take_vector = [&](int j, double nrm) {
+    for (int k = lane; k < n; k += 64) { const double2 v = x[k]; const double2 q = make_double2(v.x / nrm, v.y / nrm); x[k] = q; Vo[(size_t)j * n + k] = q; }
+    M::sync();                                                   // v_j for every lane
+    if (j < m) for (int p = lane; p < P; p += 64) {
+      const int pp = u.pairs[2 * p], pn = u.pairs[2 * p + 1];
+      const double2 xp = pp >= 0 ? x[pp] : make_double2(0.0, 0.0), xn = pn >= 0 ? x[pn] : make_double2(0.0, 0.0);
+      const double2 d = make_double2(xp.x - xn.x, xp.y - xn.y);
+      if (!isfinite(d.x) || !isfinite(d.y)) bad = 1;
+      lo[(size_t)j * P + p] = d;
+    }
+  };
+  // ---- 3. the start vector
+  double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane);
+  const double beta = ac_wave_norm(x, n, lane);
+  if (!isfinite(beta)) bad = 1;
+  if (!(beta > 0.0) || !isfinite(beta)) flag = 2;
+  else {
+    take_vector(0, beta);
+    nvec = 1; meff = m;
+    // ---- 4. the steps
+    for (int j = 0; j < m; ++j) {
+      for (int i = lane; i < n; i += 64) {
+        double2 acc = make_double2(0.0, 0.0);
+        const int p1 = a.rowptr[i + 1];
+        for (int p = a.rowptr[i]; p < p1; ++p) { const double c = C[p]; const double2 v = x[a.colidx[p]]; acc = make_double2(fma(c, v.x, acc.x), fma(c, v.y, acc.y)); }
+        t[i] = acc;
+      }
+      M::sync();                                                 // t complete; the last reads of v_j in x before the column's words
+      const double wj = ac_lu_column<M>(a, wk, G, C, om, t, lane);
+      worst = (wj > worst || wj != wj) ? wj : worst;             // a NaN stays
+      const double nu0 = ac_wave_norm(x, n, lane);
+      for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i <= j; ++i) {
+          const double2* vi = Vo + (size_t)i * n;
+          double re = 0.0, im = 0.0;
+          for (int k = lane; k < n; k += 64) {
+            const double2 v = vi[k], w = x[k];
+            re = fma(v.x, w.x, fma(v.y, w.y, re)); im = fma(v.x, w.y, fma(-v.y, w.x, im));
+          }
+          const double2 h = make_double2(ac_wave_add(re), ac_wave_add(im));
+          for (int k = lane; k < n; k += 64) x[k] = cmsub(x[k], h, vi[k]);
+          if (lane == 0) {
+            double2 hs = h;
+            if (pass) { const double2 h0 = Ho[(size_t)i * m + j]; hs = make_double2(h0.x + h.x, h0.y + h.y); }
+            if (!isfinite(hs.x) || !isfinite(hs.y)) bad = 1;
+            Ho[(size_t)i * m + j] = hs;
+          }
+        }
+      const double nu1 = ac_wave_norm(x, n, lane);
+      if (nu0 == 0.0 || nu1 <= u.tol * nu0) { meff = j + 1; flag |= 4; break; }
+      if (!isfinite(nu1)) bad = 1;
+      if (lane == 0) Ho[(size_t)(j + 1) * m + j] = make_double2(nu1, 0.0);
+      take_vector(j + 1, nu1);
+      nvec = j + 2;
+    }
+  }
+  // ---- 5. the words no step wrote, and the status
+  for (int e = lane; e < (m + 1) * m; e += 64) { const int i = e / m, j = e - i * m; if (j >= meff || i > j + 1 || (i == j + 1 && i >= nvec)) Ho[e] = make_double2(0.0, 0.0); }
+  for (int e = lane + meff * P; e < m * P; e += 64) lo[e] = make_double2(0.0, 0.0);
+  for (size_t e = (size_t)nvec * n + lane; e < (size_t)(m + 1) * n; e += 64) Vo[e] = make_double2(0.0, 0.0);
+  worst = ac_wave_berr(worst);
+  bad = wave_any(bad);
+  if (lane == 0) { u.beta[ls] = beta; u.meff[ls] = meff; a.berr[ls] = worst; a.flags[ls] = flag | (bad ? 1 : 0); }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_arnoldi(AcArnArgs u) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= u.a.n_sys) return;                                 // the tail workgroup: no workgroup barrier anywhere below
+  const LdsAcSens<double*> L = lds_ac_sens((double*)sm, u.a.nnz_lu, u.a.n, w, W);
+  ac_arnoldi_system<AcInLds>(u, ls, AcWork{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y}, (double2*)L.xf, lane);
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_arnoldi_hbm(AcArnArgs u, AcHbmArgs m) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.a.n_sys : 0;
+  const LdsAcSens<double*> L = lds_ac_sens(m.work, u.a.nnz_lu, u.a.n, g, m.n_waves);   // size_t offsets (lds_layout.hpp)
+  const AcWork wk{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y};
+  for (int ls = g; ls < end; ls += m.n_waves) {
+    ac_arnoldi_system<AcInHbm>(u, ls, wk, (double2*)L.xf, lane);
+    AcInHbm::sync();                                           // the last reads of x and t before the next system's words
+  }
+}
+
 // The launch plan -- the one place that sizes the LDS block and picks W, and the only reader of CADNIP_AC_WPB.  A compute unit holds
 // min(32 waves, LDS_BUDGET / block) workgroups' worth of systems: the plan takes the W with the most resident systems (ties: the largest),
 // then halves it while the launch would not put a workgroup on half of the 256 compute units.
@@ -901,6 +1050,33 @@ int launch_ac_sens(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int 
   ProfScope ps(h, "ac_sens");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
   TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_sens<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
+  HIP_TRY(hipGetLastError());
+  return CADNIP_OK;
+}
+
+int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& L, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs) {
+  AcState& A = h->ac;
+  if (L.memory < 0 || n_sys <= 0 || m < 1 || m > h->n || !(tol > 0.0 && tol < 1.0) || n_pairs < 0 || A.dirty) return CADNIP_BADARG;
+  AcArnArgs u;
+  u.a = ac_args(h, n_shift, s0, n_sys, gmin);
+  u.a.bac = A.d_arn_bac; u.a.x = nullptr; u.a.berr = A.d_arn_berr; u.a.flags = A.d_arn_flags;
+  u.pairs = A.d_arn_pairs; u.H = A.d_arn_H; u.beta = A.d_arn_beta; u.l = A.d_arn_l; u.V = A.d_arn_V; u.meff = A.d_arn_meff;
+  u.tol = tol; u.m = m; u.n_pairs = n_pairs;
+  if (L.memory == CADNIP_AC_HBM) {
+    const AcHbmPlan& p = L.hbm;
+    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
+    TRY_RC(ac_work_reserve(h, p.work_bytes));
+    ProfScope ps(h, "ac_arnoldi_hbm");
+    const AcHbmArgs hm{A.d_work, p.n_waves};
+    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
+    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_arnoldi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, hm); return CADNIP_OK; }));
+    HIP_TRY(hipGetLastError());
+    return CADNIP_OK;
+  }
+  const AcPlan& p = L.lds;
+  ProfScope ps(h, "ac_arnoldi");
+  const int grid = (n_sys + p.wpb - 1) / p.wpb;
+  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_arnoldi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }

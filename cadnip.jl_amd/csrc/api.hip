@@ -220,6 +220,7 @@ void cadnip_destroy(CadnipHandle* h) {
   h->ac.each_adjoint_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->ac.each_multi_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->ac.each_sens_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
+  h->ac.each_arn_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->f2.release();
   for (auto& g : h->step_graph) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (auto& b : h->blocks) {
@@ -996,6 +997,64 @@ int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega, double 
     if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * 4 * n, A.d_sens_x, ns * 4 * n * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(berr_host + s0 * 2, A.d_sens_berr, ns * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0 * K, A.d_sens_flags, ns * K * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  ac_report(h, plan, tail, S, chunk, info);
+  return CADNIP_OK;
+}
+
+// The Arnoldi sweep: per (instance b, shift s) m steps of K = A^-1 C started at A^-1 b_ac[b], A = G[b] + gmin + j omega[s] C[b] -- S = B n_shift
+// systems through k_ac_arnoldi (ac_lu.hip), one factorisation and up to m + 1 columns each.  Same rules as cadnip_ac_solve; a system's device
+// output is 16 ((m+1) m + m n_pairs + (m+1) n) bytes and a few words -- the basis is the kernel's own storage and counts whether the caller
+// wants it or not -- and a single system beyond AC_CHUNK_BYTES runs as a chunk of one.  Buffers live in AcState.
+int cadnip_ac_arnoldi(CadnipHandle* h, int32_t n_shift, const double* omega, double gmin, const double* b_host, int32_t m, double breakdown_tol,
+                      int32_t n_pairs, const int32_t* pairs, int32_t wpb, double* H_host, double* beta_host, int32_t* meff_host, double* l_host,
+                      double* v_host, double* berr_host, int32_t* flags_host, int32_t* info) {
+  if (!h || n_shift <= 0 || !omega || !b_host || m < 1 || !(breakdown_tol > 0.0 && breakdown_tol < 1.0) || n_pairs < 0 || (n_pairs > 0 && (!pairs || !l_host)) ||
+      !H_host || !beta_host || !meff_host || !berr_host || !flags_host || !info || !h->analyzed || m > h->n) return CADNIP_BADARG;
+  const size_t B = h->B, n = h->n, F = n_shift, S = B * F, P = n_pairs, M = m;
+  for (size_t k = 0; k < 2 * P; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
+  const size_t hw = (M + 1) * M, lw = M * P, vw = (M + 1) * n;           // complex words of a system's H, l, V
+  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * (hw + lw + vw))));
+  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb, true);       // the work arrays are the sensitivity kernel's: four n-vectors
+  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb, true) : plan;
+  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  TRY(ac_lu_prepare(h));
+  AcState& A = h->ac;
+  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
+  auto grow = [](auto** p, size_t* cap, size_t need, size_t words) {       // one buffer to `need` units of `words` elements
+    if (*cap >= need) return (int)CADNIP_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    *cap = 0;
+    TRY(dev_alloc(p, need * words));
+    *cap = need;
+    return (int)CADNIP_OK;
+  };
+  TRY(grow(&A.d_arn_bac, &A.cap_arn_bac, B * n, 2));
+  TRY(grow(&A.d_arn_H, &A.cap_arn_H, chunk * hw, 2));
+  TRY(grow(&A.d_arn_V, &A.cap_arn_V, chunk * vw, 2));
+  if (P) { TRY(grow(&A.d_arn_pairs, &A.cap_arn_pairs, P, 2)); TRY(grow(&A.d_arn_l, &A.cap_arn_l, chunk * lw, 2)); }
+  if (A.cap_arn_sys < chunk) {                                   // beta, berr, m_eff, flags: one capacity
+    void** four[] = {(void**)&A.d_arn_beta, (void**)&A.d_arn_berr, (void**)&A.d_arn_meff, (void**)&A.d_arn_flags};
+    for (void** p : four) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    A.cap_arn_sys = 0;
+    TRY(dev_alloc(&A.d_arn_beta, chunk)); TRY(dev_alloc(&A.d_arn_berr, chunk)); TRY(dev_alloc(&A.d_arn_meff, chunk)); TRY(dev_alloc(&A.d_arn_flags, chunk));
+    A.cap_arn_sys = chunk;
+  }
+  HIP_TRY(hipMemcpy(A.d_arn_bac, b_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
+  if (P) HIP_TRY(hipMemcpy(A.d_arn_pairs, pairs, P * 2 * sizeof(int), hipMemcpyHostToDevice));
+  for (size_t s0 = 0; s0 < S; s0 += chunk) {
+    const size_t ns = std::min(chunk, S - s0);
+    TRY(launch_ac_arnoldi(h, ns == chunk ? plan : tail, n_shift, (long)s0, (int)ns, gmin, m, breakdown_tol, n_pairs));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(H_host + s0 * hw * 2, A.d_arn_H, ns * hw * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (P) HIP_TRY(hipMemcpy(l_host + s0 * lw * 2, A.d_arn_l, ns * lw * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (v_host) HIP_TRY(hipMemcpy(v_host + s0 * vw * 2, A.d_arn_V, ns * vw * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(beta_host + s0, A.d_arn_beta, ns * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(meff_host + s0, A.d_arn_meff, ns * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(berr_host + s0, A.d_arn_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flags_host + s0, A.d_arn_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
   }
   ac_report(h, plan, tail, S, chunk, info);
   return CADNIP_OK;

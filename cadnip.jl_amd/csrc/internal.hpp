@@ -168,6 +168,14 @@ struct AcState {
     f((void**)&d_sens_idx); f((void**)&d_sens_scale); f((void**)&d_sens_bac); f((void**)&d_sens_db); f((void**)&d_sens_c);
     f((void**)&d_sens_y); f((void**)&d_sens_berr); f((void**)&d_sens_s); f((void**)&d_sens_x); f((void**)&d_sens_flags);
   }
+  // Arnoldi sweep (k_ac_arnoldi, cadnip_ac_arnoldi): its own transfer buffers, each grown on demand to the capacity beside it
+  double *d_arn_bac = nullptr, *d_arn_H = nullptr, *d_arn_beta = nullptr, *d_arn_l = nullptr, *d_arn_V = nullptr, *d_arn_berr = nullptr;   // [B][n], [S][m+1][m], -, [S][m][pairs], [S][m+1][n] complex; beta, berr [S]
+  int *d_arn_pairs = nullptr, *d_arn_meff = nullptr, *d_arn_flags = nullptr;                                                              // [pairs][2]; [S]; [S]
+  size_t cap_arn_bac = 0, cap_arn_H = 0, cap_arn_l = 0, cap_arn_V = 0, cap_arn_pairs = 0, cap_arn_sys = 0;   // complex words (four); pairs; systems (beta, berr, meff, flags)
+  template <class F> void each_arn_buffer(F f) {
+    f((void**)&d_arn_bac); f((void**)&d_arn_H); f((void**)&d_arn_beta); f((void**)&d_arn_l); f((void**)&d_arn_V); f((void**)&d_arn_berr);
+    f((void**)&d_arn_pairs); f((void**)&d_arn_meff); f((void**)&d_arn_flags);
+  }
   // HBM-resident variant (k_ac_lu_hbm / k_ac_adj_hbm; cadnip_ac_set_memory, ac_hbm_plan.hpp): the setting, the persistent waves' workspace
   // (grown on demand like the buffers above, released with the handle) and what the last AC / adjoint call ran (cadnip_ac_plan_info)
   int memory = CADNIP_AC_LDS, max_waves = 0;
@@ -301,6 +309,10 @@ int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long
 // (needs ac_lu_prepare(h, true); p must come from ac_launch_plan(.., sens = true)): inputs and outputs in the d_sens_* buffers, outputs from
 // index 0; n_par columns, db: a db buffer was uploaded (else zeros), pair: the output pair
 int launch_ac_sens(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, bool db, const int* pair, bool want_x);
+// systems [s0, s0 + n_sys) of the B x n_shift grid of cadnip_ac_arnoldi (s = b * n_shift + shift) through k_ac_arnoldi (p must come from
+// ac_launch_plan(.., sens = true): the same four n-vectors): inputs and outputs in the d_arn_* buffers, outputs from index 0; m steps,
+// breakdown tolerance tol, n_pairs probe pairs
+int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& p, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs);
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

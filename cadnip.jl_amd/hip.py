@@ -17,13 +17,19 @@ OK, BADARG, SINGULAR, NONFINITE, HIPERROR, NOTREADY, NOCONV = range(7)
 STATUS_NAMES = {0: "CADNIP_OK", 1: "CADNIP_BADARG", 2: "CADNIP_SINGULAR", 3: "CADNIP_NONFINITE",
                 4: "CADNIP_HIPERROR", 5: "CADNIP_NOTREADY", 6: "CADNIP_NOCONV"}
 
+# cadnip_ac_arnoldi's default breakdown tolerance: the geometric middle of the gap measured with the numpy port (tests/pz_ref.py,
+# tests/test_pz_cpu.py) over the test circuits, the MOS linearisations included.  At a step where the dense pencil says the space has closed
+# the norm ratio after / before orthogonalisation is at most 1.2e-14 (the eight-section ladder); at every other step it is at least 3.0e-3 (the
+# inverter's MOS linearisations; the linear circuits: 4.5e-2).  The flip-flop has steps as low as 1.5e-9 that do not close its space and is
+# not among the circuits the figure is taken from
+AC_BREAKDOWN_TOL = 6e-9
 AC_MEMORY = {"lds": 0, "hbm": 1, "auto": 2}     # CADNIP_AC_LDS / _HBM / _AUTO (Handle.ac_set_memory)
 
 # every symbol declared in include/cadnip_hip.h
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_sens", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_sens", "cadnip_ac_arnoldi", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
@@ -482,6 +488,38 @@ class Handle:
                                        C.c_int32(int(wpb)), y.ctypes.data_as(_D), s.ctypes.data_as(_D), None if x is None else x.ctypes.data_as(_D),
                                        _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_sens")
         return y, s, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+
+    def ac_arnoldi(self, omega, gmin, b, m, pairs=None, breakdown_tol=AC_BREAKDOWN_TOL, wpb=0, want_v=False):
+        """cadnip_ac_arnoldi: per (instance, shift) m steps of shift-invert Arnoldi on K = A^-1 C started at A^-1 b, A = G + gmin + j omega[s] C as
+        ``ac_solve`` -- one factorisation and m_eff + 1 columns per system, all in one launch (csrc/ac_lu.hip: k_ac_arnoldi).  ``omega`` [S] the
+        shifts' angular frequencies, ``b`` [B, n] complex (or [n], broadcast), ``pairs`` [P, 2] unknown indices (-1 = ground) or None.  Returns
+        (H complex128 [B, S, m+1, m], beta [B, S], m_eff int32 [B, S], l [B, S, m, P] -- l[.., j, p] = v_j[p_p] - v_j[n_p] -- or None without
+        pairs, V [B, S, m+1, n] or None without ``want_v``, berr [B, S], flags [B, S], info).  beta v_0 is ``ac_solve``'s x; the eigenvalues theta
+        of H[:m_eff, :m_eff] give the poles j omega[s] - 1 / theta.  flags: bit 0 a zero / non-finite pivot or non-finite output, bit 1 beta zero
+        or non-finite (m_eff = 0), bit 2 the Krylov space closed at step m_eff (informational).  berr and info as ``ac_solve``.  An empty shift
+        list launches nothing.  A ``b`` of the wrong shape raises ValueError; m outside [1, n], a tolerance outside (0, 1), a pair index outside
+        [-1, n), a circuit the memory setting refuses or an invalid ``wpb`` raise CadnipError(CADNIP_BADARG)."""
+        om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
+        B, n, S, m = self.B, self.st.n, om.size, int(m)
+        bb = np.asarray(b, dtype=np.complex128)
+        if bb.shape not in ((n,), (B, n)):
+            raise ValueError("b must be [n] or [B, n]")
+        bb = np.ascontiguousarray(np.broadcast_to(bb, (B, n)))
+        pr = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        P = 0 if pr is None else pr.shape[0]
+        mm = max(m, 0)
+        H = np.zeros((B, S, mm + 1, mm), dtype=np.complex128)
+        beta, meff = np.zeros((B, S)), np.zeros((B, S), dtype=np.int32)
+        ll = np.zeros((B, S, mm, P), dtype=np.complex128) if P else None
+        V = np.zeros((B, S, mm + 1, n), dtype=np.complex128) if want_v else None
+        berr, flags, info = np.zeros((B, S)), np.zeros((B, S), dtype=np.int32), np.zeros(4, dtype=np.int32)
+        if S == 0:
+            return H, beta, meff, ll, V, berr, flags, dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
+        _check(self.lib.cadnip_ac_arnoldi(self.h, C.c_int32(S), _dp(om), C.c_double(gmin), bb.ctypes.data_as(_D), C.c_int32(m), C.c_double(breakdown_tol),
+                                          C.c_int32(P), _ip(pr) if P else None, C.c_int32(int(wpb)), H.ctypes.data_as(_D), _dp(beta), _ip(meff),
+                                          None if ll is None else ll.ctypes.data_as(_D), None if V is None else V.ctypes.data_as(_D),
+                                          _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_arnoldi")
+        return H, beta, meff, ll, V, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
 
     def ac_set_memory(self, mode="lds", max_waves=0):
         """cadnip_ac_set_memory: where ``ac_solve`` / ``ac_adjoint`` keep a system's work arrays from now on.  "lds" (the default of a new handle):

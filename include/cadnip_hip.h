@@ -297,6 +297,31 @@ int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega /* [F] *
                    const int32_t* pair /* [2], -1 = ground */, int32_t wpb, double* y_host /* [NB][F][2] */, double* s_host /* [NB][F][K][2] */,
                    double* x_host /* [NB][F][2][n][2]: x, lambda; or NULL */, double* berr_host /* [NB][F][2] */,
                    int32_t* flags_host /* [NB][F][K] */, int32_t* info /* [4] */);
+/* Pole-zero analysis: shift-invert Arnoldi on the descriptor system (E, A) = (C, -G) of an AC solution.  Per system (b, s) -- instance b, shift
+ * j omega[s] on the imaginary axis -- with A = G[b] + gmin + j omega[s] C[b], the matrix, pivot order and factors of cadnip_ac_solve, the wave
+ * (csrc/ac_lu.hip: k_ac_arnoldi) builds an orthonormal basis of the Krylov space of K = A^-1 C started at r = A^-1 b[b]:
+ *   beta = ||r||_2, v_0 = r / beta;   for j = 0 .. m-1:  w = A^-1 (C v_j), two passes of modified Gram-Schmidt against v_0 .. v_j with
+ *   H[i][j] the sum of the two coefficients <v_i, w> (v_i conjugated), H[j+1][j] = ||w||_2 after them, v_{j+1} = w / H[j+1][j].
+ * So C V_m = A V_{m+1} H, the eigenvalues theta of H[:m_eff][:m_eff] give the poles p = j omega[s] - 1 / theta nearest the shift, and with
+ * l[j][p] = v_j[p_p] - v_j[n_p] (unconjugated; pairs as cadnip_ac_adjoint, n_pairs may be 0) the transfer function to probe p is
+ * l^T (I + (s - j omega[s]) H)^-1 beta e_1.  Every one of the m_eff + 1 columns is the column of cadnip_ac_solve -- solve, one refinement step,
+ * backward error -- and r is bit-identical to that call's x for (b, omega[s]).  Breakdown: when the norm after the two passes is at most
+ * breakdown_tol times the norm before them (or that norm is 0) at step j, the space has closed: m_eff = j + 1, H[j+1][j] = 0 and the system
+ * is finished; otherwise m_eff = m.  Layouts: H (m+1) x m, row-major, zero beyond m_eff; l m x n_pairs, zero beyond m_eff; V (with v_host
+ * non-NULL) (m+1) x n, rows that hold no vector zero; berr the worst backward error of the system's columns (a NaN stays).  flags: bit 0 a
+ * zero / non-finite pivot or a non-finite word of H, beta or l; bit 1 beta zero or non-finite (m_eff = 0, no step made); bit 2 breakdown --
+ * informational, not an error.  Flags, never traps: the call returns CADNIP_OK.  Dot products and norms are per-lane sums in index order and
+ * a fixed butterfly: every output is bit-identical for wpb 1 / 2 / 4 / 8 and between LDS and device memory.  wpb, info, cadnip_ac_set_memory
+ * and cadnip_ac_plan_info as cadnip_ac_sens (four n-vectors: 16 (nnz(L+U) + 4 n) bytes per system); the basis lives in device memory in both
+ * homes.  Chunks of at most 64 MiB of device output, 16 ((m+1) m + m n_pairs + (m+1) n) bytes per system, the basis counted whether asked for or
+ * not (a single system beyond that runs as a chunk of one).  CADNIP_BADARG -- nothing launched, nothing written, no plan recorded -- without
+ * an analysis, with n_shift <= 0, m < 1, m > n, breakdown_tol outside (0, 1), n_pairs < 0, a pair index outside [-1, n), an invalid wpb, or
+ * when the memory setting refuses the work arrays. */
+int cadnip_ac_arnoldi(CadnipHandle* h, int32_t n_shift, const double* omega /* [S] */, double gmin, const double* b_host /* [B][n][2] */, int32_t m,
+                      double breakdown_tol, int32_t n_pairs, const int32_t* pairs /* [n_pairs][2], -1 = ground */, int32_t wpb,
+                      double* H_host /* [B][S][m+1][m][2] */, double* beta_host /* [B][S] */, int32_t* meff_host /* [B][S] */,
+                      double* l_host /* [B][S][m][n_pairs][2]; NULL with n_pairs = 0 */, double* v_host /* [B][S][m+1][n][2] or NULL */,
+                      double* berr_host /* [B][S] */, int32_t* flags_host /* [B][S] */, int32_t* info /* [4] */);
 
 /* Where the AC and adjoint sweeps keep a system's work arrays -- a handle setting, LDS by default: every call exactly as without it.
  *   CADNIP_AC_LDS   in LDS (k_ac_lu / k_ac_adj): one wave per system, refused beyond 160 KB as described above,

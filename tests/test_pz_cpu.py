@@ -1,0 +1,195 @@
+"""Pole-zero analysis on the CPU: the numpy port of k_ac_arnoldi's algorithm (tests/pz_ref.py) and api.pz_solve / subsystem / poles_dense /
+zeros_dense against the dense pencils, on the Butterworth filter of tests/ac_ref.py, RC ladders and a lead-lag network with one finite zero;
+the two measured gaps behind hip.AC_BREAKDOWN_TOL and api.PZ_THETA_TOL; the flip-flop's poles from the port alone.  Systems come from the CPU
+port of the oracle.  Bound of a Ritz value against the dense pencil, relative to |p - j w0| = 1 / |theta|: Bauer-Fike on the m_eff x m_eff
+Hessenberg matrix, 64 eps cond(X) ||H|| / |theta| with X its eigenvectors -- both sides are backward stable in double, 64 covers the m <= 16
+operations per entry of either."""
+import numpy as np
+import pytest
+
+from cadnip_jl_amd import api, hip
+from tests import ac_ref as R
+from tests import pz_ref as Z
+
+EPS = R.EPS
+TOL = hip.AC_BREAKDOWN_TOL
+# flip-flop, shifts one per decade over its grid, 16 steps: the poles the PORT accepts at every corner (tests/test_gpu_pz.py holds the GPU path
+# to the same set)
+DFF_MIN_ACCEPTED = 11
+
+
+def hook(G, C, b, c, m, tol=TOL, log=None):
+    def f(w0):
+        o = Z.arnoldi_port(G, C, b, w0, m, tol, c)
+        if log is not None:
+            log[w0] = o
+        return o["H"], o["beta"], o["m_eff"], o["l"]
+    return f
+
+
+def ritz_bound(o):
+    me = o["m_eff"]
+    Hm = o["H"][:me, :me]
+    th, X = np.linalg.eig(Hm)
+    return 64 * EPS * np.linalg.cond(X) * np.linalg.norm(Hm, 2) / np.abs(th), th
+
+
+def shifts_of(G, C):
+    pd = api.poles_dense(G, C)
+    return [0.0] + [float(abs(p)) for p in pd[:2]]
+
+
+_SYS = {}
+
+
+def system(name):
+    if name not in _SYS:
+        _SYS[name] = Z.linear_system(name)
+    return _SYS[name]
+
+
+@pytest.mark.parametrize("name", list(Z.LINEAR))
+def test_the_port_against_the_dense_pencils(name):
+    st, G, C, b, c = system(name)
+    dense, zd = api.poles_dense(G, C), api.zeros_dense(G, C, b, c)
+    assert len(dense) == {"butterworth": 3, "ladder4": 4, "ladder8": 8, "leadlag": 1}[name]
+    out = (int(np.flatnonzero(c)[0]), -1)
+    for w0 in shifts_of(G, C):
+        log = {}
+        sol, nb = api.pz_solve(st, G, C, b, out, [w0], st.n, hook(G, C, b, c[None], st.n, log=log))
+        o = log[w0]
+        assert o["m_eff"] == len(dense) + 1 == Z.krylov_dimension(G, C, b, w0, st.n) and o["flag"] == 4 and nb == 1      # finite poles + 1
+        bound, th = ritz_bound(o)
+        keep = np.abs(th) > api.PZ_THETA_TOL * np.abs(th).max()
+        assert keep.sum() == len(dense) == len(sol.poles) and np.all(sol.pole_resid == 0.0) and np.all(sol.pole_shift == w0)
+        err = Z.match_error(sol.poles, dense, w0)
+        print("%s w0 %.3g pole errors %s bound %.3g" % (name, w0, err, bound[keep].max()))
+        assert np.all(err <= bound[keep].max()) and np.all(Z.match_error(dense, sol.poles, w0) <= bound[keep].max())
+        nv = Z.n_vectors(st.n, o["m_eff"], o["flag"])
+        # the port's solve is np.linalg's unrefined LU: normwise backward stable, not componentwise -- its Arnoldi relation is held normwise
+        # here (the componentwise figure of tests/pz_ref.py is what the GPU tests compare the kernel's with)
+        me = o["m_eff"]
+        A, Vt, Hb = G + 1j * w0 * C, o["V"][:me + 1].T, o["H"][:me + 1, :me]
+        rel = np.linalg.norm(A @ Vt @ Hb - C @ Vt[:, :me]) / (np.linalg.norm(A) * np.linalg.norm(Hb) + np.linalg.norm(C))
+        assert Z.orthogonality_error(o["V"], nv) <= 64 * EPS and rel <= 64 * EPS
+        # zeros: the spurious ones of the reduced pencil are filtered, the finite one stays
+        assert len(sol.zeros) == len(zd) == (1 if name == "leadlag" else 0)
+        if len(zd):
+            assert np.all(Z.match_error(sol.zeros, zd, w0) <= bound[keep].max()) and abs(sol.zeros[0] + 1e4) <= 1e-6 * 1e4
+        gain = c @ np.linalg.solve(G, b)
+        assert abs(sol.gain - gain) <= 1e-9 * abs(gain)
+        s = 1j * np.array([0.3, 2.0]) * abs(dense[0])
+        ref = np.array([c @ np.linalg.solve(G + sv * C, b) for sv in s])
+        assert np.all(np.abs(sol.transfer(s) - ref) <= 1e-9 * max(abs(gain), np.abs(ref).max()))    # the reduced model of a closed space IS the transfer function
+    if name == "butterworth":
+        exact = np.array([-1.0, -0.5 + 0.5j * np.sqrt(3.0), -0.5 - 0.5j * np.sqrt(3.0)])
+        assert np.all(Z.match_error(sol.poles, exact) <= bound[keep].max() + 16 * Z.GMIN)       # gmin on the node diagonals moves a pole by its order
+
+
+def test_the_unfiltered_reduced_pencil_has_spurious_zeros():
+    st, G, C, b, c = system("leadlag")
+    o = Z.arnoldi_port(G, C, b, 0.0, st.n, TOL, c[None])
+    me = o["m_eff"]
+    M0, M1 = np.zeros((me + 1, me + 1), complex), np.zeros((me + 1, me + 1), complex)
+    M0[:me, :me], M0[0, me], M0[me, :me] = np.eye(me), -o["beta"], o["l"][:me, 0]
+    M1[:me, :me] = o["H"][:me, :me]
+    import scipy.linalg as sla
+    with np.errstate(all="ignore"):
+        raw = sla.eig(-M0, M1, right=False)
+    big = np.abs(np.linalg.eigvals(o["H"][:me, :me])).max()
+    finite = raw[np.isfinite(raw) & (np.abs(raw) * api.PZ_THETA_TOL * big < 1.0)]
+    assert len(raw) == me + 1 and len(finite) == 1 and abs(finite[0] + 1e4) <= 1e-6 * 1e4
+
+
+def test_poles_of_several_shifts_are_merged():
+    st, G, C, b, c = system("ladder8")
+    dense = api.poles_dense(G, C)
+    out = (int(np.flatnonzero(c)[0]), -1)
+    shifts = [0.0, 1e6, 5e6]
+    sol, nb = api.pz_solve(st, G, C, b, out, shifts, st.n, hook(G, C, b, c[None], st.n))
+    assert nb == 3 and len(sol.poles) == 8 and np.all(Z.match_error(sol.poles, dense) <= 1e-9)
+    assert set(sol.pole_shift) <= set(shifts) and sorted(sol._models) == shifts
+    # too few steps: only converged Ritz pairs are accepted, each from the shift that found it, and all of them are poles
+    few, nb = api.pz_solve(st, G, C, b, out, shifts, 5, hook(G, C, b, c[None], 5))
+    assert nb == 0 and len(few.poles) < 8 and np.all(few.pole_resid <= api.PZ_RESID_MAX)
+    assert np.all(Z.match_error(few.poles, dense) <= 1e-6)
+    H, beta, l = few.reduced(1e6)
+    assert H.shape == (5, 5) and l.shape == (5,) and beta > 0
+
+
+def test_pz_solve_defaults_to_the_host_arnoldi_and_takes_a_hook():
+    st, G, C, b, c = system("ladder4")
+    out = (int(np.flatnonzero(c)[0]), -1)
+    a, _ = api.pz_solve(st, G, C, b, out, [0.0], st.n)
+    calls = []
+
+    def arn(w0):
+        calls.append(w0)
+        return api.arnoldi_host(G, C, b, w0, st.n, c[None])
+    h, _ = api.pz_solve(st, G, C, b, out, [0.0], st.n, arn)
+    assert calls == [0.0] and np.array_equal(a.poles, h.poles) and np.array_equal(a.zeros, h.zeros) and a.gain == h.gain
+    p = Z.arnoldi_port(G, C, b, 0.0, st.n, TOL, c[None])
+    Hh, bh, mh, lh = api.arnoldi_host(G, C, b, 0.0, st.n, c[None])
+    assert mh == p["m_eff"] and np.allclose(Hh, p["H"], rtol=1e-9, atol=1e-12 * np.abs(p["H"]).max()) and np.isclose(bh, p["beta"], rtol=1e-12)
+    pair, _ = api.pz_solve(st, G, C, b, (-1, out[0]), [0.0], st.n)                      # the pair form: the negated output
+    assert np.isclose(pair.gain, -a.gain, rtol=1e-12) and np.allclose(np.sort_complex(pair.poles), np.sort_complex(a.poles), rtol=1e-9)
+
+
+def test_subsystem_is_the_descriptor_tuple():
+    st, G, C, b, c = system("butterworth")
+    ac = api.ACSol(st, G, C, b, np.zeros(st.n), [1.0])
+    A, E, B, Cr, D = api.subsystem(ac, "vout")
+    assert np.array_equal(A, -G) and np.array_equal(E, C) and B.shape == (st.n, 1) and np.array_equal(B[:, 0], b)
+    assert Cr.shape == (1, st.n) and Cr[0, st.index_of("vout")] == 1.0 and Cr.sum() == 1.0 and D.shape == (1, 1) and D[0, 0] == 0.0
+    w = 0.7
+    assert np.isclose((Cr @ np.linalg.solve(1j * w * E - A, B))[0, 0], R.butterworth_h(w), rtol=1e-9)
+    for bad in ("0", "gnd", "nowhere"):
+        with pytest.raises(ValueError):
+            api.subsystem(ac, bad)
+
+
+def mos_systems(name):
+    st, Gs, Cs, bs, om = R.port_case(name)
+    c = np.zeros(st.n)
+    c[st.index_of(Z.MOS_OUT[name])] = 1.0
+    return st, [R.system(st, Gs[k], Cs[k], 0.0, Z.GMIN).real for k in range(len(Gs))], [R.dense_csr(st, Cs[k]) for k in range(len(Gs))], bs, om, c
+
+
+def test_the_two_gaps_are_four_decades_wide_and_the_defaults_sit_in_their_middle():
+    """Over the linear circuits and the inverter's MOS linearisations (the flip-flop has steps as low as 1.5e-9 that do not close its space: no
+    gap of four decades): the norm ratio of a step at which the dense pencil says the space has closed against the ratio
+    of every other step, and |theta| / max |theta| of the genuine against the spurious Ritz values of the closed spaces."""
+    closing, other, genuine, spurious = [], [], [], []
+    cases = [(nm,) + system(nm)[1:4] + (shifts_of(*system(nm)[1:3]),) for nm in Z.LINEAR]
+    st, Gd, Cd, bs, om, c = mos_systems("inverter")
+    cases += [("inverter", Gd[k], Cd[k], bs[k], [0.0, om[len(om) // 2], om[-1]]) for k in range(3)]
+    for nm, G, C, b, shifts in cases:
+        n = len(b)
+        nfin = len(api.poles_dense(G, C))
+        for w0 in shifts:
+            d = Z.krylov_dimension(G, C, b, w0, n)
+            o = Z.arnoldi_port(G, C, b, w0, n, 1e-300, None)     # no breakdown test worth the name: every step is made and its ratio recorded
+            for j, q in enumerate(o["ratios"][:d]):
+                (closing if j == d - 1 else other).append(q)
+            th = np.sort(np.abs(np.linalg.eigvals(o["H"][:d, :d])))
+            th /= th[-1]
+            spurious += list(th[:d - nfin])
+            genuine += list(th[d - nfin:])
+    print("breakdown: largest closing ratio %.3g, smallest other %.3g; theta: largest spurious %.3g, smallest genuine %.3g" % (
+        max(closing), min(other), max(spurious), min(genuine)))
+    assert min(other) >= 1e4 * max(closing) and min(genuine) >= 1e4 * max(spurious)
+    for default, lo, hi in ((TOL, max(closing), min(other)), (api.PZ_THETA_TOL, max(spurious), min(genuine))):
+        mid = np.sqrt(lo * hi)
+        assert mid / 3 <= default <= 3 * mid and 100 * lo <= default <= hi / 100
+
+
+def test_the_port_alone_finds_the_flip_flops_poles():
+    st, Gd, Cd, bs, om, c = mos_systems("dff")
+    shifts = 2.0 * np.pi * np.logspace(3, 12, 10)
+    out = (int(np.flatnonzero(c)[0]), -1)
+    for k in range(3):
+        sol, nb = api.pz_solve(st, Gd[k], Cd[k], bs[k], out, shifts, 16, hook(Gd[k], Cd[k], bs[k], c[None], 16))
+        dense = api.poles_dense(Gd[k], Cd[k])
+        err = Z.match_error(sol.poles, dense, sol.pole_shift)
+        print("dff corner %d: %d accepted, %d closed spaces, worst error %.3g" % (k, len(sol.poles), nb, err.max()))
+        assert len(sol.poles) >= DFF_MIN_ACCEPTED and np.all(sol.pole_resid <= api.PZ_RESID_MAX)
