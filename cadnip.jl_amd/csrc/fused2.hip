@@ -7,6 +7,7 @@
 //   * sweep kernel k_fused2<WPB, DC, VAR> (fused2_kernel.hpp): WPB instances per workgroup, one 64-lane wave each, waves never wait for
 //     each other.  VAR 0, the benchmark's kernel: lean device set (linear elements, sources, plain sp_mos1), every device emits its residual
 //     directly (devices.hpp, Rn), the linear solve runs from list-scheduled step descriptors staged behind the lean range of the tables.
+//     VAR 3: VAR 0 with the default transient call's switches fixed at compile time (lds_layout.hpp: f2_fixed_ok), taken whenever they hold.
 //     VAR 1: direct residuals for every device type, the linear solve as the pass program of the full table.  VAR 2 (diagnostic,
 //     CADNIP_F2_NODIRECT=1): the assembled residual r = J u + C beta - b from a J*u pass over the resident matrix.
 //   * team kernel k_fteam<NW, STEP> (fused_team_kernel.hpp): 2 or 4 waves share one instance when the batch cannot fill the chip; STEP
@@ -231,11 +232,11 @@ static int fused2_blocks(CadnipHandle* h) {
 }
 
 // The one place that decides what a fused launch runs, and the only reader of the diagnostic switches CADNIP_F2_NODIRECT / _TEAM / _WPB / _STEPS_PACKED /
-// _SRC_CACHE
+// _SRC_CACHE / _FIXED
 // (CADNIP_F2_NC: f2_prepare, where the tables are built; CADNIP_F2_DEBUG prints the plan, launch_fused2).
 static bool env_is_zero(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }
 
-F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode) {
+F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode, const TranArgs* topt) {
   F2Plan p;
   FusedState& S = h->f2;
   p.rc = CADNIP_BADARG;
@@ -310,12 +311,17 @@ F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode) {
       shmem = lds_bytes(lds_sweep((size_t)0, p.tab_len, dw, S.lu_words, h->n, 0, wpb, sw));
     }
   }
+  // The default transient call on a lean circuit takes the fixed form of variant 0 (k_fused2<wpb, false, 3>: the call's switches are compile-time
+  // constants there); f2_fixed_ok is the list of what that kernel assumes.  CADNIP_F2_FIXED=0 (diagnostic, tests: bit-identical results either
+  // way) keeps the generic kernel, and so do CADNIP_F2_STEPS_PACKED=1 and CADNIP_F2_SRC_CACHE=0 through step_predec / src_words.
+  p.fixed = topt && f2_fixed_ok(mode == F2_TRAN, p.var == 0, topt->newton_mode, p.step_predec, p.src_words, h->n, S.nc, topt->max_order, topt->step_rule,
+                                topt->use_pcnr, !env_is_zero("CADNIP_F2_FIXED"));
   p.wpb = wpb; p.shmem = shmem; p.grid = std::min((h->B + wpb - 1) / wpb, S.n_cu * wg_per_cu); p.rc = CADNIP_OK;
   return p;
 }
 
 static int launch_fused2(CadnipHandle* h, const TranArgs& t, int rounds, const F2DcOpts* dc, const F2StepOpts* step = nullptr) {
-  const F2Plan p = fused2_plan(h, dc ? F2_DC : step ? F2_STEP : F2_TRAN, t.newton_mode);
+  const F2Plan p = fused2_plan(h, dc ? F2_DC : step ? F2_STEP : F2_TRAN, t.newton_mode, dc || step ? nullptr : &t);
   if (p.rc) return p.rc;
   ProfScope ps(h, dc ? "fused2_dc" : step ? "fused_step" : "fused2_newton");
   FusedState& S = h->f2;
@@ -357,8 +363,9 @@ static int launch_fused2(CadnipHandle* h, const TranArgs& t, int rounds, const F
     else TRY_RC(fteam_launch(p.nw, p.grid, p.shmem, h->stream, f));
   } else {
     const size_t tab_b = (size_t)p.tab_len / 2 * 8, desc_b = (size_t)lds_sweep_desc_words(f.team_desc_len, p.step_predec) * 8;
-    if (debug) fprintf(stderr, "[cadnip f2] B %d n_cu %d wpb %d grid %d shmem %zu (tables %zu, steps %zu, per instance %zu) rounds %d nc %d passes %d+%d steps %d+%d / %d (%s) variant %d src-cache %d\n", h->B, S.n_cu, p.wpb, p.grid, p.shmem, tab_b, desc_b, (p.shmem - tab_b - desc_b) / p.wpb, rounds, S.nc, S.n_pre, S.n_post, f.ts_pre, f.ts_post, f.ts_fwd, p.step_predec ? "pre-decoded" : "packed", p.var, p.src_words);
-    TRY_RC(p.var == 0 ? f2_launch_variant<0>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
+    if (debug) fprintf(stderr, "[cadnip f2] B %d n_cu %d wpb %d grid %d shmem %zu (tables %zu, steps %zu, per instance %zu) rounds %d nc %d passes %d+%d steps %d+%d / %d (%s) variant %d src-cache %d fixed %d\n", h->B, S.n_cu, p.wpb, p.grid, p.shmem, tab_b, desc_b, (p.shmem - tab_b - desc_b) / p.wpb, rounds, S.nc, S.n_pre, S.n_post, f.ts_pre, f.ts_post, f.ts_fwd, p.step_predec ? "pre-decoded" : "packed", p.var, p.src_words, p.fixed ? 1 : 0);
+    TRY_RC(p.fixed ? f2_launch_variant<3>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
+         : p.var == 0 ? f2_launch_variant<0>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
          : p.var == 1 ? f2_launch_variant<1>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
                       : f2_launch_variant<2>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f));
   }

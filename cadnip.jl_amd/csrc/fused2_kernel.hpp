@@ -1,6 +1,6 @@
 // fused2_kernel.hpp -- the fused Newton kernel itself (template k_fused2<WPB, DC, VAR>) and its argument block.  Included by
-// fused2.hip (host side: tables, launch geometry) and by the three translation units that instantiate the kernel, one per
-// variant (fused2_v0/1/2.hip), so that the variants compile in parallel.  See fused2.hip for the design notes.
+// fused2.hip (host side: tables, launch geometry) and by the four translation units that instantiate the kernel, one per
+// variant (fused2_v0/1/2/3.hip), so that the variants compile in parallel.  See fused2.hip for the design notes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "devices.hpp"
@@ -87,14 +87,17 @@ struct TranStateView {
   int newton_mode; double *mn_a0f, *mn_ss, *mn_dnp; int* mn_flags;
   int max_order; double* hp3;
 };
+// FIXED (the sweep kernel's fixed form, k_fused2<.., 3>): Newton mode 1 and max_order <= 2 are known -- load_state / store_state carry no test
+// of them and no hp3
+template <bool FIXED = false>
 __device__ __forceinline__ TranStateView state_view() {
   const F2ArgsK p = kargs();
   TranStateView v;
   v.t = p->t.t; v.h = p->t.h; v.hprev = p->t.hprev; v.hpp = p->t.hpp; v.tcur = p->t.tcur; v.gamma = p->t.gamma;
   v.nhist = p->t.nhist; v.order = p->t.order; v.k = p->t.k; v.status = p->t.status; v.bp_idx = p->t.bp_idx; v.save_idx = p->t.save_idx;
   v.active = p->t.active; v.cnt = p->t.cnt; v.breaks = p->t.breaks; v.save_t = p->t.save_t; v.n_break = p->t.n_break; v.n_save = p->t.n_save;
-  v.newton_mode = p->t.newton_mode; v.mn_a0f = p->t.mn_a0f; v.mn_ss = p->t.mn_ss; v.mn_dnp = p->t.mn_dnp; v.mn_flags = p->t.mn_flags;
-  v.max_order = p->t.max_order; v.hp3 = p->t.hp3;
+  v.newton_mode = FIXED ? 1 : p->t.newton_mode; v.mn_a0f = p->t.mn_a0f; v.mn_ss = p->t.mn_ss; v.mn_dnp = p->t.mn_dnp; v.mn_flags = p->t.mn_flags;
+  v.max_order = FIXED ? 2 : p->t.max_order; v.hp3 = FIXED ? nullptr : p->t.hp3;
   return v;
 }
 
@@ -222,12 +225,16 @@ __device__ __forceinline__ void dispatch_stamp2(int type, const LdsCtx& d, const
 }
 
 // controller vector policy of the fused kernel (see tran_ctrl.hpp): u, beta and the Newton step in LDS
+// FIXED_: the fixed form of the sweep kernel (k_fused2<.., 3>) -- the controller's options are the default call's at compile time
+// (tran_ctrl.hpp: V::FIXED) and n <= 64 KPF, so no element lies beyond the register-held ones
+template <bool FIXED_ = false>
 struct FusedVecs {
   // per-lane elements kept in registers (covers n <= 256): the history u0 / u1 / u2 and the predictor for the whole
   // residence of the instance, the error weights from `prefetch` to the update.  Elements beyond stay in HBM.
   static constexpr int KPF = 4;
   static constexpr bool OWN_REDUCE = false;
   static constexpr int NT = 64;          // one wave per instance (tran_ctrl.hpp: grp_sum / grp_sync)
+  static constexpr bool FIXED = FIXED_;
   double *us, *betas; const double* W; const u16* qinv;
   size_t vo;                   // this instance's offset into the per-unknown vectors; their bases come from the kernarg segment
   const double* lw;
@@ -332,10 +339,13 @@ __device__ __forceinline__ void dense_core_solve(double* W, int dn0, int yc0, in
 }
 
 // VAR: 0 = direct residuals, lean device set; 1 = direct residuals, every device type; 2 = assembled residual
-// r = J u + C beta - b (diagnostic, CADNIP_F2_NODIRECT=1), every device type
+// r = J u + C beta - b (diagnostic, CADNIP_F2_NODIRECT=1), every device type; 3 = variant 0 with the default transient call's switches
+// fixed at compile time (lds_layout.hpp: f2_fixed_ok is the list; fused2.hip: fused2_plan decides): Newton mode 1, pre-decoded steps, source
+// cache on, core of 8, no PCNR, max_order <= 2, step_rule 0, n <= 256.  Same statements, same order: results are variant 0's to the bit.
 template <int WPB, bool DC, int VAR>
 __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
-  constexpr bool DIRECT = VAR != 2, LEAN = VAR == 0;
+  constexpr bool DIRECT = VAR != 2, LEAN = VAR == 0 || VAR == 3, FIXED = VAR == 3;
+  static_assert(!(FIXED && DC), "the fixed form is a transient kernel");
   extern __shared__ double sm[];
   // w is the same for all lanes of a wave: say so (readfirstlane), or every address derived from it lives in VGPRs
   const int tid = threadIdx.x, lane0 = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), n = f.n;
@@ -349,7 +359,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   const unsigned* tab = (const unsigned*)sm;
   // lean variant: the linear solve as straight-line steps (f2_program.cpp: f2_build_steps), their 16-byte lane descriptors staged behind the tables
   // ... as the host packs them, or pre-decoded on the way in (lds_layout.hpp: lds_step_predecode; one flag byte per lane and step behind them)
-  const bool predec = LEAN && f.step_predec;
+  const bool predec = FIXED ? true : LEAN && f.step_predec;
   const LdsSweep<double*> L = lds_sweep((double*)sm, f.tab_len, LEAN ? lds_sweep_desc_words(f.team_desc_len, predec) : 0, f.nnz_lu, n, w, WPB, f.src_words);
   const uint4* tdesc = (const uint4*)L.desc;
   const unsigned char* tflag = (const unsigned char*)(L.desc + (LEAN ? f.team_desc_len : 0));
@@ -449,7 +459,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   StepState st;
   bool have = false;
   while (inst < f.B) {
-    const TranStateView sv = state_view();
+    const TranStateView sv = state_view<FIXED>();
     if (DC) st.status = __builtin_amdgcn_readfirstlane(sv.status[inst]);
     else { st = load_state(sv, inst); make_uniform(st); }
     if (st.status == 0) { have = true; break; }
@@ -461,8 +471,8 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   const size_t vo = (size_t)inst * n;
   // limit_w is read only by the PCNR corrector of the update: without it the stamps need not write it (each write is an
   // HBM store that later vector-memory waits would queue behind)
-  double* lw = (DC ? f.dc_pcnr : a.use_pcnr) ? kargs()->t.limit_w + vo : nullptr;
-  FusedVecs vec{us, betas, W, qinv, vo, lw};
+  double* lw = FIXED ? nullptr : (DC ? f.dc_pcnr : a.use_pcnr) ? kargs()->t.limit_w + vo : nullptr;
+  FusedVecs<FIXED> vec{us, betas, W, qinv, vo, lw};
   if (!DC) vec.load_history(n, lane0);
   {
     const F2ArgsK ka = kargs();
@@ -470,7 +480,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
     for (int i = lane0; i < n; i += 64) { us[i] = ug[i]; betas[i] = DC ? 0.0 : betag[i]; }
   }
   // Newton mode 1: the factors this instance kept when it last left a wave
-  const bool mn = !DC && LEAN && a.newton_mode != 0;     // (lean variant only: the host refuses the mode otherwise, fused2.hip)
+  const bool mn = FIXED ? true : !DC && LEAN && a.newton_mode != 0;     // (lean variant only: the host refuses the mode otherwise, fused2.hip)
   if (mn && (st.mflags & MN_VALID)) {
     const double* src = kargs()->lufac + (size_t)inst * f.nnz_lu;
     for (int i = lane0; i < f.nnz_lu; i += 64) W[i] = src[i];
@@ -488,7 +498,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   // source segment cache of this residence (src_cache.hpp; LDS behind beta): a DC source's entry answers every time point, every other
   // source starts with an entry that cannot hit and caches the PWL segment its first evaluation finds
   // (whether the launch has one is read from the kernarg segment where it is needed, like the pointers above: not one more scalar held, or spilled, across the round)
-  auto sc_on = [&]() -> bool { return !DC && DIRECT && kargs()->src_words > 0; };
+  auto sc_on = [&]() -> bool { return FIXED ? true : !DC && DIRECT && kargs()->src_words > 0; };
   if (sc_on()) {
     const F2Block B = load_block(f.blk, f.src_blk);
     const int cl = src_cache_lanes(B.count);
@@ -517,6 +527,9 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
     }
     if (refresh) {
       for (int i = lane; i < (nW >> 1); i += 64) ((double2*)W)[i] = make_double2(0.0, 0.0);   // nW is even (f2_program.cpp), W 16-byte aligned
+    } else if constexpr (FIXED) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) { const int i = f.nnz_lu + lane + 64 * k; if (i < nW) W[i] = 0.0; }   // rhs | trash: n + 64 <= 320 words
     } else {
       for (int i = f.nnz_lu + lane; i < nW; i += 64) W[i] = 0.0;
     }
@@ -856,7 +869,12 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
       else run_passes(f.n_pre + f.n_post, f.n_fwd);
     }
     CADNIP_TRACE_POINT(4);
-    if (f.nc > 0) {
+    if constexpr (FIXED) {
+      const int yc0 = f.nnz_lu + n - 8;
+      if (refresh) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, true);
+      else dense_core_solve<8, 1>(W, f.dn0, yc0, lane, bad, false);
+      CADNIP_WAVE_SYNC();
+    } else if (f.nc > 0) {
       const int yc0 = f.nnz_lu + n - f.nc;
       if (refresh) {
         if (f.nc == 8) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, mn);
@@ -909,7 +927,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
         for (int i = lane0; i < f.nnz_lu; i += 64) dst[i] = W[i];
       }
       vec.store_history(n, lane0);
-      store_state(state_view(), inst, lane0, st);
+      store_state(state_view<FIXED>(), inst, lane0, st);
     }
   }
   CADNIP_WAVE_SYNC();

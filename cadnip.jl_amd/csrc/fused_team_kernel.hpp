@@ -28,6 +28,7 @@ struct TeamVecs {
   static constexpr int KPF = KPF_;
   static constexpr int NT = NT_;
   static constexpr bool OWN_REDUCE = true;
+  static constexpr bool FIXED = false;   // the call's options are read at run time (tran_ctrl.hpp: V::FIXED)
   double *us, *betas; const double* W; const u16* qinv;
   double* red;                 // [NT / 64][4] exchange words of the update's reductions
   int qi[KPF];                 // W word of this thread's unknowns' Newton step (a property of the circuit)

@@ -344,8 +344,10 @@ struct F2Plan {
   bool step_predec = false;   // sweep kernel: the descriptors are staged pre-decoded, a flag byte per lane and step behind them (lds_layout.hpp)
   bool keep_factors = false;  // Newton mode 1 / single step: kept factors in HBM
   int src_words = 0;          // sweep kernel: doubles of the per-instance source segment cache in LDS (src_cache.hpp), 0 = the launch runs without it
+  bool fixed = false;         // sweep kernel, variant 0: the launch takes the fixed form k_fused2<wpb, false, 3> (lds_layout.hpp: f2_fixed_ok)
 };
-F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode);
+// topt: the transient options of the call the plan is for (null: none -- the fixed form is then never chosen)
+F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode, const TranArgs* topt = nullptr);
 int launch_fused2_dc(CadnipHandle* h, const TranArgs& t, int rounds, double abstol, int maxiters, int use_pcnr, int mode, int initjct, int* d_dcstate);
 struct ProfScope {
   CadnipHandle* h; int idx;

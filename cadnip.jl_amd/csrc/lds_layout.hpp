@@ -45,6 +45,14 @@ LDS_HD StepPredec lds_step_predecode(unsigned x, unsigned y, unsigned z, unsigne
   return r;
 }
 LDS_HD bool lds_steps_predec_ok(int lu_words, int n) { return lu_words + n + F2_TRASH + LDS_CONSTS <= 8192; }
+// ---- the sweep kernel's FIXED form (k_fused2<WPB, false, 3>, fused2_kernel.hpp): the lean transient kernel with every switch of the default
+// call a compile-time constant.  THE list of what that kernel assumes; a launch that misses one condition takes the generic variant 0, which
+// computes the same to the bit.  `enabled`: CADNIP_F2_FIXED is not 0 (diagnostic, tests; fused2.hip: fused2_plan reads it and calls this).
+LDS_HD bool f2_fixed_ok(bool tran, bool lean, int newton_mode, bool step_predec, int src_words, int n, int nc, int max_order, int step_rule,
+                        int use_pcnr, bool enabled) {
+  return tran && lean && newton_mode == 1 && step_predec && src_words > 0 && n <= 256 && nc == 8 && max_order <= 2 && step_rule == 0 &&
+         use_pcnr == 0 && enabled;
+}
 // 64-bit words of the descriptor area: desc_len as uploaded (two per lane and step), plus one flag byte per lane and step when pre-decoded
 LDS_HD int lds_sweep_desc_words(int desc_len, bool predec) { return desc_len + (predec ? desc_len / 16 : 0); }
 

@@ -210,12 +210,18 @@ template <class V> __device__ __forceinline__ void grp_reduce3(V& v, double& s1,
   }
 }
 
+// Options of the call that a vector policy may fix at compile time (V::FIXED: the fixed form of the fused sweep kernel, fused2_kernel.hpp): the
+// default call's Newton mode 1, max_order <= 2 (the order in flight is 1 or 2), step_rule 0, no PCNR corrector, and n <= NT KPF -- no element
+// beyond the register-held ones.  Where the controller below asks for one of them it says `V::FIXED ? <that value> : <the runtime member>`,
+// a constant under V::FIXED and for every other policy the expression that stood there before.
+
 // every per-unknown vector in HBM (per-op path)
 template <int NT_>
 struct GlobalVecsT {
   static constexpr int KPF = 0;
   static constexpr int NT = NT_;
   static constexpr bool OWN_REDUCE = false;
+  static constexpr bool FIXED = false;
   double *__restrict__ u, *__restrict__ du, *__restrict__ up, *__restrict__ beta, *__restrict__ u0, *__restrict__ u1, *__restrict__ u2;
   double* u3;
   const double *__restrict__ delta, *__restrict__ lw;
@@ -264,7 +270,7 @@ __device__ __forceinline__ void each_elem(int n, int tid, F&& f) {
   if constexpr (V::KPF == 0) {
 #pragma unroll 4
     for (int i = tid; i < n; i += V::NT) f(i, -1);
-  } else {
+  } else if constexpr (!V::FIXED) {
     for (int i = tid + V::NT * V::KPF; i < n; i += V::NT) f(i, -1);
   }
 }
@@ -295,7 +301,7 @@ __device__ inline void prepare_step(const TranArgs& a, V& v, StepState& s, int t
       double b = fast_div(-x0, h);
       v.set_beta(i, b); v.set_du(i, a0 * p + b);
     });
-  } else if (nhist >= 4 && a.max_order >= 3) {
+  } else if (nhist >= 4 && (!V::FIXED && a.max_order >= 3)) {
     // variable-step BDF3: the derivative at t_n of the cubic through (t_n, u) and the three last accepted points (d1 < d2 < d3: their distances
     // from t_n); the predictor is the cubic through the FOUR last accepted points.  oracle/cpu_port.cpp carries the same operations in the same order.
     ord = 3;
@@ -387,7 +393,7 @@ __device__ inline void tran_update_body(const TranArgs& a, V& v, StepState& s, i
   CADNIP_TRACE_POINT(30);
   s.c_newton += 1;
   bool conv = !bad && dnorm < a.newton_tol, diverge = false;
-  if (a.newton_mode) {
+  if (V::FIXED || a.newton_mode) {
     conv = false;
     if (!bad) {
       if (s.k == 0) conv = dnorm <= 0.33e-4;
@@ -406,7 +412,7 @@ __device__ inline void tran_update_body(const TranArgs& a, V& v, StepState& s, i
     if (tested) {
       double errc;
       if (s.ord == 1) errc = fast_div(h, h + hprev);
-      else if (s.ord == 3) errc = fast_div(fast_div(1.0, s.a0), ((h + hprev) + hpp) + s.hp3);
+      else if (!V::FIXED && s.ord == 3) errc = fast_div(fast_div(1.0, s.a0), ((h + hprev) + hpp) + s.hp3);
       else { double w = fast_div(h, hprev); errc = fast_div(fast_div((1.0 + w) * h, 1.0 + 2.0 * w), h + hprev + hpp); }
       errn = errc * sqrt(fast_div(s2, (double)a.n_err));
       accept = errn <= 1.0;
@@ -414,21 +420,21 @@ __device__ inline void tran_update_body(const TranArgs& a, V& v, StepState& s, i
     if (accept) {
       grp_sync<V>();
       save_outputs(a, v, s, inst, tid);
-      if (a.max_order >= 3) each_elem<V>(n, tid, [&](int i, int k) { v.set_h3(i, k, v.h2(i, k)); });
+      if (!V::FIXED && a.max_order >= 3) each_elem<V>(n, tid, [&](int i, int k) { v.set_h3(i, k, v.h2(i, k)); });
       each_elem<V>(n, tid, [&](int i, int k) { double v1 = v.h1(i, k), v0 = v.h0(i, k); v.set_h2(i, k, v1); v.set_h1(i, k, v0); v.set_h0(i, k, v.get_u(i)); });
       const double tn = s.tn;
       bool landed = tn == s.t_break;
-      const int nh_cap = a.max_order >= 3 ? 4 : 3;
+      const int nh_cap = (!V::FIXED && a.max_order >= 3) ? 4 : 3;
       int nh_new = s.nhist + 1 > nh_cap ? nh_cap : s.nhist + 1;
       double hnext;
       if (tested) {
         double fac;
-        if (a.step_rule == 0) {
-          fac = errn > 0.0 ? 0.9 * step_root(errn, s.ord) : 2.0;
+        if (V::FIXED || a.step_rule == 0) {
+          fac = errn > 0.0 ? 0.9 * step_root(errn, (V::FIXED ? (s.ord == 1 ? 1 : 2) : s.ord)) : 2.0;
           fac = fmin(2.0, fmax(0.2, fac));
         } else {
           // IDA (ida.c: IDACompleteStep / IDASetEta): double the step when the estimate allows it, shrink it by 0.5 .. 0.9 when it must, keep it otherwise
-          const double eta = errn > 0.0 ? fast_div(1.0, fast_div(1.0, step_root(2.0 * errn, s.ord)) + 1e-4) : 2.0;
+          const double eta = errn > 0.0 ? fast_div(1.0, fast_div(1.0, step_root(2.0 * errn, (V::FIXED ? (s.ord == 1 ? 1 : 2) : s.ord))) + 1e-4) : 2.0;
           fac = eta >= 2.0 ? 2.0 : (eta <= 1.0 ? fmax(0.5, fmin(0.9, eta)) : 1.0);
         }
         hnext = h * fac;
@@ -454,8 +460,8 @@ __device__ inline void tran_update_body(const TranArgs& a, V& v, StepState& s, i
       CADNIP_TRACE_POINT(32);
     } else {
       double fac;
-      if (a.step_rule == 0) { fac = 0.9 * step_root(errn, s.ord); fac = fmin(0.9, fmax(0.1, fac)); }
-      else { fac = fast_div(0.9, fast_div(1.0, step_root(2.0 * errn, s.ord)) + 1e-4); fac = fmin(0.9, fmax(0.25, fac)); }   // IDA after a failed error test
+      if (V::FIXED || a.step_rule == 0) { fac = 0.9 * step_root(errn, (V::FIXED ? (s.ord == 1 ? 1 : 2) : s.ord)); fac = fmin(0.9, fmax(0.1, fac)); }
+      else { fac = fast_div(0.9, fast_div(1.0, step_root(2.0 * errn, (V::FIXED ? (s.ord == 1 ? 1 : 2) : s.ord))) + 1e-4); fac = fmin(0.9, fmax(0.25, fac)); }   // IDA after a failed error test
       double hn = h * fac;
       s.c_reject += 1;
       if (hn < a.hmin) { s.status = -1; return; }
@@ -463,7 +469,7 @@ __device__ inline void tran_update_body(const TranArgs& a, V& v, StepState& s, i
       prepare_step(a, v, s, tid, s.t, hn, s.nhist, hprev, hpp);
     }
   } else {
-    if (a.newton_mode && (bad || diverge || s.k + 1 >= a.max_newton) && !(s.mflags & MN_JCUR)) {
+    if ((V::FIXED || a.newton_mode) && (bad || diverge || s.k + 1 >= a.max_newton) && !(s.mflags & MN_JCUR)) {
       // the iteration failed on a stale Jacobian: same step again, refactored first (IDA: IDA_NLS recoverable with callSetup)
       s.mflags |= MN_NEED;
       grp_sync<V>();
@@ -476,11 +482,11 @@ __device__ inline void tran_update_body(const TranArgs& a, V& v, StepState& s, i
       prepare_step(a, v, s, tid, s.t, hn, s.nhist, hprev, hpp);
     } else {
       grp_sync<V>();
-      if (a.use_pcnr && a.n_limits > 0)
+      if (!V::FIXED && a.use_pcnr && a.n_limits > 0)
         for (int i = n - a.n_limits + tid; i < n; i += V::NT) v.set_u(i, v.get_lw(i));
       grp_sync<V>();
       const double a0 = s.a0;
-      for (int i = tid; i < n; i += V::NT) v.set_du(i, a0 * v.get_u(i) + v.get_beta(i));
+      if constexpr (!V::FIXED) for (int i = tid; i < n; i += V::NT) v.set_du(i, a0 * v.get_u(i) + v.get_beta(i));   // (the fixed form's set_du is empty: du is rebuilt at exit)
       s.k += 1;
     }
   }
