@@ -489,6 +489,17 @@ enum { M1_TYPE = 0, M1_VT, M1_TPHI, M1_TVBI, M1_TVTO, M1_GAMMA, M1_LAMBDA, M1_BE
        M1_F2D, M1_F3D, M1_F4D, M1_MJ, M1_MJSW, M1_CGSOV, M1_CGDOV, M1_CGBOV, M1_GD, M1_GS, M1_MFACTOR, M1_GMIN };
 static_assert(M1_GMIN == 33 && M1_OXCAP == 8 && M1_GD == 30 && M1_GS == 31, "keep CADNIP_MOS1_PAR_* (internal.hpp) in step");
 
+// Quotients of the sp_mos1 load section (m1_junction, m1_channel, m1_qdep and gmin / mfactor in the three stamps).  Where the denominator is
+// provably finite, non-zero and of normal range, and the numerator either at least 2^-969 in magnitude (1.0 and 0.5 in the dual forms below; a
+// simulator gmin) or a zero whose sign nothing downstream looks at, the quotient is fast_div (tran_ctrl.hpp, which every translation
+// unit that instantiates an sp_mos1 stamp includes): there it IS the IEEE quotient, bit for bit, at 8 vector instructions instead of the
+// compiler's range-scaled sequence -- so oracle/cpu_port.cpp's plain divisions stay the exact counterpart.  Each such site says why it
+// qualifies; every other division of the model stays `/`.  FQ = false (csrc/probe/prim_probe.hip, tests/test_gpu_mos1_quotients.py) compiles
+// the same statements with IEEE division everywhere: the two must agree to the bit on every branch.  The generic Dual operators, dsqrt and
+// dlog are shared with models whose arguments may be zero and stay as they are; the forms below repeat their operations in their order.
+__device__ __forceinline__ double fast_div(double a, double b);
+template <bool FQ> __device__ __forceinline__ double m1_quot(double a, double b) { return FQ ? fast_div(a, b) : a / b; }
+
 __device__ inline double m1_fetlim(double vnew, double vold, double vto) {   // DEVfetlim mos1.va:542-605
   double vlimited = vnew;
   double vtsthi = fabs(2 * (vold - vto)) + 2;
@@ -541,6 +552,34 @@ __device__ inline double m1_pnjlim(double vnew, double vold, double vt, double v
 
 typedef Dual<3> D3;
 
+// exact-range forms of Dual / double, 1.0 / Dual, dsqrt and dlog for the sites of the load section that qualify (m1_quot above): the generic
+// helpers' operations in their order, the reciprocal alone taken through m1_quot
+template <bool FQ> __device__ __forceinline__ D3 m1_over(const D3& a, double b) {          // a / b
+  D3 r; double ib = m1_quot<FQ>(1.0, b); r.v = a.v * ib;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r.p[i] = a.p[i] * ib;
+  return r;
+}
+template <bool FQ> __device__ __forceinline__ D3 m1_recip(const D3& a) {                   // 1.0 / a
+  D3 r; double ia = m1_quot<FQ>(1.0, a.v), q = 1.0 * ia; r.v = q;
+  const double f = -q * ia;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r.p[i] = f * a.p[i];
+  return r;
+}
+template <bool FQ> __device__ __forceinline__ D3 m1_dsqrt(const D3& a) {
+  D3 r; double s = sqrt(a.v); r.v = s; double f = m1_quot<FQ>(0.5, s);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r.p[i] = a.p[i] * f;
+  return r;
+}
+template <bool FQ> __device__ __forceinline__ D3 m1_dlog(const D3& a) {
+  D3 r; r.v = log(a.v); const double ia = m1_quot<FQ>(1.0, a.v);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) r.p[i] = a.p[i] * ia;
+  return r;
+}
+
 // DEVqmeyer (mos1.va:401-465): Meyer capacitances, evaluated on duals
 __device__ inline void m1_qmeyer(const D3& vgs, const D3& vgd, const D3& von, const D3& vdsat_in, double phi, double cox,
                                  D3& capgs, D3& capgd, D3& capgb) {
@@ -572,14 +611,20 @@ __device__ inline void m1_qmeyer(const D3& vgs, const D3& vgd, const D3& von, co
 }
 
 // depletion charge (mos1.va:1049-1109)
+// (what the quotients rest on: a card whose junction has capacitance has a finite tBulkPot != 0, fc < 1 and mj, mjsw != 1 -- mos1_params.derive
+// divides by tBulkPot, 1 - fc, 1 - mj and 1 - mjsw itself, so any other card has no finite f2 / f3 / f4 to begin with; and on this branch
+// v < tDepCap = fc tBulkPot, so arg = 1 - v / tBulkPot >= 1 - fc > 0, finite and below 2^1022 for every iterate |v| < 1e300)
+template <bool FQ = true>
 __device__ inline D3 m1_qdep(const D3& v, double Cb, double Cbsw, double tBulkPot, double tDepCap, double mj, double mjsw,
                              double f2, double f3, double f4) {
   if (Cb != 0 || Cbsw != 0) {
     if (v.v < tDepCap) {
-      D3 arg = 1.0 - v / tBulkPot;
-      D3 sarg = (mj == 0.5) ? 1.0 / dsqrt(arg) : dexp(-mj * dlog(arg));
-      D3 sargsw = (mjsw == mj) ? sarg : ((mjsw == 0.5) ? 1.0 / dsqrt(arg) : dexp(-mjsw * dlog(arg)));
-      return tBulkPot * (Cb * (1.0 - arg * sarg) / (1 - mj) + Cbsw * (1.0 - arg * sargsw) / (1 - mjsw));
+      D3 arg = 1.0 - m1_over<FQ>(v, tBulkPot);                                // 1 / tBulkPot: finite, non-zero (above)
+      // 1 / sqrt(arg): s = sqrt(arg) > 0 (arg >= 1 - fc) in 0.5 / s and in 1 / s;  dlog: 1 / arg, arg >= 1 - fc
+      D3 sarg = (mj == 0.5) ? m1_recip<FQ>(m1_dsqrt<FQ>(arg)) : dexp(-mj * m1_dlog<FQ>(arg));
+      D3 sargsw = (mjsw == mj) ? sarg : ((mjsw == 0.5) ? m1_recip<FQ>(m1_dsqrt<FQ>(arg)) : dexp(-mjsw * m1_dlog<FQ>(arg)));
+      // 1 / (1 - mj), 1 / (1 - mjsw): grading coefficients != 1 (above)
+      return tBulkPot * (m1_over<FQ>(Cb * (1.0 - arg * sarg), 1 - mj) + m1_over<FQ>(Cbsw * (1.0 - arg * sargsw), 1 - mjsw));
     }
     return f4 + v * (f2 + v * (f3 / 2));
   }
@@ -587,6 +632,8 @@ __device__ inline D3 m1_qdep(const D3& v, double Cb, double Cbsw, double tBulkPo
 }
 
 // $limit sites of the load section (mos1.va:919-980): limited branch voltages w = (vgs, vds, vbs, vbd), sign-adjusted
+// (The limiters keep IEEE division: (vnew - vold) / vt and o_vbs / (2 sqrt(tPhi)) qualify for m1_quot, vnew / vt does not, but the three of them
+// as fast quotients cost k_fused2<8, false, 3> a seventh spilled VGPR, and they run only in the rounds that are not quiet -- DESIGN.md section 9, round 7.)
 template <class Ctx>
 __device__ inline void m1_limit(const Ctx& d, const double* u, double type, double vt, double tPhi, double tVbi, double gamma, double Vg, double Vb,
                                 double Vdi, double Vsi, int l0, int l1, int l2, int l3, double& w_gs, double& w_ds, double& w_bs, double& w_bd) {
@@ -640,20 +687,22 @@ __device__ inline void m1_limit(const Ctx& d, const double* u, double type, doub
 }
 
 // junction current of one bulk diode (mos1.va:983-998)
+template <bool FQ = true>
 __device__ inline D3 m1_junction(const D3& v, double vt, double gmin_m, double isat) {
   if (v.v <= -3 * vt) return gmin_m * v - isat;
-  D3 x = v / vt;
+  D3 x = m1_over<FQ>(v, vt);                      // 1 / vt: vt = kT/q > 0
   D3 e = dexp(709.0 < x.v ? D3(709.0) : x);
   return isat * (e - 1.0) + gmin_m * v;
 }
 
 // threshold, saturation voltage and drain current (mos1.va:1000-1040)
+template <bool FQ = true>
 __device__ inline void m1_channel(const D3& a, const D3& b, const D3& c, const D3& dvbd, const D3& dvgd, double tPhi, double tVbi, double type,
                                   double gamma, double lambda, double Beta, int& mode, D3& dvon, D3& vdsat, D3& cdrain) {
   mode = b.v >= 0 ? 1 : -1;
   D3 sel = mode == 1 ? c : dvbd, sarg;
-  if (sel.v <= 0) sarg = dsqrt(tPhi - sel);
-  else { double s0 = sqrt(tPhi); sarg = s0 - sel / (s0 + s0); if (0 > sarg.v) sarg = D3(0.0); }
+  if (sel.v <= 0) sarg = m1_dsqrt<FQ>(tPhi - sel);                                                        // 0.5 / s: s = sqrt(tPhi - sel) >= sqrt(tPhi) > 0 on this branch
+  else { double s0 = sqrt(tPhi); sarg = s0 - m1_over<FQ>(sel, s0 + s0); if (0 > sarg.v) sarg = D3(0.0); }   // 1 / (2 s0): s0 = sqrt(tPhi), tPhi > 0
   dvon = tVbi * type + gamma * sarg;
   D3 vgst = (mode == 1 ? a : dvgd) - dvon;
   vdsat = vgst.v > 0 ? vgst : D3(0.0);
@@ -673,7 +722,7 @@ template <class Ctx, class Out> __device__ inline void stamp_mos1(const Ctx& d, 
   double Vd = volt(u, nd), Vg = volt(u, ng), Vs = volt(u, ns), Vb = volt(u, nb), Vdi = volt(u, ndi), Vsi = volt(u, nsi);
   double type = par_of(d, M1_TYPE), vt = par_of(d, M1_VT), tPhi = par_of(d, M1_TPHI), tVbi = par_of(d, M1_TVBI);
   double gamma = par_of(d, M1_GAMMA), lambda = par_of(d, M1_LAMBDA), Beta = par_of(d, M1_BETA), OxideCap = par_of(d, M1_OXCAP);
-  double mf = par_of(d, M1_MFACTOR), gmin_m = par_of(d, M1_GMIN) / mf;
+  double mf = par_of(d, M1_MFACTOR), gmin_m = fast_div(par_of(d, M1_GMIN), mf);   // mf > 0 (the multiplicity); gmin >= 0, a zero's sign is IEEE's for mf > 0
   CADNIP_TRACE_POINT(20);
   // ---- limiting (mos1.va:919-980), on values
   double w_gs, w_ds, w_bs, w_bd;
@@ -859,7 +908,7 @@ __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out&
   D3 a = D3::seed(type * w_gs, 0), b = D3::seed(type * w_ds, 1), c = D3::seed(type * w_bs, 2);
   D3 dvbd = c - b, dvgd = a - b;
   const D3 vj = m1_sel(D, dvbd, c);
-  const double gmin_m = gmin_p / mf;                               // isat: this lane's junction, source side or drain side
+  const double gmin_m = fast_div(gmin_p, mf);                      // mf > 0 (the multiplicity); gmin >= 0, a zero's sign is IEEE's for mf > 0.  isat: this lane's junction, source side or drain side
   // third group (depletion charge of this lane's junction), in flight during the junction and channel arithmetic
   const double q_cb = par_of(d, D ? M1_CBD : M1_CBS), q_cbsw = par_of(d, D ? M1_CBDSW : M1_CBSSW), q_pot = par_of(d, M1_TBULKPOT), q_dep = par_of(d, M1_TDEPCAP);
   const double q_mj = par_of(d, M1_MJ), q_mjsw = par_of(d, M1_MJSW), q_f2 = par_of(d, D ? M1_F2D : M1_F2S), q_f3 = par_of(d, D ? M1_F3D : M1_F3S), q_f4 = par_of(d, D ? M1_F4D : M1_F4S);
@@ -1040,7 +1089,7 @@ __device__ inline void stamp_mos1_team(const Ctx& d, const double* u, const Out&
     CADNIP_TRACE_POINT(26);
   }
   if (roles & M1_ROLE_J) {
-    const double gmin_m = par_of(d, M1_GMIN) / mf, isat = par_side(d, M1_SSATCUR, M1_DSATCUR, D);
+    const double gmin_m = fast_div(par_of(d, M1_GMIN), mf), isat = par_side(d, M1_SSATCUR, M1_DSATCUR, D);   // mf > 0, gmin >= 0 (stamp_mos1_pair)
     const D3 cj = m1_junction(vj, vt, gmin_m, isat);
     CADNIP_TRACE_POINT(23);
     const D3 Ib = type * cj;                                  // into row b; the junction's own terminal row takes the negative

@@ -219,6 +219,49 @@ PROBE(limiters, 4, 4, 0, 0,
       OUT(0) = pnjlim(IN(0), IN(1), IN(2), IN(3)); OUT(1) = m1_pnjlim(IN(0), IN(1), IN(2), IN(3));
       OUT(2) = m1_fetlim(IN(0), IN(1), IN(3)); OUT(3) = m1_limvds(IN(0), IN(1));)
 
+// ---- sp_mos1: the parts of the load section, with the exact fast quotients (FQ = true, what the stamps run) and with IEEE division ----------
+// (tests/test_gpu_mos1_quotients.py: the two must agree to the bit).  The parameter block is the product's own ([M1_NPAR] rows, devices.hpp M1_*).
+namespace {
+struct M1ProbeCtx { const double* par; int count, dev, initjct; };
+
+// in: vgs, vds, vbs (type-adjusted, as the stamps seed them), then the parameter block.  out: cbs, cbd (m1_junction, source / drain side), dvon,
+// vdsat, cdrain (m1_channel), qbs, qbd (m1_qdep) -- value and three partials each, rows 0..27 -- then mode and gmin / mfactor
+template <bool FQ> __device__ void m1_parts_body(int n, int i, const double* in, double* out) {
+  const M1ProbeCtx d{in + (size_t)3 * n, n, i, 0};
+  const double type = par_of(d, M1_TYPE), vt = par_of(d, M1_VT), tPhi = par_of(d, M1_TPHI), tVbi = par_of(d, M1_TVBI), gamma = par_of(d, M1_GAMMA);
+  const double gmin_m = m1_quot<FQ>(par_of(d, M1_GMIN), par_of(d, M1_MFACTOR));
+  const D3 a = D3::seed(IN(0), 0), b = D3::seed(IN(1), 1), c = D3::seed(IN(2), 2);
+  const D3 dvbd = c - b, dvgd = a - b;
+  st_dual(out, n, i, 0, m1_junction<FQ>(c, vt, gmin_m, par_of(d, M1_SSATCUR)));
+  st_dual(out, n, i, 4, m1_junction<FQ>(dvbd, vt, gmin_m, par_of(d, M1_DSATCUR)));
+  int mode;
+  D3 dvon, vdsat, cdrain;
+  m1_channel<FQ>(a, b, c, dvbd, dvgd, tPhi, tVbi, type, gamma, par_of(d, M1_LAMBDA), par_of(d, M1_BETA), mode, dvon, vdsat, cdrain);
+  st_dual(out, n, i, 8, dvon); st_dual(out, n, i, 12, vdsat); st_dual(out, n, i, 16, cdrain);
+  st_dual(out, n, i, 20, m1_qdep<FQ>(c, par_of(d, M1_CBS), par_of(d, M1_CBSSW), par_of(d, M1_TBULKPOT), par_of(d, M1_TDEPCAP), par_of(d, M1_MJ),
+                                     par_of(d, M1_MJSW), par_of(d, M1_F2S), par_of(d, M1_F3S), par_of(d, M1_F4S)));
+  st_dual(out, n, i, 24, m1_qdep<FQ>(dvbd, par_of(d, M1_CBD), par_of(d, M1_CBDSW), par_of(d, M1_TBULKPOT), par_of(d, M1_TDEPCAP), par_of(d, M1_MJ),
+                                     par_of(d, M1_MJSW), par_of(d, M1_F2D), par_of(d, M1_F3D), par_of(d, M1_F4D)));
+  OUT(28) = (double)mode; OUT(29) = gmin_m;
+}
+// in: V(g), V(b), V(d_int), V(s_int), the four limit unknowns (the previous round's limited vgs, vds, vbs, vbd), then the parameter block.
+// iin: initjct.  out: the limited vgs, vds, vbs, vbd (m1_limit).  (m1_limit holds no fast quotient at present -- devices.hpp says why -- so the two
+// instantiations are the same code today; the pair stays in the macro so that a site converted later is compared like the others.)
+template <bool FQ> __device__ void m1_limit_body(int n, int i, const double* in, double* out, const int* iin) {
+  const M1ProbeCtx d{in + (size_t)8 * n, n, i, II(0)};
+  const double uo[4] = {IN(4), IN(5), IN(6), IN(7)};
+  double w[4];
+  m1_limit(d, uo, par_of(d, M1_TYPE), par_of(d, M1_VT), par_of(d, M1_TPHI), par_of(d, M1_TVBI), par_of(d, M1_GAMMA), IN(0), IN(1), IN(2), IN(3),
+               0, 1, 2, 3, w[0], w[1], w[2], w[3]);
+  OUT(0) = w[0]; OUT(1) = w[1]; OUT(2) = w[2]; OUT(3) = w[3];
+}
+}  // namespace
+#define M1_PROBES(tag, FQ)                                                             \
+  PROBE(m1_parts_##tag, 3 + M1_NPAR, 30, 0, 0, m1_parts_body<FQ>(n, i, in, out);)      \
+  PROBE(m1_limit_##tag, 8 + M1_NPAR, 4, 1, 0, m1_limit_body<FQ>(n, i, in, out, iin);)
+M1_PROBES(fq, true)
+M1_PROBES(ieee, false)
+
 // ---- source waves -----------------------------------------------------------------------------------------------------------------------
 // in: t.  iin: offset of ts in tab, number of points (ys follow ts), hint (-1: no hint pointer).  out: value.  iout: the hint afterwards
 PROBE(pwl, 1, 1, 3, 1,
