@@ -536,15 +536,16 @@ class ACSol:
     voltage or a branch current over the grid (ac.jl name-based access); ``freqresp(name, omegas)`` evaluates at angular
     frequencies (ac.jl:185-215); ``magnitude_db`` / ``phase_deg`` as in ac.jl:228-273."""
 
-    def __init__(self, st, G, C, b_ac, dc_x, freqs):
+    def __init__(self, st, G, C, b_ac, dc_x, freqs, delay=None):
         self.st, self.G, self.C, self.b_ac, self.dc_x, self.freqs = st, G, C, b_ac, dc_x, np.asarray(freqs, dtype=float)
+        self.delay = delay       # None, or omega -> the n x n addend of the circuit's delayed elements (AcDelayOverlay.of): A = G + j w C + delay(w)
         self._cache = {}
         self.stats = {}          # ac(..., solver="gpu" | "auto"): what the batched GPU sweep did (``ac_gpu_sweep``); empty on the host path
 
     def _solve(self, omegas):
         key = tuple(np.asarray(omegas, dtype=float))
         if key not in self._cache:
-            self._cache[key] = np.array([np.linalg.solve(self.G + 1j * w * self.C, self.b_ac) for w in key]) if len(key) else np.zeros((0, self.st.n), complex)
+            self._cache[key] = np.array([np.linalg.solve(ac_matrix(self.G, self.C, w, self.delay), self.b_ac) for w in key]) if len(key) else np.zeros((0, self.st.n), complex)
         return self._cache[key]
 
     def freqresp(self, name, omegas):
@@ -610,6 +611,117 @@ def ac_pivot_sample(st, G_csr, C_csr, omegas, gmin):
     return s
 
 
+# ---- delayed controlled sources (Circuit.E/G/H/F(..., delay=), Circuit.T) in the frequency domain ------------------------------------------
+# The stamps of a controlled source that carry its gain: type -> (parameter, {G slot of structure.PROGRAMS: d stamp / d parameter}), from
+# csrc/devices.hpp (stamp_vcvs, stamp_vccs, stamp_ccvs, stamp_cccs).  A delay tau multiplies exactly these by e^{-j w tau}.
+DELAY_STAMPS = {"E": ("gain", {4: -1.0, 5: 1.0}), "G": ("gm", {0: -1.0, 1: 1.0, 2: 1.0, 3: -1.0}), "H": ("rm", {8: -1.0}), "F": ("gain", {4: -1.0, 5: 1.0})}
+
+
+def has_delay(circuit):
+    """does the circuit hold a delayed controlled source (a transmission line is made of them)?"""
+    return any("delay" in d.params for d in circuit.devices)
+
+
+def refuse_delay(circuit, what, why):
+    """the analyses that cannot take a delayed element say so before any device work"""
+    if has_delay(circuit):
+        raise NotImplementedError("%s: the circuit has a delayed controlled source or a transmission line; %s" % (what, why))
+
+
+class AcDelayOverlay:
+    """What the delayed elements of a circuit add to A(w) = G + j w C at a batch of points: D[b](w), non-zero at the CSR positions ``pos`` [O]
+    (ascending; ``rows`` / ``cols`` their coordinates), D[b](w)[pos[o]] = sum over the delayed stamps t at that position of
+    (e^{-j w tau_t[b]} - 1) w_t[b], with w_t the stamp's own contribution to G.  ``val`` [B, F, O] is the table on the grid ``omegas`` the
+    overlay was made for -- what hip.Handle.ac_set_overlay takes; ``values(omegas)`` evaluates it on any grid, ``dense(b, omega)`` gives the
+    n x n addend of point b at one frequency, and ``of(b)`` that as a function of omega alone."""
+
+    def __init__(self, n, pos, rows, cols, terms, B, omegas):
+        self.n, self.pos, self.rows, self.cols, self.terms, self.B = n, pos, rows, cols, terms, B
+        self.omegas = np.asarray(omegas, dtype=float).ravel()
+        self.val = self.values(self.omegas)
+
+    def values(self, omegas):
+        w = np.asarray(omegas, dtype=float).ravel()
+        val = np.zeros((self.B, w.size, len(self.pos)), dtype=complex)
+        for o, tau, wt in self.terms:
+            x = w[None, :] * tau[:, None]
+            val[:, :, o] += (-2.0 * np.sin(0.5 * x) ** 2 - 1j * np.sin(x)) * wt[:, None]      # e^{-jx} - 1 without the cancellation at small x
+        return val
+
+    def dense(self, b, omega):
+        D = np.zeros((self.n, self.n), dtype=complex)
+        D[self.rows, self.cols] = self.values([omega])[b, 0]
+        return D
+
+    def of(self, b):
+        return lambda omega: self.dense(b, omega)
+
+
+def ac_delay_overlay(st, circuit, params, omegas=(), B=None):
+    """The one place that turns delayed elements into numbers -- pure host code, shared by the dense host solves, the redo rows of the GPU
+    gates and the GPU sweeps (which hand ``pos`` / ``val`` to the overlay kernels): circuit, structure and point parameters (name -> a
+    number or one value per point; ``B``: the number of points when no parameter tells) in, an AcDelayOverlay out, or None for a circuit without a delayed element.  The table is computed here,
+    not on the device: it is B x F x a handful of entries, needs sin / cos of arguments that must agree with the host path's to the bit, and
+    the kernels stay ignorant of what produced it."""
+    from .circuit import resolve
+    from .opinfo import _index
+    if not has_delay(circuit):
+        return None
+    B = int(B) if B is not None else max([np.size(v) for v in params.values()] + [1])
+    info = {d["name"]: d for d in st.opinfo}
+    at, terms = {}, []
+    for d in circuit.devices:
+        if "delay" not in d.params:
+            continue
+        if d.type not in DELAY_STAMPS:
+            raise NotImplementedError("a delay on a %s element" % d.type)
+        par, slots = DELAY_STAMPS[d.type]
+        oi = info[d.name]
+        gl = [_index(st, t) for t in oi["nodes"]]
+        tau = np.broadcast_to(np.asarray(resolve(d.params["delay"], params), dtype=float), (B,))
+        gain = np.broadcast_to(np.asarray(resolve(d.params[par], params), dtype=float), (B,))
+        for stream, k, rl, cl in oi["prog"]:
+            if stream != "G" or k not in slots or gl[rl] < 0 or gl[cl] < 0:
+                continue
+            terms.append(((gl[rl], gl[cl]), tau, slots[k] * gain))
+            at.setdefault((gl[rl], gl[cl]), None)
+    rowptr, colidx = np.asarray(st.rowptr), np.asarray(st.colidx)
+    csr = lambda r, c: int(rowptr[r] + np.flatnonzero(colidx[rowptr[r]:rowptr[r + 1]] == c)[0])
+    coords = sorted(at, key=lambda rc: csr(*rc))
+    o_of = {rc: o for o, rc in enumerate(coords)}
+    return AcDelayOverlay(st.n, np.array([csr(*rc) for rc in coords], dtype=np.int32), np.array([rc[0] for rc in coords], dtype=np.int64),
+                          np.array([rc[1] for rc in coords], dtype=np.int64), [(o_of[rc], tau, wt) for rc, tau, wt in terms], B, omegas)
+
+
+def ac_matrix(G, C, omega, delay=None):
+    """A(w) of the dense host solves: G + j w C, plus the delayed elements' addend when there is one (``delay``: omega -> n x n)"""
+    A = G + 1j * omega * C
+    return A if delay is None else A + delay(omega)
+
+
+class _ac_overlay_of:
+    """``with _ac_overlay_of(h, ovl)``: the handle's overlay for one sweep; None makes no call at all"""
+
+    def __init__(self, h, ovl):
+        self.h, self.ovl = h, ovl
+
+    def __enter__(self):
+        if self.ovl is not None:
+            self.h.ac_set_overlay(self.ovl.pos, self.ovl.omegas, self.ovl.val)
+
+    def __exit__(self, *exc):
+        if self.ovl is not None:
+            self.h.ac_clear_overlay()
+
+
+def _overlay_sample(sample_csr, ovl):
+    """the pivot sample of a sweep under an overlay: max_f |D| joins the sample at the overlay's positions"""
+    if ovl is not None and ovl.val.size:
+        sample_csr = np.array(sample_csr)
+        sample_csr[ovl.pos] += np.max(np.abs(ovl.val), axis=(0, 1))
+    return sample_csr
+
+
 AC_MEMORIES = ("lds", "hbm", "auto")
 
 
@@ -635,7 +747,7 @@ class _ac_memory_of:
             self.h.ac_set_memory("lds")
 
 
-def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory="lds"):
+def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory="lds", overlay=None):
     """The frequency sweep of one structure class on the GPU: ``h`` (a hip.Handle holding the restamp at the DC points) re-analyses its
     pivot order on ``ac_pivot_sample`` and solves all points x all frequencies in ONE ``ac_solve`` call; every ACSol of ``sols`` gets the
     rows of its point into its cache under the key ``tuple(omegas)``.  A system whose flag is set or whose backward error exceeds
@@ -644,7 +756,9 @@ def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory=
     solver="gpu"; with "auto" nothing is cached -- the sols solve on the host on demand -- and stats["fallback"] says why.
     ``memory``: where the kernel keeps a system's work arrays (hip.Handle.ac_set_memory) -- "lds" (the default; DESIGN section 9 has
     the figures and leaves another default to a later change): circuits beyond the LDS budget are refused as above; "hbm": a workspace in device memory, so
-    such a circuit is solved on the GPU; "auto": LDS where the circuit fits, else HBM.  stats["memory"] is what the launch used."""
+    such a circuit is solved on the GPU; "auto": LDS where the circuit fits, else HBM.  stats["memory"] is what the launch used.
+    ``overlay``: the AcDelayOverlay of the class on ``omegas`` (the sols then carry its ``of(k)`` as their ``delay``), or None: it is set on
+    the handle for the call and cleared after it, and its max_f |D| joins the pivot sample."""
     from . import hip
     _ac_memory(memory)
     omegas = np.asarray(omegas, dtype=float)
@@ -656,10 +770,10 @@ def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory=
         return
     to_ref = np.asarray(st.to_ref_nz)
     sample_ref = np.empty(st.nnz)
-    sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+    sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
     h.analyze_values(sample_ref)
     try:
-        with _ac_memory_of(h, memory):
+        with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
             x, berr, flags, info = h.ac_solve(omegas, gmin, np.array([s.b_ac for s in sols]))
             used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
     except hip.CadnipError as e:
@@ -672,7 +786,7 @@ def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory=
     for k, s in enumerate(sols):
         rows = np.array(x[k])
         for f in np.flatnonzero(redo[k]):
-            rows[f] = np.linalg.solve(s.G + 1j * omegas[f] * s.C, s.b_ac)
+            rows[f] = np.linalg.solve(ac_matrix(s.G, s.C, omegas[f], s.delay), s.b_ac)
         s._cache[key] = rows
     kept = berr[~redo]
     stats["gpu_systems"] += int((~redo).sum())
@@ -747,13 +861,14 @@ def port_rows(st, ports):
     return rows
 
 
-def ac_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, rhs, pairs, want_x, solver, stats, memory="lds"):
+def ac_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, rhs, pairs, want_x, solver, stats, memory="lds", overlay=None):
     """K excitations per point against ONE factorisation per (point, frequency), on the GPU: ``h`` (holding the restamp at the DC points)
     re-analyses its pivot order on ``ac_pivot_sample`` -- as ``ac_gpu_sweep`` -- and solves points x frequencies x the K columns of ``rhs``
     ([K, n]) in ONE ``ac_solve_multi`` call.  Returns (h [B, F, K, P] for the probe ``pairs`` or None, x [B, F, K, n] or None without
     ``want_x``).  The gate is ``ac_gpu_sweep``'s, per column: a column whose flag is set or whose backward error exceeds AC_BERR_MAX is solved
     again by the host's dense solve on ``Gd`` / ``Cd`` (per point; gmin on the node diagonals).  ``stats`` counts columns as systems.  A
-    circuit the memory home refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why."""
+    circuit the memory home refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why.  ``overlay`` as
+    for ``ac_gpu_sweep``: the redo solves add its ``dense(b, w)``."""
     from . import hip
     _ac_memory(memory)
     omegas = np.asarray(omegas, dtype=float)
@@ -762,10 +877,10 @@ def ac_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, rhs, pairs, wa
     stats["rhs"] = K
     to_ref = np.asarray(st.to_ref_nz)
     sample_ref = np.empty(st.nnz)
-    sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+    sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
     h.analyze_values(sample_ref)
     try:
-        with _ac_memory_of(h, memory):
+        with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
             hh, x, berr, flags, info = h.ac_solve_multi(omegas, gmin, rhs, pairs, 0, want_x)
             used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
     except hip.CadnipError as e:
@@ -778,7 +893,7 @@ def ac_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, rhs, pairs, wa
     if redo.any():
         pr = None if hh is None else np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         for b, f, k in zip(*np.nonzero(redo)):
-            xh = np.linalg.solve(Gd[b] + 1j * omegas[f] * Cd[b], rhs[k])
+            xh = np.linalg.solve(ac_matrix(Gd[b], Cd[b], omegas[f], overlay and overlay.of(b)), rhs[k])
             if x is not None:
                 x[b, f, k] = xh
             if hh is not None:
@@ -808,7 +923,10 @@ def ac(target, freqs=(), gmin=1e-12, device=0, solver="host", memory="lds", sour
     ``sources`` (default None: the call is exactly what it is without the keyword): a list of names of independent sources.  The result is
     then, per point, a dict name -> ACSol whose excitation is that source ALONE at unit magnitude (``source_rhs``; the circuit's ``ac=``
     values are ignored): the separate responses from one DC solve and one restamp, and with a GPU solver from one factorisation per (point,
-    frequency) serving all of them (``ac_multi_gpu_sweep``; ``stats`` then counts columns as systems and has "rhs": the number of sources)."""
+    frequency) serving all of them (``ac_multi_gpu_sweep``; ``stats`` then counts columns as systems and has "rhs": the number of sources).
+    A circuit with delayed controlled sources or transmission lines (``Circuit.E/G/H/F(..., delay=)``, ``Circuit.T``) is solved as
+    A(w) = G + j w C + D(w) on every path -- ``ac_delay_overlay`` computes D, the host solves add it, the GPU sweeps hand it to the overlay
+    kernels -- and so are ``network``, ``noise`` and ``network_noise``; the ACSols then carry ``delay``."""
     from contextlib import closing
     if solver not in ("host", "gpu", "auto"):
         raise ValueError("solver must be 'host', 'gpu' or 'auto'")
@@ -819,17 +937,18 @@ def ac(target, freqs=(), gmin=1e-12, device=0, solver="host", memory="lds", sour
     omegas = 2.0 * np.pi * np.asarray(freqs, dtype=float)
     with closing(_ac_classes(sweep, mc, pts, gmin, device, "ac")) as classes:
         for sim, st, idx, G, C, lin in classes:
+            ovl = ac_delay_overlay(st, mc.circuit, sim.params, omegas, sim.B)
             if sources is None:
-                for i, Gd, Cd, p_i, u_i in lin:
-                    sols[i] = ACSol(st, Gd, Cd, rhs_ac(st, mc.circuit, p_i), u_i, freqs)
+                for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin):
+                    sols[i] = ACSol(st, Gd, Cd, rhs_ac(st, mc.circuit, p_i), u_i, freqs, ovl and ovl.of(k))
                 if solver != "host":
-                    ac_gpu_sweep(sim.h, st, [sols[i] for i in idx], G, C, omegas, gmin, solver, stats, memory)
+                    ac_gpu_sweep(sim.h, st, [sols[i] for i in idx], G, C, omegas, gmin, solver, stats, memory, ovl)
                 continue
             rhs = np.array([source_rhs(st, mc.circuit, nm) for nm in sources]).reshape(len(sources), st.n)
-            for i, Gd, Cd, p_i, u_i in lin:
-                sols[i] = {nm: ACSol(st, Gd, Cd, rhs[j], u_i, freqs) for j, nm in enumerate(sources)}
+            for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin):
+                sols[i] = {nm: ACSol(st, Gd, Cd, rhs[j], u_i, freqs, ovl and ovl.of(k)) for j, nm in enumerate(sources)}
             if solver != "host" and omegas.size and len(sources):
-                got = ac_multi_gpu_sweep(sim.h, st, [l[1] for l in lin], [l[2] for l in lin], G, C, omegas, gmin, rhs, None, True, solver, stats, memory)
+                got = ac_multi_gpu_sweep(sim.h, st, [l[1] for l in lin], [l[2] for l in lin], G, C, omegas, gmin, rhs, None, True, solver, stats, memory, ovl)
                 if got is not None:
                     for k, i in enumerate(idx):
                         for j, nm in enumerate(sources):
@@ -879,7 +998,7 @@ class NetworkSol:
         return 20.0 * np.log10(np.abs(self.s[:, self._port(i), self._port(j)]))
 
 
-def network_solve(st, G, C, ports, freqs, z0=50.0, dc_x=None):
+def network_solve(st, G, C, ports, freqs, z0=50.0, dc_x=None, delay=None):
     """The host path of ``network`` on dense G (gmin already on the voltage-node diagonals) and C: per frequency ONE dense LU serves the P
     columns -- column j has 1 on the branch row of port j's source and 0 elsewhere -- and y[f, i, j] = -x_j[I_<Vi>]: a V source's branch
     current flows from + through the source to -, so the current into the port from outside is its negative."""
@@ -889,7 +1008,7 @@ def network_solve(st, G, C, ports, freqs, z0=50.0, dc_x=None):
     E[rows, np.arange(len(rows))] = 1.0
     y = np.zeros((len(freqs), len(rows), len(rows)), dtype=complex)
     for fi, f in enumerate(freqs):
-        y[fi] = -np.linalg.solve(G + 1j * 2.0 * np.pi * f * C, E)[rows]
+        y[fi] = -np.linalg.solve(ac_matrix(G, C, 2.0 * np.pi * f, delay), E)[rows]
     return NetworkSol(freqs, ports, y, z0, dc_x)
 
 
@@ -917,15 +1036,16 @@ def network(target, ports, freqs, z0=50.0, gmin=1e-12, device=0, solver="host", 
     with closing(_ac_classes(sweep, mc, pts, gmin, device, "network")) as classes:
         for sim, st, idx, G, C, lin in classes:
             rows = port_rows(st, ports)
+            ovl = ac_delay_overlay(st, mc.circuit, sim.params, omegas, sim.B)
             got = None
             if solver != "host" and freqs.size and rows:
                 rhs = np.zeros((len(rows), st.n), dtype=complex)
                 rhs[np.arange(len(rows)), rows] = 1.0
                 got = ac_multi_gpu_sweep(sim.h, st, [l[1] for l in lin], [l[2] for l in lin], G, C, omegas, gmin, rhs, [(r, -1) for r in rows], False,
-                                         solver, stats, memory)
+                                         solver, stats, memory, ovl)
             for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin):
                 if got is None:
-                    sols[i] = network_solve(st, Gd, Cd, ports, freqs, z0, u_i)
+                    sols[i] = network_solve(st, Gd, Cd, ports, freqs, z0, u_i, ovl and ovl.of(k))
                 else:
                     sols[i] = NetworkSol(freqs, ports, -np.swapaxes(got[0][k], 1, 2), z0, u_i)      # h[f, column j, port i] -> y[f, i, j]
     if solver != "host":
@@ -1071,7 +1191,7 @@ def noise_indices(st, output, input=None):
     return out_idx, in_idx
 
 
-def noise_solve(st, G, C, sources, output, freqs, input=None, temp_c=27.0, adjoint=None):
+def noise_solve(st, G, C, sources, output, freqs, input=None, temp_c=27.0, adjoint=None, delay=None):
     """noise.jl:150-188 on dense G (gmin already on the voltage-node diagonals) and C: one adjoint solve per frequency,
     S_out(f) = sum_k |x_adj[p_k] - x_adj[n_k]|^2 S_k(f); the same adjoint gives the gain from the input source's branch row.
     ``adjoint``: None -- the dense solve here -- or (index, H): the probe differences H[f, index[(p, n)]] = x_adj[p] - x_adj[n] of this
@@ -1089,7 +1209,7 @@ def noise_solve(st, G, C, sources, output, freqs, input=None, temp_c=27.0, adjoi
     inoise = np.zeros(len(freqs)) if input is not None else np.zeros(0)
     for fi, f in enumerate(freqs):
         if adjoint is None:
-            x_adj = np.linalg.solve((1j * 2.0 * np.pi * f * C + G).T, e_out)
+            x_adj = np.linalg.solve((1j * 2.0 * np.pi * f * C + G).T if delay is None else ac_matrix(G, C, 2.0 * np.pi * f, delay).T, e_out)
         for s in sources:
             if adjoint is None:
                 Hk = (x_adj[s[0]] if s[0] >= 0 else 0.0) - (x_adj[s[1]] if s[1] >= 0 else 0.0)
@@ -1129,7 +1249,7 @@ def noise_probe_pairs(source_lists, in_idx=None):
 
 
 def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, input=None, temps=27.0, gmin=1e-12, solver="gpu", stats=None,
-                    memory="lds"):
+                    memory="lds", overlay=None):
     """The adjoint sweep of one structure class on the GPU, reachable without ``noise_sources``: ``h`` (a hip.Handle holding the restamp at the
     DC points; ``G_ref`` / ``C_ref`` [B, nnz] are its get_GCb) re-analyses its pivot order on ``ac_pivot_sample`` and solves all points x all
     frequencies in ONE ``ac_adjoint`` call for the class's probe pairs; ``Gd`` / ``Cd`` (dense, gmin on the node diagonals) and
@@ -1151,19 +1271,20 @@ def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, in
     out_idx, in_idx = noise_indices(st, output, input)
     omegas = 2.0 * np.pi * freqs
     pairs, index = noise_probe_pairs(source_lists, in_idx)
-    host = lambda k, adj=None: noise_solve(st, Gd[k], Cd[k], source_lists[k], output, freqs, input, float(temps[k]), adjoint=adj)
+    host = lambda k, adj=None: noise_solve(st, Gd[k], Cd[k], source_lists[k], output, freqs, input, float(temps[k]), adjoint=adj,
+                                           delay=overlay and overlay.of(k))
     if len(pairs) == 0:                                  # no source and no input: nothing to probe, the sums are empty
         sols = [host(k) for k in range(B)]
         stats["host_systems"] += B * F
     else:
         to_ref = np.asarray(st.to_ref_nz)
         sample_ref = np.empty(st.nnz)
-        sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+        sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
         h.analyze_values(sample_ref)
         e_out = np.zeros(st.n, dtype=complex)
         e_out[out_idx] = 1.0
         try:
-            with _ac_memory_of(h, memory):
+            with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
                 H, _, berr, flags, info = h.ac_adjoint(omegas, gmin, e_out, pairs)
                 used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
         except hip.CadnipError as e:
@@ -1179,7 +1300,7 @@ def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, in
         H = np.array(H)
         pp, nn = pairs[:, 0], pairs[:, 1]
         for k, f in zip(*np.nonzero(redo)):
-            x_adj = np.linalg.solve((1j * omegas[f] * Cd[k] + Gd[k]).T, e_out)
+            x_adj = np.linalg.solve(ac_matrix(Gd[k], Cd[k], omegas[f], overlay and overlay.of(k)).T, e_out)
             H[k, f] = np.where(pp >= 0, x_adj[pp], 0.0) - np.where(nn >= 0, x_adj[nn], 0.0)
         sols = [host(k, (index, H[k])) for k in range(B)]
         kept = berr[~redo]
@@ -1240,15 +1361,16 @@ def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"
                 p_k = {kk: float(v[k]) for kk, v in sim.params.items()}
                 temps.append(float(pts[i].get("temp", mc.spec.temp)))
                 srcs.append(noise_sources(st, mc.circuit, p_k, u[k], temps[k], mc.spec.gmin))
+            ovl = ac_delay_overlay(st, mc.circuit, sim.params, 2.0 * np.pi * np.asarray(freqs, dtype=float), sim.B)
             if not isinstance(output, str):
                 if solver == "host":
-                    got = [{o: noise_solve(st, Gd[k], Cd[k], srcs[k], o, freqs, input, temps[k]) for o in outputs} for k in range(len(idx))]
+                    got = [{o: noise_solve(st, Gd[k], Cd[k], srcs[k], o, freqs, input, temps[k], delay=ovl and ovl.of(k)) for o in outputs} for k in range(len(idx))]
                 else:
-                    got = noise_multi_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, outputs, freqs, input, temps, gmin, solver, stats, memory)
+                    got = noise_multi_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, outputs, freqs, input, temps, gmin, solver, stats, memory, ovl)
             elif solver == "host":
-                got = [noise_solve(st, Gd[k], Cd[k], srcs[k], output, freqs, input, temps[k]) for k in range(len(idx))]
+                got = [noise_solve(st, Gd[k], Cd[k], srcs[k], output, freqs, input, temps[k], delay=ovl and ovl.of(k)) for k in range(len(idx))]
             else:
-                got = noise_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, output, freqs, input, temps, gmin, solver, stats, memory)
+                got = noise_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, output, freqs, input, temps, gmin, solver, stats, memory, ovl)
             for k, i in enumerate(idx):
                 sols[i] = got[k]
         finally:
@@ -1256,7 +1378,7 @@ def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"
     return SweepResult(pts, sols) if sweep else sols[0]
 
 
-def adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, cols, pairs, solver, stats, memory="lds"):
+def adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, cols, pairs, solver, stats, memory="lds", overlay=None):
     """K adjoint right-hand sides per point against ONE factorisation per (point, frequency), on the GPU -- the transposed counterpart of
     ``ac_multi_gpu_sweep``: ``h`` re-analyses its pivot order on ``ac_pivot_sample`` and solves A^T x = cols[k] for points x frequencies x the
     K columns of ``cols`` ([K, n]) in ONE ``ac_adjoint_multi`` call.  Returns the probe differences H [B, F, K, P] for ``pairs``.  The gate is
@@ -1271,10 +1393,10 @@ def adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, cols, pai
     stats["rhs"] = K
     to_ref = np.asarray(st.to_ref_nz)
     sample_ref = np.empty(st.nnz)
-    sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
+    sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
     h.analyze_values(sample_ref)
     try:
-        with _ac_memory_of(h, memory):
+        with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
             H, _, berr, flags, info = h.ac_adjoint_multi(omegas, gmin, cols, pairs)
             used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
     except hip.CadnipError as e:
@@ -1287,7 +1409,7 @@ def adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, cols, pai
     pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     pp, nn = pr[:, 0], pr[:, 1]
     for b, f, k in zip(*np.nonzero(redo)):
-        x_adj = np.linalg.solve((1j * omegas[f] * Cd[b] + Gd[b]).T, cols[k])
+        x_adj = np.linalg.solve(ac_matrix(Gd[b], Cd[b], omegas[f], overlay and overlay.of(b)).T, cols[k])
         H[b, f, k] = np.where(pp >= 0, x_adj[pp], 0.0) - np.where(nn >= 0, x_adj[nn], 0.0)
     kept = berr[~redo]
     stats["gpu_systems"] += int((~redo).sum())
@@ -1299,7 +1421,7 @@ def adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, cols, pai
 
 
 def noise_multi_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, outputs, freqs, input=None, temps=27.0, gmin=1e-12, solver="gpu", stats=None,
-                          memory="lds"):
+                          memory="lds", overlay=None):
     """``noise_solve_gpu`` for several outputs: column j of ONE ``ac_adjoint_multi`` call is e_out of ``outputs[j]``, the probe pairs are those of
     the single-output call (``noise_probe_pairs``), and the weighting is ``noise_solve``'s per output.  Returns one dict output -> NoiseSol per
     point; the kernel's columns are bit-identical to the single-column kernel's, so each NoiseSol equals ``noise_solve_gpu``'s for that output."""
@@ -1312,13 +1434,14 @@ def noise_multi_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, outputs, fr
     temps = np.broadcast_to(np.asarray(temps, dtype=float), (B,))
     idxs = [noise_indices(st, o, input) for o in outputs]
     pairs, index = noise_probe_pairs(source_lists, idxs[0][1])
-    host = lambda k, o, adj=None: noise_solve(st, Gd[k], Cd[k], source_lists[k], o, freqs, input, float(temps[k]), adjoint=adj)
+    host = lambda k, o, adj=None: noise_solve(st, Gd[k], Cd[k], source_lists[k], o, freqs, input, float(temps[k]), adjoint=adj,
+                                              delay=overlay and overlay.of(k))
     H = None
     stats["rhs"] = K
     if len(pairs):
         cols = np.zeros((K, st.n), dtype=complex)
         cols[np.arange(K), [i[0] for i in idxs]] = 1.0
-        H = adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, 2.0 * np.pi * freqs, gmin, cols, pairs, solver, stats, memory)
+        H = adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, 2.0 * np.pi * freqs, gmin, cols, pairs, solver, stats, memory, overlay)
     else:                                                # no source and no input: nothing to probe, the sums are empty
         stats["host_systems"] += B * F * K
     sols = [{o: host(k, o, None if H is None else (index, H[k, :, j])) for j, o in enumerate(outputs)} for k in range(B)]
@@ -1410,7 +1533,7 @@ def network_noise_pairs(rows, source_lists):
     return np.array(list(index), dtype=np.int32).reshape(-1, 2), index
 
 
-def network_noise_solve(st, G, C, sources, ports, freqs, z0=50.0, temp_c=27.0, dc_x=None, adjoint=None):
+def network_noise_solve(st, G, C, sources, ports, freqs, z0=50.0, temp_c=27.0, dc_x=None, adjoint=None, delay=None):
     """The host path of ``network_noise`` on dense G (gmin already on the voltage-node diagonals) and C: per frequency ONE dense LU of A^T serves
     the P adjoint columns -- column i solves A^T l_i = e_row_i with row_i the branch row of port i's source.  From them y[f, i, j] = -l_i[row_j]
     and the transfer of noise source s to the short-circuit current of port i, T[i, s] = l_i[p_s] - l_i[n_s];
@@ -1434,7 +1557,7 @@ def network_noise_solve(st, G, C, sources, ports, freqs, z0=50.0, temp_c=27.0, d
     by_source = {s[5]: np.zeros((len(freqs), P, P), dtype=complex) for s in sources}
     for fi, f in enumerate(freqs):
         if adjoint is None:
-            lam = np.linalg.solve((1j * 2.0 * np.pi * f * C + G).T, E)                       # [n, P]: column i is l_i
+            lam = np.linalg.solve((1j * 2.0 * np.pi * f * C + G).T if delay is None else ac_matrix(G, C, 2.0 * np.pi * f, delay).T, E)                       # [n, P]: column i is l_i
             Hf = (np.where(pp >= 0, lam[pp[:, 0]], 0.0) - np.where(nn >= 0, lam[nn[:, 0]], 0.0)).T
         else:
             Hf = adjoint[1][fi]                                                              # [P, pairs]
@@ -1448,7 +1571,7 @@ def network_noise_solve(st, G, C, sources, ports, freqs, z0=50.0, temp_c=27.0, d
 
 
 def network_noise_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, ports, freqs, z0=50.0, temps=27.0, gmin=1e-12, solver="gpu", stats=None,
-                      memory="lds", dc_x=None):
+                      memory="lds", dc_x=None, overlay=None):
     """The P adjoint columns of one structure class on the GPU, shaped like ``noise_solve_gpu``: ``h`` (holding the restamp at the DC points)
     solves all points x frequencies x ports in ONE ``ac_adjoint_multi`` call (``adjoint_multi_gpu_sweep``: one factorisation per (point,
     frequency), the gate NOISE_BERR_MAX per column, a rejected column solved again by the host's dense adjoint solve) for the class's probe
@@ -1466,9 +1589,9 @@ def network_noise_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, ports, freqs, z
     if freqs.size and rows:
         cols = np.zeros((len(rows), st.n), dtype=complex)
         cols[np.arange(len(rows)), rows] = 1.0
-        H = adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, 2.0 * np.pi * freqs, gmin, cols, pairs, solver, stats, memory)
+        H = adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, 2.0 * np.pi * freqs, gmin, cols, pairs, solver, stats, memory, overlay)
     sols = [network_noise_solve(st, Gd[k], Cd[k], source_lists[k], ports, freqs, z0, float(temps[k]), None if dc_x is None else dc_x[k],
-                                None if H is None else (index, H[k])) for k in range(B)]
+                                None if H is None else (index, H[k]), overlay and overlay.of(k)) for k in range(B)]
     for s in sols:
         s.stats = stats
     return sols
@@ -1499,11 +1622,13 @@ def network_noise(target, ports, freqs, z0=50.0, gmin=1e-12, device=0, solver="h
             port_rows(st, ports)
             temps = [float(pts[i].get("temp", mc.spec.temp)) for i in idx]
             srcs = [noise_sources(st, mc.circuit, p_i, u_i, temps[k], mc.spec.gmin) for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin)]
+            ovl = ac_delay_overlay(st, mc.circuit, sim.params, 2.0 * np.pi * freqs, sim.B)
             if solver == "host":
-                got = [network_noise_solve(st, Gd, Cd, srcs[k], ports, freqs, z0, temps[k], u_i) for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin)]
+                got = [network_noise_solve(st, Gd, Cd, srcs[k], ports, freqs, z0, temps[k], u_i, None, ovl and ovl.of(k))
+                       for k, (i, Gd, Cd, p_i, u_i) in enumerate(lin)]
             else:
                 got = network_noise_gpu(sim.h, st, G, C, [l[1] for l in lin], [l[2] for l in lin], srcs, ports, freqs, z0, temps, gmin, solver,
-                                        stats, memory, [l[4] for l in lin])
+                                        stats, memory, [l[4] for l in lin], ovl)
             for k, i in enumerate(idx):
                 sols[i] = got[k]
     return SweepResult(pts, sols) if sweep else sols[0]
@@ -1618,6 +1743,7 @@ def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device
     if not rel_step > 0:
         raise ValueError("sensitivity: rel_step must be positive")
     sweep, mc, pts = _ac_target(target)
+    refuse_delay(mc.circuit, "sensitivity", "the bilinear forms over perturbed stamps do not know e^{-j w tau}, and its derivative with respect to tau is not built")
     for nm in params:
         if nm != "temp" and nm not in mc.params:
             raise ValueError("sensitivity: %s is not a parameter of the circuit (parameters: %s, or \"temp\")" % (nm, sorted(mc.params)))
@@ -1736,6 +1862,9 @@ def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device
 def subsystem(ac, name):
     """subsystem(ac, name) -- src/ac.jl:358-388: the single-output descriptor system E x' = A x + B u, y = C x + D u of an ACSol as the tuple
     (A, E, B, C_row, D) = (-G, C, b_ac[:, None], e_name^T, 0) -- what a control-systems package takes.  Ground is not an unknown: ValueError."""
+    if getattr(ac, "delay", None) is not None:
+        raise NotImplementedError("subsystem: the circuit has a delayed controlled source or a transmission line; A(w) = G + j w C + D(w) is not a "
+                                  "descriptor system (E, A, B, C, D)")
     if name in ("0", "gnd", "gnd!"):
         raise ValueError("subsystem: ground is not an unknown of the system")
     try:
@@ -1778,14 +1907,23 @@ def _finite_eigs(M0, M1):
     return ab[0][keep] / ab[1][keep] * (n0 / n1)
 
 
-def poles_dense(G, C):
-    """The finite generalized eigenvalues of (-G, C): every finite pole of (G + s C)^-1 -- the host path of ``pz`` and the tests' reference."""
+def _no_pencil(what, delay):
+    if delay is not None:
+        raise NotImplementedError("%s: with a delayed element (G + s C + D(s)) is not a matrix pencil; its poles and zeros are those of a "
+                                  "transcendental equation" % what)
+
+
+def poles_dense(G, C, delay=None):
+    """The finite generalized eigenvalues of (-G, C): every finite pole of (G + s C)^-1 -- the host path of ``pz`` and the tests' reference.
+    ``delay``: an ACSol's ``delay``; anything but None is refused (NotImplementedError)."""
+    _no_pencil("poles_dense", delay)
     return _finite_eigs(G, C)
 
 
-def zeros_dense(G, C, b, c):
+def zeros_dense(G, C, b, c, delay=None):
     """The finite transmission zeros of c^T (G + s C)^-1 b: the finite generalized eigenvalues of the bordered pencil [[G, -b], [c^T, 0]] +
-    s [[C, 0], [0, 0]]."""
+    s [[C, 0], [0, 0]].  ``delay`` as for ``poles_dense``."""
+    _no_pencil("zeros_dense", delay)
     n = len(b)
     M0, M1 = np.zeros((n + 1, n + 1), dtype=complex), np.zeros((n + 1, n + 1), dtype=complex)
     M0[:n, :n], M0[:n, n], M0[n, :n] = G, -np.asarray(b), np.asarray(c)
@@ -1986,6 +2124,7 @@ def pz(target, output, input=None, shifts=(0.0,), order=16, gmin=1e-12, device=0
     if solver != "host" and (omegas.size == 0 or int(order) < 1):
         raise ValueError("pz: at least one shift and one Arnoldi step")
     sweep, mc, pts = _ac_target(target)
+    refuse_delay(mc.circuit, "pz", "(G + s C + D(s)) is not a matrix pencil, so neither the dense eigenvalue path nor the Arnoldi kernel applies")
     stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0, "order": int(order), "shifts": int(omegas.size), "breakdowns": 0}
     sols = [None] * len(pts)
     with closing(_ac_classes(sweep, mc, pts, gmin, device, "pz")) as classes:
@@ -2021,6 +2160,8 @@ def pz(target, output, input=None, shifts=(0.0,), order=16, gmin=1e-12, device=0
 
 def tran(target, tspan, abstol=1e-10, reltol=1e-8, saveat=None, device=0, **kw):
     """tran!(circuit, tspan) / tran!(cs::CircuitSweep, tspan) -- sweeps.jl:588-665, 692-707."""
+    refuse_delay((target.circuit if isinstance(target, CircuitSweep) else target).circuit, "tran",
+                 "a transient needs the delayed quantity's history, and a delay-differential integrator is not built")
     tspan = (float(tspan[0]), float(tspan[1]))
     if saveat is None:
         saveat = np.linspace(tspan[0], tspan[1], 501)

@@ -60,17 +60,35 @@ class Circuit:
     def I(self, name, p, n, dc=0.0, wave=None, scale=1.0, ac=0.0):
         return self._add("I", name, (p, n), {"dc": dc, "scale": scale, "ac": ac}, wave=wave)
 
-    def E(self, name, op, on, ip, in_, gain):
-        return self._add("E", name, (op, on, ip, in_), {"gain": gain})
+    # ``delay``: a transport delay (seconds; a number or a Param) on the controlled quantity -- Verilog-A's absdelay.  It exists in the frequency
+    # domain only: the AC analyses multiply the stamps that carry the gain by e^{-j w delay} (api.ac_delay_overlay); at DC it is ignored, as an
+    # absdelay without history is; nothing the stamping reads changes, and the analyses that would need its history refuse such a circuit.
+    # Without a delay the device row is exactly what it was.
+    def E(self, name, op, on, ip, in_, gain, delay=0.0):
+        return self._add("E", name, (op, on, ip, in_), _delayed({"gain": gain}, delay))
 
-    def G(self, name, op, on, ip, in_, gm):
-        return self._add("G", name, (op, on, ip, in_), {"gm": gm})
+    def G(self, name, op, on, ip, in_, gm, delay=0.0):
+        return self._add("G", name, (op, on, ip, in_), _delayed({"gm": gm}, delay))
 
-    def H(self, name, op, on, ip, in_, rm):
-        return self._add("H", name, (op, on, ip, in_), {"rm": rm})
+    def H(self, name, op, on, ip, in_, rm, delay=0.0):
+        return self._add("H", name, (op, on, ip, in_), _delayed({"rm": rm}, delay))
 
-    def F(self, name, op, on, ip, in_, gain):
-        return self._add("F", name, (op, on, ip, in_), {"gain": gain})
+    def F(self, name, op, on, ip, in_, gain, delay=0.0):
+        return self._add("F", name, (op, on, ip, in_), _delayed({"gain": gain}, delay))
+
+    def T(self, name, p1, n1, p2, n2, z0, td):
+        """Ideal lossless transmission line between port 1 (p1, n1) and port 2 (p2, n2): characteristic impedance ``z0``, delay ``td`` (numbers or
+        Params).  Expanded by Branin's method of characteristics into existing elements: per port a conductance 1 / z0 from the terminal to an
+        internal node, and from that node to the port's reference two VCVS in series, both delayed by ``td`` -- gain 2 on the OTHER port's
+        terminal voltage, gain -1 on the other port's internal node, i.e. the incident wave v_other + z0 i_other that left there td ago.  The
+        conductances are G elements wired as conductances, not resistors: a lossless line registers no thermal noise.  The pieces are named
+        <name>_g1, <name>_a1, <name>_b1, ... and the internal nodes <name>_x1, <name>_m1, ...."""
+        for k, (p, n, q, m) in enumerate(((p1, n1, p2, n2), (p2, n2, p1, n1)), 1):
+            x, mid, xo = "%s_x%d" % (name, k), "%s_m%d" % (name, k), "%s_x%d" % (name, 3 - k)
+            self._add("G", "%s_g%d" % (name, k), (p, x, x, p), {"gm": _Recip(z0)})
+            self.E("%s_a%d" % (name, k), x, mid, q, m, 2.0, delay=td)
+            self.E("%s_b%d" % (name, k), mid, n, xo, m, -1.0, delay=td)
+        return self
 
     def BV(self, name, p, n, expr, scale=1.0):
         """BehavioralVoltageSource (devices.jl:1003-1029, stamp :1079-1102): V(p,n) = scale * expr, expr a string
@@ -122,7 +140,24 @@ class Circuit:
         return out
 
 
+def _delayed(params, delay):
+    """the device parameters with the delay among them when there is one: a device without delay keeps the row it always had"""
+    if isinstance(delay, Param) or delay != 0.0:
+        params["delay"] = delay
+    return params
+
+
+@dataclass(frozen=True)
+class _Recip:
+    """1 / value of a number or a Param: the conductance of a line's z0"""
+    of: Any
+
+
 def _plain(v, params=None):
+    if isinstance(v, _Recip):
+        if params is None and isinstance(v.of, Param):
+            raise ValueError("the conductance of a line whose z0 is a Param cannot be exported by name; pass params to evaluate it")
+        return 1.0 / float(_plain(v.of, params))
     if isinstance(v, Param):
         if params is not None:
             return float(resolve(v, params))
@@ -136,4 +171,6 @@ def resolve(v, params):
     """Evaluate a device parameter for one parameter set (numbers or numpy arrays)."""
     if isinstance(v, Param):
         return v.scale * params[v.name] + v.offset
+    if isinstance(v, _Recip):
+        return 1.0 / resolve(v.of, params)
     return v

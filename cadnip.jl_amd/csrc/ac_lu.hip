@@ -23,6 +23,8 @@
 // over the stamps of perturbed instances: the response and its K parameter derivatives from one factorisation.
 // k_ac_arnoldi / k_ac_arnoldi_hbm (cadnip_ac_arnoldi) factor at a shift j w_s and run m Arnoldi steps of A^-1 C there -- m + 1 columns with
 // the same factors, each right-hand side C times the previous solution, kept in the wave: the pole-zero analysis.
+// k_ac_lu_ovl, k_ac_adj_ovl, k_ac_lu_multi_ovl, k_ac_adj_multi_ovl and their _hbm forms (cadnip_ac_set_overlay) are the first four with a sparse
+// complex addend D[b][f] on A -- delayed stamps, e^{-j w tau} -- added wherever A is formed: steps 1, 4 and 5 (struct AcOvl below).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -61,9 +63,34 @@ __device__ __forceinline__ double2 crecip(double2 p) {
 }
 __device__ __forceinline__ double cabs2(double2 a) { return hypot(a.x, a.y); }
 
-// A at CSR position e of instance-local G / C
-__device__ __forceinline__ double2 ac_entry(const AcArgs& a, const double* G, const double* C, double om, int e) {
-  return make_double2(G[e] + (a.diag_flag[e] ? a.gmin : 0.0), om * C[e]);
+// The overlay (cadnip_ac_set_overlay): a sparse complex addend D[b][f] on A -- a delayed stamp's e^{-j w tau} is neither a G nor a C.  It is
+// non-zero at n CSR positions pos[] shared by the whole batch (distinct; map[nnz] is the inverse, -1 = none), with the values of system
+// (b, f) at val + (b n_freq + f) n: indexed by the system's own (inst, fi), so a chunk seam cannot shift it.  The host computes the values;
+// the kernels only add them.  The overlay is a compile-time policy of every function that forms an entry of A -- the load, the two
+// residuals and, through them, the backward error's |A| -- so the factors, the refinement step and berr belong to ONE matrix.  AcNoOvl is
+// empty: the kernels without overlay are the statements they were.  The addend is added component by component to the entry ac_entry
+// forms, in the load and in the residuals alike: the same doubles in both, whatever W and wherever the work arrays live.
+struct AcOvlArgs { const int *pos, *map; const double* val; int n; };
+struct AcNoOvl {
+  static constexpr bool on = false;
+  __device__ __forceinline__ AcNoOvl at(int, int, int) const { return *this; }
+};
+struct AcOvl {
+  static constexpr bool on = true;
+  const int *pos, *map; const double2* val; int n;
+  __device__ __forceinline__ AcOvl at(int inst, int fi, int n_freq) const { AcOvl o = *this; o.val = val + ((size_t)inst * n_freq + fi) * n; return o; }
+};
+__host__ __device__ __forceinline__ AcOvl ac_ovl(const AcOvlArgs& v) { return AcOvl{v.pos, v.map, (const double2*)v.val, v.n}; }
+
+// A at CSR position e of instance-local G / C; o: the overlay of the system (AcOvl::at), or none
+template <class O = AcNoOvl>
+__device__ __forceinline__ double2 ac_entry(const AcArgs& a, const double* G, const double* C, double om, int e, const O& o = O()) {
+  double2 v = make_double2(G[e] + (a.diag_flag[e] ? a.gmin : 0.0), om * C[e]);
+  if constexpr (O::on) {
+    const int k = o.map[e];
+    if (k >= 0) { const double2 d = o.val[k]; v = make_double2(v.x + d.x, v.y + d.y); }
+  }
+  return v;
 }
 
 // How the lanes of a wave order their accesses to the work arrays between two steps: a level's lanes read words that OTHER lanes of the wave
@@ -87,14 +114,18 @@ struct AcInHbm {
 
 // Steps 1 and 2 of every kernel -- load A into lu, factor in place -- so that k_ac_lu and k_ac_adj hold the same doubles by construction.
 // Returns 1 in the lanes that met a zero / non-finite pivot.
-template <class M>
-__device__ __forceinline__ int ac_load_factor(const AcArgs& a, double2* lu, const double* G, const double* C, double om, int lane) {
+template <class M, class O = AcNoOvl>
+__device__ __forceinline__ int ac_load_factor(const AcArgs& a, double2* lu, const double* G, const double* C, double om, int lane, const O& o = O()) {
   int bad = 0;
   // ---- 1. load
   for (int p = lane; p < a.nnz_lu; p += 64) lu[p] = make_double2(0.0, 0.0);
   M::sync();
   for (int e = lane; e < a.nnz; e += 64) lu[a.load_dst[e]] = ac_entry(a, G, C, om, e);
   M::sync();
+  if constexpr (O::on) {                                       // the overlay's pass: distinct positions, one lane each
+    for (int k = lane; k < o.n; k += 64) { double2* w = lu + a.load_dst[o.pos[k]]; const double2 v = *w, d = o.val[k]; *w = make_double2(v.x + d.x, v.y + d.y); }
+    M::sync();
+  }
   // ---- 2. factor; the pivots of list l are final before level l runs (list 0: after the load)
   auto pivots = [&](int l) {
     const int k1 = a.piv_lev_ptr[l + 1];
@@ -153,9 +184,9 @@ __device__ __forceinline__ void ac_solve(const AcArgs& a, const double2* lu, dou
 }
 
 // r = b - A x, one row per lane; with DEN the backward error of the wave's rows is returned
-template <class M, bool DEN>
+template <class M, bool DEN, class O = AcNoOvl>
 __device__ __forceinline__ double ac_residual(const AcArgs& a, const double* G, const double* C, double om, const double2* bac, const double2* x,
-                                              double2* r, int lane) {
+                                              double2* r, int lane, const O& o = O()) {
   const double gmin = a.gmin;
   double worst = 0.0;
   for (int i = lane; i < a.n; i += 64) {
@@ -164,7 +195,7 @@ __device__ __forceinline__ double ac_residual(const AcArgs& a, const double* G, 
     double den = DEN ? cabs2(bi) : 0.0;
     const int p1 = a.rowptr[i + 1];
     for (int p = a.rowptr[i]; p < p1; ++p) {
-      const double2 av = ac_entry(a, G, C, om, p), xv = x[a.colidx[p]];
+      const double2 av = ac_entry(a, G, C, om, p, o), xv = x[a.colidx[p]];
       acc = cmsub(acc, av, xv);
       if (DEN) den = fma(cabs2(av), cabs2(xv), den);
     }
@@ -197,8 +228,9 @@ __device__ __forceinline__ void ac_store_status(const AcArgs& a, int ls, double 
 // Steps 3 to 5 of ONE column: A x = bac through the factors in lu, the refinement step and the backward error of the wave's rows (returned).
 // x is left in wk.x, visible to every lane.  Shared by k_ac_lu, k_ac_lu_multi and k_ac_sens: the same statements on the same doubles in the
 // same x / r / y.  Every word of x, r and y is written before it is read, so a column leaves nothing to the next one
-template <class M>
-__device__ __forceinline__ double ac_lu_column(const AcArgs& a, const AcWork& wk, const double* G, const double* C, double om, const double2* bac, int lane) {
+template <class M, class O = AcNoOvl>
+__device__ __forceinline__ double ac_lu_column(const AcArgs& a, const AcWork& wk, const double* G, const double* C, double om, const double2* bac, int lane,
+                                               const O& o = O()) {
   const int n = a.n;
   double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
   for (int i = lane; i < n; i += 64) y[i] = bac[a.rperm[i]];
@@ -206,20 +238,20 @@ __device__ __forceinline__ double ac_lu_column(const AcArgs& a, const AcWork& wk
   ac_solve<M>(a, lu, y, lane);
   for (int i = lane; i < n; i += 64) x[a.cperm[i]] = y[i];
   M::sync();
-  (void)ac_residual<M, false>(a, G, C, om, bac, x, r, lane);
+  (void)ac_residual<M, false>(a, G, C, om, bac, x, r, lane, o);
   for (int i = lane; i < n; i += 64) y[i] = r[a.rperm[i]];
   M::sync();
   ac_solve<M>(a, lu, y, lane);
   for (int i = lane; i < n; i += 64) { const int j = a.cperm[i]; const double2 xv = x[j], dv = y[i]; x[j] = make_double2(xv.x + dv.x, xv.y + dv.y); }
   M::sync();
   // ---- 5. backward error
-  return ac_residual<M, true>(a, G, C, om, bac, x, r, lane);
+  return ac_residual<M, true>(a, G, C, om, bac, x, r, lane, o);
 }
 
 // Steps 1 to 6 for system ls of the launch, by one wave, in the work arrays wk.  Everything a system leaves behind is in wk, and every word of
 // wk is written before it is read: lu by step 1, y / x / r by the full-length loops of ac_lu_column -- a wave may run system after system in one wk
-template <class M>
-__device__ __forceinline__ void ac_lu_system(const AcArgs& a, int ls, const AcWork& wk, int lane) {
+template <class M, class O = AcNoOvl>
+__device__ __forceinline__ void ac_lu_system(const AcArgs& a, int ls, const AcWork& wk, int lane, const O& ovl = O()) {
   const int n = a.n;
   const long s = a.s0 + ls;
   const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
@@ -228,8 +260,9 @@ __device__ __forceinline__ void ac_lu_system(const AcArgs& a, int ls, const AcWo
   const double* C = a.C + (size_t)inst * a.nnz;
   const double2* bac = (const double2*)a.bac + (size_t)inst * n;
   const double om = a.omega[fi];
-  int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
-  const double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane);
+  const O o = ovl.at(inst, fi, a.n_freq);
+  int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane, o);
+  const double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane, o);
   // ---- 6. store
   double2* xo = (double2*)a.x + (size_t)ls * n;
   for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; xo[i] = v; }
@@ -306,9 +339,9 @@ __device__ __forceinline__ void ac_adj_solve(const AcAdjArgs& t, const double2* 
 }
 
 // r = c - A^T x, one column of A per lane; with DEN the backward error of the wave's columns is returned
-template <class M, bool DEN>
+template <class M, bool DEN, class O = AcNoOvl>
 __device__ __forceinline__ double ac_adj_residual(const AcAdjArgs& t, const double* G, const double* C, double om, const double2* c, const double2* x,
-                                                  double2* r, int lane) {
+                                                  double2* r, int lane, const O& o = O()) {
   const AcArgs& a = t.a;
   const double gmin = a.gmin;
   double worst = 0.0;
@@ -318,7 +351,7 @@ __device__ __forceinline__ double ac_adj_residual(const AcAdjArgs& t, const doub
     double den = DEN ? cabs2(cj) : 0.0;
     const int p1 = t.a_colptr[j + 1];
     for (int p = t.a_colptr[j]; p < p1; ++p) {
-      const double2 av = ac_entry(a, G, C, om, t.a_pos[p]), xv = x[t.a_row[p]];
+      const double2 av = ac_entry(a, G, C, om, t.a_pos[p], o), xv = x[t.a_row[p]];
       acc = cmsub(acc, av, xv);
       if (DEN) den = fma(cabs2(av), cabs2(xv), den);
     }
@@ -343,8 +376,9 @@ __device__ __forceinline__ double ac_adj_residual(const AcAdjArgs& t, const doub
 // the flag, x when asked for.  `bad`: what ac_load_factor returned for the system.  Shared by k_ac_adj (one column per system, lk = ls),
 // k_ac_adj_multi and -- the solve -- k_ac_sens: the same statements on the same doubles in the same x / r / y.  Every word of x, r and y is
 // written before it is read, so a column leaves nothing to the next one
-template <class M>
-__device__ __forceinline__ double ac_adj_solve_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c, int lane) {
+template <class M, class O = AcNoOvl>
+__device__ __forceinline__ double ac_adj_solve_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c, int lane,
+                                                      const O& o = O()) {
   const AcArgs& a = t.a;
   const int n = a.n;
   double2 *lu = wk.lu, *x = wk.x, *r = wk.r, *y = wk.y;
@@ -353,23 +387,23 @@ __device__ __forceinline__ double ac_adj_solve_column(const AcAdjArgs& t, const 
   ac_adj_solve<M>(t, lu, y, lane);
   for (int i = lane; i < n; i += 64) x[a.rperm[i]] = y[i];
   M::sync();
-  (void)ac_adj_residual<M, false>(t, G, C, om, c, x, r, lane);
+  (void)ac_adj_residual<M, false>(t, G, C, om, c, x, r, lane, o);
   for (int j = lane; j < n; j += 64) y[j] = r[a.cperm[j]];
   M::sync();
   ac_adj_solve<M>(t, lu, y, lane);
   for (int i = lane; i < n; i += 64) { const int k = a.rperm[i]; const double2 xv = x[k], dv = y[i]; x[k] = make_double2(xv.x + dv.x, xv.y + dv.y); }
   M::sync();
   // ---- 5. backward error
-  return ac_adj_residual<M, true>(t, G, C, om, c, x, r, lane);
+  return ac_adj_residual<M, true>(t, G, C, om, c, x, r, lane, o);
 }
 
-template <class M>
+template <class M, class O = AcNoOvl>
 __device__ __forceinline__ void ac_adj_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c,
-                                              size_t lk, int bad, int lane) {
+                                              size_t lk, int bad, int lane, const O& o = O()) {
   const AcArgs& a = t.a;
   const int n = a.n;
   const double2* x = wk.x;
-  const double worst = ac_adj_solve_column<M>(t, wk, G, C, om, c, lane);
+  const double worst = ac_adj_solve_column<M>(t, wk, G, C, om, c, lane, o);
   // ---- 6. store
   double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
   for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
@@ -383,8 +417,8 @@ __device__ __forceinline__ void ac_adj_column(const AcAdjArgs& t, const AcWork& 
 }
 
 // Steps 1 to 6 of the adjoint system ls of the launch; what ac_lu_system says about wk holds here word for word
-template <class M>
-__device__ __forceinline__ void ac_adj_system(const AcAdjArgs& t, int ls, const AcWork& wk, int lane) {
+template <class M, class O = AcNoOvl>
+__device__ __forceinline__ void ac_adj_system(const AcAdjArgs& t, int ls, const AcWork& wk, int lane, const O& ovl = O()) {
   const AcArgs& a = t.a;
   const long s = a.s0 + ls;
   const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
@@ -392,8 +426,9 @@ __device__ __forceinline__ void ac_adj_system(const AcAdjArgs& t, int ls, const 
   const double* C = a.C + (size_t)inst * a.nnz;
   const double2* c = (const double2*)a.bac + (size_t)inst * a.n;
   const double om = a.omega[fi];
-  const int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
-  ac_adj_column<M>(t, wk, G, C, om, c, (size_t)ls, bad, lane);
+  const O o = ovl.at(inst, fi, a.n_freq);
+  const int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane, o);
+  ac_adj_column<M>(t, wk, G, C, om, c, (size_t)ls, bad, lane, o);
 }
 
 template <int W>
@@ -431,8 +466,8 @@ struct AcMultiArgs {
   int n_rhs, n_pairs;
 };
 
-template <class M>
-__device__ __forceinline__ void ac_multi_system(const AcMultiArgs& t, int ls, const AcWork& wk, int lane) {
+template <class M, class O = AcNoOvl>
+__device__ __forceinline__ void ac_multi_system(const AcMultiArgs& t, int ls, const AcWork& wk, int lane, const O& ovl = O()) {
   const AcArgs& a = t.a;
   const int n = a.n;
   const long s = a.s0 + ls;
@@ -441,12 +476,13 @@ __device__ __forceinline__ void ac_multi_system(const AcMultiArgs& t, int ls, co
   const double* G = a.G + (size_t)inst * a.nnz;
   const double* C = a.C + (size_t)inst * a.nnz;
   const double om = a.omega[fi];
-  const int bad_pivot = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
+  const O o = ovl.at(inst, fi, a.n_freq);
+  const int bad_pivot = ac_load_factor<M>(a, wk.lu, G, C, om, lane, o);
   for (int k = 0; k < t.n_rhs; ++k) {
     const double2* bac = (const double2*)t.rhs + (size_t)inst * t.rhs_stride + (size_t)k * n;
     const size_t lk = (size_t)ls * t.n_rhs + k;               // (system, column) of the launch: within int (api.hip bounds a launch's output)
     int bad = bad_pivot;
-    const double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane);
+    const double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane, o);
     // ---- 6. store
     double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
     for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
@@ -490,19 +526,20 @@ struct AcAdjMultiArgs {
   int n_rhs;
 };
 
-template <class M>
-__device__ __forceinline__ void ac_adj_multi_system(const AcAdjMultiArgs& u, int ls, const AcWork& wk, int lane) {
+template <class M, class O = AcNoOvl>
+__device__ __forceinline__ void ac_adj_multi_system(const AcAdjMultiArgs& u, int ls, const AcWork& wk, int lane, const O& ovl = O()) {
   const AcArgs& a = u.t.a;
   const long s = a.s0 + ls;
   const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
   const double* G = a.G + (size_t)inst * a.nnz;
   const double* C = a.C + (size_t)inst * a.nnz;
   const double om = a.omega[fi];
-  const int bad_pivot = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
+  const O o = ovl.at(inst, fi, a.n_freq);
+  const int bad_pivot = ac_load_factor<M>(a, wk.lu, G, C, om, lane, o);
   for (int k = 0; k < u.n_rhs; ++k) {
     const double2* c = (const double2*)u.rhs + (size_t)inst * u.rhs_stride + (size_t)k * a.n;
     const size_t lk = (size_t)ls * u.n_rhs + k;               // (system, column) of the launch: within int (api.hip bounds a launch's output)
-    ac_adj_column<M>(u.t, wk, G, C, om, c, lk, bad_pivot, lane);
+    ac_adj_column<M>(u.t, wk, G, C, om, c, lk, bad_pivot, lane, o);
     M::sync();                                                 // the last reads of this column's x before the next column's (next system's) words
   }
 }
@@ -522,6 +559,83 @@ __global__ void __launch_bounds__(64 * W) k_ac_adj_multi_hbm(AcAdjMultiArgs u, A
   const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.t.a.n_sys : 0;
   const AcWork wk = ac_work(lds_ac(m.work, u.t.a.nnz_lu, u.t.a.n, g, m.n_waves));
   for (int ls = g; ls < end; ls += m.n_waves) ac_adj_multi_system<AcInHbm>(u, ls, wk, lane);   // a system's last column ends in the fence the next one needs
+}
+
+// ---- the overlay forms of the four kernels above (cadnip_ac_set_overlay): the same __device__ functions with the policy AcOvl in place of
+// AcNoOvl, launched in their parents' place while an overlay is set.  Same launch plans, same LDS layout, same lane order, no workgroup
+// barrier, no atomics; the table is read from global memory.  k_ac_sens and k_ac_arnoldi have no overlay form: their entry points refuse.
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu_ovl(AcArgs a, AcOvlArgs v) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= a.n_sys) return;
+  ac_lu_system<AcInLds>(a, ls, ac_work(lds_ac((double*)sm, a.nnz_lu, a.n, w, W)), lane, ac_ovl(v));
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu_ovl_hbm(AcArgs a, AcHbmArgs m, AcOvlArgs v) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? a.n_sys : 0;
+  const AcWork wk = ac_work(lds_ac(m.work, a.nnz_lu, a.n, g, m.n_waves));
+  for (int ls = g; ls < end; ls += m.n_waves) {
+    ac_lu_system<AcInHbm>(a, ls, wk, lane, ac_ovl(v));
+    AcInHbm::sync();
+  }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj_ovl(AcAdjArgs t, AcOvlArgs v) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= t.a.n_sys) return;
+  ac_adj_system<AcInLds>(t, ls, ac_work(lds_ac((double*)sm, t.a.nnz_lu, t.a.n, w, W)), lane, ac_ovl(v));
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj_ovl_hbm(AcAdjArgs t, AcHbmArgs m, AcOvlArgs v) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
+  const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
+  for (int ls = g; ls < end; ls += m.n_waves) {
+    ac_adj_system<AcInHbm>(t, ls, wk, lane, ac_ovl(v));
+    AcInHbm::sync();
+  }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu_multi_ovl(AcMultiArgs t, AcOvlArgs v) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= t.a.n_sys) return;
+  ac_multi_system<AcInLds>(t, ls, ac_work(lds_ac((double*)sm, t.a.nnz_lu, t.a.n, w, W)), lane, ac_ovl(v));
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_lu_multi_ovl_hbm(AcMultiArgs t, AcHbmArgs m, AcOvlArgs v) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
+  const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
+  for (int ls = g; ls < end; ls += m.n_waves) ac_multi_system<AcInHbm>(t, ls, wk, lane, ac_ovl(v));
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj_multi_ovl(AcAdjMultiArgs u, AcOvlArgs v) {
+  extern __shared__ double sm[];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ls = blockIdx.x * W + w;
+  if (ls >= u.t.a.n_sys) return;
+  ac_adj_multi_system<AcInLds>(u, ls, ac_work(lds_ac((double*)sm, u.t.a.nnz_lu, u.t.a.n, w, W)), lane, ac_ovl(v));
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W) k_ac_adj_multi_ovl_hbm(AcAdjMultiArgs u, AcHbmArgs m, AcOvlArgs v) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.t.a.n_sys : 0;
+  const AcWork wk = ac_work(lds_ac(m.work, u.t.a.nnz_lu, u.t.a.n, g, m.n_waves));
+  for (int ls = g; ls < end; ls += m.n_waves) ac_adj_multi_system<AcInHbm>(u, ls, wk, lane, ac_ovl(v));
 }
 
 // ---- the sensitivity kernel: the response y = x[p] - x[n] of A x = b_ac and its derivatives with respect to K parameters from ONE factorisation
@@ -912,9 +1026,13 @@ static AcArgs ac_args(CadnipHandle* h, int n_freq, long s0, int n_sys, double gm
   return a;
 }
 
+// the handle's overlay (cadnip_ac_set_overlay) as the overlay kernels take it; n == 0: none is set, the plain kernels run
+static AcOvlArgs ac_ovl_args(const CadnipHandle* h) { return AcOvlArgs{h->ac.d_ovl_pos, h->ac.d_ovl_map, h->ac.d_ovl_val, h->ac.ovl_n}; }
+
 int launch_ac_lu(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin) {
   if (L.memory < 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
   const AcArgs a = ac_args(h, n_freq, s0, n_sys, gmin);
+  const AcOvlArgs v = ac_ovl_args(h); const bool ovl = v.n > 0;
   if (L.memory == CADNIP_AC_HBM) {
     const AcHbmPlan& p = L.hbm;
     if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
@@ -922,14 +1040,16 @@ int launch_ac_lu(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_
     ProfScope ps(h, "ac_lu_hbm");
     const AcHbmArgs m{h->ac.d_work, p.n_waves};
     const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, a, m); return CADNIP_OK; }));
+    if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_ovl_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, a, m, v); return CADNIP_OK; }));
+    else TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, a, m); return CADNIP_OK; }));
     HIP_TRY(hipGetLastError());
     return CADNIP_OK;
   }
   const AcPlan& p = L.lds;
   ProfScope ps(h, "ac_lu");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, a); }));
+  if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_ovl<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, a, v); }));
+  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, a); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }
@@ -952,6 +1072,7 @@ int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, i
   AcAdjArgs t = ac_adj_args(h, n_freq, s0, n_sys, gmin);
   t.a.x = want_x ? A.d_adj_x : nullptr; t.a.berr = A.d_adj_berr; t.a.flags = A.d_adj_flags;
   t.pairs = A.d_pairs; t.h = A.d_h; t.n_pairs = n_pairs;
+  const AcOvlArgs v = ac_ovl_args(h); const bool ovl = v.n > 0;
   if (L.memory == CADNIP_AC_HBM) {
     const AcHbmPlan& p = L.hbm;
     if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
@@ -959,14 +1080,16 @@ int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, i
     ProfScope ps(h, "ac_adj_hbm");
     const AcHbmArgs m{A.d_work, p.n_waves};
     const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m); return CADNIP_OK; }));
+    if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_ovl_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m, v); return CADNIP_OK; }));
+    else TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m); return CADNIP_OK; }));
     HIP_TRY(hipGetLastError());
     return CADNIP_OK;
   }
   const AcPlan& p = L.lds;
   ProfScope ps(h, "ac_adj");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
+  if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_ovl<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t, v); }));
+  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }
@@ -979,6 +1102,7 @@ int launch_ac_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int
   t.a.bac = nullptr; t.a.x = want_x ? A.d_multi_x : nullptr; t.a.berr = A.d_multi_berr; t.a.flags = A.d_multi_flags;
   t.rhs = A.d_multi_rhs; t.rhs_stride = (long)n_rhs * h->n;
   t.pairs = A.d_multi_pairs; t.h = A.d_multi_h; t.n_rhs = n_rhs; t.n_pairs = n_pairs;
+  const AcOvlArgs v = ac_ovl_args(h); const bool ovl = v.n > 0;
   if (L.memory == CADNIP_AC_HBM) {
     const AcHbmPlan& p = L.hbm;
     if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
@@ -986,14 +1110,16 @@ int launch_ac_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int
     ProfScope ps(h, "ac_lu_multi_hbm");
     const AcHbmArgs m{A.d_work, p.n_waves};
     const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_multi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m); return CADNIP_OK; }));
+    if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_multi_ovl_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m, v); return CADNIP_OK; }));
+    else TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_multi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m); return CADNIP_OK; }));
     HIP_TRY(hipGetLastError());
     return CADNIP_OK;
   }
   const AcPlan& p = L.lds;
   ProfScope ps(h, "ac_lu_multi");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
+  if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_multi_ovl<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t, v); }));
+  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }
@@ -1006,6 +1132,7 @@ int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long
   u.t.a.bac = nullptr; u.t.a.x = want_x ? A.d_multi_x : nullptr; u.t.a.berr = A.d_multi_berr; u.t.a.flags = A.d_multi_flags;
   u.t.pairs = A.d_multi_pairs; u.t.h = A.d_multi_h; u.t.n_pairs = n_pairs;
   u.rhs = A.d_multi_rhs; u.rhs_stride = (long)n_rhs * h->n; u.n_rhs = n_rhs;
+  const AcOvlArgs v = ac_ovl_args(h); const bool ovl = v.n > 0;
   if (L.memory == CADNIP_AC_HBM) {
     const AcHbmPlan& p = L.hbm;
     if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
@@ -1013,14 +1140,16 @@ int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long
     ProfScope ps(h, "ac_adj_multi_hbm");
     const AcHbmArgs m{A.d_work, p.n_waves};
     const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_multi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, m); return CADNIP_OK; }));
+    if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_multi_ovl_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, m, v); return CADNIP_OK; }));
+    else TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_multi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, m); return CADNIP_OK; }));
     HIP_TRY(hipGetLastError());
     return CADNIP_OK;
   }
   const AcPlan& p = L.lds;
   ProfScope ps(h, "ac_adj_multi");
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
+  if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_multi_ovl<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u, v); }));
+  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }

@@ -215,7 +215,8 @@ void cadnip_destroy(CadnipHandle* h) {
                   h->d_resid, h->d_delta, h->d_limit_w, h->d_LU, h->d_tmp, h->d_flags, h->d_active, h->d_nonfinite, h->d_gshunt, h->d_srcfact, h->d_cold, h->d_load_src, h->d_load_dst, h->d_ent_pos,
                   h->d_ent_diag, h->d_ent_ptr, h->d_term_a, h->d_term_b, h->d_lev_ptr, h->d_lu_rowptr, h->d_lu_col, h->d_lu_diag, h->d_rperm,
                   h->d_cperm, h->d_fwd_rows, h->d_fwd_lev_ptr, h->d_bwd_rows, h->d_bwd_lev_ptr,
-                  h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_bac, h->ac.d_omega, h->ac.d_x, h->ac.d_berr, h->ac.d_flags, h->ac.d_work};
+                  h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_bac, h->ac.d_omega, h->ac.d_x, h->ac.d_berr, h->ac.d_flags, h->ac.d_work,
+                  h->ac.d_ovl_pos, h->ac.d_ovl_map, h->ac.d_ovl_val};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   h->ac.each_adjoint_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
   h->ac.each_multi_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
@@ -779,6 +780,47 @@ int cadnip_ac_set_memory(CadnipHandle* h, int32_t mode, int32_t max_waves) {
   return CADNIP_OK;
 }
 
+// The overlay: a sparse complex addend per system on the A of the four sweeps below (ac_lu.hip: AcOvl).  Everything is checked before anything
+// is touched, and the new buffers are complete before the old ones go: a refused or failed call leaves the previous setting in force.
+#define AC_OVERLAY_MAX_BYTES ((size_t)256 << 20)
+int cadnip_ac_set_overlay(CadnipHandle* h, int32_t n_ovl, const int32_t* pos, int32_t n_freq, const double* omega, const double* val) {
+  if (!h || n_ovl < 0) return CADNIP_BADARG;
+  AcState& A = h->ac;
+  auto clear = [&] {
+    for (void** p : {(void**)&A.d_ovl_pos, (void**)&A.d_ovl_map, (void**)&A.d_ovl_val}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    A.ovl_n = 0; A.ovl_omega.clear();
+  };
+  if (n_ovl == 0) { HIP_TRY(hipStreamSynchronize(h->stream)); clear(); return CADNIP_OK; }
+  if (!pos || n_freq <= 0 || !omega || !val || n_ovl > h->nnz) return CADNIP_BADARG;
+  std::vector<int> map((size_t)h->nnz, -1);
+  for (int o = 0; o < n_ovl; ++o) {
+    if (pos[o] < 0 || pos[o] >= h->nnz || map[pos[o]] >= 0) return CADNIP_BADARG;
+    map[pos[o]] = o;
+  }
+  const size_t cap = AC_OVERLAY_MAX_BYTES / 16;                  // complex words; the quotients keep the product inside size_t
+  if ((size_t)n_ovl > cap || (size_t)n_freq > cap / (size_t)n_ovl || (size_t)h->B > cap / (size_t)n_ovl / (size_t)n_freq) return CADNIP_BADARG;
+  const size_t words = (size_t)h->B * (size_t)n_freq * (size_t)n_ovl * 2;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  int *d_pos = nullptr, *d_map = nullptr; double* d_val = nullptr;
+  int rc = dev_alloc(&d_pos, (size_t)n_ovl);
+  if (!rc) rc = dev_alloc(&d_map, (size_t)h->nnz);
+  if (!rc) rc = dev_alloc(&d_val, words);
+  if (!rc && hipMemcpy(d_pos, pos, (size_t)n_ovl * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = CADNIP_HIPERROR;
+  if (!rc && hipMemcpy(d_map, map.data(), (size_t)h->nnz * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = CADNIP_HIPERROR;
+  if (!rc && hipMemcpy(d_val, val, words * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = CADNIP_HIPERROR;
+  if (rc) { for (void* p : {(void*)d_pos, (void*)d_map, (void*)d_val}) if (p) (void)hipFree(p); return rc; }
+  clear();
+  A.d_ovl_pos = d_pos; A.d_ovl_map = d_map; A.d_ovl_val = d_val; A.ovl_n = n_ovl;
+  A.ovl_omega.assign(omega, omega + n_freq);
+  return CADNIP_OK;
+}
+
+// a sweep under an overlay must name the overlay's own grid, bit for bit (memcmp: -0.0 is not 0.0, a NaN equals itself)
+static bool ac_overlay_grid_ok(const CadnipHandle* h, int32_t n_freq, const double* omega) {
+  const AcState& A = h->ac;
+  return A.ovl_n == 0 || ((size_t)n_freq == A.ovl_omega.size() && memcmp(omega, A.ovl_omega.data(), (size_t)n_freq * sizeof(double)) == 0);
+}
+
 int cadnip_ac_plan_info(CadnipHandle* h, int64_t out[4]) {
   if (!h || !out) return CADNIP_BADARG;
   for (int i = 0; i < 4; ++i) out[i] = h->ac.last[i];
@@ -793,6 +835,7 @@ int cadnip_ac_plan_info(CadnipHandle* h, int64_t out[4]) {
 int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, const double* bac_host, int32_t wpb, double* x_host,
                     double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || !bac_host || !x_host || !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
+  if (!ac_overlay_grid_ok(h, n_freq, omega)) return CADNIP_BADARG;
   const size_t B = h->B, n = h->n, F = n_freq, S = B * F;
   const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * n)));
   const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb);             // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
@@ -830,6 +873,7 @@ int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega, double
 int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, const double* c_host, int32_t n_pairs, const int32_t* pairs,
                       int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || !c_host || n_pairs < 1 || !pairs || !h_host || !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
+  if (!ac_overlay_grid_ok(h, n_freq, omega)) return CADNIP_BADARG;
   const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_pairs;
   for (size_t k = 0; k < 2 * K; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
   const bool want_x = x_host != nullptr;
@@ -878,6 +922,7 @@ static int ac_multi_call(CadnipHandle* h, bool adjoint, int32_t n_freq, const do
                          const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || n_rhs < 1 || !b_host || n_pairs < 0 || (n_pairs > 0 && (!pairs || !h_host)) || (n_pairs == 0 && !x_host) ||
       !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
+  if (!ac_overlay_grid_ok(h, n_freq, omega)) return CADNIP_BADARG;
   const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_rhs, P = n_pairs;
   for (size_t k = 0; k < 2 * P; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
   const bool want_x = x_host != nullptr;
@@ -942,6 +987,7 @@ int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega, double 
                    int32_t wpb, double* y_host, double* s_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || n_base < 1 || !base || n_par < 1 || !plus || !minus || !scale || !bac_host || !c_host || !pair || !y_host || !s_host ||
       !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
+  if (h->ac.ovl_n > 0) return CADNIP_BADARG;                    // the bilinear forms over perturbed stamps do not know the overlay
   const size_t B = h->B, n = h->n, F = n_freq, NB = n_base, K = n_par, S = NB * F;
   for (size_t b = 0; b < NB; ++b) if (base[b] < 0 || base[b] >= (int32_t)B) return CADNIP_BADARG;
   for (size_t k = 0; k < NB * K; ++k) if (plus[k] < 0 || plus[k] >= (int32_t)B || minus[k] < 0 || minus[k] >= (int32_t)B) return CADNIP_BADARG;
@@ -1011,6 +1057,7 @@ int cadnip_ac_arnoldi(CadnipHandle* h, int32_t n_shift, const double* omega, dou
                       double* v_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_shift <= 0 || !omega || !b_host || m < 1 || !(breakdown_tol > 0.0 && breakdown_tol < 1.0) || n_pairs < 0 || (n_pairs > 0 && (!pairs || !l_host)) ||
       !H_host || !beta_host || !meff_host || !berr_host || !flags_host || !info || !h->analyzed || m > h->n) return CADNIP_BADARG;
+  if (h->ac.ovl_n > 0) return CADNIP_BADARG;                    // A with an overlay is not a (G, C) pencil
   const size_t B = h->B, n = h->n, F = n_shift, S = B * F, P = n_pairs, M = m;
   for (size_t k = 0; k < 2 * P; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
   const size_t hw = (M + 1) * M, lw = M * P, vw = (M + 1) * n;           // complex words of a system's H, l, V

@@ -182,6 +182,12 @@ struct AcState {
   double* d_work = nullptr; size_t cap_work = 0;   // cap_work: bytes
   int n_cu = 0;                                    // compute units of the device (queried by the first HBM plan)
   int64_t last[4] = {CADNIP_AC_LDS, 0, 0, 0};      // memory, n_waves, work_bytes, lds_bytes
+  // the overlay (cadnip_ac_set_overlay; ac_lu.hip: AcOvl): positions, their inverse map over the CSR pattern, the values [B][F][ovl_n] complex
+  // and the grid the table was made for -- a solve under it must name the same grid, bit for bit.  ovl_n == 0: none is set
+  int ovl_n = 0;
+  std::vector<double> ovl_omega;
+  int *d_ovl_pos = nullptr, *d_ovl_map = nullptr;
+  double* d_ovl_val = nullptr;
   template <class F> void each_adjoint_buffer(F f) {
     f((void**)&d_t_colptr); f((void**)&d_t_pos); f((void**)&d_t_row); f((void**)&d_t_diag); f((void**)&d_ut_rows); f((void**)&d_ut_lev_ptr);
     f((void**)&d_lt_rows); f((void**)&d_lt_lev_ptr); f((void**)&d_a_colptr); f((void**)&d_a_row); f((void**)&d_a_pos); f((void**)&d_pairs);

@@ -122,10 +122,10 @@ template <class L> LDS_HD size_t lds_bytes(const L& l) { return (size_t)l.end * 
 
 #ifdef __HIPCC__
 // launch `kernel` with `shmem` bytes of dynamic LDS, opting in to more than LDS_OPTIN first
-template <class K, class A>
-static int lds_launch(K kernel, int grid, int threads, size_t shmem, hipStream_t stream, const A& args) {
+template <class K, class... A>
+static int lds_launch(K kernel, int grid, int threads, size_t shmem, hipStream_t stream, const A&... args) {
   if (shmem > LDS_OPTIN) HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), shmem, stream, args);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), shmem, stream, args...);
   return CADNIP_OK;
 }
 // the kernels are instantiated for 1, 2, 4, 8 waves per workgroup: fn(std::integral_constant<int, W>) for the one that matches

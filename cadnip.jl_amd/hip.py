@@ -29,7 +29,7 @@ AC_MEMORY = {"lds": 0, "hbm": 1, "auto": 2}     # CADNIP_AC_LDS / _HBM / _AUTO (
 EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
-    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_sens", "cadnip_ac_arnoldi", "cadnip_ac_set_memory", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
+    "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_sens", "cadnip_ac_arnoldi", "cadnip_ac_set_memory", "cadnip_ac_set_overlay", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
     "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
@@ -529,6 +529,30 @@ class Handle:
         unknown mode or a negative ``max_waves`` raises CadnipError(CADNIP_BADARG) and leaves the setting as it was."""
         code = AC_MEMORY.get(mode, -1) if isinstance(mode, str) else int(mode)
         _check(self.lib.cadnip_ac_set_memory(self.h, C.c_int32(code), C.c_int32(int(max_waves))), "cadnip_ac_set_memory")
+
+    def ac_set_overlay(self, pos, omegas, val):
+        """cadnip_ac_set_overlay: from now on ``ac_solve``, ``ac_adjoint``, ``ac_solve_multi`` and ``ac_adjoint_multi`` solve
+        A[b, f] = G[b] + gmin + j omega[f] C[b] + D[b, f], with D non-zero at the CSR positions ``pos`` [O] (distinct, in the order of the
+        structure's rowptr / colidx) and ``val`` [B, F, O] complex (or [F, O], broadcast) its values on the grid ``omegas`` [F] -- how a delayed
+        stamp's e^{-j w tau} enters (api.ac_delay_overlay computes such a table).  The overlay kernels (csrc/ac_lu.hip: k_ac_lu_ovl and its
+        kin) add it in the load, the residuals and the backward error; results stay bit-identical across ``wpb``, memory homes and between the
+        multi calls' columns and the single-column calls.  While it is set those four calls must be made on exactly ``omegas``, and
+        ``ac_sens`` / ``ac_arnoldi`` raise CadnipError(CADNIP_BADARG).  A non-finite value flags its own system (bit 0).  An empty ``pos``
+        clears the setting, as ``ac_clear_overlay``.  A ``val`` of the wrong shape raises ValueError; a position outside [0, nnz) or named
+        twice, an empty grid or a table beyond 256 MiB raise CadnipError(CADNIP_BADARG) and leave the previous setting in force."""
+        ps = np.ascontiguousarray(np.asarray(pos, dtype=np.int32).ravel())
+        om = np.ascontiguousarray(np.asarray(omegas, dtype=np.float64).ravel())
+        if ps.size == 0:
+            return self.ac_clear_overlay()
+        vv = np.asarray(val, dtype=np.complex128)
+        if vv.shape not in ((om.size, ps.size), (self.B, om.size, ps.size)):
+            raise ValueError("val must be [F, O] or [B, F, O] for F frequencies and O positions")
+        vv = np.ascontiguousarray(np.broadcast_to(vv, (self.B, om.size, ps.size)))
+        _check(self.lib.cadnip_ac_set_overlay(self.h, C.c_int32(ps.size), _ip(ps), C.c_int32(om.size), _dp(om), vv.ctypes.data_as(_D)), "cadnip_ac_set_overlay")
+
+    def ac_clear_overlay(self):
+        """cadnip_ac_set_overlay with n_ovl = 0: no overlay; every AC call is again exactly what it is on a new handle."""
+        _check(self.lib.cadnip_ac_set_overlay(self.h, C.c_int32(0), None, C.c_int32(0), None, None), "cadnip_ac_set_overlay")
 
     def ac_plan_info(self):
         """cadnip_ac_plan_info: {memory ("lds" / "hbm"), n_waves, work_bytes, lds_bytes} of the last ``ac_solve`` / ``ac_adjoint`` call that launched."""

@@ -354,7 +354,17 @@ def read_spice(text, models=None, includes=None, sweep=(), title=""):
         elif kind in "rcl":
             others.append((kind.upper(), name, (sc.node(toks[1]), sc.node(toks[2])), {"value": sc.val(toks[3])}))
         elif kind in "eg":
-            others.append((kind.upper(), name, tuple(sc.node(t) for t in toks[1:5]), {"value": sc.val(toks[5])}))
+            # Ename out+ out- in+ in- gain [TD=delay]: TD is the transport delay of the controlled quantity (Circuit.E / G: delay=)
+            pos, kv = _split_params(toks[1:])
+            if len(pos) != 5 or set(kv) - {"td"}:
+                raise ValueError("controlled source needs four nets, a value and at most TD=: %r" % line)
+            others.append((kind.upper(), name, tuple(sc.node(t) for t in pos[:4]), {"value": sc.val(pos[4]), "delay": sc.val(kv["td"]) if "td" in kv else 0.0}))
+        elif kind == "t":
+            # Tname n1+ n1- n2+ n2- Z0=... TD=...: the ideal lossless line (Circuit.T)
+            pos, kv = _split_params(toks[1:])
+            if len(pos) != 4 or set(kv) != {"z0", "td"}:
+                raise ValueError("transmission line needs four nets, Z0= and TD=: %r" % line)
+            others.append(("T", name, tuple(sc.node(t) for t in pos), {"z0": sc.val(kv["z0"]), "td": sc.val(kv["td"])}))
         elif kind == "d":
             card = models.get(toks[3].lower())
             if card is None:
@@ -436,9 +446,11 @@ def read_spice(text, models=None, includes=None, sweep=(), title=""):
         elif ty == "L":
             c.L(name, nodes[0], nodes[1], a["value"])
         elif ty == "E":
-            c.E(name, nodes[0], nodes[1], nodes[2], nodes[3], a["value"])
+            c.E(name, nodes[0], nodes[1], nodes[2], nodes[3], a["value"], delay=a["delay"])
         elif ty == "G":
-            c.G(name, nodes[0], nodes[1], nodes[2], nodes[3], a["value"])
+            c.G(name, nodes[0], nodes[1], nodes[2], nodes[3], a["value"], delay=a["delay"])
+        elif ty == "T":
+            c.T(name, nodes[0], nodes[1], nodes[2], nodes[3], a["z0"], a["td"])
         elif ty == "D":
             c.D(name, nodes[0], nodes[1], Is=a["card"].get("is", 1e-14), n_=a["card"].get("n", 1.0))
         elif ty == "MOS1":

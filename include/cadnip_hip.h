@@ -337,6 +337,23 @@ int cadnip_ac_arnoldi(CadnipHandle* h, int32_t n_shift, const double* omega /* [
 #define CADNIP_AC_HBM 1
 #define CADNIP_AC_AUTO 2
 int cadnip_ac_set_memory(CadnipHandle* h, int32_t mode, int32_t max_waves);
+/* A sparse complex addend per system on the A of the AC sweeps -- a handle setting, none by default: every call exactly as without it.
+ * While it is set, system (b, f) of cadnip_ac_solve, cadnip_ac_adjoint, cadnip_ac_solve_multi and cadnip_ac_adjoint_multi is
+ *   A = G[b] + gmin on the voltage-node diagonals + j omega[f] C[b] + D[b][f],
+ * D non-zero at the n_ovl CSR positions pos[] (distinct, in [0, nnz), in the order of the structure's rowptr / colidx; the same for the
+ * whole batch) with the values val[b][f][o] (interleaved re, im).  This is how an element that is neither a G nor a C enters an AC
+ * analysis: a transport delay tau on a stamp w is the addend (e^{-j omega tau} - 1) w.  The caller computes the values; the kernels
+ * (csrc/ac_lu.hip: k_ac_lu_ovl, k_ac_adj_ovl, k_ac_lu_multi_ovl, k_ac_adj_multi_ovl and their _hbm forms) add them wherever A is formed --
+ * in the load, in both residuals and in the |A| of the backward error -- so factors, refinement and berr belong to one matrix, and the
+ * results stay bit-identical for wpb 1 / 2 / 4 / 8, between LDS and device memory, and between the multi calls' columns and the
+ * single-column calls.  The setting names its grid: while it is set, the four calls require their own n_freq / omega to equal the
+ * setting's bit for bit (CADNIP_BADARG otherwise, nothing launched), so a table is never applied to other frequencies; cadnip_ac_sens and
+ * cadnip_ac_arnoldi are CADNIP_BADARG while it is set (A is then not a (G, C) pencil).  A non-finite value is not an argument error: it
+ * surfaces as flag bit 0 of its own system.  The values are copied to the device: the arrays may be released after the call.
+ * n_ovl = 0 clears the setting (the other arguments are not read).  CADNIP_BADARG -- the previous setting stays in force -- with
+ * n_ovl < 0, a position outside [0, nnz) or named twice, n_freq <= 0, or a table (16 B n_freq n_ovl bytes) beyond 256 MiB. */
+int cadnip_ac_set_overlay(CadnipHandle* h, int32_t n_ovl, const int32_t* pos /* [n_ovl] */, int32_t n_freq, const double* omega /* [F] */,
+                          const double* val /* [B][F][n_ovl][2] */);
 /* of the last cadnip_ac_solve / cadnip_ac_adjoint call that launched: the memory used (CADNIP_AC_LDS / CADNIP_AC_HBM), n_waves and work_bytes of
  * its largest launch (0 under LDS), LDS bytes of a workgroup (0 under HBM) */
 int cadnip_ac_plan_info(CadnipHandle* h, int64_t out[4]);

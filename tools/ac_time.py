@@ -6,10 +6,16 @@ the same run.  After one warm-up every figure is the median of --reps timed repe
                       fallback ladder; the sweep does not care): 208 KB of work arrays, beyond the LDS kernels
   --memory lds|hbm|auto   where the kernel keeps a system's work arrays (hip.Handle.ac_set_memory).  With hbm / auto on a circuit that fits
                       LDS the LDS kernel is timed as well, in the same run: the price of leaving LDS.
+  --overlay N         instead of the above: what an N-entry overlay (hip.Handle.ac_set_overlay: the delayed elements' addend) costs k_ac_lu
+                      on the flip-flop at B = 64 x the 61 frequencies.  The baseline is the kernel without overlay -- the parent's, instruction
+                      for instruction -- in the same process; the two are timed in ALTERNATING repetitions (plain, overlay, plain, ...)
+                      so drift hits both alike.  The table is all zeros at N positions spread evenly over the pattern: the kernel's
+                      work does not depend on the values, and the results must equal the plain kernel's.
 The host is timed on at most HOST_POINTS points (chain200: one point, HOST_FREQS frequencies -- a dense solve of n = 2204 takes a second) and
 scaled to the grid (its cost per system does not depend on B); the line says so.
 
 usage:  timeout -k 10 600 python tools/ac_time.py [--circuit dff] [--memory lds] [--reps 5] [B ...]        (default: 1 64 1024)
+        timeout -k 10 600 python tools/ac_time.py --overlay 8 [--memory lds] [--reps 5]
 """
 import argparse
 import os
@@ -128,12 +134,50 @@ def run(B, circuit, memory, reps, gmin=1e-12):
         sim.close()
 
 
+def run_overlay(n_ovl, memory, reps, B=64, gmin=1e-12):
+    omegas = 2.0 * np.pi * api.acdec(10, 1e3, 1e9)
+    sim, circ, pts, u, b_ac1 = linearised("dff", B)
+    try:
+        st, h = sim.st, sim.h
+        G, C, _, _ = h.get_GCb()
+        to_ref = np.asarray(st.to_ref_nz)
+        sample_ref = np.empty(st.nnz)
+        sample_ref[to_ref] = api.ac_pivot_sample(st, G[:, to_ref], C[:, to_ref], omegas, gmin)
+        h.analyze_values(sample_ref)
+        h.ac_set_memory(memory)
+        b_ac = np.tile(b_ac1, (B, 1))
+        pos = np.unique(np.linspace(0, st.nnz - 1, n_ovl).round().astype(np.int32))
+        val = np.zeros((B, omegas.size, pos.size), dtype=complex)
+        x0, berr0, _, _ = h.ac_solve(omegas, gmin, b_ac)                                       # warm-up of both kernels; the results must agree
+        name = "ac_lu_hbm" if h.ac_plan_info()["memory"] == "hbm" else "ac_lu"
+        h.ac_set_overlay(pos, omegas, val)
+        x1, berr1, _, _ = h.ac_solve(omegas, gmin, b_ac)
+        assert np.array_equal(x0, x1) and np.array_equal(berr0, berr1), "an all-zero overlay changed the results"
+        t_plain, t_ovl = [], []
+        for _ in range(reps):
+            h.ac_clear_overlay()
+            t_plain += kernel_times(h, lambda: h.ac_solve(omegas, gmin, b_ac), name, 1)
+            h.ac_set_overlay(pos, omegas, val)
+            t_ovl += kernel_times(h, lambda: h.ac_solve(omegas, gmin, b_ac), name, 1)
+        h.ac_clear_overlay()
+        S = B * omegas.size
+        print("dff B %d  systems %d  memory %s  overlay entries %d (table %.1f KiB)\n    kernel without overlay %s\n    kernel with overlay    %s\n"
+              "    overlay / plain %.3f  (+%.3f us/system)" % (B, S, h.ac_plan_info()["memory"], pos.size, val.nbytes / 1024, med(t_plain), med(t_ovl),
+                                                               np.median(t_ovl) / np.median(t_plain), (np.median(t_ovl) - np.median(t_plain)) * 1e6 / S), flush=True)
+    finally:
+        sim.close()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--circuit", choices=["dff", "chain200"], default="dff")
     ap.add_argument("--memory", choices=["lds", "hbm", "auto"], default="lds")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--overlay", type=int, default=0, metavar="N")
     ap.add_argument("B", type=int, nargs="*")
     a = ap.parse_args()
+    if a.overlay > 0:
+        run_overlay(a.overlay, a.memory, max(1, a.reps))
+        sys.exit(0)
     for B in a.B or [1, 64, 1024]:
         run(B, a.circuit, a.memory, max(1, a.reps))
