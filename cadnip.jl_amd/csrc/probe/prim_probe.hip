@@ -10,6 +10,25 @@
 // behavioural programs, node voltages).  n must be a multiple of block (64 or 256): a kernel has no tail guard, because the cross-lane
 // helpers need every lane of a wave active.  The row counts are the caller's view of the entry; a mismatch is refused (-1) before anything
 // is launched.  Returns the HIP error code (0 = success).
+//
+// One entry has a signature of its own -- the transient controller called ONCE on a state of the caller's choosing:
+//   int probe_tran_ctrl(int policy, int op, int B, int n, int stride, const int* isc, const double* dsc,
+//                       double* ds, int* is, long long* cnt, double* vec,
+//                       const double* atol, const double* emask, const double* breaks, const double* save_t, const int* obs,
+//                       double* out, int* nactive)
+// policy 0 = GlobalVecsT<64>, 1 = GlobalVecsT<256>, 2 = the fixed form (GlobalVecsT<64> with KPF = 4, FIXED = true: n <= 256, and the
+// switches of isc must be the ones it fixes).  One workgroup of V::NT threads per instance, B instances: load_state, then
+// op 0 = prepare_step(a, v, s, tid, t, h, nhist, hprev, hpp) with the five arguments from ds / is, op 1 = tran_update_body(a, v, s, inst, tid,
+// bad) with bad = flags & 1 (flags cleared, as k_tran_update does); then store_state.  The Newton-mode setup lines of k_tran_update are NOT
+// run: mn_* are the caller's, and s.dsc is set from ds after load_state.  An instance whose status is not 0 is left alone.
+//   isc[10]: n_limits n_break n_save n_obs n_err max_newton max_order use_pcnr newton_mode step_rule   dsc[7]: t0 t1 reltol h0 hmin hmax newton_tol
+//   ds [B][15] in/out: t h hprev hpp tcur gamma mn_a0f mn_ss mn_dnp hp3 | in: dsc, prepare_step's t h hprev hpp
+//   is [B][10] in/out: nhist order k status bp_idx save_idx flags mn_flags | out: active | in: prepare_step's nhist
+//   cnt [B][4] in/out;  vec [10][B][stride] in/out: u du delta limit_w u0 u1 u2 u3 up beta, stride >= n + 64 (the words behind n are guards
+//   the caller fills and checks);  atol, emask [n], breaks [n_break], save_t [n_save], obs [n_obs] shared by all instances;
+//   out [B n_save n_obs + 64] and nactive [1] are filled with 0xFF bytes on the device before the launch and copied back whole.
+// Arguments that would let the controller index outside these arrays (obs outside [0, n), negative bp / save indices, a non-finite time or
+// step: an infinite tn satisfies every save-time test) are refused with -1 before anything is launched.
 #include "../devices.hpp"
 #include "../tran_ctrl.hpp"
 
@@ -280,3 +299,114 @@ PROBE(source_value, 3, 1, 5, 1,
 PROBE(bsrc, 2, 1, 3, 0,
       ProbeCtx d; d.ipar = iin; d.par = in; d.wave = tab; d.count = n; d.dev = i; d.t = IN(1); d.mode = 1;
       OUT(0) = bsrc_value(d, tab + II(2));)
+
+// ---- tran_ctrl.hpp: the controller, one call on a given state (signature in the header comment) ----------------------------------------------
+namespace {
+// the fixed form's compile-time switches over the per-op path's vectors: what V::FIXED changes in prepare_step / tran_update_body, nothing else
+struct FixedGlobalVecs : GlobalVecsT<64> {
+  static constexpr int KPF = 4;
+  static constexpr bool FIXED = true;
+  __device__ FixedGlobalVecs(const TranArgs& a, int inst) : GlobalVecsT<64>(a, inst) {}
+};
+enum { TC_NDS = 15, TC_NIS = 10, TC_NVEC = 10, TC_GUARD = 64 };
+struct CtrlIO { double* ds; int* is; long long* cnt; double* vec; double* out; int B, stride, op; };
+
+template <class V>
+__global__ void __launch_bounds__(V::NT) k_tran_ctrl(TranArgs a, CtrlIO io) {
+  const int inst = blockIdx.x, tid = threadIdx.x;
+  // the instance's own view: every per-instance pointer moved to this instance, which the controller then addresses as instance 0
+  double* d = io.ds + (size_t)inst * TC_NDS;
+  int* q = io.is + (size_t)inst * TC_NIS;
+  a.t = d; a.h = d + 1; a.hprev = d + 2; a.hpp = d + 3; a.tcur = d + 4; a.gamma = d + 5; a.mn_a0f = d + 6; a.mn_ss = d + 7; a.mn_dnp = d + 8; a.hp3 = d + 9;
+  a.nhist = q; a.order = q + 1; a.k = q + 2; a.status = q + 3; a.bp_idx = q + 4; a.save_idx = q + 5; a.flags = q + 6; a.mn_flags = q + 7; a.active = q + 8;
+  a.cnt = io.cnt + (size_t)inst * 4;
+  auto vec = [&](int k) { return io.vec + ((size_t)k * io.B + inst) * io.stride; };
+  a.u = vec(0); a.du = vec(1); a.delta = vec(2); a.limit_w = vec(3); a.u0 = vec(4); a.u1 = vec(5); a.u2 = vec(6); a.u3 = vec(7); a.up = vec(8); a.beta = vec(9);
+  a.out = io.out + (size_t)inst * a.n_save * a.n_obs;
+  StepState s = load_state(a, 0);
+  s.dsc = d[10];
+  const double pt = d[11], ph = d[12], phprev = d[13], phpp = d[14];
+  const int pnhist = q[9], bad = q[6] & 1;
+  __syncthreads();            // every thread has read the state before thread 0 writes any of it
+  if (s.status != 0) return;
+  V v(a, 0);
+  if (io.op == 0) prepare_step(a, v, s, tid, pt, ph, pnhist, phprev, phpp);
+  else {
+    if (tid == 0) q[6] = 0;
+    tran_update_body(a, v, s, 0, tid, bad);
+  }
+  store_state(a, 0, tid, s);
+}
+}  // namespace
+
+extern "C" int probe_tran_ctrl(int policy, int op, int B, int n, int stride, const int* isc, const double* dsc, double* ds, int* is, long long* cnt,
+                               double* vec, const double* atol, const double* emask, const double* breaks, const double* save_t, const int* obs,
+                               double* out, int* nactive) {
+  TranArgs a = {};
+  a.B = B; a.n = n;
+  a.n_limits = isc[0]; a.n_break = isc[1]; a.n_save = isc[2]; a.n_obs = isc[3]; a.n_err = isc[4];
+  a.max_newton = isc[5]; a.max_order = isc[6]; a.use_pcnr = isc[7]; a.newton_mode = isc[8]; a.step_rule = isc[9];
+  a.t0 = dsc[0]; a.t1 = dsc[1]; a.reltol = dsc[2]; a.h0 = dsc[3]; a.hmin = dsc[4]; a.hmax = dsc[5]; a.newton_tol = dsc[6];
+  // refuse whatever could make the controller index outside the arrays
+  if (policy < 0 || policy > 2 || op < 0 || op > 1 || B <= 0 || B > 4096 || n <= 0 || n > (1 << 16) || stride < n + TC_GUARD) return -1;
+  if (a.n_limits < 0 || a.n_limits > n || a.n_break < 0 || a.n_save < 0 || a.n_obs < 0 || a.n_err < 0 || a.n_break > 4096 || a.n_save > 4096 || a.n_obs > 4096) return -1;
+  if (policy == 2 && (n > 256 || a.newton_mode != 1 || a.step_rule != 0 || a.max_order > 2 || a.use_pcnr != 0)) return -1;
+  if (a.newton_mode != 0 && a.newton_mode != 1) return -1;
+  for (int j = 0; j < a.n_obs; ++j) if (obs[j] < 0 || obs[j] >= n) return -1;
+  if (!isfinite(a.t1)) return -1;
+  for (int b = 0; b < B; ++b) {
+    const double* d = ds + (size_t)b * TC_NDS;
+    const int* q = is + (size_t)b * TC_NIS;
+    for (int k = 0; k < 5; ++k) if (!isfinite(d[k])) return -1;
+    for (int k = 11; k < 15; ++k) if (!isfinite(d[k])) return -1;
+    if (!(d[1] > 0.0) || !(d[2] > 0.0) || !(d[3] > 0.0) || !(d[12] > 0.0) || !(d[13] > 0.0) || !(d[14] > 0.0)) return -1;
+    if (q[4] < 0 || q[5] < 0 || q[4] > a.n_break || q[5] > a.n_save) return -1;
+  }
+  const size_t nds = (size_t)B * TC_NDS, nis = (size_t)B * TC_NIS, ncnt = (size_t)B * 4, nvec = (size_t)TC_NVEC * B * stride;
+  const size_t nout = (size_t)B * a.n_save * a.n_obs + TC_GUARD;
+  auto atleast = [](int k) { return (size_t)(k > 0 ? k : 1); };
+  double *d_ds = nullptr, *d_vec = nullptr, *d_out = nullptr, *d_atol = nullptr, *d_emask = nullptr, *d_breaks = nullptr, *d_save = nullptr;
+  int *d_is = nullptr, *d_obs = nullptr, *d_nactive = nullptr;
+  long long* d_cnt = nullptr;
+  hipError_t e = hipSuccess;
+  auto ck = [&](hipError_t r) { if (e == hipSuccess) e = r; return e == hipSuccess; };
+  ck(hipMalloc(&d_ds, nds * sizeof(double))) && ck(hipMalloc(&d_is, nis * sizeof(int))) && ck(hipMalloc(&d_cnt, ncnt * sizeof(long long))) &&
+      ck(hipMalloc(&d_vec, nvec * sizeof(double))) && ck(hipMalloc(&d_out, nout * sizeof(double))) && ck(hipMalloc(&d_atol, (size_t)n * sizeof(double))) &&
+      ck(hipMalloc(&d_emask, (size_t)n * sizeof(double))) && ck(hipMalloc(&d_breaks, atleast(a.n_break) * sizeof(double))) &&
+      ck(hipMalloc(&d_save, atleast(a.n_save) * sizeof(double))) && ck(hipMalloc(&d_obs, atleast(a.n_obs) * sizeof(int))) &&
+      ck(hipMalloc(&d_nactive, sizeof(int)));
+  if (e == hipSuccess) {
+    ck(hipMemcpy(d_ds, ds, nds * sizeof(double), hipMemcpyHostToDevice));
+    ck(hipMemcpy(d_is, is, nis * sizeof(int), hipMemcpyHostToDevice));
+    ck(hipMemcpy(d_cnt, cnt, ncnt * sizeof(long long), hipMemcpyHostToDevice));
+    ck(hipMemcpy(d_vec, vec, nvec * sizeof(double), hipMemcpyHostToDevice));
+    ck(hipMemcpy(d_atol, atol, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    ck(hipMemcpy(d_emask, emask, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (a.n_break) ck(hipMemcpy(d_breaks, breaks, (size_t)a.n_break * sizeof(double), hipMemcpyHostToDevice));
+    if (a.n_save) ck(hipMemcpy(d_save, save_t, (size_t)a.n_save * sizeof(double), hipMemcpyHostToDevice));
+    if (a.n_obs) ck(hipMemcpy(d_obs, obs, (size_t)a.n_obs * sizeof(int), hipMemcpyHostToDevice));
+    // results never written read back as NaN / -1
+    ck(hipMemset(d_out, 0xFF, nout * sizeof(double)));
+    ck(hipMemset(d_nactive, 0xFF, sizeof(int)));
+  }
+  if (e == hipSuccess) {
+    a.atol = d_atol; a.emask = d_emask; a.breaks = d_breaks; a.save_t = d_save; a.obs = d_obs; a.nactive = d_nactive;
+    const CtrlIO io{d_ds, d_is, d_cnt, d_vec, d_out, B, stride, op};
+    if (policy == 0) hipLaunchKernelGGL(k_tran_ctrl<GlobalVecsT<64>>, dim3(B), dim3(64), 0, 0, a, io);
+    else if (policy == 1) hipLaunchKernelGGL(k_tran_ctrl<GlobalVecsT<256>>, dim3(B), dim3(256), 0, 0, a, io);
+    else hipLaunchKernelGGL(k_tran_ctrl<FixedGlobalVecs>, dim3(B), dim3(64), 0, 0, a, io);
+    ck(hipGetLastError());
+    ck(hipDeviceSynchronize());
+  }
+  if (e == hipSuccess) {
+    ck(hipMemcpy(ds, d_ds, nds * sizeof(double), hipMemcpyDeviceToHost));
+    ck(hipMemcpy(is, d_is, nis * sizeof(int), hipMemcpyDeviceToHost));
+    ck(hipMemcpy(cnt, d_cnt, ncnt * sizeof(long long), hipMemcpyDeviceToHost));
+    ck(hipMemcpy(vec, d_vec, nvec * sizeof(double), hipMemcpyDeviceToHost));
+    ck(hipMemcpy(out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost));
+    ck(hipMemcpy(nactive, d_nactive, sizeof(int), hipMemcpyDeviceToHost));
+  }
+  (void)hipFree(d_ds); (void)hipFree(d_is); (void)hipFree(d_cnt); (void)hipFree(d_vec); (void)hipFree(d_out); (void)hipFree(d_atol); (void)hipFree(d_emask);
+  (void)hipFree(d_breaks); (void)hipFree(d_save); (void)hipFree(d_obs); (void)hipFree(d_nactive);
+  return (int)e;
+}

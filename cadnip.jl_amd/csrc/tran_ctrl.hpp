@@ -420,6 +420,10 @@ __device__ inline void tran_update_body(const TranArgs& a, V& v, StepState& s, i
     if (accept) {
       grp_sync<V>();
       save_outputs(a, v, s, inst, tid);
+      // a group of several waves: an observer may read u0 / u1 of an unknown that another wave owns, and that wave, with no observer of its own
+      // left, would go on to shift the history under the reader (tests/test_gpu_tran_ctrl.py: a save point at n = 256).  One wave runs the two
+      // loops in program order and needs nothing here.
+      if constexpr (V::NT > 64) __syncthreads();
       if (!V::FIXED && a.max_order >= 3) each_elem<V>(n, tid, [&](int i, int k) { v.set_h3(i, k, v.h2(i, k)); });
       each_elem<V>(n, tid, [&](int i, int k) { double v1 = v.h1(i, k), v0 = v.h0(i, k); v.set_h2(i, k, v1); v.set_h1(i, k, v0); v.set_h0(i, k, v.get_u(i)); });
       const double tn = s.tn;

@@ -30,10 +30,15 @@ NEWTON_MAX = 50
 
 
 # ---- Lagrange weights from the definition, exact -------------------------------------------------------------------------------------
+def _exact(v):
+    """A double or a Fraction as the rational it is (a Fraction passes through unrounded: node distances that are sums of doubles)."""
+    return v if isinstance(v, Fraction) else Fraction(float(v))
+
+
 def lagrange_values(nodes, x):
-    """[l_j(x)] for the Lagrange basis on ``nodes`` (distinct doubles), as Fractions."""
-    xs = [Fraction(float(v)) for v in nodes]
-    x = Fraction(float(x))
+    """[l_j(x)] for the Lagrange basis on ``nodes`` (distinct doubles or Fractions), as Fractions."""
+    xs = [_exact(v) for v in nodes]
+    x = _exact(x)
     out = []
     for j, xj in enumerate(xs):
         w = Fraction(1)
@@ -46,8 +51,8 @@ def lagrange_values(nodes, x):
 
 def lagrange_derivatives(nodes, x):
     """[l_j'(x)]: l_j' = sum_{m != j} 1 / (x_j - x_m) prod_{l != j, m} (x - x_l) / (x_j - x_l), as Fractions."""
-    xs = [Fraction(float(v)) for v in nodes]
-    x = Fraction(float(x))
+    xs = [_exact(v) for v in nodes]
+    x = _exact(x)
     out = []
     for j, xj in enumerate(xs):
         s = Fraction(0)
