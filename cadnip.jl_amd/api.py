@@ -700,7 +700,7 @@ def ac_matrix(G, C, omega, delay=None):
 
 
 class _ac_overlay_of:
-    """``with _ac_overlay_of(h, ovl)``: the handle's overlay for one sweep; None makes no call at all"""
+    """the handle's overlay for one sweep, as a ``with`` block (``_ac_gated_launch``); None makes no call at all"""
 
     def __init__(self, h, ovl):
         self.h, self.ovl = h, ovl
@@ -731,9 +731,20 @@ def _ac_memory(memory):
     return memory
 
 
+def _ac_solver(solver):
+    if solver not in ("host", "gpu", "auto"):
+        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
+    return solver
+
+
+def _ac_stats(**more):
+    """what the GPU sweeps of one call count into (``_ac_gated_launch``), plus the analysis' own keys"""
+    return dict({"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}, **more)
+
+
 class _ac_memory_of:
-    """``with _ac_memory_of(h, memory)``: the handle's AC memory setting for one sweep.  "lds" -- the default -- makes no call of its own: the
-    sweep is call for call what it was, under the setting of a new handle; "hbm" / "auto" are set for the block and LDS restored after it."""
+    """the handle's AC memory setting for one sweep, as a ``with`` block (``_ac_gated_launch``).  "lds" -- the default -- makes no call of its
+    own: the sweep is call for call what it was, under the setting of a new handle; "hbm" / "auto" are set for the block and LDS restored after it."""
 
     def __init__(self, h, memory):
         self.h, self.memory = h, memory
@@ -747,19 +758,82 @@ class _ac_memory_of:
             self.h.ac_set_memory("lds")
 
 
+def ac_analyze_pivots(h, st, G_ref, C_ref, omegas, gmin, overlay=None):
+    """Re-analyse the handle's pivot order for a small-signal sweep: ``ac_pivot_sample`` of the class (``G_ref`` / ``C_ref`` [B, nnz]: the
+    handle's get_GCb) on the grid, joined by the overlay's max_f |D|, handed to ``analyze_values`` in the reference order it takes."""
+    to_ref = np.asarray(st.to_ref_nz)
+    sample_ref = np.empty(st.nnz)
+    sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
+    h.analyze_values(sample_ref)
+
+
+def _ac_gated_launch(h, st, G_ref, C_ref, omegas, gmin, solver, stats, memory, overlay, call, rejected, n_systems, fallback="host solve"):
+    """The one way a small-signal sweep reaches the GPU, and the one gate its results pass: the pivot order is re-analysed
+    (``ac_analyze_pivots``), then ``call(h)`` makes the ONE kernel call -- a Handle method whose tuple ends in (berr, flags, info) -- under the
+    memory setting and the overlay of the sweep, and ``rejected(berr, flags)`` gives the boolean mask of the systems the caller must solve
+    again on the host.  ``stats`` is updated: gpu_systems / host_systems by the mask, max_berr over the accepted systems, wpb, and memory --
+    what the launch used.  Returns (what ``call`` returned, the mask).  A circuit the memory setting refuses (CADNIP_BADARG) raises with
+    solver="gpu"; with "auto" ``n_systems`` are counted as host systems, stats["fallback"] says why and None is returned."""
+    from . import hip
+    ac_analyze_pivots(h, st, G_ref, C_ref, omegas, gmin, overlay)
+    try:
+        with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
+            got = call(h)
+            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
+    except hip.CadnipError as e:
+        if solver == "auto" and e.code == hip.BADARG:
+            stats["host_systems"] += n_systems
+            stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: " + fallback
+            return None
+        raise
+    berr, flags, info = got[-3:]
+    redo = rejected(berr, flags)
+    kept = berr[~redo]
+    stats["gpu_systems"] += int((~redo).sum())
+    stats["host_systems"] += int(redo.sum())
+    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
+    stats["wpb"] = info["wpb"]
+    stats["memory"] = used
+    return got, redo
+
+
+def probe_differences(x, pairs):
+    """x[p] - x[n] along the first axis of ``x`` for the (p, n) rows of ``pairs``, -1 = ground"""
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    at = lambda j: np.where((j >= 0).reshape((-1,) + (1,) * (np.ndim(x) - 1)), x[j], 0.0)
+    return at(pr[:, 0]) - at(pr[:, 1])
+
+
+def pair_column(n, pair):
+    """the column e_p - e_n of an output pair of unknown indices (-1 = ground)"""
+    e = np.zeros(n, dtype=complex)
+    for j, sgn in zip(pair, (1.0, -1.0)):
+        if j >= 0:
+            e[j] += sgn
+    return e
+
+
+def dense_of_ref(st, nz, gmin=None):
+    """one instance's values in reference order (a row of get_GCb) as a dense n x n matrix; ``gmin`` joins the voltage-node diagonals"""
+    import scipy.sparse as sp
+    A = sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
+    if gmin is not None:
+        A[np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
+    return A
+
+
 def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory="lds", overlay=None):
     """The frequency sweep of one structure class on the GPU: ``h`` (a hip.Handle holding the restamp at the DC points) re-analyses its
     pivot order on ``ac_pivot_sample`` and solves all points x all frequencies in ONE ``ac_solve`` call; every ACSol of ``sols`` gets the
     rows of its point into its cache under the key ``tuple(omegas)``.  A system whose flag is set or whose backward error exceeds
     AC_BERR_MAX is solved again by the host's dense solve, which replaces the GPU row.  ``stats`` (shared by the call) is updated:
-    gpu_systems / host_systems, max_berr over the accepted GPU rows, wpb.  A circuit that does not fit the launch plan raises with
+    gpu_systems / host_systems, max_berr over the accepted GPU rows, wpb (``_ac_gated_launch``).  A circuit that does not fit the launch plan raises with
     solver="gpu"; with "auto" nothing is cached -- the sols solve on the host on demand -- and stats["fallback"] says why.
     ``memory``: where the kernel keeps a system's work arrays (hip.Handle.ac_set_memory) -- "lds" (the default; DESIGN section 9 has
     the figures and leaves another default to a later change): circuits beyond the LDS budget are refused as above; "hbm": a workspace in device memory, so
     such a circuit is solved on the GPU; "auto": LDS where the circuit fits, else HBM.  stats["memory"] is what the launch used.
     ``overlay``: the AcDelayOverlay of the class on ``omegas`` (the sols then carry its ``of(k)`` as their ``delay``), or None: it is set on
     the handle for the call and cleared after it, and its max_f |D| joins the pivot sample."""
-    from . import hip
     _ac_memory(memory)
     omegas = np.asarray(omegas, dtype=float)
     B, F = len(sols), omegas.size
@@ -768,32 +842,17 @@ def ac_gpu_sweep(h, st, sols, G_ref, C_ref, omegas, gmin, solver, stats, memory=
         for s in sols:
             s._cache[key] = np.zeros((0, st.n), complex)
         return
-    to_ref = np.asarray(st.to_ref_nz)
-    sample_ref = np.empty(st.nnz)
-    sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
-    h.analyze_values(sample_ref)
-    try:
-        with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
-            x, berr, flags, info = h.ac_solve(omegas, gmin, np.array([s.b_ac for s in sols]))
-            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
-    except hip.CadnipError as e:
-        if solver == "auto" and e.code == hip.BADARG:
-            stats["host_systems"] += B * F
-            stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
-            return
-        raise
-    redo = (flags != 0) | ~(berr <= AC_BERR_MAX)
+    got = _ac_gated_launch(h, st, G_ref, C_ref, omegas, gmin, solver, stats, memory, overlay,
+                           lambda h: h.ac_solve(omegas, gmin, np.array([s.b_ac for s in sols])),
+                           lambda berr, flags: (flags != 0) | ~(berr <= AC_BERR_MAX), B * F)
+    if got is None:
+        return
+    (x, _, _, _), redo = got
     for k, s in enumerate(sols):
         rows = np.array(x[k])
         for f in np.flatnonzero(redo[k]):
             rows[f] = np.linalg.solve(ac_matrix(s.G, s.C, omegas[f], s.delay), s.b_ac)
         s._cache[key] = rows
-    kept = berr[~redo]
-    stats["gpu_systems"] += int((~redo).sum())
-    stats["host_systems"] += int(redo.sum())
-    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
-    stats["wpb"] = info["wpb"]
-    stats["memory"] = used
 
 
 def _ac_target(target):
@@ -805,11 +864,10 @@ def _ac_target(target):
 
 
 def _ac_classes(sweep, mc, pts, gmin, device, what):
-    """The linearisation ``ac`` and ``network`` share, one structure class at a time: a resident batch per class, its DC operating points, the
+    """The linearisation ``ac``, ``network``, ``noise``, ``network_noise`` and ``pz`` share, one structure class at a time: a resident batch per class, its DC operating points, the
     restamp at them, and per point the dense G (``gmin`` on the voltage-node diagonals) and C.  Yields (sim, st, idx, G, C, lin) with G / C the
     handle's get_GCb ([B, nnz]) and lin = [(point index, G dense, C dense, point parameters, DC solution)]; the batch is closed when the
     consumer moves on -- or closes the generator."""
-    import scipy.sparse as sp
     for idx, st in structure_classes(mc, pts) if sweep else [(list(range(1)), None)]:
         sim = BatchSimulator(mc, [pts[i] for i in idx] if sweep else None, device, st=st)
         try:
@@ -819,13 +877,8 @@ def _ac_classes(sweep, mc, pts, gmin, device, what):
                 raise RuntimeError("%s: the DC operating point did not converge for %d point(s)" % (what, int((~conv).sum())))
             sim.h.rebuild(u, 0.0)
             G, C, _, _ = sim.h.get_GCb()
-            lin = []
-            for k, i in enumerate(idx):
-                dense = lambda nz: sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
-                Gd, Cd = dense(G[k]), dense(C[k])
-                Gd[np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
-                lin.append((i, Gd, Cd, {kk: float(v[k]) for kk, v in sim.params.items()}, u[k].copy()))
-            yield sim, st, idx, G, C, lin
+            yield sim, st, idx, G, C, [(i, dense_of_ref(st, G[k], gmin), dense_of_ref(st, C[k]), {kk: float(v[k]) for kk, v in sim.params.items()}, u[k].copy())
+                                       for k, i in enumerate(idx)]
         finally:
             sim.close()
 
@@ -869,41 +922,23 @@ def ac_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, rhs, pairs, wa
     again by the host's dense solve on ``Gd`` / ``Cd`` (per point; gmin on the node diagonals).  ``stats`` counts columns as systems.  A
     circuit the memory home refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why.  ``overlay`` as
     for ``ac_gpu_sweep``: the redo solves add its ``dense(b, w)``."""
-    from . import hip
     _ac_memory(memory)
     omegas = np.asarray(omegas, dtype=float)
     rhs = np.asarray(rhs, dtype=complex)
     B, F, K = len(Gd), omegas.size, rhs.shape[0]
     stats["rhs"] = K
-    to_ref = np.asarray(st.to_ref_nz)
-    sample_ref = np.empty(st.nnz)
-    sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
-    h.analyze_values(sample_ref)
-    try:
-        with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
-            hh, x, berr, flags, info = h.ac_solve_multi(omegas, gmin, rhs, pairs, 0, want_x)
-            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
-    except hip.CadnipError as e:
-        if solver == "auto" and e.code == hip.BADARG:
-            stats["host_systems"] += B * F * K
-            stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
-            return None
-        raise
-    redo = (flags != 0) | ~(berr <= AC_BERR_MAX)
-    if redo.any():
-        pr = None if hh is None else np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-        for b, f, k in zip(*np.nonzero(redo)):
-            xh = np.linalg.solve(ac_matrix(Gd[b], Cd[b], omegas[f], overlay and overlay.of(b)), rhs[k])
-            if x is not None:
-                x[b, f, k] = xh
-            if hh is not None:
-                hh[b, f, k] = np.where(pr[:, 0] >= 0, xh[pr[:, 0]], 0.0) - np.where(pr[:, 1] >= 0, xh[pr[:, 1]], 0.0)
-    kept = berr[~redo]
-    stats["gpu_systems"] += int((~redo).sum())
-    stats["host_systems"] += int(redo.sum())
-    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
-    stats["wpb"] = info["wpb"]
-    stats["memory"] = used
+    got = _ac_gated_launch(h, st, G_ref, C_ref, omegas, gmin, solver, stats, memory, overlay,
+                           lambda h: h.ac_solve_multi(omegas, gmin, rhs, pairs, 0, want_x),
+                           lambda berr, flags: (flags != 0) | ~(berr <= AC_BERR_MAX), B * F * K)
+    if got is None:
+        return None
+    (hh, x, _, _, _), redo = got
+    for b, f, k in zip(*np.nonzero(redo)):
+        xh = np.linalg.solve(ac_matrix(Gd[b], Cd[b], omegas[f], overlay and overlay.of(b)), rhs[k])
+        if x is not None:
+            x[b, f, k] = xh
+        if hh is not None:
+            hh[b, f, k] = probe_differences(xh, pairs)
     return hh, x
 
 
@@ -928,10 +963,8 @@ def ac(target, freqs=(), gmin=1e-12, device=0, solver="host", memory="lds", sour
     A(w) = G + j w C + D(w) on every path -- ``ac_delay_overlay`` computes D, the host solves add it, the GPU sweeps hand it to the overlay
     kernels -- and so are ``network``, ``noise`` and ``network_noise``; the ACSols then carry ``delay``."""
     from contextlib import closing
-    if solver not in ("host", "gpu", "auto"):
-        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
-    _ac_memory(memory)
-    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    _ac_solver(solver), _ac_memory(memory)
+    stats = _ac_stats()
     sweep, mc, pts = _ac_target(target)
     sols = [None] * len(pts)
     omegas = 2.0 * np.pi * np.asarray(freqs, dtype=float)
@@ -1024,13 +1057,11 @@ def network(target, ports, freqs, z0=50.0, gmin=1e-12, device=0, solver="host", 
     again on the host); "auto" -- as "gpu", with the host path for a circuit the memory home refuses.  ``memory`` as for ``ac``.
     ``stats`` = {"gpu_systems", "host_systems", "max_berr", "wpb", "memory", "rhs"} with columns counted as systems."""
     from contextlib import closing
-    if solver not in ("host", "gpu", "auto"):
-        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
-    _ac_memory(memory)
+    _ac_solver(solver), _ac_memory(memory)
     ports = list(ports)
     freqs = np.asarray(freqs, dtype=float)
     omegas = 2.0 * np.pi * freqs
-    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    stats = _ac_stats()
     sweep, mc, pts = _ac_target(target)
     sols = [None] * len(pts)
     with closing(_ac_classes(sweep, mc, pts, gmin, device, "network")) as classes:
@@ -1259,56 +1290,32 @@ def noise_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, output, freqs, in
     solved on the host and stats["fallback"] says why.  ``memory``: "lds" (the default; DESIGN section 9 has the figures and leaves
     another default to a later change), "hbm" or "auto", as for ``ac_gpu_sweep``: with the latter two a circuit beyond the LDS budget is solved on the GPU;
     stats["memory"] is what the launch used."""
-    from . import hip
     _ac_memory(memory)
     freqs = np.asarray(freqs, dtype=float)
     if freqs.size == 0:
         raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
     if stats is None:
-        stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+        stats = _ac_stats()
     B, F = len(Gd), freqs.size
     temps = np.broadcast_to(np.asarray(temps, dtype=float), (B,))
     out_idx, in_idx = noise_indices(st, output, input)
     omegas = 2.0 * np.pi * freqs
     pairs, index = noise_probe_pairs(source_lists, in_idx)
-    host = lambda k, adj=None: noise_solve(st, Gd[k], Cd[k], source_lists[k], output, freqs, input, float(temps[k]), adjoint=adj,
-                                           delay=overlay and overlay.of(k))
+    H = None                                             # stays None where the host solves: no pairs, or the fallback of "auto"
     if len(pairs) == 0:                                  # no source and no input: nothing to probe, the sums are empty
-        sols = [host(k) for k in range(B)]
         stats["host_systems"] += B * F
     else:
-        to_ref = np.asarray(st.to_ref_nz)
-        sample_ref = np.empty(st.nnz)
-        sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
-        h.analyze_values(sample_ref)
-        e_out = np.zeros(st.n, dtype=complex)
-        e_out[out_idx] = 1.0
-        try:
-            with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
-                H, _, berr, flags, info = h.ac_adjoint(omegas, gmin, e_out, pairs)
-                used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
-        except hip.CadnipError as e:
-            if solver == "auto" and e.code == hip.BADARG:
-                stats["host_systems"] += B * F
-                stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
-                sols = [host(k) for k in range(B)]
-                for s in sols:
-                    s.stats = stats
-                return sols
-            raise
-        redo = (flags != 0) | ~(berr <= NOISE_BERR_MAX)
-        H = np.array(H)
-        pp, nn = pairs[:, 0], pairs[:, 1]
-        for k, f in zip(*np.nonzero(redo)):
-            x_adj = np.linalg.solve(ac_matrix(Gd[k], Cd[k], omegas[f], overlay and overlay.of(k)).T, e_out)
-            H[k, f] = np.where(pp >= 0, x_adj[pp], 0.0) - np.where(nn >= 0, x_adj[nn], 0.0)
-        sols = [host(k, (index, H[k])) for k in range(B)]
-        kept = berr[~redo]
-        stats["gpu_systems"] += int((~redo).sum())
-        stats["host_systems"] += int(redo.sum())
-        stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
-        stats["wpb"] = info["wpb"]
-        stats["memory"] = used
+        e_out = pair_column(st.n, (out_idx, -1))
+        got = _ac_gated_launch(h, st, G_ref, C_ref, omegas, gmin, solver, stats, memory, overlay,
+                               lambda h: h.ac_adjoint(omegas, gmin, e_out, pairs),
+                               lambda berr, flags: (flags != 0) | ~(berr <= NOISE_BERR_MAX), B * F)
+        if got is not None:
+            H = np.array(got[0][0])
+            for k, f in zip(*np.nonzero(got[1])):
+                x_adj = np.linalg.solve(ac_matrix(Gd[k], Cd[k], omegas[f], overlay and overlay.of(k)).T, e_out)
+                H[k, f] = probe_differences(x_adj, pairs)
+    sols = [noise_solve(st, Gd[k], Cd[k], source_lists[k], output, freqs, input, float(temps[k]), adjoint=None if H is None else (index, H[k]),
+                        delay=overlay and overlay.of(k)) for k in range(B)]
     for s in sols:
         s.stats = stats
     return sols
@@ -1329,52 +1336,34 @@ def noise(target, output, freqs, input=None, gmin=1e-12, device=0, solver="host"
     and one restamp; the host path runs ``noise_solve`` once per output, a GPU solver makes ONE ``ac_adjoint_multi`` call per structure class
     -- one factorisation per (point, frequency) serving every output (``noise_multi_solve_gpu``; ``stats`` then counts columns as systems and
     has "rhs": the number of outputs).  Each NoiseSol equals the single-output call's to the bit."""
-    import scipy.sparse as sp
-    if solver not in ("host", "gpu", "auto"):
-        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
-    _ac_memory(memory)
+    from contextlib import closing
+    _ac_solver(solver), _ac_memory(memory)
     if len(freqs) == 0:
         raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
-    sweep = isinstance(target, CircuitSweep)
-    mc0 = target.circuit if sweep else target
-    mc = MNACircuit(mc0.circuit, mc0.params, MNASpec(temp=mc0.spec.temp, mode="dcop", gmin=mc0.spec.gmin))
-    pts = target.points() if sweep else [{}]
-    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    stats = _ac_stats()
+    sweep, mc, pts = _ac_target(target)
     sols = [None] * len(pts)
     outputs = None if isinstance(output, str) else list(output)
     if outputs is not None and (not outputs or len(set(outputs)) != len(outputs)):
         raise ValueError("noise: output as a list needs at least one name, each once")
-    for idx, st in structure_classes(mc, pts) if sweep else [([0], None)]:
-        sim = BatchSimulator(mc, [pts[i] for i in idx] if sweep else None, device, st=st)
-        try:
-            st = sim.st
-            u, conv, _ = sim.dc()
-            if not np.all(conv):
-                raise RuntimeError("noise: the DC operating point did not converge" + (" for %d point(s)" % int((~conv).sum()) if sweep else ""))
-            sim.h.rebuild(u, 0.0)
-            G, C, _, _ = sim.h.get_GCb()
-            dense = lambda nz: sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
-            Gd, Cd, srcs, temps = [], [], [], []
-            for k, i in enumerate(idx):
-                Gd.append(dense(G[k])), Cd.append(dense(C[k]))
-                Gd[k][np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
-                p_k = {kk: float(v[k]) for kk, v in sim.params.items()}
-                temps.append(float(pts[i].get("temp", mc.spec.temp)))
-                srcs.append(noise_sources(st, mc.circuit, p_k, u[k], temps[k], mc.spec.gmin))
+    with closing(_ac_classes(sweep, mc, pts, gmin, device, "noise")) as classes:
+        for sim, st, idx, G, C, lin in classes:
+            Gd, Cd = [l[1] for l in lin], [l[2] for l in lin]
+            temps = [float(pts[i].get("temp", mc.spec.temp)) for i in idx]
+            srcs = [noise_sources(st, mc.circuit, p_i, u_i, temps[k], mc.spec.gmin) for k, (i, _, _, p_i, u_i) in enumerate(lin)]
             ovl = ac_delay_overlay(st, mc.circuit, sim.params, 2.0 * np.pi * np.asarray(freqs, dtype=float), sim.B)
-            if not isinstance(output, str):
+            host = lambda k, o: noise_solve(st, Gd[k], Cd[k], srcs[k], o, freqs, input, temps[k], delay=ovl and ovl.of(k))
+            if outputs is not None:
                 if solver == "host":
-                    got = [{o: noise_solve(st, Gd[k], Cd[k], srcs[k], o, freqs, input, temps[k], delay=ovl and ovl.of(k)) for o in outputs} for k in range(len(idx))]
+                    got = [{o: host(k, o) for o in outputs} for k in range(len(idx))]
                 else:
                     got = noise_multi_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, outputs, freqs, input, temps, gmin, solver, stats, memory, ovl)
             elif solver == "host":
-                got = [noise_solve(st, Gd[k], Cd[k], srcs[k], output, freqs, input, temps[k], delay=ovl and ovl.of(k)) for k in range(len(idx))]
+                got = [host(k, output) for k in range(len(idx))]
             else:
                 got = noise_solve_gpu(sim.h, st, G, C, Gd, Cd, srcs, output, freqs, input, temps, gmin, solver, stats, memory, ovl)
             for k, i in enumerate(idx):
                 sols[i] = got[k]
-        finally:
-            sim.close()
     return SweepResult(pts, sols) if sweep else sols[0]
 
 
@@ -1385,38 +1374,20 @@ def adjoint_multi_gpu_sweep(h, st, Gd, Cd, G_ref, C_ref, omegas, gmin, cols, pai
     ``noise_solve_gpu``'s, per column: a column whose flag is set or whose backward error exceeds NOISE_BERR_MAX is solved again by the host's
     dense adjoint solve on ``Gd`` / ``Cd``.  ``stats`` counts columns as systems and carries "rhs" and "memory".  A circuit the memory home
     refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why."""
-    from . import hip
     _ac_memory(memory)
     omegas = np.asarray(omegas, dtype=float)
     cols = np.asarray(cols, dtype=complex)
     B, F, K = len(Gd), omegas.size, cols.shape[0]
     stats["rhs"] = K
-    to_ref = np.asarray(st.to_ref_nz)
-    sample_ref = np.empty(st.nnz)
-    sample_ref[to_ref] = _overlay_sample(ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin), overlay)
-    h.analyze_values(sample_ref)
-    try:
-        with _ac_memory_of(h, memory), _ac_overlay_of(h, overlay):
-            H, _, berr, flags, info = h.ac_adjoint_multi(omegas, gmin, cols, pairs)
-            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
-    except hip.CadnipError as e:
-        if solver == "auto" and e.code == hip.BADARG:
-            stats["host_systems"] += B * F * K
-            stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
-            return None
-        raise
-    redo = (flags != 0) | ~(berr <= NOISE_BERR_MAX)
-    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    pp, nn = pr[:, 0], pr[:, 1]
+    got = _ac_gated_launch(h, st, G_ref, C_ref, omegas, gmin, solver, stats, memory, overlay,
+                           lambda h: h.ac_adjoint_multi(omegas, gmin, cols, pairs),
+                           lambda berr, flags: (flags != 0) | ~(berr <= NOISE_BERR_MAX), B * F * K)
+    if got is None:
+        return None
+    H, redo = got[0][0], got[1]
     for b, f, k in zip(*np.nonzero(redo)):
         x_adj = np.linalg.solve(ac_matrix(Gd[b], Cd[b], omegas[f], overlay and overlay.of(b)).T, cols[k])
-        H[b, f, k] = np.where(pp >= 0, x_adj[pp], 0.0) - np.where(nn >= 0, x_adj[nn], 0.0)
-    kept = berr[~redo]
-    stats["gpu_systems"] += int((~redo).sum())
-    stats["host_systems"] += int(redo.sum())
-    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
-    stats["wpb"] = info["wpb"]
-    stats["memory"] = used
+        H[b, f, k] = probe_differences(x_adj, pairs)
     return H
 
 
@@ -1429,7 +1400,7 @@ def noise_multi_solve_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, outputs, fr
     if freqs.size == 0:
         raise ValueError("noise(circuit, output, freqs=...) needs a non-empty grid in hertz (e.g. acdec(20, 1, 1e6))")
     if stats is None:
-        stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+        stats = _ac_stats()
     B, F, K = len(Gd), freqs.size, len(outputs)
     temps = np.broadcast_to(np.asarray(temps, dtype=float), (B,))
     idxs = [noise_indices(st, o, input) for o in outputs]
@@ -1546,7 +1517,6 @@ def network_noise_solve(st, G, C, sources, ports, freqs, z0=50.0, temp_c=27.0, d
     P = len(rows)
     if adjoint is None:
         pairs, index = network_noise_pairs(rows, [sources])
-        pp, nn = pairs[:, 0].astype(np.int64)[:, None], pairs[:, 1].astype(np.int64)[:, None]
         E = np.zeros((st.n, P), dtype=complex)
         E[rows, np.arange(P)] = 1.0
     else:
@@ -1558,7 +1528,7 @@ def network_noise_solve(st, G, C, sources, ports, freqs, z0=50.0, temp_c=27.0, d
     for fi, f in enumerate(freqs):
         if adjoint is None:
             lam = np.linalg.solve((1j * 2.0 * np.pi * f * C + G).T if delay is None else ac_matrix(G, C, 2.0 * np.pi * f, delay).T, E)                       # [n, P]: column i is l_i
-            Hf = (np.where(pp >= 0, lam[pp[:, 0]], 0.0) - np.where(nn >= 0, lam[nn[:, 0]], 0.0)).T
+            Hf = probe_differences(lam, pairs).T
         else:
             Hf = adjoint[1][fi]                                                              # [P, pairs]
         y[fi] = -Hf[:, at_rows]
@@ -1580,7 +1550,7 @@ def network_noise_gpu(h, st, G_ref, C_ref, Gd, Cd, source_lists, ports, freqs, z
     _ac_memory(memory)
     freqs = np.asarray(freqs, dtype=float)
     if stats is None:
-        stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+        stats = _ac_stats()
     B = len(Gd)
     temps = np.broadcast_to(np.asarray(temps, dtype=float), (B,))
     rows = port_rows(st, ports)
@@ -1609,12 +1579,10 @@ def network_noise(target, ports, freqs, z0=50.0, gmin=1e-12, device=0, solver="h
     (``network_noise_gpu``); "auto" -- as "gpu", with the host path for a circuit the memory home refuses.  ``memory`` as for ``ac``.
     ``stats`` = {"gpu_systems", "host_systems", "max_berr", "wpb", "memory", "rhs"} with columns counted as systems."""
     from contextlib import closing
-    if solver not in ("host", "gpu", "auto"):
-        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
-    _ac_memory(memory)
+    _ac_solver(solver), _ac_memory(memory)
     ports = list(ports)
     freqs = np.asarray(freqs, dtype=float)
-    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    stats = _ac_stats()
     sweep, mc, pts = _ac_target(target)
     sols = [None] * len(pts)
     with closing(_ac_classes(sweep, mc, pts, gmin, device, "network_noise")) as classes:
@@ -1693,12 +1661,7 @@ def sensitivity_solve(st, Gd, Cd, b, dG, dC, db, out, omegas):
     omegas = np.asarray(omegas, dtype=float).ravel()
     dG, dC = np.asarray(dG, dtype=float), np.asarray(dC, dtype=float)
     K, n = dG.shape[0], st.n
-    p, q = out
-    e = np.zeros(n, dtype=complex)
-    if p >= 0:
-        e[p] += 1.0
-    if q >= 0:
-        e[q] -= 1.0
+    e = pair_column(n, out)
     b = np.asarray(b, dtype=complex)
     y, dy = np.zeros(omegas.size, dtype=complex), np.zeros((omegas.size, K), dtype=complex)
     for f, w in enumerate(omegas):
@@ -1711,6 +1674,29 @@ def sensitivity_solve(st, Gd, Cd, b, dG, dC, db, out, omegas):
                 rhs = rhs + db[k]
             dy[f, k] = lam @ rhs
     return y, dy
+
+
+def sens_gpu_sweep(h, st, G_ref, C_ref, base, plus, minus, scale, bac, out, db, omegas, gmin, solver, stats, host, memory="lds"):
+    """The responses and derivatives of one structure class on the GPU: ``h`` (holding the restamp of the expanded batch; ``G_ref`` / ``C_ref``
+    [B, nnz] its get_GCb) re-analyses its pivot order on ``ac_pivot_sample`` over all instances -- as ``ac_gpu_sweep`` -- and runs base points x
+    frequencies systems in ONE ``ac_sens`` call: ``base`` [NB], ``plus`` / ``minus`` [NB, K] instance indices, ``scale`` [NB, K], ``bac``
+    [NB, n], ``out`` the (p, n) output pair, ``db`` [NB, K, n] or None.  A system with a flag set in any column, a forward backward error
+    above AC_BERR_MAX or an adjoint one above NOISE_BERR_MAX is solved again by the host: ``host(a)`` gives base a's solver, angular
+    frequencies -> (y [F'], s [F', K]) (``sensitivity_solve``).  Returns [(y [F], s [F, K])] per base and updates ``stats`` as ``ac_gpu_sweep``
+    does.  A circuit the memory setting refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why."""
+    _ac_memory(memory)
+    omegas = np.asarray(omegas, dtype=float)
+    got = _ac_gated_launch(h, st, G_ref, C_ref, omegas, gmin, solver, stats, memory, None,
+                           lambda h: h.ac_sens(omegas, gmin, base, plus, minus, scale, bac, pair_column(st.n, out), out, db),
+                           lambda berr, flags: flags.any(axis=2) | ~(berr[:, :, 0] <= AC_BERR_MAX) | ~(berr[:, :, 1] <= NOISE_BERR_MAX),
+                           len(base) * omegas.size)
+    if got is None:
+        return None
+    y, s, redo = np.array(got[0][0]), np.array(got[0][1]), got[1]
+    for a in np.flatnonzero(redo.any(axis=1)):
+        ff = np.flatnonzero(redo[a])
+        y[a, ff], s[a, ff] = host(a)(omegas[ff])
+    return [(y[a], s[a]) for a in range(len(base))]
 
 
 def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device=0, solver="host", memory="lds"):
@@ -1729,11 +1715,7 @@ def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device
     system with a flag set, a forward backward error above AC_BERR_MAX or an adjoint one above NOISE_BERR_MAX is redone by the host path;
     "auto" -- as "gpu", with the host path for a circuit the memory home refuses.  ``memory`` as for ``ac``.  ``stats`` =
     {"gpu_systems", "host_systems", "max_berr", "wpb", "memory", "params"}.  Several outputs: call once per output."""
-    import scipy.sparse as sp
-    from . import hip
-    if solver not in ("host", "gpu", "auto"):
-        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
-    _ac_memory(memory)
+    _ac_solver(solver), _ac_memory(memory)
     params = [params] if isinstance(params, str) else list(params)
     if not params or len(set(params)) != len(params):
         raise ValueError("sensitivity: params needs at least one parameter name, each once")
@@ -1772,7 +1754,7 @@ def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device
                 raise ValueError("sensitivity: a step of %g in %s at point %d changes the structure of the circuit (its unknowns or its pattern): "
                                  "the derivative does not exist there" % (steps[i, k], nm, i))
     outs = [sens_output(st, output) for _, st in classes]
-    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0, "params": K}
+    stats = _ac_stats(params=K)
     sols = [None] * len(pts)
     for (members, st), out in zip(classes, outs):
         bases = [j for j in members if j % per == 0]
@@ -1798,7 +1780,7 @@ def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device
             u[~is_base] = uv[~is_base]
             sim.h.rebuild(u, 0.0)
             G, C, _, _ = sim.h.get_GCb()
-            dense = lambda nz: sp.csc_matrix((nz, st.ref_rowval, st.ref_colptr), shape=(st.n, st.n)).toarray()
+            dense = lambda nz: dense_of_ref(st, nz)
             par_of = lambda m: {kk: float(v[m]) for kk, v in sim.params.items()}
             scale = np.array([[1.0 / (2.0 * steps[b // per, k]) for k in range(K)] for b in bases])
             bac = np.array([rhs_ac(st, mc.circuit, par_of(m)) for m in base])
@@ -1809,43 +1791,11 @@ def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device
             val = lambda m: (u[m, out[0]] if out[0] >= 0 else 0.0) - (u[m, out[1]] if out[1] >= 0 else 0.0)
 
             def host(a):
-                Gd, Cd = dense(G[base[a]]), dense(C[base[a]])
-                Gd[np.arange(st.n_nodes), np.arange(st.n_nodes)] += gmin
                 dG = np.array([(dense(G[plus[a, k]]) - dense(G[minus[a, k]])) * scale[a, k] for k in range(K)])
                 dC = np.array([(dense(C[plus[a, k]]) - dense(C[minus[a, k]])) * scale[a, k] for k in range(K)])
-                return lambda om: sensitivity_solve(st, Gd, Cd, bac[a], dG, dC, None if db is None else db[a], out, om)
+                return lambda om: sensitivity_solve(st, dense_of_ref(st, G[base[a]], gmin), dense(C[base[a]]), bac[a], dG, dC, None if db is None else db[a], out, om)
 
-            got = None
-            if solver != "host":
-                to_ref = np.asarray(st.to_ref_nz)
-                sample_ref = np.empty(st.nnz)
-                sample_ref[to_ref] = ac_pivot_sample(st, G[:, to_ref], C[:, to_ref], omegas, gmin)
-                sim.h.analyze_values(sample_ref)
-                e = np.zeros(st.n, dtype=complex)
-                for j, sgn in zip(out, (1.0, -1.0)):
-                    if j >= 0:
-                        e[j] += sgn
-                try:
-                    with _ac_memory_of(sim.h, memory):
-                        y, s, _, berr, flags, info = sim.h.ac_sens(omegas, gmin, base, plus, minus, scale, bac, e, out, db)
-                        used = sim.h.ac_plan_info()["memory"] if memory != "lds" else "lds"
-                    redo = flags.any(axis=2) | ~(berr[:, :, 0] <= AC_BERR_MAX) | ~(berr[:, :, 1] <= NOISE_BERR_MAX)
-                    y, s = np.array(y), np.array(s)
-                    for a in np.flatnonzero(redo.any(axis=1)):
-                        ff = np.flatnonzero(redo[a])
-                        y[a, ff], s[a, ff] = host(a)(omegas[ff])
-                    kept = berr[~redo]
-                    stats["gpu_systems"] += int((~redo).sum())
-                    stats["host_systems"] += int(redo.sum())
-                    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
-                    stats["wpb"] = info["wpb"]
-                    stats["memory"] = used
-                    got = [(y[a], s[a]) for a in range(NB)]
-                except hip.CadnipError as err:
-                    if not (solver == "auto" and err.code == hip.BADARG):
-                        raise
-                    stats["host_systems"] += NB * omegas.size
-                    stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host solve"
+            got = None if solver == "host" else sens_gpu_sweep(sim.h, st, G, C, base, plus, minus, scale, bac, out, db, omegas, gmin, solver, stats, host, memory)
             if got is None:
                 got = [host(a)(omegas) for a in range(NB)]
             for a, b in enumerate(bases):
@@ -2010,10 +1960,7 @@ def pz_solve(st, G, C, b, out, shifts, order, arnoldi=None):
     Returns (PZSol, breakdowns)."""
     n = len(b)
     m = min(int(order), n)
-    c = np.zeros(n, dtype=complex)
-    for j, sgn in zip(out, (1.0, -1.0)):
-        if j >= 0:
-            c[j] += sgn
+    c = pair_column(n, out)
     if arnoldi is None:
         arnoldi = lambda w0: arnoldi_host(G, C, b, w0, m, c[None])
     cand, models, closed, breakdowns = [], {}, [], 0
@@ -2077,29 +2024,14 @@ def pz_gpu_sweep(h, st, G_ref, C_ref, rhs, out, omegas, m, gmin, solver, stats, 
     with the probe pair ``out``.  Returns (H [B, S, m+1, m], beta, m_eff, l [B, S, m, 1], redo [B, S]) -- ``redo``: flag bit 0 or 1 set, or
     a backward error above AC_BERR_MAX: the caller reduces that system on the host -- and updates ``stats`` as ``ac_gpu_sweep`` does.  A
     circuit the memory home refuses raises with solver="gpu"; with "auto" None is returned and stats["fallback"] says why."""
-    from . import hip
     _ac_memory(memory)
     omegas = np.asarray(omegas, dtype=float)
-    to_ref = np.asarray(st.to_ref_nz)
-    sample_ref = np.empty(st.nnz)
-    sample_ref[to_ref] = ac_pivot_sample(st, np.asarray(G_ref)[:, to_ref], np.asarray(C_ref)[:, to_ref], omegas, gmin)
-    h.analyze_values(sample_ref)
-    try:
-        with _ac_memory_of(h, memory):
-            H, beta, meff, l, _, berr, flags, info = h.ac_arnoldi(omegas, gmin, rhs, m, [out])
-            used = h.ac_plan_info()["memory"] if memory != "lds" else "lds"
-    except hip.CadnipError as err:
-        if not (solver == "auto" and err.code == hip.BADARG):
-            raise
-        stats["host_systems"] += len(rhs) * omegas.size
-        stats["fallback"] = "the circuit's work arrays exceed the AC kernel's LDS budget: host Arnoldi"
+    got = _ac_gated_launch(h, st, G_ref, C_ref, omegas, gmin, solver, stats, memory, None,
+                           lambda h: h.ac_arnoldi(omegas, gmin, rhs, m, [out]),
+                           lambda berr, flags: ((flags & 3) != 0) | ~(berr <= AC_BERR_MAX), len(rhs) * omegas.size, fallback="host Arnoldi")
+    if got is None:
         return None
-    redo = ((flags & 3) != 0) | ~(berr <= AC_BERR_MAX)
-    kept = berr[~redo]
-    stats["gpu_systems"] += int((~redo).sum())
-    stats["host_systems"] += int(redo.sum())
-    stats["max_berr"] = max(stats["max_berr"], float(kept.max()) if kept.size else 0.0)
-    stats["wpb"], stats["memory"] = info["wpb"], used
+    (H, beta, meff, l, _, _, _, _), redo = got
     return H, beta, meff, l, redo
 
 
@@ -2117,23 +2049,18 @@ def pz(target, output, input=None, shifts=(0.0,), order=16, gmin=1e-12, device=0
     ``stats["fallback"]``.  ``memory`` as ``ac``.  ``stats`` = ``ACSol.stats``' keys plus "order", "shifts", "breakdowns" (systems whose Krylov
     space closed before ``order`` steps: their poles are exact)."""
     from contextlib import closing
-    if solver not in ("host", "gpu", "auto"):
-        raise ValueError("solver must be 'host', 'gpu' or 'auto'")
-    _ac_memory(memory)
+    _ac_solver(solver), _ac_memory(memory)
     omegas = 2.0 * np.pi * np.asarray(shifts, dtype=float).ravel()
     if solver != "host" and (omegas.size == 0 or int(order) < 1):
         raise ValueError("pz: at least one shift and one Arnoldi step")
     sweep, mc, pts = _ac_target(target)
     refuse_delay(mc.circuit, "pz", "(G + s C + D(s)) is not a matrix pencil, so neither the dense eigenvalue path nor the Arnoldi kernel applies")
-    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0, "order": int(order), "shifts": int(omegas.size), "breakdowns": 0}
+    stats = _ac_stats(order=int(order), shifts=int(omegas.size), breakdowns=0)
     sols = [None] * len(pts)
     with closing(_ac_classes(sweep, mc, pts, gmin, device, "pz")) as classes:
         for sim, st, idx, G, C, lin in classes:
             out = sens_output(st, output)
-            c = np.zeros(st.n, dtype=complex)
-            for j, sgn in zip(out, (1.0, -1.0)):
-                if j >= 0:
-                    c[j] += sgn
+            c = pair_column(st.n, out)
             rhs = [rhs_ac(st, mc.circuit, p_i) if input is None else source_rhs(st, mc.circuit, input) for _, _, _, p_i, _ in lin]
             if solver == "host":
                 for (i, Gd, Cd, p_i, u_i), b in zip(lin, rhs):

@@ -162,7 +162,12 @@ def _check(code, where):
     raise CadnipError(code, where)
 
 
-MODE = {"dcop": 0, "tran": 1, "tranop": 2}
+def _ac_info(info=(0, 0, 0, 0)):
+    """the ``info`` of the AC entry points from the four integers the library fills in; without them that of a call that launched nothing"""
+    return dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+
+
+MODE ={"dcop": 0, "tran": 1, "tranop": 2}
 
 # cadnip_factor_solve's kernel argument (CADNIP_LUK_*): auto, k_lu_steps<4>, k_lu_f2_mw<4>, k_lu_f2s<W>, k_lu_f2<W>, k_lu with the fused Jacobian
 LU_KERNELS = ("auto", "steps4", "mw4", "f2s", "f2", "plain")
@@ -376,13 +381,13 @@ class Handle:
         om = np.ascontiguousarray(np.asarray(omega, dtype=np.float64).ravel())
         B, n, F = self.B, self.st.n, om.size
         if F == 0:
-            return np.zeros((B, 0, n), dtype=complex), np.zeros((B, 0)), np.zeros((B, 0), dtype=np.int32), dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
+            return np.zeros((B, 0, n), dtype=complex), np.zeros((B, 0)), np.zeros((B, 0), dtype=np.int32), _ac_info()
         b = np.ascontiguousarray(np.broadcast_to(np.asarray(b_ac, dtype=np.complex128), (B, n)))
         x = np.empty((B, F, n), dtype=np.complex128)
         berr, flags, info = np.empty((B, F)), np.zeros((B, F), dtype=np.int32), np.zeros(4, dtype=np.int32)
         _check(self.lib.cadnip_ac_solve(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), b.ctypes.data_as(_D), C.c_int32(int(wpb)),
                                         x.ctypes.data_as(_D), _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_solve")
-        return x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+        return x, berr, flags, _ac_info(info)
 
     def ac_adjoint(self, omega, gmin, c, pairs, wpb=0, want_x=False):
         """cadnip_ac_adjoint: x[b, f] solves A^T x = c[b] with A = G[b] + gmin on the node diagonals + j omega[f] C[b] as ``ac_solve`` -- same pivot
@@ -395,7 +400,7 @@ class Handle:
         B, n, F, K = self.B, self.st.n, om.size, pr.shape[0]
         if F == 0:
             return (np.zeros((B, 0, K), dtype=complex), np.zeros((B, 0, n), dtype=complex) if want_x else None, np.zeros((B, 0)),
-                    np.zeros((B, 0), dtype=np.int32), dict(wpb=0, lds_bytes=0, systems=0, workgroups=0))
+                    np.zeros((B, 0), dtype=np.int32), _ac_info())
         cc = np.ascontiguousarray(np.broadcast_to(np.asarray(c, dtype=np.complex128), (B, n)))
         hh = np.empty((B, F, K), dtype=np.complex128)
         x = np.empty((B, F, n), dtype=np.complex128) if want_x else None
@@ -403,7 +408,7 @@ class Handle:
         _check(self.lib.cadnip_ac_adjoint(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), cc.ctypes.data_as(_D), C.c_int32(K),
                                           _ip(pr) if K else None, C.c_int32(int(wpb)), hh.ctypes.data_as(_D), None if x is None else x.ctypes.data_as(_D),
                                           _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_adjoint")
-        return hh, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+        return hh, x, berr, flags, _ac_info(info)
 
     def ac_solve_multi(self, omega, gmin, b, pairs=None, wpb=0, want_x=True, x_out=None):
         """cadnip_ac_solve_multi: x[b, f, k] = A[b, f]^-1 b[b, k] for K right-hand sides per instance against ONE factorisation per system, A and
@@ -442,11 +447,11 @@ class Handle:
         x = x_out if x_out is not None else np.empty((B, F, K, n), dtype=np.complex128) if want_x else None
         berr, flags, info = np.empty((B, F, K)), np.zeros((B, F, K), dtype=np.int32), np.zeros(4, dtype=np.int32)
         if F == 0:
-            return hh, x, berr, flags, dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
+            return hh, x, berr, flags, _ac_info()
         _check(getattr(self.lib, entry)(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), C.c_int32(K), bb.ctypes.data_as(_D), C.c_int32(P),
                                         _ip(pr) if P else None, C.c_int32(int(wpb)), None if hh is None else hh.ctypes.data_as(_D),
                                         None if x is None else x.ctypes.data_as(_D), _dp(berr), _ip(flags), _ip(info)), entry)
-        return hh, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+        return hh, x, berr, flags, _ac_info(info)
 
     def ac_sens(self, omega, gmin, base, plus, minus, scale, b_ac, c, pair, db=None, wpb=0, want_x=False):
         """cadnip_ac_sens: per (base instance, frequency) the response y = x[p] - x[n] of A x = b_ac and its derivatives with respect to K
@@ -482,12 +487,12 @@ class Handle:
         x = np.empty((NB, F, 2, n), dtype=np.complex128) if want_x else None
         berr, flags, info = np.empty((NB, F, 2)), np.zeros((NB, F, K), dtype=np.int32), np.zeros(4, dtype=np.int32)
         if F == 0:
-            return y, s, x, berr, flags, dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
+            return y, s, x, berr, flags, _ac_info()
         _check(self.lib.cadnip_ac_sens(self.h, C.c_int32(F), _dp(om), C.c_double(gmin), C.c_int32(NB), _ip(bs), C.c_int32(K), _ip(pl), _ip(mi), _dp(sc),
                                        bb.ctypes.data_as(_D), None if dd is None else dd.ctypes.data_as(_D), cc.ctypes.data_as(_D), _ip(pr),
                                        C.c_int32(int(wpb)), y.ctypes.data_as(_D), s.ctypes.data_as(_D), None if x is None else x.ctypes.data_as(_D),
                                        _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_sens")
-        return y, s, x, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+        return y, s, x, berr, flags, _ac_info(info)
 
     def ac_arnoldi(self, omega, gmin, b, m, pairs=None, breakdown_tol=AC_BREAKDOWN_TOL, wpb=0, want_v=False):
         """cadnip_ac_arnoldi: per (instance, shift) m steps of shift-invert Arnoldi on K = A^-1 C started at A^-1 b, A = G + gmin + j omega[s] C as
@@ -514,12 +519,12 @@ class Handle:
         V = np.zeros((B, S, mm + 1, n), dtype=np.complex128) if want_v else None
         berr, flags, info = np.zeros((B, S)), np.zeros((B, S), dtype=np.int32), np.zeros(4, dtype=np.int32)
         if S == 0:
-            return H, beta, meff, ll, V, berr, flags, dict(wpb=0, lds_bytes=0, systems=0, workgroups=0)
+            return H, beta, meff, ll, V, berr, flags, _ac_info()
         _check(self.lib.cadnip_ac_arnoldi(self.h, C.c_int32(S), _dp(om), C.c_double(gmin), bb.ctypes.data_as(_D), C.c_int32(m), C.c_double(breakdown_tol),
                                           C.c_int32(P), _ip(pr) if P else None, C.c_int32(int(wpb)), H.ctypes.data_as(_D), _dp(beta), _ip(meff),
                                           None if ll is None else ll.ctypes.data_as(_D), None if V is None else V.ctypes.data_as(_D),
                                           _dp(berr), _ip(flags), _ip(info)), "cadnip_ac_arnoldi")
-        return H, beta, meff, ll, V, berr, flags, dict(zip(("wpb", "lds_bytes", "systems", "workgroups"), (int(v) for v in info)))
+        return H, beta, meff, ll, V, berr, flags, _ac_info(info)
 
     def ac_set_memory(self, mode="lds", max_waves=0):
         """cadnip_ac_set_memory: where ``ac_solve`` / ``ac_adjoint`` keep a system's work arrays from now on.  "lds" (the default of a new handle):

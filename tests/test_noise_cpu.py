@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import cadnip_jl_amd as cj
-from cadnip_jl_amd import api, netlist, va
+from cadnip_jl_amd import api, hip, netlist, va
 from oracle import mna_ref as M
 from oracle.netlist_ref import make_builder
 
@@ -209,3 +209,81 @@ def test_builtin_diode_flicker_noise(kind):
     assert np.allclose(on, expected, rtol=1e-5) and on[0] > 1.5 * on[2]          # the flicker term is visible at 1 Hz
     ns = product_noise_at_the_oracle_point(c, "out", freqs)
     assert np.allclose(ns["onoise"], on, rtol=1e-10) and np.allclose(ns["d1"], cc["d1"], rtol=1e-10)
+
+
+class StubHandle:
+    """Handle.analyze_values / ac_adjoint of the gate test: dense transposed solves, with chosen (point, frequency) systems spoiled; ``fit``
+    False: the call raises as for a circuit the launch plan refuses"""
+
+    def __init__(self, Gd, Cd, spoil, fit=True):
+        self.Gd, self.Cd, self.spoil, self.fit, self.calls = Gd, Cd, spoil, fit, 0
+
+    def analyze_values(self, sample_ref):
+        pass
+
+    def ac_adjoint(self, omega, gmin, c, pairs, wpb=0, want_x=False):
+        self.calls += 1
+        if not self.fit:
+            raise hip.CadnipError(hip.BADARG, "cadnip_ac_adjoint")
+        B, F, n = len(self.Gd), len(omega), len(c)
+        x, berr, flags = np.zeros((B, F, n), complex), np.zeros((B, F)), np.zeros((B, F), dtype=np.int32)
+        for k in range(B):
+            for f, w in enumerate(omega):
+                x[k, f] = np.linalg.solve((1j * w * self.Cd[k] + self.Gd[k]).T, c)
+        pr = np.asarray(pairs).reshape(-1, 2)
+        h = np.where(pr[:, 0] >= 0, x[..., pr[:, 0]], 0.0) - np.where(pr[:, 1] >= 0, x[..., pr[:, 1]], 0.0)
+        for (k, f), kind in self.spoil.items():
+            h[k, f] = 123.0
+            if kind == "flag":
+                flags[k, f] = 1
+            else:
+                berr[k, f] = np.nan if kind == "nan" else 2 * api.NOISE_BERR_MAX
+        return h, None, berr, flags, dict(wpb=4, lds_bytes=0, systems=B * F, workgroups=0)
+
+
+def _rc_class():
+    """the RC low-pass as a structure class of two points: (st, Gd, Cd, sources per point, temperatures, G_ref = C_ref) -- the second point
+    has twice the conductances and runs at 85 degrees"""
+    circ = netlist.read_spice(RC)[0]
+    st = cj.discover(circ, {})
+    G = np.zeros((st.n, st.n))
+    i, o, v = st.index_of("in"), st.index_of("out"), api.noise_indices(st, "out", "V1")[1]
+    G[i, i] = G[o, o] = 1e-3
+    G[i, o] = G[o, i] = -1e-3
+    G[i, v] = G[v, i] = 1.0
+    G[np.arange(st.n_nodes), np.arange(st.n_nodes)] += 1e-12
+    C = np.zeros((st.n, st.n))
+    C[o, o] = 1e-6
+    temps = [27.0, 85.0]
+    srcs = [api.noise_sources(st, circ, {}, np.zeros(st.n), t) for t in temps]
+    return st, [G, 2.0 * G], [C, C], srcs, temps, np.zeros((2, st.nnz))
+
+
+def test_noise_solve_gpu_gate_on_a_stub_handle():
+    """noise_solve_gpu on a stub handle: one call for the class; a system with its flag set, a backward error above NOISE_BERR_MAX or a NaN one
+    is solved again by the host's adjoint solve; the accounting; the fallback of "auto"; no probe pairs, no launch"""
+    st, Gd, Cd, srcs, temps, ref = _rc_class()
+    freqs = np.array([1.0, 1e3, 1e6])
+    host = [api.noise_solve(st, Gd[k], Cd[k], srcs[k], "out", freqs, "V1", temps[k]) for k in range(2)]
+    stub = StubHandle(Gd, Cd, {(0, 1): "flag", (1, 0): "berr", (1, 2): "nan"})
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    got = api.noise_solve_gpu(stub, st, ref, ref, Gd, Cd, srcs, "out", freqs, "V1", temps, 1e-12, "gpu", stats)
+    assert stub.calls == 1 and stats == {"gpu_systems": 3, "host_systems": 3, "max_berr": 0.0, "wpb": 4, "memory": "lds"}
+    for k in range(2):
+        assert got[k].stats is stats and got[k].temp == temps[k]
+        assert np.allclose(got[k]["onoise"], host[k]["onoise"], rtol=1e-13, atol=0.0)
+        assert np.allclose(got[k].gain, host[k].gain, rtol=1e-13, atol=0.0) and np.allclose(got[k]["inoise"], host[k]["inoise"], rtol=1e-13, atol=0.0)
+    # a circuit the launch plan refuses: "auto" is the host path, "gpu" raises
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    refused = StubHandle(Gd, Cd, {}, fit=False)
+    got = api.noise_solve_gpu(refused, st, ref, ref, Gd, Cd, srcs, "out", freqs, "V1", temps, 1e-12, "auto", stats)
+    assert refused.calls == 1 and stats["gpu_systems"] == 0 and stats["host_systems"] == 6 and "fallback" in stats and "memory" not in stats
+    for k in range(2):
+        assert got[k].stats is stats and np.array_equal(got[k]["onoise"], host[k]["onoise"]) and np.array_equal(got[k]["inoise"], host[k]["inoise"])
+    with pytest.raises(hip.CadnipError):
+        api.noise_solve_gpu(refused, st, ref, ref, Gd, Cd, srcs, "out", freqs, "V1", temps, 1e-12, "gpu", dict(stats))
+    # no source and no input: nothing to probe
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    idle = StubHandle(Gd, Cd, {})
+    got = api.noise_solve_gpu(idle, st, ref, ref, Gd, Cd, [[], []], "out", freqs, None, temps, 1e-12, "gpu", stats)
+    assert idle.calls == 0 and stats["host_systems"] == 6 and stats["gpu_systems"] == 0 and np.all(got[0]["onoise"] == 0.0)

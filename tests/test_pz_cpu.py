@@ -193,3 +193,48 @@ def test_the_port_alone_finds_the_flip_flops_poles():
         err = Z.match_error(sol.poles, dense, sol.pole_shift)
         print("dff corner %d: %d accepted, %d closed spaces, worst error %.3g" % (k, len(sol.poles), nb, err.max()))
         assert len(sol.poles) >= DFF_MIN_ACCEPTED and np.all(sol.pole_resid <= api.PZ_RESID_MAX)
+
+
+class StubHandle:
+    """Handle.analyze_values / ac_arnoldi of the gate test: zero arrays of the documented shapes with chosen flags and backward errors; ``fit``
+    False: the call raises as for a circuit the memory setting refuses"""
+
+    def __init__(self, n, flags, berr, fit=True):
+        self.n, self.flags, self.berr, self.fit, self.calls, self.samples = n, flags, berr, fit, 0, 0
+
+    def analyze_values(self, sample_ref):
+        self.samples += 1
+
+    def ac_arnoldi(self, omega, gmin, b, m, pairs=None, breakdown_tol=TOL, wpb=0, want_v=False):
+        self.calls += 1
+        if not self.fit:
+            raise hip.CadnipError(hip.BADARG, "cadnip_ac_arnoldi")
+        B, S, P = len(b), len(omega), len(pairs)
+        berr, flags = np.zeros((B, S)), np.zeros((B, S), dtype=np.int32)
+        for k, v in self.flags.items():
+            flags[k] = v
+        for k, v in self.berr.items():
+            berr[k] = v
+        return (np.zeros((B, S, m + 1, m), complex), np.zeros((B, S)), np.zeros((B, S), dtype=np.int32), np.zeros((B, S, m, P), complex), None,
+                berr, flags, dict(wpb=4, lds_bytes=0, systems=B * S, workgroups=0))
+
+
+def test_pz_gpu_sweep_gate_on_a_stub_handle():
+    """pz_gpu_sweep on a stub handle: flag bits 0 and 1 reject a system, bit 2 (the space closed) does not; a backward error above AC_BERR_MAX
+    or a NaN one rejects; the accounting; the fallback of "auto" names the host Arnoldi"""
+    st, G, C, b, c = system("ladder4")
+    out = (int(np.flatnonzero(c)[0]), -1)
+    omegas, ref, rhs = np.array([0.0, 1e5, 1e6]), np.zeros((2, st.nnz)), np.array([b, b])
+    stub = StubHandle(st.n, {(0, 0): 1, (0, 1): 2, (0, 2): 4}, {(1, 0): np.nan, (1, 1): 2 * api.AC_BERR_MAX, (1, 2): 1e-10})
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    H, beta, meff, l, redo = api.pz_gpu_sweep(stub, st, ref, ref, rhs, out, omegas, 2, Z.GMIN, "gpu", stats)
+    assert stub.calls == 1 and stub.samples == 1
+    assert H.shape == (2, 3, 3, 2) and beta.shape == meff.shape == (2, 3) and l.shape == (2, 3, 2, 1)
+    assert redo.tolist() == [[True, True, False], [True, True, False]]
+    assert stats == {"gpu_systems": 2, "host_systems": 4, "max_berr": 1e-10, "wpb": 4, "memory": "lds"}
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0}
+    refused = StubHandle(st.n, {}, {}, fit=False)
+    assert api.pz_gpu_sweep(refused, st, ref, ref, rhs, out, omegas, 2, Z.GMIN, "auto", stats) is None
+    assert refused.calls == 1 and stats["gpu_systems"] == 0 and stats["host_systems"] == 6 and "Arnoldi" in stats["fallback"] and "memory" not in stats
+    with pytest.raises(hip.CadnipError):
+        api.pz_gpu_sweep(refused, st, ref, ref, rhs, out, omegas, 2, Z.GMIN, "gpu", dict(stats))

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import cadnip_jl_amd as cj
-from cadnip_jl_amd import api
+from cadnip_jl_amd import api, hip
 from tests import ac_ref as R
 from tests import noise_ref as N
 from tests import sens_ref as SR
@@ -146,3 +146,69 @@ def test_a_step_across_a_structure_class_names_the_parameter():
     mc = api.MNACircuit(circ, {"rd": 0.0, "vg": 1.5})
     with pytest.raises(ValueError, match="rd"):
         api.sensitivity(mc, "I_vd", ["vg", "rd"], [1e3])
+
+
+class StubHandle:
+    """Handle.analyze_values / ac_sens of the gate test: ``solve(a, omegas)`` -- sensitivity_solve per base -- with chosen (base, frequency)
+    systems spoiled; ``fit`` False: the call raises as for a circuit the memory setting refuses"""
+
+    def __init__(self, solve, spoil, fit=True):
+        self.solve, self.spoil, self.fit, self.calls, self.samples = solve, spoil, fit, 0, 0
+
+    def analyze_values(self, sample_ref):
+        self.samples += 1
+
+    def ac_sens(self, omega, gmin, base, plus, minus, scale, b_ac, c, pair, db=None, wpb=0, want_x=False):
+        self.calls += 1
+        if not self.fit:
+            raise hip.CadnipError(hip.BADARG, "cadnip_ac_sens")
+        NB, F, K = len(base), len(omega), np.shape(plus)[1]
+        got = [self.solve(a, omega) for a in range(NB)]
+        y, s = np.array([g[0] for g in got]), np.array([g[1] for g in got])
+        berr, flags = np.zeros((NB, F, 2)), np.zeros((NB, F, K), dtype=np.int32)
+        for (a, f), kind in self.spoil.items():
+            if kind != "control":
+                y[a, f], s[a, f] = 123.0, 123.0
+            if kind == "flag":
+                flags[a, f, 1] = 2
+            elif kind == "adjoint":
+                berr[a, f, 1] = 2 * api.NOISE_BERR_MAX
+            else:
+                berr[a, f, 0] = np.nan if kind == "nan" else 2 * api.AC_BERR_MAX if kind == "forward" else 2 * api.NOISE_BERR_MAX
+        return y, s, None, berr, flags, dict(wpb=4, lds_bytes=0, systems=NB * F, workgroups=0)
+
+
+def test_sens_gpu_sweep_gate_on_a_stub_handle():
+    """sens_gpu_sweep on a stub handle, the inverter's three points as two bases of K = 2 parameters: a system with a flag in one column, a
+    forward backward error above AC_BERR_MAX, an adjoint one above NOISE_BERR_MAX or a NaN is solved again by the host; a forward error of
+    2 NOISE_BERR_MAX -- far below AC_BERR_MAX -- is accepted (the two bounds must not be swapped); the accounting; the fallback of "auto\""""
+    st, G, C, bac, om = R.port_case("inverter")
+    out = (N.output_index("inverter", st), -1)
+    omegas = om[:: len(om) // 4][:4]
+    NB, K = 2, 2
+    Gd, Cd = [SR.dense_G(st, G[a], GMIN) for a in range(NB)], [R.dense_csr(st, C[a]) for a in range(NB)]
+    dG = np.array([R.dense_csr(st, G[2] - G[0]), R.dense_csr(st, G[1] - G[0])])
+    dC = np.array([R.dense_csr(st, C[2] - C[0]), R.dense_csr(st, C[1] - C[0])])
+    solves = []
+    host = lambda a: lambda w: (solves.append((a, tuple(w))), api.sensitivity_solve(st, Gd[a], Cd[a], bac[a], dG, dC, None, out, w))[1]
+    want = [api.sensitivity_solve(st, Gd[a], Cd[a], bac[a], dG, dC, None, out, omegas) for a in range(NB)]
+    spoil = {(0, 0): "flag", (0, 2): "forward", (1, 1): "adjoint", (1, 3): "nan", (0, 3): "control"}
+    stub = StubHandle(lambda a, w: api.sensitivity_solve(st, Gd[a], Cd[a], bac[a], dG, dC, None, out, w), spoil)
+    base, plus, minus, scale = np.array([0, 3], dtype=np.int32), np.zeros((NB, K), dtype=np.int32), np.zeros((NB, K), dtype=np.int32), np.ones((NB, K))
+    ref = np.zeros((6, st.nnz))
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0, "params": K}
+    got = api.sens_gpu_sweep(stub, st, ref, ref, base, plus, minus, scale, bac[:NB], out, None, omegas, GMIN, "gpu", stats, host)
+    assert stub.calls == 1 and stub.samples == 1
+    assert stats == {"gpu_systems": 4, "host_systems": 4, "max_berr": 2 * api.NOISE_BERR_MAX, "wpb": 4, "params": K, "memory": "lds"}
+    assert sorted(solves) == [(0, (omegas[0], omegas[2])), (1, (omegas[1], omegas[3]))]      # one host call per base, at its rejected frequencies
+    for a in range(NB):
+        y, s = got[a]
+        assert y.shape == (4,) and s.shape == (4, K)
+        # the stub's numbers are sensitivity_solve's: a redone system and an untouched one both equal them, a spoiled one that was kept does not
+        assert np.array_equal(y, want[a][0]) and np.array_equal(s, want[a][1]), a
+    stats = {"gpu_systems": 0, "host_systems": 0, "max_berr": 0.0, "wpb": 0, "params": K}
+    refused = StubHandle(None, {}, fit=False)
+    assert api.sens_gpu_sweep(refused, st, ref, ref, base, plus, minus, scale, bac[:NB], out, None, omegas, GMIN, "auto", stats, host) is None
+    assert refused.calls == 1 and stats["gpu_systems"] == 0 and stats["host_systems"] == 8 and "host solve" in stats["fallback"] and "memory" not in stats
+    with pytest.raises(hip.CadnipError):
+        api.sens_gpu_sweep(refused, st, ref, ref, base, plus, minus, scale, bac[:NB], out, None, omegas, GMIN, "gpu", dict(stats), host)

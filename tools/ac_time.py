@@ -140,10 +140,7 @@ def run_overlay(n_ovl, memory, reps, B=64, gmin=1e-12):
     try:
         st, h = sim.st, sim.h
         G, C, _, _ = h.get_GCb()
-        to_ref = np.asarray(st.to_ref_nz)
-        sample_ref = np.empty(st.nnz)
-        sample_ref[to_ref] = api.ac_pivot_sample(st, G[:, to_ref], C[:, to_ref], omegas, gmin)
-        h.analyze_values(sample_ref)
+        api.ac_analyze_pivots(h, st, G, C, omegas, gmin)
         h.ac_set_memory(memory)
         b_ac = np.tile(b_ac1, (B, 1))
         pos = np.unique(np.linspace(0, st.nnz - 1, n_ovl).round().astype(np.int32))

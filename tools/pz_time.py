@@ -53,10 +53,8 @@ def run(B, memory, reps, orders, n_shifts, dense_points, gmin=1e-12):
     try:
         st, h, n = sim.st, sim.h, sim.st.n
         G, C, _, _ = h.get_GCb()
+        api.ac_analyze_pivots(h, st, G, C, omegas, gmin)
         to_ref = np.asarray(st.to_ref_nz)
-        sample_ref = np.empty(st.nnz)
-        sample_ref[to_ref] = api.ac_pivot_sample(st, np.asarray(G)[:, to_ref], np.asarray(C)[:, to_ref], omegas, gmin)
-        h.analyze_values(sample_ref)
         h.ac_set_memory(memory)
         rows = np.repeat(np.arange(n), np.diff(st.rowptr))
         Gd, Cd = np.zeros((B, n, n)), np.zeros((B, n, n))

@@ -35,10 +35,7 @@ def run(B, circuit, memory, reps, K, gmin=1e-12):
     try:
         st, h, n = sim.st, sim.h, sim.st.n
         G, C, _, _ = h.get_GCb()
-        to_ref = np.asarray(st.to_ref_nz)
-        sample_ref = np.empty(st.nnz)
-        sample_ref[to_ref] = api.ac_pivot_sample(st, np.asarray(G)[:, to_ref], np.asarray(C)[:, to_ref], omegas, gmin)
-        h.analyze_values(sample_ref)
+        api.ac_analyze_pivots(h, st, G, C, omegas, gmin)
         h.ac_set_memory(memory)
         base = np.arange(B) * per
         plus = base[:, None] + 1 + 2 * np.arange(K)[None, :]
