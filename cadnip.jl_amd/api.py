@@ -403,15 +403,89 @@ class BatchSimulator:
             total["stages"] += 1
         return u, conv, total
 
-    def tran(self, tspan, abstol, reltol, saveat, initializealg="tranop", u0=None, warmup_dt=1e-12, **kw):
+    def tran(self, tspan, abstol, reltol, saveat, initializealg="tranop", u0=None, warmup_dt=1e-12, delays="refuse", delay_depth=0, **kw):
         """``initializealg``: "tranop" = CedarTranOp, a DC solve in :tranop mode at t0 (dcop.jl:160-212); "uic" = CedarUICOp
         (dcop.jl:109-151, 304-411): no DC solve -- the run starts from ``u0`` (zeros by default) and the integrator's first
         steps, backward Euler from ``warmup_dt``, relax the algebraic constraints (for oscillators and for circuits whose
-        static operating point Newton does not find)."""
+        static operating point Newton does not find).
+
+        ``delays``: what to do with delayed controlled sources and transmission lines.  "refuse" (the default, and for now the only
+        behaviour a caller gets without asking: flipping it is a later change): NotImplementedError.  "history": the terms of
+        ``ac_delay_overlay`` go to the handle (``hip.Handle.tran_set_delay``), which integrates with the delayed values read from a ring
+        of ``delay_depth`` (0 = 1024) accepted points per instance, linearly interpolated; the steps are clamped to the smallest delay,
+        the source break points are propagated through the delays (``delay_breakpoints``; stats["delay_breaks"] /
+        ["delay_breaks_truncated"]), and the run uses the per-op kernels whatever ``fused`` says.  A delay that is not positive and
+        finite at any point is a ValueError.  A circuit without a delayed element runs exactly as without the keyword."""
         st = self.st
         if initializealg not in ("tranop", "uic"):
             raise ValueError("initializealg must be 'tranop' or 'uic'")
+        if delays not in ("refuse", "history"):
+            raise ValueError("delays must be 'refuse' or 'history'")
         breaks = expand_breakpoints(st.breakpoints, tspan)
+        if self.mc is not None and has_delay(self.mc.circuit):
+            if delays == "refuse":
+                refuse_delay(self.mc.circuit, "tran", "a transient needs the delayed quantity's history: ask for it with delays=\"history\" "
+                             "(without it a delay-differential integrator is not built into the call)")
+            return self._tran_delayed(tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, delay_depth, breaks, kw)
+        return self._tran(tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, breaks, kw)
+
+    def _tran_delayed(self, tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, delay_depth, breaks, kw):
+        """the run of ``tran`` under delays="history": spec on the handle, propagated break points, spec off again"""
+        spec = self.delay_spec()
+        breaks, n_new, truncated = delay_breakpoints(breaks, spec["tau"], tspan)
+        self.h.tran_set_delay(depth=delay_depth, **spec)
+        restore = []
+        try:
+            # the initialisation (a DC solve on G, delays ignored) keeps the order it has; the time loop solves G - W and gets its own
+            out, per, stats = self._tran(tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, breaks, kw,
+                                         before_run=lambda: restore.append(self.analyze_delayed(spec, tspan[0])))
+        finally:
+            self.h.tran_clear_delay()
+            if restore:
+                self.h.analyze_values(restore[0])
+        stats["delay_breaks"], stats["delay_breaks_truncated"] = n_new, truncated
+        return out, per, stats
+
+    def delay_spec(self):
+        """The delayed stamps of the circuit at the simulator's points as ``hip.Handle.tran_set_delay`` takes them, from the one pure function
+        (``ac_delay_overlay`` without a grid): {pos, term_pos, term_row, term_col, tau [B, T], w [B, T]}.  A delay that is not positive and
+        finite at any point is a ValueError."""
+        ovl = ac_delay_overlay(self.st, self.mc.circuit, self.params, omegas=(), B=self.B)
+        tau = np.array([t for _, t, _ in ovl.terms]).T.reshape(self.B, len(ovl.terms))
+        w = np.array([wt for _, _, wt in ovl.terms]).T.reshape(self.B, len(ovl.terms))
+        if not np.all(np.isfinite(tau) & (tau > 0.0)):
+            raise ValueError("tran: every delay must be positive and finite at every point (a zero delay is no delay: leave it out of the circuit)")
+        o = np.array([k for k, _, _ in ovl.terms], dtype=np.int64)
+        return dict(pos=ovl.pos, term_pos=o, term_row=ovl.rows[o], term_col=ovl.cols[o], tau=tau, w=w)
+
+    def analyze_delayed(self, spec, t=0.0):
+        """Symbolic LU phase for the matrix a delayed transient solves, G - W + a0 C (``spec``: ``delay_spec()``).  The composite sample of
+        ``analyze`` holds the delayed stamps as if they were coefficients of the present state, and a pivot chosen on one of them -- the gain
+        entry of a line's E elements is the largest of its row -- is an exact zero in G - W.  So the sample is taken again with what is LEFT
+        at the delayed positions once W is gone (measured on the stamps at the handle's current state, which is preserved); a position only
+        delayed stamps fill enters as zero and is never a pivot.  Returns the sample that was in force (``h.analyze_values`` of it restores
+        the order)."""
+        u = self.h.get_u()
+        if getattr(self, "pivot_sample", None) is None:
+            self.analyze()
+        base = np.array(self.pivot_sample, dtype=float)
+        to_ref = np.asarray(self.st.to_ref_nz)
+        W = np.zeros((self.B, len(spec["pos"])))
+        for k, o in enumerate(spec["term_pos"]):
+            W[:, o] += spec["w"][:, k]
+        self.h.rebuild(u, t)
+        G = self.h.get_GCb()[0][:, to_ref]
+        csr = base[to_ref]
+        csr[spec["pos"]] = np.max(np.abs(G[:, spec["pos"]] - W), axis=0)
+        sample = base.copy()
+        sample[to_ref] = csr
+        self.h.analyze_values(sample)
+        self.h.set_u(u)
+        self._analyzed = True
+        return base
+
+    def _tran(self, tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, breaks, kw, before_run=lambda: None):
+        st = self.st
         if initializealg == "uic":
             if isinstance(u0, dict):          # {unknown name: value}: the usual .IC form
                 start = np.zeros((self.B, st.n))
@@ -424,6 +498,7 @@ class BatchSimulator:
             self.h.set_u(start)
             self.h.set_spec(mode="tran")
             kw.setdefault("h0", warmup_dt)
+            before_run()
             out, per, stats = self.h.tran_run(tspan[0], tspan[1], abstol, reltol, breaks=breaks, save_t=saveat, **kw)
             stats["dc_newton_iters"] = 0
             return out, per, stats
@@ -433,6 +508,7 @@ class BatchSimulator:
         if not np.all(conv):
             raise RuntimeError("transient initialisation (CedarTranOp) failed for %d instance(s)" % int((~conv).sum()))
         self.h.set_spec(mode="tran")
+        before_run()
         out, per, stats = self.h.tran_run(tspan[0], tspan[1], abstol, reltol, breaks=breaks, save_t=saveat, **kw)
         stats["dc_newton_iters"] = dcs["newton_iters"]
         return out, per, stats
@@ -2085,10 +2161,76 @@ def pz(target, output, input=None, shifts=(0.0,), order=16, gmin=1e-12, device=0
     return SweepResult(pts, sols) if sweep else sols[0]
 
 
+TRAN_RETCODES = {1: "Success", -4: "DelayHistoryOverflow"}      # per-instance status of cadnip_tran_run -> TranSolution.retcode; anything else: "Failure"
+
+
+def delay_breakpoints(breaks, taus, tspan, max_points=100000):
+    """Source break points propagated through transport delays: a kink of a source at t_b reappears at t_b + sum k_i tau_i wherever a delayed
+    element passes it on, so those times join the stop list.  ``breaks``: the sorted stop times inside ``tspan``
+    (``structure.expand_breakpoints``); the start of the run, where every source leaves its DC value, is a seed as well.  ``taus``: the
+    delays of all terms at all points -- the break list is global, so the images are taken over the distinct values of all instances.
+    Generated breadth-first, by number of delays added, until nothing new falls inside ``tspan`` or the total reaches ``max_points`` (the
+    cap of ``expand_breakpoints``); sorted and deduplicated by that function's 4-ulp rule.  Returns (stop times, number added, truncated)."""
+    import bisect
+    import math
+    t0, t1 = float(tspan[0]), float(tspan[1])
+    near = lambda a, b: abs(a - b) <= 4 * max(math.ulp(a), math.ulp(b))
+
+    def dedupe(ts):
+        out = []
+        for t in sorted(ts):
+            if not out or not near(out[-1], t):
+                out.append(t)
+        return out
+
+    def known(ts, t):
+        k = bisect.bisect_left(ts, t)
+        return any(0 <= j < len(ts) and near(ts[j], t) for j in (k - 1, k))
+
+    taus = sorted({float(x) for x in np.ravel(taus)})
+    pts = dedupe(float(b) for b in breaks)
+    n_base, level, truncated = len(pts), [t0] + pts, False
+    while level and taus and not truncated:
+        new = [t for t in dedupe(t + tau for t in level for tau in taus if t0 < t + tau < t1) if not known(pts, t)]
+        if len(pts) + len(new) > max_points:
+            new, truncated = new[:max(max_points - len(pts), 0)], True
+        pts = dedupe(pts + new)
+        level = new
+    return pts, len(pts) - n_base, truncated
+
+
+def _check_delays(target):
+    """every delay of the circuit at every point of the target is a positive finite number, or ValueError -- before any device work"""
+    from .circuit import resolve
+    mc = target.circuit if isinstance(target, CircuitSweep) else target
+    pts = target.points() if isinstance(target, CircuitSweep) else [{}]
+    for d in mc.circuit.devices:
+        if "delay" not in d.params:
+            continue
+        for pt in pts:
+            p = dict(mc.params)
+            p.update({k: v for k, v in pt.items() if k != "temp"})
+            tau = float(resolve(d.params["delay"], p))
+            if not (np.isfinite(tau) and tau > 0.0):
+                raise ValueError("tran: the delay of %s is %r at the point %r; every delay must be positive and finite (a zero delay is no delay: "
+                                 "leave it out of the circuit)" % (d.name, tau, pt))
+
+
 def tran(target, tspan, abstol=1e-10, reltol=1e-8, saveat=None, device=0, **kw):
-    """tran!(circuit, tspan) / tran!(cs::CircuitSweep, tspan) -- sweeps.jl:588-665, 692-707."""
-    refuse_delay((target.circuit if isinstance(target, CircuitSweep) else target).circuit, "tran",
-                 "a transient needs the delayed quantity's history, and a delay-differential integrator is not built")
+    """tran!(circuit, tspan) / tran!(cs::CircuitSweep, tspan) -- sweeps.jl:588-665, 692-707.
+
+    A circuit with delayed controlled sources or transmission lines (``Circuit.E/G/H/F(..., delay=)``, ``Circuit.T``, ``TD=`` in a deck) is
+    refused (NotImplementedError) unless the call says ``delays="history"``: then the handle keeps a history ring of ``delay_depth``
+    accepted points per instance and integrates the delay-differential system (``BatchSimulator.tran``).  "refuse"
+    stays the default for now -- flipping it is a later change.  An instance whose delayed look-up fell off the ring has retcode
+    "DelayHistoryOverflow"."""
+    if kw.get("delays", "refuse") not in ("refuse", "history"):
+        raise ValueError("delays must be 'refuse' or 'history'")
+    if kw.get("delays", "refuse") == "refuse":
+        refuse_delay((target.circuit if isinstance(target, CircuitSweep) else target).circuit, "tran",
+                     "a transient needs the delayed quantity's history: ask for it with delays=\"history\" (without it a delay-differential integrator is not built into the call)")
+    else:
+        _check_delays(target)
     tspan = (float(tspan[0]), float(tspan[1]))
     if saveat is None:
         saveat = np.linspace(tspan[0], tspan[1], 501)
@@ -2102,7 +2244,7 @@ def tran(target, tspan, abstol=1e-10, reltol=1e-8, saveat=None, device=0, **kw):
         sols = []
         for i in range(sim.B):
             s = {"nnonliniter": int(per[i, 0]), "naccept": int(per[i, 1]), "nreject": int(per[i, 2])}
-            sols.append(TranSolution(sim.st, saveat, out[i], s, "Success" if per[i, 3] == 1 else "Failure"))
+            sols.append(TranSolution(sim.st, saveat, out[i], s, TRAN_RETCODES.get(int(per[i, 3]), "Failure")))
         if isinstance(target, CircuitSweep):
             res = SweepResult(target.points(), sols)
             res.stats = stats

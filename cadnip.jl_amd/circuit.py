@@ -60,10 +60,11 @@ class Circuit:
     def I(self, name, p, n, dc=0.0, wave=None, scale=1.0, ac=0.0):
         return self._add("I", name, (p, n), {"dc": dc, "scale": scale, "ac": ac}, wave=wave)
 
-    # ``delay``: a transport delay (seconds; a number or a Param) on the controlled quantity -- Verilog-A's absdelay.  It exists in the frequency
-    # domain only: the AC analyses multiply the stamps that carry the gain by e^{-j w delay} (api.ac_delay_overlay); at DC it is ignored, as an
-    # absdelay without history is; nothing the stamping reads changes, and the analyses that would need its history refuse such a circuit.
-    # Without a delay the device row is exactly what it was.
+    # ``delay``: a transport delay (seconds; a number or a Param) on the controlled quantity -- Verilog-A's absdelay.  The AC analyses multiply
+    # the stamps that carry the gain by e^{-j w delay} (api.ac_delay_overlay); a transient asked for with delays="history" takes the same
+    # stamps out of G and puts them, times the delayed value from a history ring in device memory, on the right-hand side (csrc/delay.hip),
+    # and refuses such a circuit without that keyword; at DC the delay is ignored, as an absdelay without history is.  Nothing the stamping
+    # reads changes: without a delay the device row is exactly what it was.
     def E(self, name, op, on, ip, in_, gain, delay=0.0):
         return self._add("E", name, (op, on, ip, in_), _delayed({"gain": gain}, delay))
 

@@ -465,13 +465,20 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
   HIP_TRY(hipMemcpy(d->emask, emask.data(), n * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (o->max_order >= 3) { TRY(dalloc(&d->u3, B * n)); TRY(dalloc(&d->hp3, B)); }
-  const TranArgs a = tran_args(h, o, n_obs, n_err);
+  TranArgs a = tran_args(h, o, n_obs, n_err);
+  // Delayed stamps (cadnip_tran_set_delay, delay.hip): no step may reach past the smallest delay, so that the delayed value is a known number
+  // for the whole step -- the same in every Newton round, the Jacobian G_tran + a0 C exact.  The rows of b that only k_delay_apply writes
+  // are cleared on every exit path: the handle leaves with the b of its own stamps
+  const bool delayed = h->dly.n_term > 0;
+  if (delayed) { a.hmax = fmin(a.hmax, h->dly.tau_min); a.h0 = fmin(a.h0, a.hmax); }
+  struct DelayGuard { CadnipHandle* h; bool on; ~DelayGuard() { if (on) { (void)launch_delay_clear(h); (void)hipStreamSynchronize(h->stream); } } } delay_guard{h, delayed};
   // the per-op kernels take over where the fused kernel cannot run: external generated models (they exist in the per-op stamping kernel only), a
-  // circuit too large for the LDS-resident kernel, Newton mode 1 on a circuit outside the lean device set
+  // circuit too large for the LDS-resident kernel, Newton mode 1 on a circuit outside the lean device set, a handle with delayed stamps
   const bool use_fused = o->fused && fused2_plan(h, F2_TRAN, o->newton_mode).circuit_ok;
   struct ModeGuard { CadnipHandle* h; int saved; ~ModeGuard() { h->spec.mode = saved; } } mode_guard{h, h->spec.mode};
   h->spec.mode = 1;   // :tran (restored on every exit path)
   hipLaunchKernelGGL(k_tran_init, dim3(h->B), dim3(64), 0, h->stream, a);
+  if (delayed) TRY(launch_delay_init(h, a.t0));
   HIP_TRY(hipStreamSynchronize(h->stream));
   auto w0 = std::chrono::steady_clock::now();
   int64_t launches = 0;
@@ -511,11 +518,13 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
   while (!use_fused && running > 0 && launches < max_it) {
     for (int c = 0; c < check_every; ++c) {
       rc = launch_rebuild(h); if (rc) break;
+      if (delayed) { rc = launch_delay_apply(h, d->status); if (rc) break; }
       rc = launch_residual(h, h->d_du); if (rc) break;
       rc = launch_factor_solve(h, true, h->d_resid, h->d_delta); if (rc) break;
       { ProfScope ps(h, "tran_update");
         if (h->n >= 4096) hipLaunchKernelGGL(k_tran_update<256>, dim3(h->B), dim3(256), 0, h->stream, a);
         else hipLaunchKernelGGL(k_tran_update<64>, dim3(h->B), dim3(64), 0, h->stream, a); }
+      if (delayed) { rc = launch_delay_record(h, d->t, d->u0, d->status); if (rc) break; }
       ++launches;
     }
     if (rc) break;

@@ -255,6 +255,8 @@ F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode, const TranArgs
   // device types (diodes, behavioural sources, sp_mos1 with series resistances, built-in Verilog-A modules ...) takes the per-op kernels
   p.keep_factors = mode != F2_DC && (newton_mode || mode == F2_STEP);
   if (p.keep_factors && !lean) return p;
+  // delayed stamps (cadnip_tran_set_delay) and their history ring exist beside the per-op kernels only (delay.hip); DC ignores them
+  if (mode == F2_TRAN && h->dly.n_term > 0) return p;
   p.circuit_ok = true;
   if (h->homotopy || h->spec.gshunt != 0.0 || h->spec.srcFact < 1.0) return p;   // homotopies run on the per-op path
   if (S.n_cu <= 0) {

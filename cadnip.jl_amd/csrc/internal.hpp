@@ -7,6 +7,7 @@
 #include "../../include/cadnip_hip.h"
 #include "stamp_plan.hpp"   // StampShape
 #include "ac_hbm_plan.hpp"  // AcHbmPlan
+#include "delay_plan.hpp"   // DelayPlan
 // rows of the derived sp_mos1 parameter card (devices.hpp: enum M1_*) that cadnip_set_params inspects
 #define CADNIP_MOS1_PAR_OXCAP 8
 #define CADNIP_MOS1_PAR_GD 30
@@ -195,6 +196,23 @@ struct AcState {
   }
 };
 
+// Transport delays in the transient (cadnip_tran_set_delay; delay.hip, delay_plan.hpp): the plan's tables, the per-instance terms and the
+// history ring, all in device memory.  n_term == 0: no spec is set -- nothing is allocated and cadnip_tran_run launches nothing new
+struct DelayState {
+  int n_pos = 0, n_term = 0, n_taps = 0, n_rows = 0, depth = 0;
+  double tau_min = 0.0, t0 = 0.0;   // smallest delay of the batch (the step clamp); start of the run in flight
+  int *d_pos = nullptr, *d_taps = nullptr, *d_rows = nullptr, *d_row_ptr = nullptr, *d_term_tap = nullptr;
+  unsigned char* d_row_store = nullptr;     // [n_rows] 1 = no device stamps this row of b: the kernel stores, and the run clears it at its end
+  double *d_tau = nullptr, *d_w = nullptr, *d_W = nullptr;               // [B][n_term] in the plan's grouped order; [B][n_pos]
+  double *d_hist_t = nullptr, *d_hist_v = nullptr, *d_v_init = nullptr;  // [B][depth], [B][n_taps][depth], [B][n_taps]
+  int *d_head = nullptr, *d_count = nullptr, *d_ovf = nullptr;           // [B] ring head and count; 1 = a look-up fell off the ring
+  template <class F> void each_buffer(F f) {
+    f((void**)&d_pos); f((void**)&d_taps); f((void**)&d_rows); f((void**)&d_row_ptr); f((void**)&d_term_tap); f((void**)&d_row_store);
+    f((void**)&d_tau); f((void**)&d_w); f((void**)&d_W); f((void**)&d_hist_t); f((void**)&d_hist_v); f((void**)&d_v_init);
+    f((void**)&d_head); f((void**)&d_count); f((void**)&d_ovf);
+  }
+};
+
 }  // namespace cadnip
 
 struct CadnipHandle {
@@ -246,6 +264,7 @@ struct CadnipHandle {
   bool va_ext = false;        // the circuit uses an external generated model (va_generated_ext.hpp): not compiled into the fused kernel
   cadnip::FusedState f2;      // the LDS-resident kernels' tables, step lists and buffers (fused2.hip, lu_f2.hip)
   cadnip::AcState ac;         // AC sweep: pivot lists and transfer buffers (ac_lu.hip; released with the handle's other buffers in cadnip_destroy)
+  cadnip::DelayState dly;     // transient: delayed stamps and their history ring (delay.hip; released in cadnip_destroy)
   // driver state (allocated lazily)
   struct Driver* drv = nullptr;
   // profiling
@@ -319,6 +338,13 @@ int launch_ac_sens(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int 
 // ac_launch_plan(.., sens = true): the same four n-vectors): inputs and outputs in the d_arn_* buffers, outputs from index 0; m steps,
 // breakdown tolerance tol, n_pairs probe pairs
 int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& p, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs);
+// delay.hip: the transient's delayed stamps (cadnip_tran_set_delay), asynchronous on h->stream.  The driver passes its own per-instance arrays:
+// status (0 = running), t (accepted time), u0 (newest accepted vector [B][n])
+void delay_release(CadnipHandle* h);                                       // frees everything; no spec is set afterwards
+int launch_delay_init(CadnipHandle* h, double t0);                         // v_init and the first ring entry (t0, u[tap]) from h->d_u
+int launch_delay_apply(CadnipHandle* h, const int* d_status);              // G -= W, b[row] -= sum w ud(col, tcur - tau) where the rebuild stamped
+int launch_delay_record(CadnipHandle* h, const double* d_t, const double* d_u0, int* d_status);   // appends accepted points; surfaces an overflow
+int launch_delay_clear(CadnipHandle* h);                                   // zeroes the rows of b that only k_delay_apply writes
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

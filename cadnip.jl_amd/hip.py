@@ -30,7 +30,7 @@ EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
     "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_sens", "cadnip_ac_arnoldi", "cadnip_ac_set_memory", "cadnip_ac_set_overlay", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
-    "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
+    "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_set_delay", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
     "cadnip_host_f2_build", "cadnip_host_f2_size", "cadnip_host_f2_get", "cadnip_host_f2_free", "cadnip_host_f2_team_steps", "cadnip_host_f2_steps",
@@ -85,6 +85,15 @@ class TranOptsC(C.Structure):
                 ("use_pcnr", C.c_int32), ("newton_tol", C.c_double), ("n_break", C.c_int32), ("breaks", _D),
                 ("n_save", C.c_int32), ("save_t", _D), ("n_obs", C.c_int32), ("obs", _I),
                 ("max_iterations", C.c_int64), ("fused", C.c_int32), ("newton_mode", C.c_int32), ("step_rule", C.c_int32)]
+
+
+class DelaySpecC(C.Structure):
+    _fields_ = [("n_pos", C.c_int32), ("pos", _I), ("n_term", C.c_int32), ("term_pos", _I), ("term_row", _I), ("term_col", _I),
+                ("tau", _D), ("w", _D), ("depth", C.c_int32)]
+
+
+# per-instance status of a transient (cadnip_tran_run's per_inst_host[:, 3]): CADNIP_TRAN_DELAY_OVERFLOW
+TRAN_DELAY_OVERFLOW = -4
 
 
 class RunStatsC(C.Structure):
@@ -615,6 +624,34 @@ class Handle:
         if rc not in (OK, NOCONV):
             _check(rc, "cadnip_tran_run")
         return out, per, _stats(st)
+
+    def tran_set_delay(self, pos, term_pos, term_row, term_col, tau, w, depth=0):
+        """cadnip_tran_set_delay: from now on ``tran_run`` treats the stamps ``w`` [B, T] (or [T], broadcast) at the CSR positions
+        ``pos[term_pos[t]]`` = (``term_row[t]``, ``term_col[t]``) as delayed by ``tau`` [B, T] seconds: G_tran = G - W and
+        b_tran[row] = b[row] - sum w u[col](tn - tau), the delayed values read from a ring of ``depth`` (0 = 1024) accepted points per
+        instance in device memory, linearly interpolated (csrc/delay.hip, csrc/delay_plan.hpp; api.ac_delay_overlay computes such terms).
+        Such a run clamps its steps to min(tau), runs on the per-op kernels whatever ``fused`` says, and an instance whose look-up falls
+        off the ring ends with status TRAN_DELAY_OVERFLOW.  No terms clears the setting, as ``tran_clear_delay``.  Arrays of the wrong
+        shape raise ValueError; an index out of range, a term that does not sit on its position or a tau that is not positive and finite
+        raise CadnipError(CADNIP_BADARG) and leave the previous setting in force."""
+        ps = np.ascontiguousarray(np.asarray(pos, dtype=np.int32).ravel())
+        tp, tr, tc = (np.ascontiguousarray(np.asarray(a, dtype=np.int32).ravel()) for a in (term_pos, term_row, term_col))
+        if tp.size == 0:
+            return self.tran_clear_delay()
+        if not (tp.size == tr.size == tc.size):
+            raise ValueError("term_pos, term_row and term_col must have one entry per term")
+        tt, ww = np.asarray(tau, dtype=np.float64), np.asarray(w, dtype=np.float64)
+        for a in (tt, ww):
+            if a.shape not in ((tp.size,), (self.B, tp.size)):
+                raise ValueError("tau and w must be [T] or [B, T] for T terms")
+        tt = np.ascontiguousarray(np.broadcast_to(tt, (self.B, tp.size)))
+        ww = np.ascontiguousarray(np.broadcast_to(ww, (self.B, tp.size)))
+        spec = DelaySpecC(ps.size, _ip(ps), tp.size, _ip(tp), _ip(tr), _ip(tc), _dp(tt), _dp(ww), int(depth))
+        _check(self.lib.cadnip_tran_set_delay(self.h, C.byref(spec)), "cadnip_tran_set_delay")
+
+    def tran_clear_delay(self):
+        """cadnip_tran_set_delay with no spec: ``tran_run`` is again exactly what it is on a new handle."""
+        _check(self.lib.cadnip_tran_set_delay(self.h, None), "cadnip_tran_set_delay")
 
     def tran_state(self):
         t, hh, o = np.empty(self.B), np.empty(self.B), np.empty(self.B, dtype=np.int32)

@@ -188,6 +188,24 @@ function ac_plan_info(ws::GPUEvalWorkspace)
     check(ccall((:cadnip_ac_plan_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), ws.handle, out), "cadnip_ac_plan_info")
     return (memory = out[1] == 1 ? :hbm : :lds, n_waves = out[2], work_bytes = out[3], lds_bytes = out[4])
 end
+# Transport delays in the transient (cadnip_tran_set_delay): term t is a delayed stamp -- its contribution w[t, b] to G at the CSR position
+# pos[term_pos[t]] = (term_row[t], term_col[t]) multiplies u[col](tn - tau[t, b]), read from a ring of `depth` (0 = 1024) accepted points per
+# instance.  All indices 0-based as the C ABI takes them; tau and w are n_term x n_instances (Julia's column-major layout is the ABI's
+# [B][n_term]).  tran_clear_delay! removes the setting.
+struct CadnipDelaySpec              # == typedef struct CadnipDelaySpec
+    n_pos::Int32; pos::Ptr{Int32}
+    n_term::Int32; term_pos::Ptr{Int32}; term_row::Ptr{Int32}; term_col::Ptr{Int32}
+    tau::Ptr{Float64}; w::Ptr{Float64}
+    depth::Int32
+end
+function tran_set_delay!(ws::GPUEvalWorkspace, pos::Vector{Int32}, term_pos::Vector{Int32}, term_row::Vector{Int32}, term_col::Vector{Int32},
+                         tau::Matrix{Float64}, w::Matrix{Float64}; depth=0)
+    GC.@preserve pos term_pos term_row term_col tau w begin
+        s = CadnipDelaySpec(length(pos), pointer(pos), length(term_pos), pointer(term_pos), pointer(term_row), pointer(term_col), pointer(tau), pointer(w), depth)
+        check(ccall((:cadnip_tran_set_delay, LIB), Cint, (Ptr{Cvoid}, Ref{CadnipDelaySpec}), ws.handle, Ref(s)), "cadnip_tran_set_delay")
+    end
+end
+tran_clear_delay!(ws::GPUEvalWorkspace) = check(ccall((:cadnip_tran_set_delay, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ws.handle, C_NULL), "cadnip_tran_set_delay")
 # the handle's pivot order (0-based): pivot k uses row rperm[k], column cperm[k]
 function lu_order(ws::GPUEvalWorkspace, n::Integer)
     rperm = Vector{Int32}(undef, n); cperm = Vector{Int32}(undef, n)

@@ -398,7 +398,8 @@ typedef struct {
                                instance for sweeps (csrc/fused2_kernel.hpp), a team of four waves per instance for batches of at most one instance per
                                compute unit (csrc/fused_team_kernel.hpp: a single transient's latency).  A circuit the fused kernel cannot run -- too
                                large for LDS, an external generated model, or newton_mode 1 with device types outside its lean set (diodes, behavioural
-                               sources, sp_mos1 with series resistances, built-in Verilog-A modules) -- runs on the per-op kernels instead */
+                               sources, sp_mos1 with series resistances, built-in Verilog-A modules) -- runs on the per-op kernels instead, and so does
+                               every run of a handle with a delay spec (cadnip_tran_set_delay) */
   int32_t newton_mode;      /* 0 = full Newton, converged when the weighted update norm < newton_tol (every round restamps and refactors);
                                1 = the nonlinear iteration as IDA runs it (the reference's integrator, src/sweeps.jl:600): refactor on a setup
                                only (first round, a0 outside [0.6, 1/0.6] of its last setup value, 20 steps, failure on a stale Jacobian), kept factors in between, rate-based
@@ -427,8 +428,34 @@ typedef struct {
 int32_t cadnip_dc_log_size(CadnipHandle* h);
 int cadnip_dc_log_get(CadnipHandle* h, int32_t* inst, int32_t* stage, double* value, int32_t* ok, int64_t* iters);
 int cadnip_dc_run(CadnipHandle* h, const CadnipDCOpts* o, double* u_host, int32_t* converged_host, CadnipRunStats* st);
+/* Transport delays in the transient -- a handle setting, none by default: the time-domain sibling of cadnip_ac_set_overlay.  A term t is
+ * a delayed stamp: its own contribution w[b][t] to G at the CSR position pos[term_pos[t]] = (term_row[t], term_col[t]) multiplies not
+ * u[col] at the trial time tn but u[col](tn - tau[b][t]).  While a spec is set, every Newton round of cadnip_tran_run solves
+ *   G_tran = G - W,   W[pos] = sum of w over the terms at pos;     b_tran[row] = b[row] - sum over the row's terms of w ud(col, tn - tau)
+ * (csrc/delay.hip: k_delay_apply between the restamp and the residual; csrc/delay_plan.hpp holds the look-up).  ud(col, tq) is the start
+ * state of the run for tq <= t0, else the LINEAR interpolant of the two accepted points that bracket tq, read from a ring of `depth`
+ * accepted points per instance in device memory (k_delay_record appends one per accepted step); a tq at or beyond the newest point takes
+ * the newest value.  The run clamps h0 and hmax to the smallest tau of the batch, so tq never falls inside the step in flight.  A tq later
+ * than t0 but older than the oldest point kept is not extrapolated: that instance stops with status CADNIP_TRAN_DELAY_OVERFLOW, the
+ * others run on.  Such a run uses the per-op kernels whatever CadnipTranOpts::fused says; DC (fused DC included) ignores the spec, as an
+ * absdelay without history does.  depth: 0 = 1024.  The arrays are copied: they may be released after the call.
+ * spec == NULL or n_term == 0 clears the setting and frees its memory.  CADNIP_BADARG -- the previous setting stays in force -- with an
+ * index out of range, a position named twice, a term whose (row, col) is not the coordinate of its position, a tau that is not a
+ * positive finite number, depth < 0 or == 1, or a ring beyond 256 MiB (8 B (n_taps + 1) depth bytes; n_taps: the distinct term_col). */
+#define CADNIP_TRAN_DELAY_OVERFLOW (-4)
+typedef struct {
+  int32_t n_pos;  const int32_t* pos;        /* [n_pos] CSR positions in [0, nnz), distinct */
+  int32_t n_term; const int32_t* term_pos;   /* [n_term] index into pos[] */
+  const int32_t* term_row;                   /* [n_term] row of b that receives the term */
+  const int32_t* term_col;                   /* [n_term] unknown whose delayed value it multiplies */
+  const double* tau;                         /* [B][n_term] seconds, > 0 */
+  const double* w;                           /* [B][n_term] the stamp's own contribution to G */
+  int32_t depth;                             /* accepted points kept per instance; 0 = 1024 */
+} CadnipDelaySpec;
+int cadnip_tran_set_delay(CadnipHandle* h, const CadnipDelaySpec* spec);
 /* starts from the handle's current state u (e.g. left by cadnip_dc_run in :tranop mode);
- * out_host [B][n_save][n_obs]; per_inst_host [B][4] = {newton_iters, accepted, rejected, status} */
+ * out_host [B][n_save][n_obs]; per_inst_host [B][4] = {newton_iters, accepted, rejected, status}; status 1 = reached t1, -1 / -2 = the step
+ * fell below hmin after a failed error test / Newton iteration, CADNIP_TRAN_DELAY_OVERFLOW = see cadnip_tran_set_delay */
 int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, int64_t* per_inst_host, CadnipRunStats* st);
 
 /* per-instance integrator state after / during a run: time reached, current step size, order */
