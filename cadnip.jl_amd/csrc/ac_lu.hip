@@ -15,16 +15,21 @@
 //   5. recomputes r and the componentwise backward error max_i |r_i| / (|A| |x| + |b|)_i, 0 / 0 = 0 (tests/lu_ref.py with complex moduli),
 //   6. stores x (interleaved re, im), berr and the flag (bit 0: zero / non-finite pivot or non-finite solution -- a flag, never a trap).
 // Every multiply-add is an explicit fma: the W instantiations compute the same doubles.
-// k_ac_lu_hbm / k_ac_adj_hbm (cadnip_ac_set_memory) run the same steps -- the same __device__ functions -- with the work arrays in a per-wave
-// workspace in global memory, for circuits beyond the LDS budget: persistent waves, planned by ac_hbm_plan.hpp.
-// k_ac_lu_multi / k_ac_lu_multi_hbm (cadnip_ac_solve_multi) run steps 1 and 2 once per system and steps 3 to 6 for each of K right-hand sides;
-// k_ac_adj_multi / k_ac_adj_multi_hbm (cadnip_ac_adjoint_multi) do the same for K adjoint right-hand sides.
-// k_ac_sens / k_ac_sens_hbm (cadnip_ac_sens) run one forward and one adjoint column per system and, from the two solutions, K bilinear forms
-// over the stamps of perturbed instances: the response and its K parameter derivatives from one factorisation.
-// k_ac_arnoldi / k_ac_arnoldi_hbm (cadnip_ac_arnoldi) factor at a shift j w_s and run m Arnoldi steps of A^-1 C there -- m + 1 columns with
-// the same factors, each right-hand side C times the previous solution, kept in the wave: the pole-zero analysis.
-// k_ac_lu_ovl, k_ac_adj_ovl, k_ac_lu_multi_ovl, k_ac_adj_multi_ovl and their _hbm forms (cadnip_ac_set_overlay) are the first four with a sparse
-// complex addend D[b][f] on A -- delayed stamps, e^{-j w tau} -- added wherever A is formed: steps 1, 4 and 5 (struct AcOvl below).
+// There are TWO kernels, both generic in a system type S (the structs named *Sys below): k_ac<W, S> keeps the work arrays in LDS, and
+// k_ac_hbm<W, S> (cadnip_ac_set_memory) runs the same steps -- the same __device__ functions -- with them in a per-wave workspace in global
+// memory, for circuits beyond the LDS budget: persistent waves, planned by ac_hbm_plan.hpp.  One launcher, ac_launch, starts either.  A
+// system type holds the family's arguments, says whether its layout has a fourth n-vector, and runs one system; the families are
+//   AcLuSys (cadnip_ac_solve): the steps above;  AcAdjSys (cadnip_ac_adjoint): A^T x = c with the same factors,
+//   AcLuMultiSys (cadnip_ac_solve_multi): steps 1 and 2 once per system and steps 3 to 6 for each of K right-hand sides;  AcAdjMultiSys
+//   (cadnip_ac_adjoint_multi): the same for K adjoint right-hand sides,
+//   AcSensSys (cadnip_ac_sens): one forward and one adjoint column per system and, from the two solutions, K bilinear forms over the stamps
+//   of perturbed instances -- the response and its K parameter derivatives from one factorisation,
+//   AcArnoldiSys (cadnip_ac_arnoldi): factor at a shift j w_s and run m Arnoldi steps of A^-1 C there -- m + 1 columns with the same factors,
+//   each right-hand side C times the previous solution, kept in the wave: the pole-zero analysis.
+// The first four take the overlay as a type parameter: AcLuSys<AcOvl> (cadnip_ac_set_overlay) is AcLuSys<AcNoOvl> with a sparse complex
+// addend D[b][f] on A -- delayed stamps, e^{-j w tau} -- added wherever A is formed: steps 1, 4 and 5 (struct AcOvl below).
+// The ABI header, DESIGN.md, the tools and the tests call the families k_ac_lu, k_ac_adj, k_ac_lu_multi, k_ac_adj_multi, k_ac_sens and
+// k_ac_arnoldi, with _hbm for the form in global memory and _ovl for AcOvl; ac_launch times them under those names ("ac_lu", "ac_lu_hbm", ...).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -70,7 +75,6 @@ __device__ __forceinline__ double cabs2(double2 a) { return hypot(a.x, a.y); }
 // residuals and, through them, the backward error's |A| -- so the factors, the refinement step and berr belong to ONE matrix.  AcNoOvl is
 // empty: the kernels without overlay are the statements they were.  The addend is added component by component to the entry ac_entry
 // forms, in the load and in the residuals alike: the same doubles in both, whatever W and wherever the work arrays live.
-struct AcOvlArgs { const int *pos, *map; const double* val; int n; };
 struct AcNoOvl {
   static constexpr bool on = false;
   __device__ __forceinline__ AcNoOvl at(int, int, int) const { return *this; }
@@ -80,7 +84,6 @@ struct AcOvl {
   const int *pos, *map; const double2* val; int n;
   __device__ __forceinline__ AcOvl at(int inst, int fi, int n_freq) const { AcOvl o = *this; o.val = val + ((size_t)inst * n_freq + fi) * n; return o; }
 };
-__host__ __device__ __forceinline__ AcOvl ac_ovl(const AcOvlArgs& v) { return AcOvl{v.pos, v.map, (const double2*)v.val, v.n}; }
 
 // A at CSR position e of instance-local G / C; o: the overlay of the system (AcOvl::at), or none
 template <class O = AcNoOvl>
@@ -112,7 +115,7 @@ struct AcInHbm {
   static __device__ __forceinline__ void sync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
 };
 
-// Steps 1 and 2 of every kernel -- load A into lu, factor in place -- so that k_ac_lu and k_ac_adj hold the same doubles by construction.
+// Steps 1 and 2 of every kernel -- load A into lu, factor in place -- so that AcLuSys and AcAdjSys hold the same doubles by construction.
 // Returns 1 in the lanes that met a zero / non-finite pivot.
 template <class M, class O = AcNoOvl>
 __device__ __forceinline__ int ac_load_factor(const AcArgs& a, double2* lu, const double* G, const double* C, double om, int lane, const O& o = O()) {
@@ -154,9 +157,19 @@ __device__ __forceinline__ int ac_load_factor(const AcArgs& a, double2* lu, cons
   return bad;
 }
 
-// the work arrays of one system (lds_layout.hpp: lds_ac), in LDS or in the wave's workspace in global memory
-struct AcWork { double2 *lu, *x, *r, *y; };
-__device__ __forceinline__ AcWork ac_work(const LdsAc<double*>& L) { return AcWork{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y}; }
+// The work arrays of one system, in LDS or in the wave's workspace in global memory: region w of `waves` over `base`, in lds_ac's layout or
+// -- FOUR: the families that keep a fourth n-vector xf -- in lds_ac_sens's (lds_layout.hpp; size_t offsets).  The one place that picks a layout
+struct AcWork { double2 *lu, *x, *r, *y, *xf; };
+template <bool FOUR>
+__device__ __forceinline__ AcWork ac_work(double* base, int nnz_lu, int n, int w, int waves) {
+  if constexpr (FOUR) {
+    const LdsAcSens<double*> L = lds_ac_sens(base, nnz_lu, n, w, waves);
+    return AcWork{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y, (double2*)L.xf};
+  } else {
+    const LdsAc<double*> L = lds_ac(base, nnz_lu, n, w, waves);
+    return AcWork{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y, nullptr};
+  }
+}
 
 // ---- 3. / 4. y := A^-1 y through the factors (y in pivot-row order on entry, pivot-column order on return)
 template <class M>
@@ -215,18 +228,50 @@ __device__ __forceinline__ double ac_residual(const AcArgs& a, const double* G, 
   return worst;
 }
 
-// the backward error of the wave from its lanes' figures, and the system's two status words: berr (a NaN stays a NaN) and the flag
-__device__ __forceinline__ void ac_store_status(const AcArgs& a, int ls, double worst, int bad, int lane) {
+// the wave's backward error from its lanes' figures: the largest, and a NaN stays a NaN
+__device__ __forceinline__ double ac_wave_berr(double worst) {
   int nan = worst != worst;
   if (nan) worst = 0.0;
   for (int off = 32; off >= 1; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
-  nan = wave_any(nan);
+  return wave_any(nan) ? __builtin_nan("") : worst;
+}
+// the two status words of (system, column) ls of the launch: berr of the wave and the flag
+__device__ __forceinline__ void ac_store_status(const AcArgs& a, int ls, double worst, int bad, int lane) {
+  worst = ac_wave_berr(worst);
   bad = wave_any(bad);
-  if (lane == 0) { a.berr[ls] = nan ? __builtin_nan("") : worst; a.flags[ls] = bad ? 1 : 0; }
+  if (lane == 0) { a.berr[ls] = worst; a.flags[ls] = bad ? 1 : 0; }
+}
+// ---- 6. the stores of (system, column) lk of the launch from the solution x in the work arrays: x itself when the caller asked for it
+// (a.x), the probe differences h[k] = x[p_k] - x[n_k] of the call's pairs (-1: ground, contributes 0; lanes striding over the pairs) and
+// the status words.  bad: what the lanes know so far; a non-finite word of x adds to it
+__device__ __forceinline__ void ac_store_column(const AcArgs& a, const double2* x, const int* pairs, double* h, int n_pairs, size_t lk, double worst, int bad,
+                                                int lane) {
+  const int n = a.n;
+  double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
+  for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
+  double2* ho = (double2*)h + lk * n_pairs;
+  for (int k = lane; k < n_pairs; k += 64) {
+    const int p = pairs[2 * k], q = pairs[2 * k + 1];
+    const double2 xp = p >= 0 ? x[p] : make_double2(0.0, 0.0), xn = q >= 0 ? x[q] : make_double2(0.0, 0.0);
+    ho[k] = make_double2(xp.x - xn.x, xp.y - xn.y);
+  }
+  ac_store_status(a, (int)lk, worst, bad, lane);
+}
+
+// What a system function derives from its index ls in the launch: system s0 + ls of the grid is (row, fi) -- row the instance, or, MAPPED
+// (the sensitivity family), an index into the list `base` of instances -- and with it the G and C of the instance, the frequency and the
+// overlay's values of that (instance, frequency)
+template <class O>
+struct AcSysCtx { int row, inst, fi; const double *G, *C; double om; O o; };
+template <bool MAPPED = false, class O = AcNoOvl>
+__device__ __forceinline__ AcSysCtx<O> ac_sys_ctx(const AcArgs& a, int ls, const O& ovl = O(), const int* base = nullptr) {
+  const long s = a.s0 + ls;
+  const int row = (int)(s / a.n_freq), fi = (int)(s - (long)row * a.n_freq), inst = MAPPED ? base[row] : row;
+  return AcSysCtx<O>{row, inst, fi, a.G + (size_t)inst * a.nnz, a.C + (size_t)inst * a.nnz, a.omega[fi], ovl.at(inst, fi, a.n_freq)};
 }
 
 // Steps 3 to 5 of ONE column: A x = bac through the factors in lu, the refinement step and the backward error of the wave's rows (returned).
-// x is left in wk.x, visible to every lane.  Shared by k_ac_lu, k_ac_lu_multi and k_ac_sens: the same statements on the same doubles in the
+// x is left in wk.x, visible to every lane.  Shared by AcLuSys, AcLuMultiSys and AcSensSys: the same statements on the same doubles in the
 // same x / r / y.  Every word of x, r and y is written before it is read, so a column leaves nothing to the next one
 template <class M, class O = AcNoOvl>
 __device__ __forceinline__ double ac_lu_column(const AcArgs& a, const AcWork& wk, const double* G, const double* C, double om, const double2* bac, int lane,
@@ -253,50 +298,29 @@ __device__ __forceinline__ double ac_lu_column(const AcArgs& a, const AcWork& wk
 template <class M, class O = AcNoOvl>
 __device__ __forceinline__ void ac_lu_system(const AcArgs& a, int ls, const AcWork& wk, int lane, const O& ovl = O()) {
   const int n = a.n;
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
+  const AcSysCtx<O> s = ac_sys_ctx(a, ls, ovl);
   const double2* x = wk.x;
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
-  const double om = a.omega[fi];
-  const O o = ovl.at(inst, fi, a.n_freq);
-  int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane, o);
-  const double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane, o);
+  const double2* bac = (const double2*)a.bac + (size_t)s.inst * n;
+  int bad = ac_load_factor<M>(a, wk.lu, s.G, s.C, s.om, lane, s.o);
+  const double worst = ac_lu_column<M>(a, wk, s.G, s.C, s.om, bac, lane, s.o);
   // ---- 6. store
   double2* xo = (double2*)a.x + (size_t)ls * n;
   for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; xo[i] = v; }
   ac_store_status(a, ls, worst, bad, lane);
 }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu(AcArgs a) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;                           // system of this wave inside the launch
-  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
-  ac_lu_system<AcInLds>(a, ls, ac_work(lds_ac((double*)sm, a.nnz_lu, a.n, w, W)), lane);
-}
+// A system type: the arguments of a family (base(): their AcArgs), `four`: its layout keeps the fourth n-vector, run<M>: one system under
+// the memory policy M, and `fenced`: in global memory, run() already ends in the fence the wave's next system needs (k_ac_hbm)
+template <class O>
+struct AcLuSys {
+  AcArgs a; O ovl;
+  static constexpr bool four = false, fenced = false;
+  __host__ __device__ const AcArgs& base() const { return a; }
+  template <class M> __device__ __forceinline__ void run(int ls, const AcWork& wk, int lane) const { ac_lu_system<M>(a, ls, wk, lane, ovl); }
+};
 
-// The HBM-resident variants: the same steps with the work arrays in the wave's workspace in global memory (ac_hbm_plan.hpp).  Persistent
-// waves: wave g of n_waves handles systems g, g + n_waves, ... of the launch in its one workspace -- region g of lds_ac's layout over
-// `work`, contiguous per wave, so a level's lanes touch neighbouring words.  The loop bound is the only tail handling: a wave beyond
-// n_waves (the last workgroup when wpb does not divide n_waves) has no workspace and no system.  No workgroup barrier.
-struct AcHbmArgs { double* work; int n_waves; };
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu_hbm(AcArgs a, AcHbmArgs m) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? a.n_sys : 0;
-  const AcWork wk = ac_work(lds_ac(m.work, a.nnz_lu, a.n, g, m.n_waves));     // size_t offsets (lds_layout.hpp)
-  for (int ls = g; ls < end; ls += m.n_waves) {
-    ac_lu_system<AcInHbm>(a, ls, wk, lane);
-    AcInHbm::sync();                                           // the last reads of x before the next system's words
-  }
-}
-
-// ---- the adjoint kernel: A^T x = c with the same factors (noise.jl:150-188: one adjoint solve per frequency serves every noise source) --------
-// Steps 1 and 2 as k_ac_lu (ac_load_factor).  Then, through the tables of lu_transpose.hpp (M = A[rperm][:, cperm] = L U, so M^T = U^T L^T and
+// ---- the adjoint family: A^T x = c with the same factors (noise.jl:150-188: one adjoint solve per frequency serves every noise source) --------
+// Steps 1 and 2 as AcLuSys (ac_load_factor).  Then, through the tables of lu_transpose.hpp (M = A[rperm][:, cperm] = L U, so M^T = U^T L^T and
 // the permutations swap roles):
 //   3. y[j] = c[cperm[j]];  U^T z = y forward, L^T w = z backward, both a gather per unknown over its COLUMN of L\U, level by level, in place
 //      in y;  x[rperm[i]] = w[i].  The diagonal word holds 1 / pivot (1 for constant-1 pivots),
@@ -304,7 +328,7 @@ __global__ void __launch_bounds__(64 * W) k_ac_lu_hbm(AcArgs a, AcHbmArgs m) {
 //      diag_flag entries and the `nodiag` nodes carry it exactly as in the plain residual,
 //   5. the componentwise backward error max_j |r_j| / (|A^T| |x| + |c|)_j, 0 / 0 = 0, a NaN stays,
 //   6. stores: h[k] = x[p_k] - x[n_k] for the K probe pairs of the call (-1: ground, contributes 0), lanes striding over K; berr; the flag
-//      (bit 0 as k_ac_lu); x itself when the caller asked for it.
+//      (bit 0 as AcLuSys); x itself when the caller asked for it.
 // Everything is a gather and every multiply-add an explicit fma: no atomics, no workgroup barrier, the W instantiations compute the same doubles.
 struct AcAdjArgs {
   AcArgs a;                                 // a.bac: c [B][n]; a.x: x out (null: not wanted); a.berr / a.flags: this kernel's outputs
@@ -373,8 +397,8 @@ __device__ __forceinline__ double ac_adj_residual(const AcAdjArgs& t, const doub
 
 // Steps 3 to 6 of ONE adjoint column: A^T x = c through the factors in lu, the refinement step, the backward error (ac_adj_solve_column: steps
 // 3 to 5, x left in wk.x, the backward error of the wave's columns returned) and the stores of (system, column) lk of the launch -- h, berr,
-// the flag, x when asked for.  `bad`: what ac_load_factor returned for the system.  Shared by k_ac_adj (one column per system, lk = ls),
-// k_ac_adj_multi and -- the solve -- k_ac_sens: the same statements on the same doubles in the same x / r / y.  Every word of x, r and y is
+// the flag, x when asked for.  `bad`: what ac_load_factor returned for the system.  Shared by AcAdjSys (one column per system, lk = ls),
+// AcAdjMultiSys and -- the solve -- AcSensSys: the same statements on the same doubles in the same x / r / y.  Every word of x, r and y is
 // written before it is read, so a column leaves nothing to the next one
 template <class M, class O = AcNoOvl>
 __device__ __forceinline__ double ac_adj_solve_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c, int lane,
@@ -400,62 +424,33 @@ __device__ __forceinline__ double ac_adj_solve_column(const AcAdjArgs& t, const 
 template <class M, class O = AcNoOvl>
 __device__ __forceinline__ void ac_adj_column(const AcAdjArgs& t, const AcWork& wk, const double* G, const double* C, double om, const double2* c,
                                               size_t lk, int bad, int lane, const O& o = O()) {
-  const AcArgs& a = t.a;
-  const int n = a.n;
-  const double2* x = wk.x;
   const double worst = ac_adj_solve_column<M>(t, wk, G, C, om, c, lane, o);
-  // ---- 6. store
-  double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
-  for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
-  double2* ho = (double2*)t.h + lk * t.n_pairs;
-  for (int k = lane; k < t.n_pairs; k += 64) {
-    const int p = t.pairs[2 * k], q = t.pairs[2 * k + 1];
-    const double2 xp = p >= 0 ? x[p] : make_double2(0.0, 0.0), xn = q >= 0 ? x[q] : make_double2(0.0, 0.0);
-    ho[k] = make_double2(xp.x - xn.x, xp.y - xn.y);
-  }
-  ac_store_status(a, (int)lk, worst, bad, lane);
+  ac_store_column(t.a, wk.x, t.pairs, t.h, t.n_pairs, lk, worst, bad, lane);
 }
 
 // Steps 1 to 6 of the adjoint system ls of the launch; what ac_lu_system says about wk holds here word for word
 template <class M, class O = AcNoOvl>
 __device__ __forceinline__ void ac_adj_system(const AcAdjArgs& t, int ls, const AcWork& wk, int lane, const O& ovl = O()) {
   const AcArgs& a = t.a;
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double2* c = (const double2*)a.bac + (size_t)inst * a.n;
-  const double om = a.omega[fi];
-  const O o = ovl.at(inst, fi, a.n_freq);
-  const int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane, o);
-  ac_adj_column<M>(t, wk, G, C, om, c, (size_t)ls, bad, lane, o);
+  const AcSysCtx<O> s = ac_sys_ctx(a, ls, ovl);
+  const double2* c = (const double2*)a.bac + (size_t)s.inst * a.n;
+  const int bad = ac_load_factor<M>(a, wk.lu, s.G, s.C, s.om, lane, s.o);
+  ac_adj_column<M>(t, wk, s.G, s.C, s.om, c, (size_t)ls, bad, lane, s.o);
 }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj(AcAdjArgs t) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= t.a.n_sys) return;                                 // the tail workgroup: no workgroup barrier anywhere below
-  ac_adj_system<AcInLds>(t, ls, ac_work(lds_ac((double*)sm, t.a.nnz_lu, t.a.n, w, W)), lane);
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj_hbm(AcAdjArgs t, AcHbmArgs m) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
-  const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
-  for (int ls = g; ls < end; ls += m.n_waves) {
-    ac_adj_system<AcInHbm>(t, ls, wk, lane);
-    AcInHbm::sync();
-  }
-}
+template <class O>
+struct AcAdjSys {
+  AcAdjArgs t; O ovl;
+  static constexpr bool four = false, fenced = false;
+  __host__ __device__ const AcArgs& base() const { return t.a; }
+  template <class M> __device__ __forceinline__ void run(int ls, const AcWork& wk, int lane) const { ac_adj_system<M>(t, ls, wk, lane, ovl); }
+};
 
 // ---- the multi-column kernel: A x_k = b_k for the K right-hand sides of an instance against ONE factorisation per system (cadnip_ac_solve_multi:
 // the columns of a network's Y matrix, the responses to several sources) -------------------------------------------------------------------------
 // Steps 1 and 2 once per system (ac_load_factor).  Then, per column k = 0 .. K-1, steps 3 to 5 of ac_lu_system word for word -- the same
-// statements on the same doubles, in the same x / r / y, so column k holds what k_ac_lu gives with b_k as its b_ac -- and the stores of step 6:
-// x when the caller asked for it, the probe differences h[j] = x[p_j] - x[n_j] (pairs as k_ac_adj: -1 = ground, contributes 0), berr, the flag
+// statements on the same doubles, in the same x / r / y, so column k holds what AcLuSys gives with b_k as its b_ac -- and the stores of step 6:
+// x when the caller asked for it, the probe differences h[j] = x[p_j] - x[n_j] (pairs as AcAdjSys: -1 = ground, contributes 0), berr, the flag
 // (bit 0: a zero / non-finite pivot of the system -- in all its K columns -- or a non-finite solution of THIS column).  Every word of x, r
 // and y is written before it is read inside a column, as in ac_lu_system, so a column leaves nothing to the next one; the M::sync() that ends
 // a column puts its last reads of x (the stores) before the next column's writes.  No atomics, no workgroup barrier.
@@ -469,55 +464,31 @@ struct AcMultiArgs {
 template <class M, class O = AcNoOvl>
 __device__ __forceinline__ void ac_multi_system(const AcMultiArgs& t, int ls, const AcWork& wk, int lane, const O& ovl = O()) {
   const AcArgs& a = t.a;
-  const int n = a.n;
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
-  const double2* x = wk.x;
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double om = a.omega[fi];
-  const O o = ovl.at(inst, fi, a.n_freq);
-  const int bad_pivot = ac_load_factor<M>(a, wk.lu, G, C, om, lane, o);
+  const AcSysCtx<O> s = ac_sys_ctx(a, ls, ovl);
+  const int bad_pivot = ac_load_factor<M>(a, wk.lu, s.G, s.C, s.om, lane, s.o);
   for (int k = 0; k < t.n_rhs; ++k) {
-    const double2* bac = (const double2*)t.rhs + (size_t)inst * t.rhs_stride + (size_t)k * n;
+    const double2* bac = (const double2*)t.rhs + (size_t)s.inst * t.rhs_stride + (size_t)k * a.n;
     const size_t lk = (size_t)ls * t.n_rhs + k;               // (system, column) of the launch: within int (api.hip bounds a launch's output)
-    int bad = bad_pivot;
-    const double worst = ac_lu_column<M>(a, wk, G, C, om, bac, lane, o);
-    // ---- 6. store
-    double2* xo = a.x ? (double2*)a.x + lk * n : nullptr;
-    for (int i = lane; i < n; i += 64) { const double2 v = x[i]; if (!isfinite(v.x) || !isfinite(v.y)) bad = 1; if (xo) xo[i] = v; }
-    double2* ho = (double2*)t.h + lk * t.n_pairs;
-    for (int j = lane; j < t.n_pairs; j += 64) {
-      const int p = t.pairs[2 * j], q = t.pairs[2 * j + 1];
-      const double2 xp = p >= 0 ? x[p] : make_double2(0.0, 0.0), xn = q >= 0 ? x[q] : make_double2(0.0, 0.0);
-      ho[j] = make_double2(xp.x - xn.x, xp.y - xn.y);
-    }
-    ac_store_status(a, (int)lk, worst, bad, lane);
+    const double worst = ac_lu_column<M>(a, wk, s.G, s.C, s.om, bac, lane, s.o);
+    ac_store_column(a, wk.x, t.pairs, t.h, t.n_pairs, lk, worst, bad_pivot, lane);
     M::sync();                                                 // the last reads of this column's x before the next column's (next system's) words
   }
 }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu_multi(AcMultiArgs t) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= t.a.n_sys) return;                                 // the tail workgroup: no workgroup barrier anywhere below
-  ac_multi_system<AcInLds>(t, ls, ac_work(lds_ac((double*)sm, t.a.nnz_lu, t.a.n, w, W)), lane);
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu_multi_hbm(AcMultiArgs t, AcHbmArgs m) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
-  const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
-  for (int ls = g; ls < end; ls += m.n_waves) ac_multi_system<AcInHbm>(t, ls, wk, lane);   // a system's last column ends in the fence the next one needs
-}
+// fenced: every system has a column (n_rhs >= 1: launch_ac_multi), and a column ends in M::sync() after its last read of the work arrays --
+// the very fence k_ac_hbm would add.  The same holds for AcAdjMultiSys
+template <class O>
+struct AcLuMultiSys {
+  AcMultiArgs t; O ovl;
+  static constexpr bool four = false, fenced = true;
+  __host__ __device__ const AcArgs& base() const { return t.a; }
+  template <class M> __device__ __forceinline__ void run(int ls, const AcWork& wk, int lane) const { ac_multi_system<M>(t, ls, wk, lane, ovl); }
+};
 
 // ---- the multi-column adjoint kernel: A^T x_k = c_k for the K columns of an instance against ONE factorisation per system (cadnip_ac_adjoint_multi:
 // the noise of several outputs, the noise correlation matrix of an N-port) ------------------------------------------------------------------------
-// Steps 1 and 2 once per system (ac_load_factor).  Then, per column k = 0 .. K-1, ac_adj_column -- the very function k_ac_adj runs, so column k
-// holds what k_ac_adj gives with c_k as its c -- with the stores indexed by (system, column) as in ac_multi_system.  Flag bit 0: a zero /
+// Steps 1 and 2 once per system (ac_load_factor).  Then, per column k = 0 .. K-1, ac_adj_column -- the very function AcAdjSys runs, so column k
+// holds what AcAdjSys gives with c_k as its c -- with the stores indexed by (system, column) as in ac_multi_system.  Flag bit 0: a zero /
 // non-finite pivot of the system -- in all its K columns -- or a non-finite solution of THIS column.  The M::sync() that ends a column puts its
 // last reads of x (the stores) before the next column's writes.  No atomics, no workgroup barrier.
 struct AcAdjMultiArgs {
@@ -529,114 +500,23 @@ struct AcAdjMultiArgs {
 template <class M, class O = AcNoOvl>
 __device__ __forceinline__ void ac_adj_multi_system(const AcAdjMultiArgs& u, int ls, const AcWork& wk, int lane, const O& ovl = O()) {
   const AcArgs& a = u.t.a;
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double om = a.omega[fi];
-  const O o = ovl.at(inst, fi, a.n_freq);
-  const int bad_pivot = ac_load_factor<M>(a, wk.lu, G, C, om, lane, o);
+  const AcSysCtx<O> s = ac_sys_ctx(a, ls, ovl);
+  const int bad_pivot = ac_load_factor<M>(a, wk.lu, s.G, s.C, s.om, lane, s.o);
   for (int k = 0; k < u.n_rhs; ++k) {
-    const double2* c = (const double2*)u.rhs + (size_t)inst * u.rhs_stride + (size_t)k * a.n;
+    const double2* c = (const double2*)u.rhs + (size_t)s.inst * u.rhs_stride + (size_t)k * a.n;
     const size_t lk = (size_t)ls * u.n_rhs + k;               // (system, column) of the launch: within int (api.hip bounds a launch's output)
-    ac_adj_column<M>(u.t, wk, G, C, om, c, lk, bad_pivot, lane, o);
+    ac_adj_column<M>(u.t, wk, s.G, s.C, s.om, c, lk, bad_pivot, lane, s.o);
     M::sync();                                                 // the last reads of this column's x before the next column's (next system's) words
   }
 }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj_multi(AcAdjMultiArgs u) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= u.t.a.n_sys) return;                               // the tail workgroup: no workgroup barrier anywhere below
-  ac_adj_multi_system<AcInLds>(u, ls, ac_work(lds_ac((double*)sm, u.t.a.nnz_lu, u.t.a.n, w, W)), lane);
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj_multi_hbm(AcAdjMultiArgs u, AcHbmArgs m) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.t.a.n_sys : 0;
-  const AcWork wk = ac_work(lds_ac(m.work, u.t.a.nnz_lu, u.t.a.n, g, m.n_waves));
-  for (int ls = g; ls < end; ls += m.n_waves) ac_adj_multi_system<AcInHbm>(u, ls, wk, lane);   // a system's last column ends in the fence the next one needs
-}
-
-// ---- the overlay forms of the four kernels above (cadnip_ac_set_overlay): the same __device__ functions with the policy AcOvl in place of
-// AcNoOvl, launched in their parents' place while an overlay is set.  Same launch plans, same LDS layout, same lane order, no workgroup
-// barrier, no atomics; the table is read from global memory.  k_ac_sens and k_ac_arnoldi have no overlay form: their entry points refuse.
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu_ovl(AcArgs a, AcOvlArgs v) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= a.n_sys) return;
-  ac_lu_system<AcInLds>(a, ls, ac_work(lds_ac((double*)sm, a.nnz_lu, a.n, w, W)), lane, ac_ovl(v));
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu_ovl_hbm(AcArgs a, AcHbmArgs m, AcOvlArgs v) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? a.n_sys : 0;
-  const AcWork wk = ac_work(lds_ac(m.work, a.nnz_lu, a.n, g, m.n_waves));
-  for (int ls = g; ls < end; ls += m.n_waves) {
-    ac_lu_system<AcInHbm>(a, ls, wk, lane, ac_ovl(v));
-    AcInHbm::sync();
-  }
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj_ovl(AcAdjArgs t, AcOvlArgs v) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= t.a.n_sys) return;
-  ac_adj_system<AcInLds>(t, ls, ac_work(lds_ac((double*)sm, t.a.nnz_lu, t.a.n, w, W)), lane, ac_ovl(v));
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj_ovl_hbm(AcAdjArgs t, AcHbmArgs m, AcOvlArgs v) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
-  const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
-  for (int ls = g; ls < end; ls += m.n_waves) {
-    ac_adj_system<AcInHbm>(t, ls, wk, lane, ac_ovl(v));
-    AcInHbm::sync();
-  }
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu_multi_ovl(AcMultiArgs t, AcOvlArgs v) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= t.a.n_sys) return;
-  ac_multi_system<AcInLds>(t, ls, ac_work(lds_ac((double*)sm, t.a.nnz_lu, t.a.n, w, W)), lane, ac_ovl(v));
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_lu_multi_ovl_hbm(AcMultiArgs t, AcHbmArgs m, AcOvlArgs v) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? t.a.n_sys : 0;
-  const AcWork wk = ac_work(lds_ac(m.work, t.a.nnz_lu, t.a.n, g, m.n_waves));
-  for (int ls = g; ls < end; ls += m.n_waves) ac_multi_system<AcInHbm>(t, ls, wk, lane, ac_ovl(v));
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj_multi_ovl(AcAdjMultiArgs u, AcOvlArgs v) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= u.t.a.n_sys) return;
-  ac_adj_multi_system<AcInLds>(u, ls, ac_work(lds_ac((double*)sm, u.t.a.nnz_lu, u.t.a.n, w, W)), lane, ac_ovl(v));
-}
-
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_adj_multi_ovl_hbm(AcAdjMultiArgs u, AcHbmArgs m, AcOvlArgs v) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.t.a.n_sys : 0;
-  const AcWork wk = ac_work(lds_ac(m.work, u.t.a.nnz_lu, u.t.a.n, g, m.n_waves));
-  for (int ls = g; ls < end; ls += m.n_waves) ac_adj_multi_system<AcInHbm>(u, ls, wk, lane, ac_ovl(v));
-}
+template <class O>
+struct AcAdjMultiSys {
+  AcAdjMultiArgs u; O ovl;
+  static constexpr bool four = false, fenced = true;
+  __host__ __device__ const AcArgs& base() const { return u.t.a; }
+  template <class M> __device__ __forceinline__ void run(int ls, const AcWork& wk, int lane) const { ac_adj_multi_system<M>(u, ls, wk, lane, ovl); }
+};
 
 // ---- the sensitivity kernel: the response y = x[p] - x[n] of A x = b_ac and its derivatives with respect to K parameters from ONE factorisation
 // per system (cadnip_ac_sens; SPICE's .SENS on an AC sweep).  With the adjoint solution A^T lambda = c, c = e_p - e_n,
@@ -644,8 +524,8 @@ __global__ void __launch_bounds__(64 * W) k_ac_adj_multi_ovl_hbm(AcAdjMultiArgs 
 // and the parameter derivatives of G and C are central differences of the stamps of two perturbed instances of the SAME resident batch.  A
 // system is (b, f) with b running over a LIST of base instances (u.base), not over the handle's instances.  The wave runs
 //   1. / 2.  ac_load_factor on the base instance's G and C,
-//   3.  the forward column (ac_lu_column: x is what k_ac_lu gives for that instance), copied into the fourth vector xf, which outlives
-//   4.  the adjoint column for c in the same x / r / y (ac_adj_solve_column: lambda is what k_ac_adj gives),
+//   3.  the forward column (ac_lu_column: x is what AcLuSys gives for that instance), copied into the fourth vector xf, which outlives
+//   4.  the adjoint column for c in the same x / r / y (ac_adj_solve_column: lambda is what AcAdjSys gives),
 //   5.  s_k = sum_i lambda_i db_k[i] - sum_e lambda[row(e)] ((G+[e] - G-[e]) + j w (C+[e] - C-[e])) scale[b][k] xf[col(e)], k = 0 .. K-1, with
 //       G+ / C+ the arrays of instance plus[b][k], G- / C- those of minus[b][k]: the differences are taken entry by entry from the handle's
 //       device arrays -- no derivative array exists anywhere.  gmin sits in both and cancels.  The lanes stride over i and over the entries
@@ -668,27 +548,19 @@ __device__ __forceinline__ double2 cmadd(double2 acc, double2 a, double2 b) {
   return make_double2(fma(a.x, b.x, fma(-a.y, b.y, acc.x)), fma(a.x, b.y, fma(a.y, b.x, acc.y)));
 }
 
-// the wave's backward error from its lanes' figures (as ac_store_status: a NaN stays a NaN)
-__device__ __forceinline__ double ac_wave_berr(double worst) {
-  int nan = worst != worst;
-  if (nan) worst = 0.0;
-  for (int off = 32; off >= 1; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off));
-  return wave_any(nan) ? __builtin_nan("") : worst;
-}
-
 template <class M>
-__device__ __forceinline__ void ac_sens_system(const AcSensArgs& u, int ls, const AcWork& wk, double2* xf, int lane) {
+__device__ __forceinline__ void ac_sens_system(const AcSensArgs& u, int ls, const AcWork& wk, int lane) {
   const AcAdjArgs& t = u.t;
   const AcArgs& a = t.a;
   const int n = a.n, K = u.n_par;
-  const long s = a.s0 + ls;
-  const int bl = (int)(s / a.n_freq), fi = (int)(s - (long)bl * a.n_freq), inst = u.base[bl];
+  const AcSysCtx<AcNoOvl> s = ac_sys_ctx<true>(a, ls, AcNoOvl(), u.base);
+  const int bl = s.row;
+  const double *G = s.G, *C = s.C;
+  const double om = s.om;
   const double2* x = wk.x;
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
+  double2* xf = wk.xf;
   const double2* bac = (const double2*)a.bac + (size_t)bl * n;
   const double2* c = (const double2*)u.c;
-  const double om = a.omega[fi];
   int bad = ac_load_factor<M>(a, wk.lu, G, C, om, lane);
   // ---- 3. the forward column; x goes to xf
   const double berr_f = ac_wave_berr(ac_lu_column<M>(a, wk, G, C, om, bac, lane));
@@ -728,33 +600,18 @@ __device__ __forceinline__ void ac_sens_system(const AcSensArgs& u, int ls, cons
   }
 }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_sens(AcSensArgs u) {
-  extern __shared__ double sm[];
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= u.t.a.n_sys) return;                               // the tail workgroup: no workgroup barrier anywhere below
-  const LdsAcSens<double*> L = lds_ac_sens((double*)sm, u.t.a.nnz_lu, u.t.a.n, w, W);
-  ac_sens_system<AcInLds>(u, ls, AcWork{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y}, (double2*)L.xf, lane);
-}
+struct AcSensSys {
+  AcSensArgs u;
+  static constexpr bool four = true, fenced = false;
+  __host__ __device__ const AcArgs& base() const { return u.t.a; }
+  template <class M> __device__ __forceinline__ void run(int ls, const AcWork& wk, int lane) const { ac_sens_system<M>(u, ls, wk, lane); }
+};
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_sens_hbm(AcSensArgs u, AcHbmArgs m) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.t.a.n_sys : 0;
-  const LdsAcSens<double*> L = lds_ac_sens(m.work, u.t.a.nnz_lu, u.t.a.n, g, m.n_waves);   // size_t offsets (lds_layout.hpp)
-  const AcWork wk{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y};
-  for (int ls = g; ls < end; ls += m.n_waves) {
-    ac_sens_system<AcInHbm>(u, ls, wk, (double2*)L.xf, lane);
-    AcInHbm::sync();                                           // the last reads of x and xf before the next system's words
-  }
-}
-
-// ---- the Arnoldi kernel: an orthonormal basis of the Krylov space of K = A^-1 C started at A^-1 b_ac, A = G + gmin + j w_s C at the SHIFT
+// ---- the Arnoldi family: an orthonormal basis of the Krylov space of K = A^-1 C started at A^-1 b_ac, A = G + gmin + j w_s C at the SHIFT
 // j w_s, from ONE factorisation per system (cadnip_ac_arnoldi: poles, zeros and a reduced model of the descriptor system (C, -G) -- the
 // eigenvalues theta of K are the poles p = j w_s - 1 / theta).  A system is (instance b, shift s).  The wave runs
 //   1. / 2.  ac_load_factor at w_s,
-//   3.  the start vector: x = A^-1 b_ac[b] by ac_lu_column (x is what k_ac_lu gives for (b, w_s)), beta = ||x||_2, v_0 = x / beta.  beta zero
+//   3.  the start vector: x = A^-1 b_ac[b] by ac_lu_column (x is what AcLuSys gives for (b, w_s)), beta = ||x||_2, v_0 = x / beta.  beta zero
 //       or non-finite: flag bit 1, m_eff = 0, no step,
 //   4.  for j = 0 .. m-1: t = C[b] v_j (CSR rows, real C times complex v_j, one row per lane, into the fourth vector); w = A^-1 t by
 //       ac_lu_column (solve, refinement, backward error, as every column of this file); nu_0 = ||w||_2; two passes of modified Gram-Schmidt
@@ -762,7 +619,7 @@ __global__ void __launch_bounds__(64 * W) k_ac_sens_hbm(AcSensArgs u, AcHbmArgs 
 //       space has closed -- m_eff = j + 1, H[j+1][j] = 0, flag bit 2 (informational), the system is finished.  Else H[j+1][j] = nu_1 and
 //       v_{j+1} = w / nu_1; without a breakdown m_eff = m,
 //   5.  stores: H ((m+1) x m, zero beyond m_eff), beta, m_eff, the unconjugated probe projections l[j][p] = v_j[p_p] - v_j[n_p] (pairs as
-//       k_ac_adj, zero beyond m_eff), berr -- the worst of the m_eff + 1 columns, a NaN stays --, the flag (bit 0: zero / non-finite pivot or a
+//       AcAdjSys, zero beyond m_eff), berr -- the worst of the m_eff + 1 columns, a NaN stays --, the flag (bit 0: zero / non-finite pivot or a
 //       non-finite word of H, beta or l; bits 1 and 2 as above), and the basis V ((m+1) x n; rows that hold no vector are zero).
 // Where the vectors live.  w is ac_lu_column's x and is orthogonalised and normalised IN PLACE there, so the current v_j sits in a work
 // array (LDS, or the wave's workspace) under the memory policy M, and everything that reads a vector ACROSS lanes -- the product C v_j
@@ -794,16 +651,14 @@ __device__ __forceinline__ double ac_wave_norm(const double2* x, int n, int lane
 }
 
 template <class M>
-__device__ __forceinline__ void ac_arnoldi_system(const AcArnArgs& u, int ls, const AcWork& wk, double2* t, int lane) {
+__device__ __forceinline__ void ac_arnoldi_system(const AcArnArgs& u, int ls, const AcWork& wk, int lane) {
   const AcArgs& a = u.a;
   const int n = a.n, m = u.m, P = u.n_pairs;
-  const long s = a.s0 + ls;
-  const int inst = (int)(s / a.n_freq), fi = (int)(s - (long)inst * a.n_freq);
-  double2* x = wk.x;
-  const double* G = a.G + (size_t)inst * a.nnz;
-  const double* C = a.C + (size_t)inst * a.nnz;
-  const double2* bac = (const double2*)a.bac + (size_t)inst * n;
-  const double om = a.omega[fi];
+  const AcSysCtx<AcNoOvl> s = ac_sys_ctx(a, ls);
+  const double *G = s.G, *C = s.C;
+  const double om = s.om;
+  double2 *x = wk.x, *t = wk.xf;
+  const double2* bac = (const double2*)a.bac + (size_t)s.inst * n;
   double2* Ho = (double2*)u.H + (size_t)ls * (m + 1) * m;
   double2* lo = (double2*)u.l + (size_t)ls * m * P;
   double2* Vo = (double2*)u.V + (size_t)ls * (m + 1) * n;
@@ -875,27 +730,48 @@ __device__ __forceinline__ void ac_arnoldi_system(const AcArnArgs& u, int ls, co
   if (lane == 0) { u.beta[ls] = beta; u.meff[ls] = meff; a.berr[ls] = worst; a.flags[ls] = flag | (bad ? 1 : 0); }
 }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_arnoldi(AcArnArgs u) {
+struct AcArnoldiSys {
+  AcArnArgs u;
+  static constexpr bool four = true, fenced = false;
+  __host__ __device__ const AcArgs& base() const { return u.a; }
+  template <class M> __device__ __forceinline__ void run(int ls, const AcWork& wk, int lane) const { ac_arnoldi_system<M>(u, ls, wk, lane); }
+};
+
+// ---- the two kernels.  Every family above runs through them: 10 system types (AcSensSys and AcArnoldiSys have no overlay form: their
+// entry points refuse) x 2 homes x W = 1, 2, 4, 8, instantiated by ac_launch below.  Same launch plans, same layout, same lane order in
+// both homes; no workgroup barrier, no atomics.
+// Work arrays in LDS: one system per wave, W per workgroup
+template <int W, class S>
+__global__ void __launch_bounds__(64 * W) k_ac(S sys) {
   extern __shared__ double sm[];
+  const AcArgs& a = sys.base();
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ls = blockIdx.x * W + w;
-  if (ls >= u.a.n_sys) return;                                 // the tail workgroup: no workgroup barrier anywhere below
-  const LdsAcSens<double*> L = lds_ac_sens((double*)sm, u.a.nnz_lu, u.a.n, w, W);
-  ac_arnoldi_system<AcInLds>(u, ls, AcWork{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y}, (double2*)L.xf, lane);
+  const int ls = blockIdx.x * W + w;                           // system of this wave inside the launch
+  if (ls >= a.n_sys) return;                                   // the tail workgroup: no workgroup barrier anywhere below
+  sys.template run<AcInLds>(ls, ac_work<S::four>((double*)sm, a.nnz_lu, a.n, w, W), lane);
 }
 
-template <int W>
-__global__ void __launch_bounds__(64 * W) k_ac_arnoldi_hbm(AcArnArgs u, AcHbmArgs m) {
+// The HBM-resident form: the same steps with the work arrays in the wave's workspace in global memory (ac_hbm_plan.hpp).  Persistent
+// waves: wave g of n_waves handles systems g, g + n_waves, ... of the launch in its one workspace -- region g of the family's layout over
+// `work`, contiguous per wave, so a level's lanes touch neighbouring words.  The loop bound is the only tail handling: a wave beyond
+// n_waves (the last workgroup when wpb does not divide n_waves) has no workspace and no system.  No workgroup barrier.
+// Every system ends with the fence that puts its last reads of the work arrays (x; xf / t where there are four) before the next system's
+// words.  A family whose run() already ends in exactly that fence says so (S::fenced) and gets no second one: the distinction is kept, not
+// flattened, so that each family's instructions are the ones it had with a kernel of its own.
+struct AcHbmArgs { double* work; int n_waves; };
+
+template <int W, class S>
+__global__ void __launch_bounds__(64 * W) k_ac_hbm(S sys, AcHbmArgs m) {
+  const AcArgs& a = sys.base();
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int g = blockIdx.x * W + w, end = g < m.n_waves ? u.a.n_sys : 0;
-  const LdsAcSens<double*> L = lds_ac_sens(m.work, u.a.nnz_lu, u.a.n, g, m.n_waves);   // size_t offsets (lds_layout.hpp)
-  const AcWork wk{(double2*)L.lu, (double2*)L.x, (double2*)L.r, (double2*)L.y};
+  const int g = blockIdx.x * W + w, end = g < m.n_waves ? a.n_sys : 0;
+  const AcWork wk = ac_work<S::four>(m.work, a.nnz_lu, a.n, g, m.n_waves);
   for (int ls = g; ls < end; ls += m.n_waves) {
-    ac_arnoldi_system<AcInHbm>(u, ls, wk, (double2*)L.xf, lane);
-    AcInHbm::sync();                                           // the last reads of x and t before the next system's words
+    sys.template run<AcInHbm>(ls, wk, lane);
+    if constexpr (!S::fenced) AcInHbm::sync();
   }
 }
+
 
 // The launch plan -- the one place that sizes the LDS block and picks W, and the only reader of CADNIP_AC_WPB.  A compute unit holds
 // min(32 waves, LDS_BUDGET / block) workgroups' worth of systems: the plan takes the W with the most resident systems (ties: the largest),
@@ -926,7 +802,7 @@ AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req, bool sens) {
 
 // Where the work arrays of a call live (cadnip_ac_set_memory) and the plan of that home: LDS -- ac_lu_plan alone, as ever; HBM -- the plan of
 // ac_hbm_plan.hpp on this device's compute units; AUTO -- LDS when ac_lu_plan accepts the circuit, else HBM.  memory < 0: refused.
-// sens: the plan of k_ac_sens / k_ac_sens_hbm, whose systems keep a fourth n-vector
+// sens: the plan of the families whose systems keep a fourth n-vector (AcSensSys, AcArnoldiSys)
 AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req, bool sens) {
   AcLaunch L;
   AcState& A = h->ac;
@@ -1026,32 +902,37 @@ static AcArgs ac_args(CadnipHandle* h, int n_freq, long s0, int n_sys, double gm
   return a;
 }
 
-// the handle's overlay (cadnip_ac_set_overlay) as the overlay kernels take it; n == 0: none is set, the plain kernels run
-static AcOvlArgs ac_ovl_args(const CadnipHandle* h) { return AcOvlArgs{h->ac.d_ovl_pos, h->ac.d_ovl_map, h->ac.d_ovl_val, h->ac.ovl_n}; }
+// the handle's overlay (cadnip_ac_set_overlay) as the system types take it; n == 0: none is set, the AcNoOvl forms run
+static AcOvl ac_ovl(const CadnipHandle* h) { return AcOvl{h->ac.d_ovl_pos, h->ac.d_ovl_map, (const double2*)h->ac.d_ovl_val, h->ac.ovl_n}; }
 
-int launch_ac_lu(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin) {
-  if (L.memory < 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
-  const AcArgs a = ac_args(h, n_freq, s0, n_sys, gmin);
-  const AcOvlArgs v = ac_ovl_args(h); const bool ovl = v.n > 0;
+// The one launch of every family: the systems of `sys` in the home and under the plan of L, timed under the family's name for that home
+template <class S>
+static int ac_launch(CadnipHandle* h, const AcLaunch& L, const char* name_lds, const char* name_hbm, const S& sys) {
+  const int n_sys = sys.base().n_sys;
   if (L.memory == CADNIP_AC_HBM) {
     const AcHbmPlan& p = L.hbm;
     if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
     TRY_RC(ac_work_reserve(h, p.work_bytes));
-    ProfScope ps(h, "ac_lu_hbm");
+    ProfScope ps(h, name_hbm);
     const AcHbmArgs m{h->ac.d_work, p.n_waves};
     const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_ovl_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, a, m, v); return CADNIP_OK; }));
-    else TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, a, m); return CADNIP_OK; }));
+    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL((k_ac_hbm<decltype(W)::value, S>), dim3(grid), dim3(64 * W.value), 0, h->stream, sys, m); return CADNIP_OK; }));
     HIP_TRY(hipGetLastError());
     return CADNIP_OK;
   }
   const AcPlan& p = L.lds;
-  ProfScope ps(h, "ac_lu");
+  ProfScope ps(h, name_lds);
   const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_ovl<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, a, v); }));
-  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, a); }));
+  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac<decltype(W)::value, S>, grid, 64 * W.value, p.shmem, h->stream, sys); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
+}
+
+int launch_ac_lu(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin) {
+  if (L.memory < 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
+  const AcArgs a = ac_args(h, n_freq, s0, n_sys, gmin);
+  const AcOvl v = ac_ovl(h);
+  return v.n > 0 ? ac_launch(h, L, "ac_lu", "ac_lu_hbm", AcLuSys<AcOvl>{a, v}) : ac_launch(h, L, "ac_lu", "ac_lu_hbm", AcLuSys<AcNoOvl>{a, {}});
 }
 
 // the transposed-solve tables and the adjoint's output pointers over ac_args
@@ -1072,26 +953,8 @@ int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, i
   AcAdjArgs t = ac_adj_args(h, n_freq, s0, n_sys, gmin);
   t.a.x = want_x ? A.d_adj_x : nullptr; t.a.berr = A.d_adj_berr; t.a.flags = A.d_adj_flags;
   t.pairs = A.d_pairs; t.h = A.d_h; t.n_pairs = n_pairs;
-  const AcOvlArgs v = ac_ovl_args(h); const bool ovl = v.n > 0;
-  if (L.memory == CADNIP_AC_HBM) {
-    const AcHbmPlan& p = L.hbm;
-    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
-    TRY_RC(ac_work_reserve(h, p.work_bytes));
-    ProfScope ps(h, "ac_adj_hbm");
-    const AcHbmArgs m{A.d_work, p.n_waves};
-    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_ovl_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m, v); return CADNIP_OK; }));
-    else TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m); return CADNIP_OK; }));
-    HIP_TRY(hipGetLastError());
-    return CADNIP_OK;
-  }
-  const AcPlan& p = L.lds;
-  ProfScope ps(h, "ac_adj");
-  const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_ovl<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t, v); }));
-  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
-  HIP_TRY(hipGetLastError());
-  return CADNIP_OK;
+  const AcOvl v = ac_ovl(h);
+  return v.n > 0 ? ac_launch(h, L, "ac_adj", "ac_adj_hbm", AcAdjSys<AcOvl>{t, v}) : ac_launch(h, L, "ac_adj", "ac_adj_hbm", AcAdjSys<AcNoOvl>{t, {}});
 }
 
 int launch_ac_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x) {
@@ -1102,26 +965,9 @@ int launch_ac_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int
   t.a.bac = nullptr; t.a.x = want_x ? A.d_multi_x : nullptr; t.a.berr = A.d_multi_berr; t.a.flags = A.d_multi_flags;
   t.rhs = A.d_multi_rhs; t.rhs_stride = (long)n_rhs * h->n;
   t.pairs = A.d_multi_pairs; t.h = A.d_multi_h; t.n_rhs = n_rhs; t.n_pairs = n_pairs;
-  const AcOvlArgs v = ac_ovl_args(h); const bool ovl = v.n > 0;
-  if (L.memory == CADNIP_AC_HBM) {
-    const AcHbmPlan& p = L.hbm;
-    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
-    TRY_RC(ac_work_reserve(h, p.work_bytes));
-    ProfScope ps(h, "ac_lu_multi_hbm");
-    const AcHbmArgs m{A.d_work, p.n_waves};
-    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_multi_ovl_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m, v); return CADNIP_OK; }));
-    else TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_lu_multi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, t, m); return CADNIP_OK; }));
-    HIP_TRY(hipGetLastError());
-    return CADNIP_OK;
-  }
-  const AcPlan& p = L.lds;
-  ProfScope ps(h, "ac_lu_multi");
-  const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_multi_ovl<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t, v); }));
-  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_lu_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, t); }));
-  HIP_TRY(hipGetLastError());
-  return CADNIP_OK;
+  const AcOvl v = ac_ovl(h);
+  return v.n > 0 ? ac_launch(h, L, "ac_lu_multi", "ac_lu_multi_hbm", AcLuMultiSys<AcOvl>{t, v})
+                 : ac_launch(h, L, "ac_lu_multi", "ac_lu_multi_hbm", AcLuMultiSys<AcNoOvl>{t, {}});
 }
 
 int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x) {
@@ -1132,26 +978,9 @@ int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long
   u.t.a.bac = nullptr; u.t.a.x = want_x ? A.d_multi_x : nullptr; u.t.a.berr = A.d_multi_berr; u.t.a.flags = A.d_multi_flags;
   u.t.pairs = A.d_multi_pairs; u.t.h = A.d_multi_h; u.t.n_pairs = n_pairs;
   u.rhs = A.d_multi_rhs; u.rhs_stride = (long)n_rhs * h->n; u.n_rhs = n_rhs;
-  const AcOvlArgs v = ac_ovl_args(h); const bool ovl = v.n > 0;
-  if (L.memory == CADNIP_AC_HBM) {
-    const AcHbmPlan& p = L.hbm;
-    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
-    TRY_RC(ac_work_reserve(h, p.work_bytes));
-    ProfScope ps(h, "ac_adj_multi_hbm");
-    const AcHbmArgs m{A.d_work, p.n_waves};
-    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_multi_ovl_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, m, v); return CADNIP_OK; }));
-    else TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_adj_multi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, m); return CADNIP_OK; }));
-    HIP_TRY(hipGetLastError());
-    return CADNIP_OK;
-  }
-  const AcPlan& p = L.lds;
-  ProfScope ps(h, "ac_adj_multi");
-  const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  if (ovl) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_multi_ovl<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u, v); }));
-  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_adj_multi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
-  HIP_TRY(hipGetLastError());
-  return CADNIP_OK;
+  const AcOvl v = ac_ovl(h);
+  return v.n > 0 ? ac_launch(h, L, "ac_adj_multi", "ac_adj_multi_hbm", AcAdjMultiSys<AcOvl>{u, v})
+                 : ac_launch(h, L, "ac_adj_multi", "ac_adj_multi_hbm", AcAdjMultiSys<AcNoOvl>{u, {}});
 }
 
 int launch_ac_sens(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, bool db, const int* pair, bool want_x) {
@@ -1164,23 +993,7 @@ int launch_ac_sens(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int 
   u.base = A.d_sens_idx; u.plus = u.base + n_base; u.minus = u.plus + (size_t)n_base * n_par;
   u.scale = A.d_sens_scale; u.db = db ? A.d_sens_db : nullptr; u.c = A.d_sens_c;
   u.y = A.d_sens_y; u.s = A.d_sens_s; u.n_par = n_par; u.p = pair[0]; u.q = pair[1];
-  if (L.memory == CADNIP_AC_HBM) {
-    const AcHbmPlan& p = L.hbm;
-    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
-    TRY_RC(ac_work_reserve(h, p.work_bytes));
-    ProfScope ps(h, "ac_sens_hbm");
-    const AcHbmArgs m{A.d_work, p.n_waves};
-    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_sens_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, m); return CADNIP_OK; }));
-    HIP_TRY(hipGetLastError());
-    return CADNIP_OK;
-  }
-  const AcPlan& p = L.lds;
-  ProfScope ps(h, "ac_sens");
-  const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_sens<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
-  HIP_TRY(hipGetLastError());
-  return CADNIP_OK;
+  return ac_launch(h, L, "ac_sens", "ac_sens_hbm", AcSensSys{u});
 }
 
 int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& L, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs) {
@@ -1191,23 +1004,8 @@ int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& L, int n_shift, long s0, 
   u.a.bac = A.d_arn_bac; u.a.x = nullptr; u.a.berr = A.d_arn_berr; u.a.flags = A.d_arn_flags;
   u.pairs = A.d_arn_pairs; u.H = A.d_arn_H; u.beta = A.d_arn_beta; u.l = A.d_arn_l; u.V = A.d_arn_V; u.meff = A.d_arn_meff;
   u.tol = tol; u.m = m; u.n_pairs = n_pairs;
-  if (L.memory == CADNIP_AC_HBM) {
-    const AcHbmPlan& p = L.hbm;
-    if (p.n_waves <= 0 || p.n_waves > n_sys) return CADNIP_BADARG;
-    TRY_RC(ac_work_reserve(h, p.work_bytes));
-    ProfScope ps(h, "ac_arnoldi_hbm");
-    const AcHbmArgs hm{A.d_work, p.n_waves};
-    const int grid = (p.n_waves + p.wpb - 1) / p.wpb;
-    TRY_RC(with_wpb(p.wpb, [&](auto W) { hipLaunchKernelGGL(k_ac_arnoldi_hbm<decltype(W)::value>, dim3(grid), dim3(64 * W.value), 0, h->stream, u, hm); return CADNIP_OK; }));
-    HIP_TRY(hipGetLastError());
-    return CADNIP_OK;
-  }
-  const AcPlan& p = L.lds;
-  ProfScope ps(h, "ac_arnoldi");
-  const int grid = (n_sys + p.wpb - 1) / p.wpb;
-  TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_ac_arnoldi<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, u); }));
-  HIP_TRY(hipGetLastError());
-  return CADNIP_OK;
+  return ac_launch(h, L, "ac_arnoldi", "ac_arnoldi_hbm", AcArnoldiSys{u});
 }
 
 }  // namespace cadnip
+

@@ -30,6 +30,39 @@ int dev_upload(T** p, const T* src, size_t count) {
 template <class T>
 int dev_upload(T** p, const std::vector<T>& v) { return dev_upload(p, v.data(), v.size()); }
 #define TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
+
+// Device buffers of ONE capacity, grown on demand (the AC sweeps' transfer buffers): below `need` units every buffer of the group is freed,
+// then each is allocated (zeroed) to need x its own `words` elements, in the order given; the capacity reads 0 until all of them stand
+template <class T> struct AcBuf { T** p; size_t words; };
+template <class T> AcBuf<T> ac_buf(T** p, size_t words = 1) { return AcBuf<T>{p, words}; }
+template <class... T>
+int ac_grow(size_t* cap, size_t need, AcBuf<T>... bufs) {
+  if (*cap >= need) return CADNIP_OK;
+  auto drop = [](auto** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } };
+  (drop(bufs.p), ...);
+  *cap = 0;
+  int rc = CADNIP_OK;
+  ((rc = rc ? rc : dev_alloc(bufs.p, need * bufs.words)), ...);
+  if (rc) return rc;
+  *cap = need;
+  return CADNIP_OK;
+}
+
+// How an AC entry point cuts its S systems into launches: chunks of at most AC_CHUNK_BYTES of device output (sys_bytes per system; at least
+// one system), so the device output buffers stay bounded however large S is.  `plan`: of the full chunks, `tail`: of the last, shorter one --
+// per chunk, because persistent waves are sized by the launch; the LDS plan is one for all.  sens: the plans of the four-vector layout.
+// !ok(): an invalid wpb, or the work arrays fit no memory the setting allows -- the entry point returns CADNIP_BADARG, nothing is launched
+#define AC_CHUNK_BYTES ((size_t)64 << 20)
+struct AcChunks {
+  size_t S, chunk;
+  AcLaunch plan, tail;
+  AcChunks(CadnipHandle* h, size_t S_, size_t sys_bytes, int32_t wpb, bool sens = false) : S(S_), chunk(std::min(S_, std::max<size_t>(1, AC_CHUNK_BYTES / sys_bytes))) {
+    plan = ac_launch_plan(h, (long)chunk, wpb, sens);
+    tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb, sens) : plan;
+  }
+  bool ok() const { return plan.memory >= 0 && tail.memory >= 0; }
+  const AcLaunch& of(size_t ns) const { return ns == chunk ? plan : tail; }   // the plan of a launch of ns systems
+};
 }  // namespace
 
 extern "C" {
@@ -765,9 +798,10 @@ int cadnip_lu_order(CadnipHandle* h, int32_t* rperm, int32_t* cperm) {
   return CADNIP_OK;
 }
 
-// info [4] of the two sweeps (W that ran, LDS bytes of a workgroup, systems, workgroups launched) and the record cadnip_ac_plan_info reads;
-// `plan`: of the full chunks, `tail`: of the last, shorter one
-static void ac_report(CadnipHandle* h, const AcLaunch& plan, const AcLaunch& tail, size_t S, size_t chunk, int32_t* info) {
+// info [4] of the sweeps (W that ran, LDS bytes of a workgroup, systems, workgroups launched) and the record cadnip_ac_plan_info reads
+static void ac_report(CadnipHandle* h, const AcChunks& ch, int32_t* info) {
+  const AcLaunch &plan = ch.plan, &tail = ch.tail;
+  const size_t S = ch.S, chunk = ch.chunk;
   const bool hbm = plan.memory == CADNIP_AC_HBM;
   info[0] = plan.wpb(); info[1] = hbm ? 0 : (int)plan.lds.shmem; info[2] = (int)S;
   info[3] = (int)((S / chunk) * plan.workgroups((long)chunk) + (S % chunk ? tail.workgroups((long)(S % chunk)) : 0));
@@ -829,47 +863,39 @@ int cadnip_ac_plan_info(CadnipHandle* h, int64_t out[4]) {
 }
 
 // The AC sweep x[b][f] = (G[b] + gmin [node diagonals] + j omega[f] C[b])^-1 b_ac[b] on the G / C of the last cadnip_rebuild, with the handle's
-// pivot order: S = B n_freq systems through k_ac_lu (ac_lu.hip).  Uploads are blocking copies at entry (the stream is idle), downloads follow a
-// stream synchronisation.  The systems are processed in chunks of at most AC_CHUNK_BYTES of solution (16 n bytes each; at least one system),
-// so the device output buffers -- allocated on first use, kept by the handle, released in cadnip_destroy -- stay bounded however large B F is.
-#define AC_CHUNK_BYTES ((size_t)64 << 20)
+// pivot order: S = B n_freq systems through AcLuSys (ac_lu.hip).  Uploads are blocking copies at entry (the stream is idle), downloads follow a
+// stream synchronisation.  The systems are processed in chunks of at most AC_CHUNK_BYTES of solution (16 n bytes each; AcChunks above), so
+// the device output buffers -- allocated on first use, kept by the handle, released in cadnip_destroy -- stay bounded however large B F is.
 int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, const double* bac_host, int32_t wpb, double* x_host,
                     double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || !bac_host || !x_host || !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
   if (!ac_overlay_grid_ok(h, n_freq, omega)) return CADNIP_BADARG;
   const size_t B = h->B, n = h->n, F = n_freq, S = B * F;
-  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * n)));
-  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb);             // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
-  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb) : plan;
-  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
+  const AcChunks ch(h, S, 16 * n, wpb);
+  if (!ch.ok()) return CADNIP_BADARG;
+  const size_t chunk = ch.chunk;
   HIP_TRY(hipStreamSynchronize(h->stream));
   TRY(ac_lu_prepare(h));
   AcState& A = h->ac;
   if (!A.d_bac) TRY(dev_alloc(&A.d_bac, B * n * 2));
-  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
-  if (A.cap_sys < chunk) {
-    void* old[] = {A.d_x, A.d_berr, A.d_flags};
-    for (void* p : old) if (p) (void)hipFree(p);
-    A.d_x = nullptr; A.d_berr = nullptr; A.d_flags = nullptr; A.cap_sys = 0;
-    TRY(dev_alloc(&A.d_x, chunk * n * 2)); TRY(dev_alloc(&A.d_berr, chunk)); TRY(dev_alloc(&A.d_flags, chunk));
-    A.cap_sys = chunk;
-  }
+  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
+  TRY(ac_grow(&A.cap_sys, chunk, ac_buf(&A.d_x, n * 2), ac_buf(&A.d_berr), ac_buf(&A.d_flags)));
   HIP_TRY(hipMemcpy(A.d_bac, bac_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
   for (size_t s0 = 0; s0 < S; s0 += chunk) {
     const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_lu(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin));
+    TRY(launch_ac_lu(h, ch.of(ns), n_freq, (long)s0, (int)ns, gmin));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(berr_host + s0, A.d_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0, A.d_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
   }
-  ac_report(h, plan, tail, S, chunk, info);
+  ac_report(h, ch, info);
   return CADNIP_OK;
 }
 
 // The adjoint sweep x[b][f] = (A[b][f])^-T c[b] with A as above, and of it the probe differences h[b][f][k] = x[p_k] - x[n_k]: S = B n_freq
-// systems through k_ac_adj (ac_lu.hip), which factors exactly as k_ac_lu does and solves through the transposed tables.  Same rules as
+// systems through AcAdjSys (ac_lu.hip), which factors exactly as AcLuSys does and solves through the transposed tables.  Same rules as
 // cadnip_ac_solve; a system's device output is 16 (K + n [x wanted]) bytes.  Buffers live in AcState.
 int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, const double* c_host, int32_t n_pairs, const int32_t* pairs,
                       int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
@@ -878,15 +904,14 @@ int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, doub
   const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_pairs;
   for (size_t k = 0; k < 2 * K; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
   const bool want_x = x_host != nullptr;
-  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * (K + (want_x ? n : 0)))));
-  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb);             // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
-  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb) : plan;
-  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
+  const AcChunks ch(h, S, 16 * (K + (want_x ? n : 0)), wpb);
+  if (!ch.ok()) return CADNIP_BADARG;
+  const size_t chunk = ch.chunk;
   HIP_TRY(hipStreamSynchronize(h->stream));
   TRY(ac_lu_prepare(h, true));
   AcState& A = h->ac;
   if (!A.d_bac) TRY(dev_alloc(&A.d_bac, B * n * 2));
-  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
+  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
   if (A.cap_pairs < K || A.cap_adj_sys < chunk) {             // d_h is [systems][pairs]: either growing reallocates it
     const size_t ck = std::max(A.cap_pairs, K), cs = std::max(A.cap_adj_sys, chunk);
     void* old[] = {A.d_pairs, A.d_h, A.d_adj_berr, A.d_adj_flags};
@@ -895,30 +920,27 @@ int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, doub
     TRY(dev_alloc(&A.d_pairs, ck * 2)); TRY(dev_alloc(&A.d_h, cs * ck * 2)); TRY(dev_alloc(&A.d_adj_berr, cs)); TRY(dev_alloc(&A.d_adj_flags, cs));
     A.cap_pairs = ck; A.cap_adj_sys = cs;
   }
-  if (want_x && A.cap_adj_x < chunk) {
-    if (A.d_adj_x) { (void)hipFree(A.d_adj_x); A.d_adj_x = nullptr; }
-    A.cap_adj_x = 0; TRY(dev_alloc(&A.d_adj_x, chunk * n * 2)); A.cap_adj_x = chunk;
-  }
+  if (want_x) TRY(ac_grow(&A.cap_adj_x, chunk, ac_buf(&A.d_adj_x, n * 2)));
   HIP_TRY(hipMemcpy(A.d_bac, c_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(A.d_pairs, pairs, K * 2 * sizeof(int), hipMemcpyHostToDevice));
   for (size_t s0 = 0; s0 < S; s0 += chunk) {
     const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_adjoint(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin, n_pairs, want_x));
+    TRY(launch_ac_adjoint(h, ch.of(ns), n_freq, (long)s0, (int)ns, gmin, n_pairs, want_x));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(h_host + s0 * K * 2, A.d_h, ns * K * 2 * sizeof(double), hipMemcpyDeviceToHost));
     if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_adj_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(berr_host + s0, A.d_adj_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0, A.d_adj_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
   }
-  ac_report(h, plan, tail, S, chunk, info);
+  ac_report(h, ch, info);
   return CADNIP_OK;
 }
 
-// The multi-column sweep x[b][f][k] = (A[b][f])^-1 b[b][k] with A as above: S = B n_freq systems through k_ac_lu_multi (ac_lu.hip), which factors
-// each system once, exactly as k_ac_lu does, and runs the solve, the refinement and the backward error per column.  Same rules as
+// The multi-column sweep x[b][f][k] = (A[b][f])^-1 b[b][k] with A as above: S = B n_freq systems through AcLuMultiSys (ac_lu.hip), which factors
+// each system once, exactly as AcLuSys does, and runs the solve, the refinement and the backward error per column.  Same rules as
 // cadnip_ac_solve; a system's device output is 16 K (n_pairs + n [x wanted]) bytes.  Buffers live in AcState.
-// cadnip_ac_adjoint_multi is the same call on A^T: x[b][f][k] = (A[b][f])^-T c[b][k] through k_ac_adj_multi, with the transposed tables built on first use.
+// cadnip_ac_adjoint_multi is the same call on A^T: x[b][f][k] = (A[b][f])^-T c[b][k] through AcAdjMultiSys, with the transposed tables built on first use.
 static int ac_multi_call(CadnipHandle* h, bool adjoint, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* b_host, int32_t n_pairs,
                          const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || n_rhs < 1 || !b_host || n_pairs < 0 || (n_pairs > 0 && (!pairs || !h_host)) || (n_pairs == 0 && !x_host) ||
@@ -927,45 +949,30 @@ static int ac_multi_call(CadnipHandle* h, bool adjoint, int32_t n_freq, const do
   const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_rhs, P = n_pairs;
   for (size_t k = 0; k < 2 * P; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
   const bool want_x = x_host != nullptr;
-  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * K * (P + (want_x ? n : 0)))));
-  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb);             // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
-  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb) : plan;
-  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
+  const AcChunks ch(h, S, 16 * K * (P + (want_x ? n : 0)), wpb);
+  if (!ch.ok()) return CADNIP_BADARG;
+  const size_t chunk = ch.chunk;
   HIP_TRY(hipStreamSynchronize(h->stream));
   TRY(ac_lu_prepare(h, adjoint));
   AcState& A = h->ac;
-  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
-  auto grow = [](auto** p, size_t* cap, size_t need, size_t words) {       // one buffer to `need` units of `words` elements
-    if (*cap >= need) return (int)CADNIP_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    *cap = 0;
-    TRY(dev_alloc(p, need * words));
-    *cap = need;
-    return (int)CADNIP_OK;
-  };
-  TRY(grow(&A.d_multi_rhs, &A.cap_multi_rhs, B * K * n, 2));
-  if (P) { TRY(grow(&A.d_multi_pairs, &A.cap_multi_pairs, P, 2)); TRY(grow(&A.d_multi_h, &A.cap_multi_h, chunk * K * P, 2)); }
-  if (want_x) TRY(grow(&A.d_multi_x, &A.cap_multi_x, chunk * K * n, 2));
-  if (A.cap_multi_cols < chunk * K) {                           // berr and flags: one capacity
-    if (A.d_multi_berr) { (void)hipFree(A.d_multi_berr); A.d_multi_berr = nullptr; }
-    if (A.d_multi_flags) { (void)hipFree(A.d_multi_flags); A.d_multi_flags = nullptr; }
-    A.cap_multi_cols = 0;
-    TRY(dev_alloc(&A.d_multi_berr, chunk * K)); TRY(dev_alloc(&A.d_multi_flags, chunk * K));
-    A.cap_multi_cols = chunk * K;
-  }
+  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
+  TRY(ac_grow(&A.cap_multi_rhs, B * K * n, ac_buf(&A.d_multi_rhs, 2)));
+  if (P) { TRY(ac_grow(&A.cap_multi_pairs, P, ac_buf(&A.d_multi_pairs, 2))); TRY(ac_grow(&A.cap_multi_h, chunk * K * P, ac_buf(&A.d_multi_h, 2))); }
+  if (want_x) TRY(ac_grow(&A.cap_multi_x, chunk * K * n, ac_buf(&A.d_multi_x, 2)));
+  TRY(ac_grow(&A.cap_multi_cols, chunk * K, ac_buf(&A.d_multi_berr), ac_buf(&A.d_multi_flags)));
   HIP_TRY(hipMemcpy(A.d_multi_rhs, b_host, B * K * n * 2 * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
   if (P) HIP_TRY(hipMemcpy(A.d_multi_pairs, pairs, P * 2 * sizeof(int), hipMemcpyHostToDevice));
   for (size_t s0 = 0; s0 < S; s0 += chunk) {
     const size_t ns = std::min(chunk, S - s0);
-    TRY((adjoint ? launch_ac_adjoint_multi : launch_ac_multi)(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin, n_rhs, n_pairs, want_x));
+    TRY((adjoint ? launch_ac_adjoint_multi : launch_ac_multi)(h, ch.of(ns), n_freq, (long)s0, (int)ns, gmin, n_rhs, n_pairs, want_x));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (P) HIP_TRY(hipMemcpy(h_host + s0 * K * P * 2, A.d_multi_h, ns * K * P * 2 * sizeof(double), hipMemcpyDeviceToHost));
     if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * K * n * 2, A.d_multi_x, ns * K * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(berr_host + s0 * K, A.d_multi_berr, ns * K * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0 * K, A.d_multi_flags, ns * K * sizeof(int), hipMemcpyDeviceToHost));
   }
-  ac_report(h, plan, tail, S, chunk, info);
+  ac_report(h, ch, info);
   return CADNIP_OK;
 }
 
@@ -981,7 +988,7 @@ int cadnip_ac_adjoint_multi(CadnipHandle* h, int32_t n_freq, const double* omega
 
 // The sensitivity sweep: per (base instance b, frequency f) the response y = x[p] - x[n] of A x = b_ac and its derivatives with respect to n_par
 // parameters, s[k] = lambda^T (db[b][k] - (dG + j w dC) x) with A^T lambda = c and dG / dC the differences of the G / C of instances
-// plus[b][k] and minus[b][k] times scale[b][k] -- S = n_base n_freq systems through k_ac_sens (ac_lu.hip), one factorisation each.  Same rules
+// plus[b][k] and minus[b][k] times scale[b][k] -- S = n_base n_freq systems through AcSensSys (ac_lu.hip), one factorisation each.  Same rules
 // as cadnip_ac_solve; a system's device output is 16 (1 + K + 2 n [x wanted]) bytes.  Buffers live in AcState.
 int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_base, const int32_t* base, int32_t n_par, const int32_t* plus,
                    const int32_t* minus, const double* scale, const double* bac_host, const double* db_host, const double* c_host, const int32_t* pair,
@@ -994,39 +1001,21 @@ int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega, double 
   for (size_t k = 0; k < NB * K; ++k) if (plus[k] < 0 || plus[k] >= (int32_t)B || minus[k] < 0 || minus[k] >= (int32_t)B) return CADNIP_BADARG;
   if (pair[0] < -1 || pair[0] >= (int32_t)n || pair[1] < -1 || pair[1] >= (int32_t)n || (pair[0] == -1 && pair[1] == -1)) return CADNIP_BADARG;
   const bool want_x = x_host != nullptr, db = db_host != nullptr;
-  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * (1 + K + (want_x ? 2 * n : 0)))));
-  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb, true);       // per chunk: persistent waves are sized by the launch; the LDS plan is one for all
-  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb, true) : plan;
-  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
+  const AcChunks ch(h, S, 16 * (1 + K + (want_x ? 2 * n : 0)), wpb, true);
+  if (!ch.ok()) return CADNIP_BADARG;
+  const size_t chunk = ch.chunk;
   HIP_TRY(hipStreamSynchronize(h->stream));
   TRY(ac_lu_prepare(h, true));
   AcState& A = h->ac;
-  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
-  auto grow = [](auto** p, size_t* cap, size_t need, size_t words) {       // one buffer to `need` units of `words` elements
-    if (*cap >= need) return (int)CADNIP_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    *cap = 0;
-    TRY(dev_alloc(p, need * words));
-    *cap = need;
-    return (int)CADNIP_OK;
-  };
-  auto grow2 = [](auto** p, auto** q, size_t* cap, size_t need, size_t pw, size_t qw) {   // two buffers of one capacity
-    if (*cap >= need) return (int)CADNIP_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (*q) { (void)hipFree(*q); *q = nullptr; }
-    *cap = 0;
-    TRY(dev_alloc(p, need * pw)); TRY(dev_alloc(q, need * qw));
-    *cap = need;
-    return (int)CADNIP_OK;
-  };
+  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
   if (!A.d_sens_c) TRY(dev_alloc(&A.d_sens_c, n * 2));
-  TRY(grow(&A.d_sens_idx, &A.cap_sens_idx, NB + 2 * NB * K, 1));
-  TRY(grow(&A.d_sens_scale, &A.cap_sens_scale, NB * K, 1));
-  TRY(grow(&A.d_sens_bac, &A.cap_sens_bac, NB * n, 2));
-  if (db) TRY(grow(&A.d_sens_db, &A.cap_sens_db, NB * K * n, 2));
-  TRY(grow2(&A.d_sens_y, &A.d_sens_berr, &A.cap_sens_sys, chunk, 2, 2));
-  TRY(grow2(&A.d_sens_s, &A.d_sens_flags, &A.cap_sens_cols, chunk * K, 2, 1));
-  if (want_x) TRY(grow(&A.d_sens_x, &A.cap_sens_x, chunk, 4 * n));
+  TRY(ac_grow(&A.cap_sens_idx, NB + 2 * NB * K, ac_buf(&A.d_sens_idx)));
+  TRY(ac_grow(&A.cap_sens_scale, NB * K, ac_buf(&A.d_sens_scale)));
+  TRY(ac_grow(&A.cap_sens_bac, NB * n, ac_buf(&A.d_sens_bac, 2)));
+  if (db) TRY(ac_grow(&A.cap_sens_db, NB * K * n, ac_buf(&A.d_sens_db, 2)));
+  TRY(ac_grow(&A.cap_sens_sys, chunk, ac_buf(&A.d_sens_y, 2), ac_buf(&A.d_sens_berr, 2)));
+  TRY(ac_grow(&A.cap_sens_cols, chunk * K, ac_buf(&A.d_sens_s, 2), ac_buf(&A.d_sens_flags)));
+  if (want_x) TRY(ac_grow(&A.cap_sens_x, chunk, ac_buf(&A.d_sens_x, 4 * n)));
   HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(A.d_sens_idx, base, NB * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(A.d_sens_idx + NB, plus, NB * K * sizeof(int), hipMemcpyHostToDevice));
@@ -1037,7 +1026,7 @@ int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega, double 
   HIP_TRY(hipMemcpy(A.d_sens_c, c_host, n * 2 * sizeof(double), hipMemcpyHostToDevice));
   for (size_t s0 = 0; s0 < S; s0 += chunk) {
     const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_sens(h, ns == chunk ? plan : tail, n_freq, (long)s0, (int)ns, gmin, n_base, n_par, db, pair, want_x));
+    TRY(launch_ac_sens(h, ch.of(ns), n_freq, (long)s0, (int)ns, gmin, n_base, n_par, db, pair, want_x));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(y_host + s0 * 2, A.d_sens_y, ns * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(s_host + s0 * K * 2, A.d_sens_s, ns * K * 2 * sizeof(double), hipMemcpyDeviceToHost));
@@ -1045,12 +1034,12 @@ int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega, double 
     HIP_TRY(hipMemcpy(berr_host + s0 * 2, A.d_sens_berr, ns * 2 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0 * K, A.d_sens_flags, ns * K * sizeof(int), hipMemcpyDeviceToHost));
   }
-  ac_report(h, plan, tail, S, chunk, info);
+  ac_report(h, ch, info);
   return CADNIP_OK;
 }
 
 // The Arnoldi sweep: per (instance b, shift s) m steps of K = A^-1 C started at A^-1 b_ac[b], A = G[b] + gmin + j omega[s] C[b] -- S = B n_shift
-// systems through k_ac_arnoldi (ac_lu.hip), one factorisation and up to m + 1 columns each.  Same rules as cadnip_ac_solve; a system's device
+// systems through AcArnoldiSys (ac_lu.hip), one factorisation and up to m + 1 columns each.  Same rules as cadnip_ac_solve; a system's device
 // output is 16 ((m+1) m + m n_pairs + (m+1) n) bytes and a few words -- the basis is the kernel's own storage and counts whether the caller
 // wants it or not -- and a single system beyond AC_CHUNK_BYTES runs as a chunk of one.  Buffers live in AcState.
 int cadnip_ac_arnoldi(CadnipHandle* h, int32_t n_shift, const double* omega, double gmin, const double* b_host, int32_t m, double breakdown_tol,
@@ -1062,39 +1051,24 @@ int cadnip_ac_arnoldi(CadnipHandle* h, int32_t n_shift, const double* omega, dou
   const size_t B = h->B, n = h->n, F = n_shift, S = B * F, P = n_pairs, M = m;
   for (size_t k = 0; k < 2 * P; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
   const size_t hw = (M + 1) * M, lw = M * P, vw = (M + 1) * n;           // complex words of a system's H, l, V
-  const size_t chunk = std::min(S, std::max<size_t>(1, AC_CHUNK_BYTES / (16 * (hw + lw + vw))));
-  const AcLaunch plan = ac_launch_plan(h, (long)chunk, wpb, true);       // the work arrays are the sensitivity kernel's: four n-vectors
-  const AcLaunch tail = plan.memory == CADNIP_AC_HBM && S % chunk ? ac_launch_plan(h, (long)(S % chunk), wpb, true) : plan;
-  if (plan.memory < 0 || tail.memory < 0) return CADNIP_BADARG;   // invalid wpb, or the work arrays fit no memory the setting allows: nothing is launched
+  const AcChunks ch(h, S, 16 * (hw + lw + vw), wpb, true);               // the work arrays are the sensitivity family's: four n-vectors
+  if (!ch.ok()) return CADNIP_BADARG;
+  const size_t chunk = ch.chunk;
   HIP_TRY(hipStreamSynchronize(h->stream));
   TRY(ac_lu_prepare(h));
   AcState& A = h->ac;
-  if (A.cap_freq < F) { if (A.d_omega) { (void)hipFree(A.d_omega); A.d_omega = nullptr; } A.cap_freq = 0; TRY(dev_alloc(&A.d_omega, F)); A.cap_freq = F; }
-  auto grow = [](auto** p, size_t* cap, size_t need, size_t words) {       // one buffer to `need` units of `words` elements
-    if (*cap >= need) return (int)CADNIP_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    *cap = 0;
-    TRY(dev_alloc(p, need * words));
-    *cap = need;
-    return (int)CADNIP_OK;
-  };
-  TRY(grow(&A.d_arn_bac, &A.cap_arn_bac, B * n, 2));
-  TRY(grow(&A.d_arn_H, &A.cap_arn_H, chunk * hw, 2));
-  TRY(grow(&A.d_arn_V, &A.cap_arn_V, chunk * vw, 2));
-  if (P) { TRY(grow(&A.d_arn_pairs, &A.cap_arn_pairs, P, 2)); TRY(grow(&A.d_arn_l, &A.cap_arn_l, chunk * lw, 2)); }
-  if (A.cap_arn_sys < chunk) {                                   // beta, berr, m_eff, flags: one capacity
-    void** four[] = {(void**)&A.d_arn_beta, (void**)&A.d_arn_berr, (void**)&A.d_arn_meff, (void**)&A.d_arn_flags};
-    for (void** p : four) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    A.cap_arn_sys = 0;
-    TRY(dev_alloc(&A.d_arn_beta, chunk)); TRY(dev_alloc(&A.d_arn_berr, chunk)); TRY(dev_alloc(&A.d_arn_meff, chunk)); TRY(dev_alloc(&A.d_arn_flags, chunk));
-    A.cap_arn_sys = chunk;
-  }
+  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
+  TRY(ac_grow(&A.cap_arn_bac, B * n, ac_buf(&A.d_arn_bac, 2)));
+  TRY(ac_grow(&A.cap_arn_H, chunk * hw, ac_buf(&A.d_arn_H, 2)));
+  TRY(ac_grow(&A.cap_arn_V, chunk * vw, ac_buf(&A.d_arn_V, 2)));
+  if (P) { TRY(ac_grow(&A.cap_arn_pairs, P, ac_buf(&A.d_arn_pairs, 2))); TRY(ac_grow(&A.cap_arn_l, chunk * lw, ac_buf(&A.d_arn_l, 2))); }
+  TRY(ac_grow(&A.cap_arn_sys, chunk, ac_buf(&A.d_arn_beta), ac_buf(&A.d_arn_berr), ac_buf(&A.d_arn_meff), ac_buf(&A.d_arn_flags)));
   HIP_TRY(hipMemcpy(A.d_arn_bac, b_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
   if (P) HIP_TRY(hipMemcpy(A.d_arn_pairs, pairs, P * 2 * sizeof(int), hipMemcpyHostToDevice));
   for (size_t s0 = 0; s0 < S; s0 += chunk) {
     const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_arnoldi(h, ns == chunk ? plan : tail, n_shift, (long)s0, (int)ns, gmin, m, breakdown_tol, n_pairs));
+    TRY(launch_ac_arnoldi(h, ch.of(ns), n_shift, (long)s0, (int)ns, gmin, m, breakdown_tol, n_pairs));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(H_host + s0 * hw * 2, A.d_arn_H, ns * hw * 2 * sizeof(double), hipMemcpyDeviceToHost));
     if (P) HIP_TRY(hipMemcpy(l_host + s0 * lw * 2, A.d_arn_l, ns * lw * 2 * sizeof(double), hipMemcpyDeviceToHost));
@@ -1104,7 +1078,7 @@ int cadnip_ac_arnoldi(CadnipHandle* h, int32_t n_shift, const double* omega, dou
     HIP_TRY(hipMemcpy(berr_host + s0, A.d_arn_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(flags_host + s0, A.d_arn_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
   }
-  ac_report(h, plan, tail, S, chunk, info);
+  ac_report(h, ch, info);
   return CADNIP_OK;
 }
 

@@ -139,7 +139,7 @@ struct AcState {
   double *d_bac = nullptr, *d_omega = nullptr, *d_x = nullptr, *d_berr = nullptr;
   int* d_flags = nullptr;
   size_t cap_freq = 0, cap_sys = 0;        // frequencies d_omega holds, systems the output buffers hold
-  // adjoint sweep (k_ac_adj, cadnip_ac_adjoint): the transposed-solve tables of the LU program (lu_transpose.hpp), built with the pivot
+  // adjoint sweep (AcAdjSys, cadnip_ac_adjoint): the transposed-solve tables of the LU program (lu_transpose.hpp), built with the pivot
   // lists under `dirty` but only once the adjoint path is asked for (`adj_ready`), and its own transfer buffers
   bool adj_ready = false;
   int *d_t_colptr = nullptr, *d_t_pos = nullptr, *d_t_row = nullptr, *d_t_diag = nullptr;
@@ -150,7 +150,7 @@ struct AcState {
   double *d_h = nullptr, *d_adj_x = nullptr, *d_adj_berr = nullptr;
   int* d_adj_flags = nullptr;
   size_t cap_pairs = 0, cap_adj_sys = 0, cap_adj_x = 0;   // pairs d_pairs and a system of d_h hold, systems of the outputs, systems of d_adj_x
-  // multi-column sweeps (k_ac_lu_multi, cadnip_ac_solve_multi; k_ac_adj_multi, cadnip_ac_adjoint_multi -- the same shapes, one set serves both):
+  // multi-column sweeps (AcLuMultiSys, cadnip_ac_solve_multi; AcAdjMultiSys, cadnip_ac_adjoint_multi -- the same shapes, one set serves both):
   // their own transfer buffers, each grown on demand to the capacity beside it
   double *d_multi_rhs = nullptr, *d_multi_h = nullptr, *d_multi_x = nullptr, *d_multi_berr = nullptr;   // [B][K][n], [S][K][pairs], [S][K][n] complex; [S][K]
   int *d_multi_pairs = nullptr, *d_multi_flags = nullptr;                                              // [pairs][2]; [S][K]
@@ -158,7 +158,7 @@ struct AcState {
   template <class F> void each_multi_buffer(F f) {
     f((void**)&d_multi_rhs); f((void**)&d_multi_h); f((void**)&d_multi_x); f((void**)&d_multi_berr); f((void**)&d_multi_pairs); f((void**)&d_multi_flags);
   }
-  // sensitivity sweep (k_ac_sens, cadnip_ac_sens): its own transfer buffers, each grown on demand to the capacity beside it
+  // sensitivity sweep (AcSensSys, cadnip_ac_sens): its own transfer buffers, each grown on demand to the capacity beside it
   int* d_sens_idx = nullptr;                                   // base [NB] | plus [NB][K] | minus [NB][K]
   double *d_sens_scale = nullptr, *d_sens_bac = nullptr, *d_sens_db = nullptr, *d_sens_c = nullptr;   // [NB][K]; [NB][n], [NB][K][n], [n] complex
   double *d_sens_y = nullptr, *d_sens_berr = nullptr, *d_sens_s = nullptr, *d_sens_x = nullptr;       // [S] complex, [S][2]; [S][K] complex; [S][2][n] complex
@@ -169,7 +169,7 @@ struct AcState {
     f((void**)&d_sens_idx); f((void**)&d_sens_scale); f((void**)&d_sens_bac); f((void**)&d_sens_db); f((void**)&d_sens_c);
     f((void**)&d_sens_y); f((void**)&d_sens_berr); f((void**)&d_sens_s); f((void**)&d_sens_x); f((void**)&d_sens_flags);
   }
-  // Arnoldi sweep (k_ac_arnoldi, cadnip_ac_arnoldi): its own transfer buffers, each grown on demand to the capacity beside it
+  // Arnoldi sweep (AcArnoldiSys, cadnip_ac_arnoldi): its own transfer buffers, each grown on demand to the capacity beside it
   double *d_arn_bac = nullptr, *d_arn_H = nullptr, *d_arn_beta = nullptr, *d_arn_l = nullptr, *d_arn_V = nullptr, *d_arn_berr = nullptr;   // [B][n], [S][m+1][m], -, [S][m][pairs], [S][m+1][n] complex; beta, berr [S]
   int *d_arn_pairs = nullptr, *d_arn_meff = nullptr, *d_arn_flags = nullptr;                                                              // [pairs][2]; [S]; [S]
   size_t cap_arn_bac = 0, cap_arn_H = 0, cap_arn_l = 0, cap_arn_V = 0, cap_arn_pairs = 0, cap_arn_sys = 0;   // complex words (four); pairs; systems (beta, berr, meff, flags)
@@ -177,7 +177,7 @@ struct AcState {
     f((void**)&d_arn_bac); f((void**)&d_arn_H); f((void**)&d_arn_beta); f((void**)&d_arn_l); f((void**)&d_arn_V); f((void**)&d_arn_berr);
     f((void**)&d_arn_pairs); f((void**)&d_arn_meff); f((void**)&d_arn_flags);
   }
-  // HBM-resident variant (k_ac_lu_hbm / k_ac_adj_hbm; cadnip_ac_set_memory, ac_hbm_plan.hpp): the setting, the persistent waves' workspace
+  // HBM-resident form (k_ac_hbm; cadnip_ac_set_memory, ac_hbm_plan.hpp): the setting, the persistent waves' workspace
   // (grown on demand like the buffers above, released with the handle) and what the last AC / adjoint call ran (cadnip_ac_plan_info)
   int memory = CADNIP_AC_LDS, max_waves = 0;
   double* d_work = nullptr; size_t cap_work = 0;   // cap_work: bytes
@@ -305,10 +305,10 @@ int launch_solve(CadnipHandle* h, const double* d_rhs, double* d_x);
 int launch_factor_solve(CadnipHandle* h, bool fuse_jacobian, const double* d_rhs, double* d_x, int kernel = CADNIP_LUK_AUTO, int* info = nullptr,
                         bool dry = false);
 int upload_lu(CadnipHandle* h);
-// ac_lu.hip: the launch plan of k_ac_lu<W> for n_sys systems -- wpb_req 0: the plan's choice (CADNIP_AC_WPB overrides it), else 1 / 2 / 4 / 8.
+// ac_lu.hip: the launch plan of k_ac<W, S> for n_sys systems -- wpb_req 0: the plan's choice (CADNIP_AC_WPB overrides it), else 1 / 2 / 4 / 8.
 // wpb 0: an invalid request, or the work arrays of wpb_req (of one, for 0) systems exceed LDS_BUDGET
 struct AcPlan { int wpb = 0; size_t shmem = 0; };
-AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req, bool sens = false);   // sens: of k_ac_sens<W>, 16 (nnz(L+U) + 4 n) bytes per system
+AcPlan ac_lu_plan(const CadnipHandle* h, long n_sys, int wpb_req, bool sens = false);   // sens: of the families with four n-vectors (AcSensSys, AcArnoldiSys), 16 (nnz(L+U) + 4 n) bytes per system
 // the home of a call's work arrays under the handle's setting (h->ac.memory) and its plan: memory CADNIP_AC_LDS -> lds, CADNIP_AC_HBM -> hbm
 // (ac_hbm_plan.hpp, on the device's compute units and h->ac.max_waves); -1: refused -- an invalid wpb, or the circuit fits neither
 struct AcLaunch {
@@ -321,20 +321,20 @@ AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req, bool sens = fa
 int ac_lu_prepare(CadnipHandle* h, bool adjoint = false);
 // systems [s0, s0 + n_sys) of the B x n_freq grid (s = b * n_freq + f) into h->ac.d_x / d_berr / d_flags from index 0
 int launch_ac_lu(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin);
-// ... of A^T x = c (c in h->ac.d_bac) through k_ac_adj: h[k] = x[p_k] - x[n_k] for the n_pairs pairs of h->ac.d_pairs into h->ac.d_h, berr and
+// ... of A^T x = c (c in h->ac.d_bac) through AcAdjSys: h[k] = x[p_k] - x[n_k] for the n_pairs pairs of h->ac.d_pairs into h->ac.d_h, berr and
 // flags into d_adj_berr / d_adj_flags, x into d_adj_x with want_x -- all from index 0
 int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x);
-// ... of A x_k = b_k for the n_rhs columns per instance in h->ac.d_multi_rhs through k_ac_lu_multi (one factorisation per system): per (system,
+// ... of A x_k = b_k for the n_rhs columns per instance in h->ac.d_multi_rhs through AcLuMultiSys (one factorisation per system): per (system,
 // column) the n_pairs probe differences into d_multi_h, x into d_multi_x with want_x, berr and flags into d_multi_berr / d_multi_flags
 int launch_ac_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x);
-// ... of A^T x_k = c_k for the n_rhs columns per instance in h->ac.d_multi_rhs through k_ac_adj_multi (one factorisation per system; needs
+// ... of A^T x_k = c_k for the n_rhs columns per instance in h->ac.d_multi_rhs through AcAdjMultiSys (one factorisation per system; needs
 // ac_lu_prepare(h, true)): the outputs as launch_ac_multi, in the same buffers
 int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x);
-// systems [s0, s0 + n_sys) of the n_base x n_freq grid of cadnip_ac_sens (s = b * n_freq + f, b an index into the base list) through k_ac_sens
+// systems [s0, s0 + n_sys) of the n_base x n_freq grid of cadnip_ac_sens (s = b * n_freq + f, b an index into the base list) through AcSensSys
 // (needs ac_lu_prepare(h, true); p must come from ac_launch_plan(.., sens = true)): inputs and outputs in the d_sens_* buffers, outputs from
 // index 0; n_par columns, db: a db buffer was uploaded (else zeros), pair: the output pair
 int launch_ac_sens(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, bool db, const int* pair, bool want_x);
-// systems [s0, s0 + n_sys) of the B x n_shift grid of cadnip_ac_arnoldi (s = b * n_shift + shift) through k_ac_arnoldi (p must come from
+// systems [s0, s0 + n_sys) of the B x n_shift grid of cadnip_ac_arnoldi (s = b * n_shift + shift) through AcArnoldiSys (p must come from
 // ac_launch_plan(.., sens = true): the same four n-vectors): inputs and outputs in the d_arn_* buffers, outputs from index 0; m steps,
 // breakdown tolerance tol, n_pairs probe pairs
 int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& p, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs);

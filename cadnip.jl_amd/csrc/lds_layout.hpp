@@ -1,4 +1,4 @@
-// lds_layout.hpp -- THE map of the dynamic LDS block of every LDS-resident kernel (k_fused2, k_fteam, k_lu_*, k_ac_lu).  The kernels take their
+// lds_layout.hpp -- THE map of the dynamic LDS block of every LDS-resident kernel (k_fused2, k_fteam, k_lu_*, k_ac).  The kernels take their
 // pointers from it and the launchers their `shmem`: nobody else adds up table, descriptor or work-array words.  Plain C++ behind the
 // __host__ __device__ markers (tests/test_lds_layout.py compiles it with the host compiler).
 //
@@ -95,7 +95,7 @@ template <class P> LDS_HD LdsLu<P> lds_lu(P base, int tab_len, int desc_len, int
   L.end = L.desc + desc_len + (size_t)waves * L.per;
   return L;
 }
-// AC kernel k_ac_lu<W>: W x [ complex L\U factors (nnz_lu) | x: rhs / solution (n) | r: residual (n) | y: correction, the solves' work
+// AC kernel k_ac<W, S> (ac_lu.hip), three-vector families: W x [ complex L\U factors (nnz_lu) | x: rhs / solution (n) | r: residual (n) | y: correction, the solves' work
 // vector (n) ], every value an interleaved (re, im) pair of doubles -- 16 (nnz_lu + 3 n) bytes per system, each region on 16 bytes.  No
 // tables: the index arrays are read from global memory.  Regions of system w of the workgroup
 template <class P> struct LdsAc { P lu, x, r, y, end; int per; };   // per: doubles of one system
@@ -107,7 +107,7 @@ template <class P> LDS_HD LdsAc<P> lds_ac(P base, int nnz_lu, int n, int w, int 
   L.end = base + (size_t)wpb * L.per;
   return L;
 }
-// Sensitivity kernel k_ac_sens<W>: lds_ac's regions in lds_ac's order, then xf (n): the forward solution, which has to outlive the adjoint
+// ... four-vector families (AcSensSys, AcArnoldiSys): lds_ac's regions in lds_ac's order, then xf (n): the forward solution, which has to outlive the adjoint
 // column that runs in x / r / y -- 16 (nnz_lu + 4 n) bytes per system
 template <class P> struct LdsAcSens { P lu, x, r, y, xf, end; int per; };   // per: doubles of one system
 template <class P> LDS_HD LdsAcSens<P> lds_ac_sens(P base, int nnz_lu, int n, int w, int wpb) {

@@ -1,5 +1,5 @@
 // lu_transpose.hpp -- the tables of a TRANSPOSED solve through row-stored factors, as host-only combinatorics (the manner of
-// stamp_plan.hpp): no HIP, no handle.  The adjoint kernel k_ac_adj (ac_lu.hip) solves A^T x = c with the factors k_ac_lu computes.  With
+// stamp_plan.hpp): no HIP, no handle.  The adjoint family AcAdjSys (ac_lu.hip) solves A^T x = c with the factors AcLuSys computes.  With
 // M = A[rperm][:, cperm] = L U (LUProgram: row-major L\U, sorted columns, lu_diag[i] = position of U(i,i)):
 //   A^T x = c  <=>  M^T x_r = c_c:   y[j] = c[cperm[j]],   U^T z = y (forward),   L^T w = z (backward),   x[rperm[i]] = w[i]
 // -- rperm and cperm swap roles against the plain solve.  Row j of U^T is column j of U, so both substitutions need the factors by column:

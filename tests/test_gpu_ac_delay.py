@@ -189,6 +189,43 @@ def test_columns_of_the_multi_calls_are_the_single_column_calls(name):
             c.h.ac_set_memory("lds")
 
 
+@pytest.mark.parametrize("adjoint", [False, True])
+def test_the_multi_calls_under_an_overlay_at_a_forced_width_and_on_strided_waves(adjoint):
+    """The two seams of the kernel pair for the multi families with an overlay, which the test above reaches only at the plan's own width:
+    the smallest circuit of ac_ref.CASES, 2 instances x 3 frequencies = 6 systems, under a table of its own (two CSR positions, values that
+    differ per instance and frequency).  W = 4 in LDS: two workgroups, the second with two waves that have no system.  Two persistent
+    waves in device memory: each runs three systems, K columns each, in its one workspace.  Both to the bit against W = 1 in LDS."""
+    from tests import test_gpu_ac_lu as T
+    c = T.case("butterworth")
+    sim = api.BatchSimulator(api.MNACircuit(c.circ, {}, api.MNASpec(mode="dcop")), [{}, {}])
+    try:
+        h, n = sim.h, c.st.n
+        h.set_spec(mode="dcop")
+        h.rebuild(c.u[[0, 0]], 0.0)
+        h.analyze_values(c.sample_ref)
+        om = c.om[[0, len(c.om) // 2, -1]]
+        rng = np.random.default_rng(11)
+        pos = np.array([0, c.st.nnz - 1], dtype=np.int32)
+        val = 1e-3 * (rng.standard_normal((2, 3, 2)) + 1j * rng.standard_normal((2, 3, 2)))
+        cols = rng.standard_normal((2, 2, n)) + 1j * rng.standard_normal((2, 2, n))
+        pairs = np.array([(i, -1) for i in range(n)], dtype=np.int32)
+        call = h.ac_adjoint_multi if adjoint else h.ac_solve_multi
+        plain = call(om, GMIN, cols, pairs, 1, True)
+        h.ac_set_overlay(pos, om, val)
+        ref = call(om, GMIN, cols, pairs, 1, True)
+        assert ref[4]["systems"] == 6 and ref[4]["workgroups"] == 6 and not ref[3].any() and not same(ref[1], plain[1])
+        got = call(om, GMIN, cols, pairs, 4, True)
+        assert got[4]["wpb"] == 4 and got[4]["workgroups"] == 2 and got[4]["lds_bytes"] > 0
+        assert same(got[0], ref[0]) and same(got[1], ref[1]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3])
+        h.ac_set_memory("hbm", 2)
+        for wpb in (1, 4):
+            got = call(om, GMIN, cols, pairs, wpb, True)
+            assert got[4]["lds_bytes"] == 0 and h.ac_plan_info()["memory"] == "hbm" and h.ac_plan_info()["n_waves"] == 2
+            assert same(got[0], ref[0]) and same(got[1], ref[1]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]), wpb
+    finally:
+        sim.close()
+
+
 def test_a_system_alone_equals_the_same_system_in_the_batch():
     c = case("tline")
     with overlay(c):
