@@ -7,8 +7,10 @@
 // k_delay_apply turns the round's stamps into G_tran = G - W, b_tran = b - sum w ud(col, tcur - tau) for exactly the instances the rebuild
 // stamped (activity mask, running status): where the rebuild skipped an instance G still holds last round's G - W.  One thread per
 // (instance, position) and per (instance, delayed row); a row sums its terms in table order -- no atomics, the same bits on every run.
-// k_delay_record appends (t, u0[tap]) whenever the controller has accepted a step (its t has moved past the ring's newest time) and
-// turns a look-up that fell off the ring into the instance's status.  Both are a few loads per thread and latency-bound: an instance's
+// A look-up that fell off the ring ends its instance there: k_delay_apply itself writes the status and clears the activity mask, so the
+// round's residual, factorisation and k_tran_update leave the instance alone -- no counter, time, history or save slot moves on a right-hand
+// side with a term missing.  k_delay_record appends (t, u0[tap]) whenever the controller has accepted a step (its t has moved past the
+// ring's newest time).  Both are a few loads per thread and latency-bound: an instance's
 // ring times are contiguous (the binary search stays in one or two cache lines for the ring depths a run fills), the term tables of
 // an instance are contiguous, and consecutive threads write consecutive positions / rows.
 #include <hip/hip_runtime.h>
@@ -24,7 +26,7 @@ namespace cadnip {
 struct DelayArgs {
   const int *pos, *taps, *rows, *row_ptr, *term_tap; const unsigned char* row_store;
   const double *tau, *w, *W;
-  double *hist_t, *hist_v, *v_init; int *head, *count, *ovf;
+  double *hist_t, *hist_v, *v_init; int *head, *count;
   double *G, *b; const double *tcur, *u; int* active;
   int B, n, nnz, n_pos, n_term, n_taps, n_rows, depth; double t0;
 };
@@ -36,10 +38,10 @@ __global__ void __launch_bounds__(64) k_delay_init(DelayArgs a) {
   const double v = a.u[(size_t)inst * a.n + a.taps[tap]];
   a.v_init[id] = v;
   a.hist_v[(size_t)id * a.depth] = v;
-  if (tap == 0) { a.hist_t[(size_t)inst * a.depth] = a.t0; a.head[inst] = a.depth > 1 ? 1 : 0; a.count[inst] = 1; a.ovf[inst] = 0; }
+  if (tap == 0) { a.hist_t[(size_t)inst * a.depth] = a.t0; a.head[inst] = a.depth > 1 ? 1 : 0; a.count[inst] = 1; }
 }
 
-__global__ void __launch_bounds__(256) k_delay_apply(DelayArgs a, const int* status) {
+__global__ void __launch_bounds__(256) k_delay_apply(DelayArgs a, int* status) {
   const int per = a.n_pos + a.n_rows;
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= (long)a.B * per) return;
@@ -55,29 +57,27 @@ __global__ void __launch_bounds__(256) k_delay_apply(DelayArgs a, const int* sta
   const int head = a.head[inst], count = a.count[inst];
   const double *tau = a.tau + (size_t)inst * a.n_term, *w = a.w + (size_t)inst * a.n_term;
   double acc = 0.0;
-  bool ovf = false;
   for (int j = a.row_ptr[r]; j < a.row_ptr[r + 1]; ++j) {
     const DelayLookup L = delay_lookup(ht, head, count, a.depth, a.t0, tn - tau[j]);
-    if (L.kind == DELAY_OVERFLOW) { ovf = true; continue; }
+    if (L.kind == DELAY_OVERFLOW) {
+      // the instance ends here, before the round is solved.  Other threads of this launch may or may not see the two stores: whatever they
+      // still write to G and b of the instance is never read (every later kernel of the run skips it, the next rebuild rewrites both)
+      status[inst] = CADNIP_TRAN_DELAY_OVERFLOW;
+      a.active[inst] = 0;
+      return;
+    }
     const size_t tap = (size_t)inst * a.n_taps + a.term_tap[j];
     acc += w[j] * delay_value(L, a.hist_v + tap * a.depth, a.v_init[tap]);
   }
   double* brow = a.b + (size_t)inst * a.n + a.rows[r];
   *brow = (a.row_store[r] ? 0.0 : *brow) - acc;         // a row no device stamps is never rewritten by the rebuild: store, do not accumulate
-  if (ovf) a.ovf[inst] = 1;
 }
 
 __global__ void __launch_bounds__(64) k_delay_record(DelayArgs a, const double* t, const double* u0, int* status) {
   const int inst = blockIdx.x * 64 + threadIdx.x;
   if (inst >= a.B) return;
-  if (a.ovf[inst]) {            // this round's look-up fell off the ring: whatever the round computed does not count
-    a.ovf[inst] = 0;
-    status[inst] = CADNIP_TRAN_DELAY_OVERFLOW;
-    a.active[inst] = 0;
-    return;
-  }
   const int st = status[inst];
-  if (st != 0 && st != 1) return;
+  if (st != 0 && st != 1) return;                                                   // (an overflow among them: k_delay_apply ended the instance)
   int head = a.head[inst], count = a.count[inst];
   const double tacc = t[inst];
   double* ht = a.hist_t + (size_t)inst * a.depth;
@@ -101,7 +101,7 @@ static DelayArgs delay_args(CadnipHandle* h) {
   DelayArgs a{};
   a.pos = D.d_pos; a.taps = D.d_taps; a.rows = D.d_rows; a.row_ptr = D.d_row_ptr; a.term_tap = D.d_term_tap; a.row_store = D.d_row_store;
   a.tau = D.d_tau; a.w = D.d_w; a.W = D.d_W;
-  a.hist_t = D.d_hist_t; a.hist_v = D.d_hist_v; a.v_init = D.d_v_init; a.head = D.d_head; a.count = D.d_count; a.ovf = D.d_ovf;
+  a.hist_t = D.d_hist_t; a.hist_v = D.d_hist_v; a.v_init = D.d_v_init; a.head = D.d_head; a.count = D.d_count;
   a.G = h->d_G; a.b = h->d_b; a.tcur = h->d_t; a.u = h->d_u; a.active = h->d_active;
   a.B = h->B; a.n = h->n; a.nnz = h->nnz; a.n_pos = D.n_pos; a.n_term = D.n_term; a.n_taps = D.n_taps; a.n_rows = D.n_rows; a.depth = D.depth;
   a.t0 = D.t0;
@@ -122,7 +122,7 @@ int launch_delay_init(CadnipHandle* h, double t0) {
   return CADNIP_OK;
 }
 
-int launch_delay_apply(CadnipHandle* h, const int* d_status) {
+int launch_delay_apply(CadnipHandle* h, int* d_status) {
   ProfScope ps(h, "delay_apply");
   const DelayArgs a = delay_args(h);
   const long total = (long)h->B * (a.n_pos + a.n_rows);
@@ -200,9 +200,15 @@ extern "C" int cadnip_tran_set_delay(CadnipHandle* h, const CadnipDelaySpec* s) 
   if (!rc) rc = dly_upload(&D.d_v_init, (const double*)nullptr, B * ntap);
   if (!rc) rc = dly_upload(&D.d_head, (const int*)nullptr, B);
   if (!rc) rc = dly_upload(&D.d_count, (const int*)nullptr, B);
-  if (!rc) rc = dly_upload(&D.d_ovf, (const int*)nullptr, B);
   if (rc) { D.each_buffer([](void** p) { if (*p) (void)hipFree(*p); }); return rc; }
   delay_release(h);
   h->dly = D;
+  return CADNIP_OK;
+}
+
+extern "C" int cadnip_tran_delay_info(CadnipHandle* h, int32_t out[5]) {
+  if (!h || !out) return CADNIP_BADARG;
+  const DelayState& D = h->dly;
+  out[0] = D.n_pos; out[1] = D.n_rows; out[2] = D.n_taps; out[3] = D.n_term; out[4] = D.depth;
   return CADNIP_OK;
 }

@@ -205,11 +205,11 @@ struct DelayState {
   unsigned char* d_row_store = nullptr;     // [n_rows] 1 = no device stamps this row of b: the kernel stores, and the run clears it at its end
   double *d_tau = nullptr, *d_w = nullptr, *d_W = nullptr;               // [B][n_term] in the plan's grouped order; [B][n_pos]
   double *d_hist_t = nullptr, *d_hist_v = nullptr, *d_v_init = nullptr;  // [B][depth], [B][n_taps][depth], [B][n_taps]
-  int *d_head = nullptr, *d_count = nullptr, *d_ovf = nullptr;           // [B] ring head and count; 1 = a look-up fell off the ring
+  int *d_head = nullptr, *d_count = nullptr;                              // [B] ring head and count
   template <class F> void each_buffer(F f) {
     f((void**)&d_pos); f((void**)&d_taps); f((void**)&d_rows); f((void**)&d_row_ptr); f((void**)&d_term_tap); f((void**)&d_row_store);
     f((void**)&d_tau); f((void**)&d_w); f((void**)&d_W); f((void**)&d_hist_t); f((void**)&d_hist_v); f((void**)&d_v_init);
-    f((void**)&d_head); f((void**)&d_count); f((void**)&d_ovf);
+    f((void**)&d_head); f((void**)&d_count);
   }
 };
 
@@ -342,8 +342,8 @@ int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& p, int n_shift, long s0, 
 // status (0 = running), t (accepted time), u0 (newest accepted vector [B][n])
 void delay_release(CadnipHandle* h);                                       // frees everything; no spec is set afterwards
 int launch_delay_init(CadnipHandle* h, double t0);                         // v_init and the first ring entry (t0, u[tap]) from h->d_u
-int launch_delay_apply(CadnipHandle* h, const int* d_status);              // G -= W, b[row] -= sum w ud(col, tcur - tau) where the rebuild stamped
-int launch_delay_record(CadnipHandle* h, const double* d_t, const double* d_u0, int* d_status);   // appends accepted points; surfaces an overflow
+int launch_delay_apply(CadnipHandle* h, int* d_status);                    // G -= W, b[row] -= sum w ud(col, tcur - tau) where the rebuild stamped; ends an instance whose look-up overflows
+int launch_delay_record(CadnipHandle* h, const double* d_t, const double* d_u0, int* d_status);   // appends accepted points
 int launch_delay_clear(CadnipHandle* h);                                   // zeroes the rows of b that only k_delay_apply writes
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again

@@ -30,7 +30,7 @@ EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
     "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_sens", "cadnip_ac_arnoldi", "cadnip_ac_set_memory", "cadnip_ac_set_overlay", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
-    "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_set_delay", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
+    "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_set_delay", "cadnip_tran_delay_info", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
     "cadnip_host_f2_build", "cadnip_host_f2_size", "cadnip_host_f2_get", "cadnip_host_f2_free", "cadnip_host_f2_team_steps", "cadnip_host_f2_steps",
@@ -648,6 +648,13 @@ class Handle:
         ww = np.ascontiguousarray(np.broadcast_to(ww, (self.B, tp.size)))
         spec = DelaySpecC(ps.size, _ip(ps), tp.size, _ip(tp), _ip(tr), _ip(tc), _dp(tt), _dp(ww), int(depth))
         _check(self.lib.cadnip_tran_set_delay(self.h, C.byref(spec)), "cadnip_tran_set_delay")
+
+    def tran_delay_info(self):
+        """cadnip_tran_delay_info: {n_pos, n_rows, n_taps, n_term, depth} of the plan built from the delay spec in force (zeros without one):
+        the sizes the delay kernels index by."""
+        out = (C.c_int32 * 5)()
+        _check(self.lib.cadnip_tran_delay_info(self.h, out), "cadnip_tran_delay_info")
+        return dict(zip(("n_pos", "n_rows", "n_taps", "n_term", "depth"), (int(x) for x in out)))
 
     def tran_clear_delay(self):
         """cadnip_tran_set_delay with no spec: ``tran_run`` is again exactly what it is on a new handle."""

@@ -441,7 +441,10 @@ int cadnip_dc_run(CadnipHandle* h, const CadnipDCOpts* o, double* u_host, int32_
  * absdelay without history does.  depth: 0 = 1024.  The arrays are copied: they may be released after the call.
  * spec == NULL or n_term == 0 clears the setting and frees its memory.  CADNIP_BADARG -- the previous setting stays in force -- with an
  * index out of range, a position named twice, a term whose (row, col) is not the coordinate of its position, a tau that is not a
- * positive finite number, depth < 0 or == 1, or a ring beyond 256 MiB (8 B (n_taps + 1) depth bytes; n_taps: the distinct term_col). */
+ * positive finite number, depth < 0 or == 1, or a ring beyond 256 MiB (8 B (n_taps + 1) depth bytes; n_taps: the distinct term_col).
+ * An instance that ended with CADNIP_TRAN_DELAY_OVERFLOW is ended by k_delay_apply in the middle of a round's launch: its saved outputs,
+ * counters and state are those of its last accepted step, but its G and b in device memory (cadnip_get_GCb before the next
+ * cadnip_rebuild) may hold a mix of G and G - W, b and b_tran -- other threads of that launch read the status without synchronisation. */
 #define CADNIP_TRAN_DELAY_OVERFLOW (-4)
 typedef struct {
   int32_t n_pos;  const int32_t* pos;        /* [n_pos] CSR positions in [0, nnz), distinct */
@@ -453,6 +456,9 @@ typedef struct {
   int32_t depth;                             /* accepted points kept per instance; 0 = 1024 */
 } CadnipDelaySpec;
 int cadnip_tran_set_delay(CadnipHandle* h, const CadnipDelaySpec* spec);
+/* The plan the handle built from the spec in force -- the sizes k_delay_init / k_delay_apply / k_delay_record index by:
+ * out = {n_pos (distinct positions), n_rows (distinct delayed rows of b), n_taps (distinct term_col), n_term, depth}; all zero without a spec */
+int cadnip_tran_delay_info(CadnipHandle* h, int32_t out[5]);
 /* starts from the handle's current state u (e.g. left by cadnip_dc_run in :tranop mode);
  * out_host [B][n_save][n_obs]; per_inst_host [B][4] = {newton_iters, accepted, rejected, status}; status 1 = reached t1, -1 / -2 = the step
  * fell below hmin after a failed error test / Newton iteration, CADNIP_TRAN_DELAY_OVERFLOW = see cadnip_tran_set_delay */

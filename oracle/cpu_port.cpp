@@ -70,6 +70,35 @@ struct Port {
   // port's own device code -- how a circuit of generated Verilog-A models (which the port does not know) gets a transient oracle: the
   // literal Python interpreter (oracle/va_ref.py through oracle/mna_ref.py's fast_rebuild!) stamps, the port's controller and LU run.
   void (*ext_stamp)(const double* u, double t, double* G, double* C, double* b, double* limit_w) = nullptr;
+  // Transport delays (port_set_delay): terms (row, col, w, tau) in table order, `pos` their CSR entry, `tap` the index of col among the
+  // distinct cols; dW the sum of the w of a CSR position (positions in order of first appearance, a position's terms in table order)
+  struct DelayTerm { int row, col, pos, tap; double w, tau; };
+  std::vector<DelayTerm> dterms;
+  std::vector<int> dpos, dtaps, drows;
+  std::vector<double> dW;
+  int ddepth = 0;
+  double dtau_min = 0.0;
+};
+
+// The history of a delayed run: every accepted point (t, u[tap]) from (t0, u0) on, never shortened.  The rule of the look-up is the one of
+// tests/tran_delay_ref.py's docstring: ud(tq) is the start value for tq <= t0, the newest value for tq at or beyond the newest accepted time,
+// otherwise the straight line v_j + (tq - t_j) / (t_{j+1} - t_j) (v_{j+1} - v_j) between the accepted points that bracket tq.  `depth` > 0
+// makes only the last `depth` points count as kept: a look-up with tq > t0 whose bracket starts before the oldest kept point has no value
+// (ok = false).  `need`: the points from the bracket's lower one through the newest that the look-up used.
+struct DelayHistory {
+  std::vector<double> t;
+  std::vector<std::vector<double>> v;   // [tap][point]
+  double value(int tap, double tq, int depth, bool& ok, int64_t& need) const {
+    const int N = (int)t.size();
+    ok = true; need = 0;
+    if (tq <= t[0]) return v[tap][0];
+    if (tq >= t[N - 1]) { need = 1; return v[tap][N - 1]; }
+    const int j = (int)(std::upper_bound(t.begin(), t.end(), tq) - t.begin()) - 1;   // the largest j with t_j <= tq; j + 1 < N
+    need = N - j;
+    if (depth > 0 && need > depth) { ok = false; return 0.0; }
+    const double vj = v[tap][j];
+    return vj + (tq - t[j]) / (t[j + 1] - t[j]) * (v[tap][j + 1] - vj);
+  }
 };
 
 // ---- waves (devices.jl:30-103,155-203) ---------------------------------------------------------
@@ -471,6 +500,32 @@ void port_set_stamp_callback(void* p, void (*cb)(const double*, double, double*,
 void port_set_spec(void* p, int mode, double gmin, double gshunt, double srcFact, int initjct) {
   Port* P = (Port*)p; P->mode = mode; P->gmin = gmin; P->gshunt = gshunt; P->srcFact = srcFact; P->initjct = initjct;
 }
+// Transport delays of port_tran: terms (rows[k], cols[k], w[k], tau[k]) on the port's unknown indices -- the coefficient w that the undelayed
+// stamp puts at G[row, col] acts on u[col](t - tau) instead.  The port finds the CSR entry itself; a term without one, a tau that is not
+// positive and finite or a negative depth is refused (returns 1, the setting in force stays).  n_term = 0 clears the setting.
+// depth > 0: only the last `depth` accepted points count as kept (DelayHistory).
+int port_set_delay(void* p, int n_term, const int* rows, const int* cols, const double* w, const double* tau, int depth) {
+  Port* P = (Port*)p;
+  std::vector<Port::DelayTerm> terms; std::vector<int> dpos, dtaps, drows; std::vector<double> dW;
+  double tau_min = 0.0;
+  if (n_term < 0 || depth < 0) return 1;
+  for (int k = 0; k < n_term; ++k) {
+    const int r = rows[k], c = cols[k];
+    if (r < 0 || r >= P->n || c < 0 || c >= P->n || !(tau[k] > 0.0) || !std::isfinite(tau[k])) return 1;
+    int e = -1;
+    for (int q = P->rowptr[r]; q < P->rowptr[r + 1]; ++q) if (P->colidx[q] == c) e = q;
+    if (e < 0) return 1;
+    auto slot_of = [](std::vector<int>& v, int x) { size_t i = std::find(v.begin(), v.end(), x) - v.begin(); if (i == v.size()) v.push_back(x); return (int)i; };
+    const int ip = slot_of(dpos, e), it = slot_of(dtaps, c);
+    slot_of(drows, r);
+    if ((size_t)ip == dW.size()) dW.push_back(0.0);
+    dW[ip] += w[k];
+    terms.push_back({r, c, e, it, w[k], tau[k]});
+    tau_min = k == 0 ? tau[k] : std::min(tau_min, tau[k]);
+  }
+  P->dterms = terms; P->dpos = dpos; P->dtaps = dtaps; P->drows = drows; P->dW = dW; P->ddepth = depth; P->dtau_min = tau_min;
+  return 0;
+}
 void port_set_lu(void* p, int nnz_lu, const int* rperm, const int* cperm, const int* rowptr, const int* col, const int* diag, const int* load_src,
                  const int* load_dst, int n_ent, const int* ent_pos, const int* ent_diag, const int* ent_ptr, const int* term_a, const int* term_b) {
   Port* P = (Port*)p; LU& L = P->lu; int n = P->n;
@@ -526,7 +581,10 @@ struct TranOpts {
                      // 2 = the same test with a refactorisation every round (what the per-op GPU path does with newton_mode 1)
   int step_rule;     // 0 = classical step controller, 1 = IDA's eta rule (tran_ctrl.hpp, CadnipTranOpts::step_rule)
 };
-struct TranStats { int64_t newton_iters, accepted, rejected, newton_failures; int status; double wall_seconds; int64_t refactorisations; };
+// status: 1 done, -1 / -2 step below hmin after a failed error test / Newton failure, -4 a delayed look-up older than the oldest kept point
+// (the product's CADNIP_TRAN_DELAY_OVERFLOW), -5 an attempted step longer than the smallest delay (the caller's hmax must prevent it).
+// delay_need: the largest number of accepted points, from the lower end of its bracket through the newest, that a delayed look-up used
+struct TranStats { int64_t newton_iters, accepted, rejected, newton_failures; int status; double wall_seconds; int64_t refactorisations, delay_need; };
 
 // the transient driver of cadnip.jl_amd/csrc/driver.hip, one instance, sequential
 int port_tran(void* p, double* u_io, const TranOpts* o, double* out, TranStats* st, double* trace_t, int trace_cap, int* trace_n) {
@@ -542,7 +600,12 @@ int port_tran(void* p, double* u_io, const TranOpts* o, double* out, TranStats* 
   int savedmode = P.mode; P.mode = 1;
   while (bp < o->n_break && o->breaks[bp] <= o->t0) ++bp;
   while (si < o->n_save && o->save_t[si] <= o->t0) { for (int j = 0; j < n_obs; ++j) out[(size_t)si * n_obs + j] = u[o->n_obs > 0 ? o->obs[j] : j]; ++si; }
-  TranStats S{0, 0, 0, 0, 0, 0.0, 0}; int ntrace = 0;
+  TranStats S{0, 0, 0, 0, 0, 0.0, 0, 0}; int ntrace = 0;
+  // delayed terms: the history starts with (t0, u0); the port does not clamp steps (the product clamps to the smallest delay of its whole
+  // batch, which one instance cannot know: the caller passes hmax and h0 clamped) -- it refuses a step longer than its own smallest delay
+  const bool delayed = !P.dterms.empty();
+  DelayHistory H; std::vector<double> dacc;
+  if (delayed) { H.t.push_back(o->t0); H.v.resize(P.dtaps.size()); for (size_t k = 0; k < P.dtaps.size(); ++k) H.v[k].push_back(u[P.dtaps[k]]); dacc.resize(P.drows.size()); }
   const char* dbg_env = getenv("PORT_DEBUG"); const double dbg_from = dbg_env ? atof(dbg_env) : 0.0; bool dbg = false;
   auto prepare = [&](double tt, double hh, int nh, double hp, double hq, double hr) {
     double tstop = o->t1; if (bp < o->n_break && o->breaks[bp] < tstop) tstop = o->breaks[bp];
@@ -584,6 +647,27 @@ int port_tran(void* p, double* u_io, const TranOpts* o, double* out, TranStats* 
   while (status == 0) {
     dbg = dbg_env && tn >= dbg_from;
     rebuild(P, u.data(), tn);
+    if (delayed) {
+      // G - W, and b[row] -= sum w ud(col, tn - tau), a row's terms summed in table order.  (A row of b that no device stamps is zero after
+      // every rebuild: the rebuild sums each row from nothing.)
+      if (h > P.dtau_min) { status = -5; break; }
+      for (size_t k = 0; k < P.dpos.size(); ++k) P.G[P.dpos[k]] -= P.dW[k];
+      bool lost = false;
+      for (size_t q = 0; q < P.drows.size() && !lost; ++q) {
+        double acc = 0.0;
+        for (const Port::DelayTerm& T : P.dterms) {
+          if (T.row != P.drows[q]) continue;
+          bool ok; int64_t used;
+          const double ud = H.value(T.tap, tn - T.tau, P.ddepth, ok, used);
+          S.delay_need = std::max(S.delay_need, used);
+          if (!ok) { lost = true; break; }
+          acc += T.w * ud;
+        }
+        dacc[q] = acc;
+      }
+      if (lost) { status = -4; break; }           // at the look-up: the round is not solved, nothing of it counts
+      for (size_t q = 0; q < P.drows.size(); ++q) P.b[P.drows[q]] -= dacc[q];
+    }
     residual(P, u.data(), du.data(), r.data());
     bool refresh = true; double dsc = 1.0;
     if (mode) {
@@ -658,6 +742,7 @@ int port_tran(void* p, double* u_io, const TranOpts* o, double* out, TranStats* 
         hp3 = hpp;
         t = tn; hprev = new_hprev; hpp = new_hpp; nhist = nh_new; S.accepted += 1; since += 1;
         if (trace_t && ntrace < trace_cap) trace_t[ntrace++] = t;
+        if (delayed) { H.t.push_back(t); for (size_t q = 0; q < P.dtaps.size(); ++q) H.v[q].push_back(u0[P.dtaps[q]]); }
         if (tn >= o->t1) { status = 1; break; }
         if (hnext < hmin) hnext = hmin;
         prepare_attempt(t, hnext, nhist, hprev, hpp);
@@ -688,7 +773,7 @@ int port_tran(void* p, double* u_io, const TranOpts* o, double* out, TranStats* 
   memcpy(u_io, u0.data(), n * sizeof(double));
   S.status = status; S.wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
   if (st) *st = S; if (trace_n) *trace_n = ntrace;
-  return status == 1 ? 0 : 6;
+  return status == 1 ? 0 : (status == -5 ? 7 : 6);
 }
 
 }  // extern "C"

@@ -36,7 +36,8 @@ class TranOptsC(C.Structure):
 
 class TranStatsC(C.Structure):
     _fields_ = [("newton_iters", C.c_int64), ("accepted", C.c_int64), ("rejected", C.c_int64),
-                ("newton_failures", C.c_int64), ("status", C.c_int32), ("wall_seconds", C.c_double), ("refactorisations", C.c_int64)]
+                ("newton_failures", C.c_int64), ("status", C.c_int32), ("wall_seconds", C.c_double), ("refactorisations", C.c_int64),
+                ("delay_need", C.c_int64)]
 
 
 _lib = None
@@ -148,6 +149,19 @@ class Port:
                           _ip(k["diag"]), _ip(k["load_src"]), _ip(k["load_dst"]), int(len(prog["ent_pos"])), _ip(k["ent_pos"]),
                           _ip(k["ent_diag"]), _ip(k["ent_ptr"]), _ip(k["term_a"]), _ip(k["term_b"]))
 
+    def set_delay(self, terms, depth=0):
+        """Transport delays of ``tran``: ``terms`` = [(row, col, w, tau)] on the port's unknown indices -- the stamp w at G[row, col] acts on
+        u[col](t - tau), read from the accepted points (straight line between the two that bracket t - tau; the start value before t0).
+        ``depth`` > 0: only the last ``depth`` accepted points count as kept, and a look-up older than them ends the run with status -4.
+        No terms clears the setting.  A term without a CSR entry or with a tau that is not positive is a ValueError.  The port does not
+        clamp its steps: pass ``hmax`` (and ``h0``) at or below the smallest delay."""
+        terms = list(terms)
+        r, c = _ia([t[0] for t in terms]), _ia([t[1] for t in terms])
+        w, tau = _da([t[2] for t in terms]), _da([t[3] for t in terms])
+        lib().port_set_delay.restype = C.c_int32
+        if lib().port_set_delay(self.p, len(terms), _ip(r), _ip(c), _dp(w), _dp(tau), int(depth)):
+            raise ValueError("port_set_delay: a term has no entry in the pattern, a delay is not positive and finite, or depth < 0")
+
     def rebuild(self, u, t=0.0):
         """fast_rebuild!: returns (G, C, b, limit_w) with G, C in the structure's CSR order."""
         st = self.st
@@ -173,6 +187,8 @@ class Port:
              max_newton=10, max_order=2, use_pcnr=True, newton_tol=1e-3, trace_cap=0, newton_mode=0, step_rule=0):
         n = self.n
         u = np.array(u0, dtype=np.float64)
+        if u.shape != (n,):
+            raise ValueError("tran: u0 must have one value per unknown (%d), got shape %r" % (n, u.shape))
         at = _da(np.broadcast_to(np.asarray(abstol, dtype=np.float64), (n,)))
         em = _da(np.ones(n) if err_mask is None else err_mask)
         br, sv = _da(breaks), _da(save_t)
@@ -185,6 +201,8 @@ class Port:
         st = TranStatsC()
         trace = np.zeros(max(trace_cap, 1))
         ntr = C.c_int32()
-        lib().port_tran(self.p, _dp(u), C.byref(o), _dp(out), C.byref(st), _dp(trace), int(trace_cap), C.byref(ntr))
+        rc = lib().port_tran(self.p, _dp(u), C.byref(o), _dp(out), C.byref(st), _dp(trace), int(trace_cap), C.byref(ntr))
+        if rc == 7:
+            raise ValueError("port_tran: an attempted step exceeds the smallest delay (pass hmax and h0 at or below it)")
         stats = {f: getattr(st, f) for f, _ in TranStatsC._fields_}
         return out[:n_save], u, stats, trace[:ntr.value]

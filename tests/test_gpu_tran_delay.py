@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import cadnip_jl_amd as cj
-from cadnip_jl_amd import api, benchmarks as bm, hip, netlist
+from cadnip_jl_amd import api, hip, netlist
 from tests import tran_delay_cases as K
 from tests import tran_delay_ref as DR
 from tests import tran_exact_cases as X
@@ -25,92 +25,10 @@ REL_TOL = X.REL_TOL_GPU
 TD = K.TD
 
 
-def _sin(freq):
-    return ("sin", 0.0, 1.0, freq, 0.0, 0.0, 0.0)
+CASES = {"buffer": K.buffer_case, "line": K.line_case, "inverter": K.inverter_case, "ghf": K.ghf_case}
 
 
-def buffer_case():
-    """SIN into the delayed buffer; tau per instance: 3 final steps (tq lands on ring times), exactly hmax, and 2.3 steps"""
-    hmax = TD / 16
-    return dict(make=lambda: K.buffer(_sin(0.5 / TD)), base={"tau": 3 * hmax}, points=[{"tau": 3 * hmax}, {"tau": hmax}, {"tau": 2.3 * hmax}],
-                h0=hmax / 64, hmax=hmax, n_steps=96, umax=2.5, start="zero")
-
-
-def line_case():
-    """the mismatched line (30 ohm into 50 ohm into 100 ohm), td swept"""
-    hmax = TD / 8
-    return dict(make=lambda: K.line(K.pwl_ramp(0.3 * TD, 0.9 * TD), 30.0, 100.0), base={"td": TD}, points=[{"td": TD}, {"td": 2.5 * TD}],
-                h0=hmax / 64, hmax=hmax, n_steps=128, umax=1.5, start="zero")
-
-
-def line_inverter():
-    """a 5 V ramp through 50 ohm and a matched line into the gates of tests/tran_exact_cases' sp_mos1 inverter"""
-    c = cj.Circuit("line into an inverter")
-    c.V("VVDD", "VDD", "0", dc=cj.Param("vdd"))
-    c.V("VS", "S", "0", dc=0.0, wave=("pwl", [0.0, 4 * TD, 16 * TD, 1.0], [0.0, 0.0, 5.0, 5.0]))
-    c.R("RS", "S", "P1", 50.0)
-    c.T("T1", "P1", "0", "D", "0", 50.0, cj.Param("td"))
-    c.MOS1("X_tn", "Q", "D", "0", "0", bm.NFET_06V0, w=0.36e-6, l=0.6e-6)
-    c.MOS1("X_tp", "Q", "D", "VDD", "VDD", bm.PFET_06V0, w=0.495e-6, l=0.5e-6)
-    c.C("CQ", "Q", "0", 1e-15)
-    for nm, d, g, s, W, L in (("tn", "Q", "D", "0", 0.36e-6, 0.6e-6), ("tp", "Q", "D", "VDD", 0.495e-6, 0.5e-6)):
-        cg = bm.lumped_gate_cap(W, L)
-        c.C("Cgs_" + nm, g, s, cg)
-        c.C("Cgd_" + nm, g, d, cg)
-    return c
-
-
-def inverter_case():
-    """nonlinear: several Newton rounds per step on one delayed value.  116 ps steps as tran_exact_cases' inverter; the edge reaches the gates
-    after td = 4 TD / 5 TD and the window (0 .. 18 TD) holds the turn-on of both transistors"""
-    hmax = TD / 8
-    return dict(make=line_inverter, base={"vdd": 5.0, "td": 4 * TD}, points=[{"vdd": 5.0, "temp": 27.0, "td": 4 * TD}, {"vdd": 4.5, "temp": 125.0, "td": 5 * TD}],
-                h0=hmax / 8, hmax=hmax, n_steps=144, umax=6.0, start="dc")
-
-
-def ghf_circuit():
-    """a delayed G, a delayed H and a delayed F in one chain: voltage- and current-controlled, current- and voltage-output stamps"""
-    c = cj.Circuit("delayed G, H, F")
-    c.V("vin", "in", "0", dc=0.0, wave=_sin(0.25 / TD))
-    c.R("r1", "in", "a", 1e3)
-    c.R("ra", "a", "0", 1e3)
-    c.G("g1", "c", "0", "a", "0", 2e-3, delay=cj.Param("t1"))
-    c.R("rc", "c", "0", 1e3)
-    c.C("cc", "c", "0", TD / 1e3)
-    c.R("rs", "c", "e", 1e3)
-    c.H("h1", "d", "0", "e", "0", 2e3, delay=cj.Param("t2"))          # senses the current of rs into its zero-volt branch e -> 0
-    c.R("rd", "d", "f", 1e3)
-    c.F("f1", "g", "0", "f", "0", 1.5, delay=1.25 * TD)               # senses the current of rd
-    c.R("rg", "g", "0", 1e3)
-    c.C("cg", "g", "0", TD / 2e3)
-    return c
-
-
-def ghf_case():
-    hmax = TD / 16
-    return dict(make=ghf_circuit, base={"t1": TD, "t2": TD}, points=[{"t1": 0.5 * TD, "t2": 0.7 * TD}, {"t1": hmax, "t2": 2 * TD}],
-                h0=hmax / 64, hmax=hmax, n_steps=96, umax=2.5, start="zero")
-
-
-CASES = {"buffer": buffer_case, "line": line_case, "inverter": inverter_case, "ghf": ghf_case}
-
-
-def _tau_tol(case):
-    return min(1e-11, 1e-10 / (case["n_steps"] * 0.33 * (1.0 + case["umax"])))
-
-
-def _params(case, i):
-    p = dict(case["base"])
-    p.update({k: v for k, v in case["points"][i].items() if k != "temp"})
-    return p
-
-
-def _save_times(case, order):
-    """every grid point, and off-grid times inside step 1, step 2, the doubling phase and the constant phase (tran_exact_cases.Case.save_times)"""
-    g = TR.schedule(0.0, case["h0"], case["hmax"], case["n_steps"], order)[0]
-    n = case["n_steps"]
-    off = [g[k - 1] + f * (g[k] - g[k - 1]) for k, f in ((1, 0.25), (2, 0.25), (3, 0.5), (n - 3, 0.8))]
-    return np.sort(np.concatenate([g, off]))
+_tau_tol, _params, _save_times = K.tau_tol, K.case_params, K.save_times
 
 
 def _set_delay(sim, depth=0):
@@ -192,7 +110,7 @@ def test_ring_overflow_stops_its_instance_and_nothing_else():
 
 
 def test_spec_validation_and_clearing():
-    case = buffer_case()
+    case = K.buffer_case()
     sim = api.BatchSimulator(api.MNACircuit(case["make"](), case["base"]), case["points"])
     try:
         good = sim.delay_spec()
