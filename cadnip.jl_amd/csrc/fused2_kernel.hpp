@@ -337,6 +337,18 @@ __device__ __forceinline__ void dense_core_solve(double* W, int dn0, int yc0, in
     }
   }
 }
+// ... for a core of nc > 0 rows: the three sizes the solve is unrolled for (fused2.hip: f2_prepare chooses nc = 0, 8, 12 or F2_NCMAX).
+// A macro on purpose: as a function template dense_core<MODE>(nc, ...) the same three lines gave each of the nine k_lu_f2 / k_lu_f2s /
+// k_lu_f2_mw kernels two more SGPRs and another block order in their pass loops; expanded in place the kernels
+// compile as they did with the chain written out.  Arguments must be free of side effects: nc is evaluated up to twice, the others
+// in the one branch taken (yc0 once)
+#define DENSE_CORE(MODE, nc, W, dn0, yc0, lane, bad, keep)                                  \
+  do {                                                                                       \
+    const int yc0_ = (yc0);                                                                  \
+    if ((nc) == 8) dense_core_solve<8, MODE>(W, dn0, yc0_, lane, bad, keep);                 \
+    else if ((nc) == 12) dense_core_solve<12, MODE>(W, dn0, yc0_, lane, bad, keep);          \
+    else dense_core_solve<F2_NCMAX, MODE>(W, dn0, yc0_, lane, bad, keep);                    \
+  } while (0)
 
 // VAR: 0 = direct residuals, lean device set; 1 = direct residuals, every device type; 2 = assembled residual
 // r = J u + C beta - b (diagnostic, CADNIP_F2_NODIRECT=1), every device type; 3 = variant 0 with the default transient call's switches
@@ -876,15 +888,8 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
       CADNIP_WAVE_SYNC();
     } else if (f.nc > 0) {
       const int yc0 = f.nnz_lu + n - f.nc;
-      if (refresh) {
-        if (f.nc == 8) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, mn);
-        else if (f.nc == 12) dense_core_solve<12, 0>(W, f.dn0, yc0, lane, bad, mn);
-        else dense_core_solve<F2_NCMAX, 0>(W, f.dn0, yc0, lane, bad, mn);
-      } else if (LEAN && !DC) {
-        if (f.nc == 8) dense_core_solve<8, 1>(W, f.dn0, yc0, lane, bad, false);
-        else if (f.nc == 12) dense_core_solve<12, 1>(W, f.dn0, yc0, lane, bad, false);
-        else dense_core_solve<F2_NCMAX, 1>(W, f.dn0, yc0, lane, bad, false);
-      }
+      if (refresh) DENSE_CORE(0, f.nc, W, f.dn0, yc0, lane, bad, mn);
+      else if (LEAN && !DC) DENSE_CORE(1, f.nc, W, f.dn0, yc0, lane, bad, false);
       CADNIP_WAVE_SYNC();
     }
     CADNIP_TRACE_POINT(5);

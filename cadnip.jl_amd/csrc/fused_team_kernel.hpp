@@ -521,15 +521,8 @@ __global__ void __launch_bounds__(64 * NW) k_fteam(F2Args f) {
       if (f.nc > 0 && !(skip & 8)) {
         if (w == 0) {
           const int yc0 = f.nnz_lu + n - f.nc;
-          if (refresh) {
-            if (f.nc == 8) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, mn);
-            else if (f.nc == 12) dense_core_solve<12, 0>(W, f.dn0, yc0, lane, bad, mn);
-            else dense_core_solve<F2_NCMAX, 0>(W, f.dn0, yc0, lane, bad, mn);
-          } else {
-            if (f.nc == 8) dense_core_solve<8, 1>(W, f.dn0, yc0, lane, bad, false);
-            else if (f.nc == 12) dense_core_solve<12, 1>(W, f.dn0, yc0, lane, bad, false);
-            else dense_core_solve<F2_NCMAX, 1>(W, f.dn0, yc0, lane, bad, false);
-          }
+          if (refresh) DENSE_CORE(0, f.nc, W, f.dn0, yc0, lane, bad, mn);
+          else DENSE_CORE(1, f.nc, W, f.dn0, yc0, lane, bad, false);
         }
         __syncthreads();
       }

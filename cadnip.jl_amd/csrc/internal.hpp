@@ -300,8 +300,11 @@ int launch_residual(CadnipHandle* h, const double* d_du);  // d_resid = C du + G
 int launch_jacobian(CadnipHandle* h);                      // d_J = G + gamma C
 int launch_factor(CadnipHandle* h, bool fuse_jacobian);    // LU of J (or of G + gamma C)
 int launch_solve(CadnipHandle* h, const double* d_rhs, double* d_x);
-// kernel: CADNIP_LUK_* (auto: the drivers' choice); info [6] (optional): what ran (cadnip_factor_solve).  dry: choose, fill info, launch
-// nothing.  A forced kernel that does not apply: CADNIP_BADARG
+// k_lu with the name of its profile class (lu_f2.hip runs it as one of launch_factor_solve's kernels); threads: lu_plain_threads with the same do_factor (whole waves, 64 .. 1024: else CADNIP_BADARG)
+int lu_plain_threads(const CadnipHandle* h, bool do_factor);
+int launch_lu(CadnipHandle* h, const char* name, int do_factor, int do_solve, bool fuse_jacobian, const double* d_rhs, double* d_x, int threads);
+// lu_f2.hip.  kernel: CADNIP_LUK_* (auto: the drivers' choice); info [6] (optional): what ran (cadnip_factor_solve).  dry: choose, fill info,
+// launch nothing.  A forced kernel that does not apply: CADNIP_BADARG
 int launch_factor_solve(CadnipHandle* h, bool fuse_jacobian, const double* d_rhs, double* d_x, int kernel = CADNIP_LUK_AUTO, int* info = nullptr,
                         bool dry = false);
 int upload_lu(CadnipHandle* h);
@@ -353,8 +356,8 @@ struct MultiCopy { struct Seg { unsigned* dst; const unsigned* src; size_t words
   void add(void* dst, const void* src, size_t bytes) { seg[n].dst = (unsigned*)dst; seg[n].src = (const unsigned*)src; seg[n].words = bytes / 4; ++n; } };
 int dev_multi_async(CadnipHandle* h, const MultiCopy& m, bool to_host);   // kernels.hip: up to 8 word copies / clears (src = null) in one launch
 int launch_norm2(CadnipHandle* h, const double* d_x, double* d_out);      // kernels.hip: per-instance 2-norm
-int dev_zero_async(CadnipHandle* h, void* p, size_t bytes);
-int dev_copy_async(CadnipHandle* h, void* dst, const void* src, size_t bytes, bool to_host);   // kernels.hip: word copy as a kernel on the handle's stream       // kernels.hip: zero-fill as a kernel on the handle's stream (ordered with the other kernels)
+int dev_zero_async(CadnipHandle* h, void* p, size_t bytes);               // kernels.hip: zero-fill as a kernel on the handle's stream (ordered with the other kernels)
+int dev_copy_async(CadnipHandle* h, void* dst, const void* src, size_t bytes, bool to_host);   // kernels.hip: word copy as a kernel on the handle's stream
 int launch_negate(CadnipHandle* h, double* d_x, long n);
 struct TranArgs;                                                          // tran_ctrl.hpp
 int launch_fused2_rounds(CadnipHandle* h, const TranArgs& t, int rounds); // fused2.hip

@@ -350,48 +350,35 @@ int launch_jacobian(CadnipHandle* h) {
   return CADNIP_OK;
 }
 
-// info (optional): kernel, waves per workgroup, waves per instance (cadnip_factor_solve); dry: fill it, launch nothing
-static int launch_lu(CadnipHandle* h, const char* name, int do_factor, int do_solve, bool fuse, const double* d_rhs, double* d_x,
-                     int* info = nullptr, bool dry = false) {
-  if (!h->analyzed) return CADNIP_NOTREADY;
-  const LUProgram& P = h->lu;
-  size_t lds = ((size_t)P.nnz_lu + h->n) * sizeof(double);
-  int use_lds = lds <= 150 * 1024;
-  if (!do_factor) use_lds = 0;
-  int threads = !use_lds ? 1024 : (P.nnz_lu >= 8192 ? 256 : 64);
+// k_lu, one workgroup per instance.  It keeps the factors and y in LDS when it factors and they fit (solve-only reads the stored factors; y
+// lives in d_tmp).  Its size follows the work per dependency level: a wave for the small systems of a sweep (the DFF: 186 computed entries in
+// 14 levels), 16 waves for a single large circuit whose factors live in HBM (c6288: 79 k entries, 352 k multiply-adds in 237 levels -- with
+// one wave the refactorisation took 9.3 ms)
+static size_t lu_plain_lds(const CadnipHandle* h) { return ((size_t)h->lu.nnz_lu + h->n) * sizeof(double); }
+static int lu_plain_use_lds(const CadnipHandle* h, bool do_factor) { return do_factor && lu_plain_lds(h) <= 150 * 1024; }
+int lu_plain_threads(const CadnipHandle* h, bool do_factor) {
+  int threads = !lu_plain_use_lds(h, do_factor) ? 1024 : (h->lu.nnz_lu >= 8192 ? 256 : 64);
   if (const char* e = getenv("CADNIP_LU_THREADS")) { const int t = atoi(e); if (t >= 64 && t <= 1024 && t % 64 == 0) threads = t; }   // diagnostic
-  if (info) { info[0] = CADNIP_LUK_PLAIN; info[1] = info[2] = threads / 64; info[3] = info[4] = info[5] = 0; }
-  if (dry) return CADNIP_OK;
+  return threads;
+}
+int launch_lu(CadnipHandle* h, const char* name, int do_factor, int do_solve, bool fuse, const double* d_rhs, double* d_x, int threads) {
+  if (!h->analyzed) return CADNIP_NOTREADY;
+  if (threads < 64 || threads > 1024 || threads % 64) return CADNIP_BADARG;   // whole waves, at most a workgroup (lu_plain_threads)
+  const LUProgram& P = h->lu;
   ProfScope ps(h, name);
   LUArgs a{h->d_J, h->d_G, h->d_C, h->d_gamma, h->d_LU, d_rhs, d_x, h->d_tmp, h->d_active, h->d_flags,
            h->d_load_dst, h->d_ent_pos, h->d_ent_diag, h->d_ent_ptr, h->d_term_a, h->d_term_b, h->d_lev_ptr,
            h->d_lu_rowptr, h->d_lu_col, h->d_lu_diag, h->d_rperm, h->d_cperm, h->d_fwd_rows, h->d_fwd_lev_ptr, h->d_bwd_rows, h->d_bwd_lev_ptr,
            h->n, h->nnz, P.nnz_lu, (int)P.lev_ptr.size() - 1, (int)P.fwd_lev_ptr.size() - 1, (int)P.bwd_lev_ptr.size() - 1,
-           do_factor, do_solve, fuse ? 1 : 0, use_lds, 1};
-  // (solve-only reads the stored factors; y lives in d_tmp.)  One workgroup per instance; its size (threads, above) follows the work per
-  // dependency level: a wave for the small systems of a sweep (the DFF: 186 computed entries in 14 levels), 16 waves for a single large
-  // circuit whose factors live in HBM (c6288: 79 k entries, 352 k multiply-adds in 237 levels -- with one wave the refactorisation took 9.3 ms)
-  size_t shmem = a.use_lds ? lds : 0;
+           do_factor, do_solve, fuse ? 1 : 0, lu_plain_use_lds(h, do_factor), 1};
+  size_t shmem = a.use_lds ? lu_plain_lds(h) : 0;
   if (shmem > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_lu, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
   hipLaunchKernelGGL(k_lu, dim3(h->B), dim3(threads), shmem, h->stream, a);
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }
 
-int launch_factor(CadnipHandle* h, bool fuse) { return launch_lu(h, "lu_factor", 1, 0, fuse, nullptr, nullptr); }
-int launch_solve(CadnipHandle* h, const double* d_rhs, double* d_x) { return launch_lu(h, "lu_solve", 0, 1, false, d_rhs, d_x); }
-int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x, int kernel, int* info, bool dry);   // lu_f2.hip
-int launch_factor_solve(CadnipHandle* h, bool fuse, const double* d_rhs, double* d_x, int kernel, int* info, bool dry) {
-  // refactor of G + gamma C followed by the solve: the entry-program kernel (lu_f2.hip) when the circuit's tables fit into
-  // LDS; CADNIP_LU_PLAIN=1 forces the level-by-level kernel below (diagnostic: the two must agree)
-  if (kernel < CADNIP_LUK_AUTO || kernel > CADNIP_LUK_PLAIN || (kernel != CADNIP_LUK_AUTO && !fuse)) return CADNIP_BADARG;
-  if (!h->analyzed) return CADNIP_NOTREADY;
-  if (fuse && kernel != CADNIP_LUK_PLAIN && (kernel != CADNIP_LUK_AUTO || !getenv("CADNIP_LU_PLAIN"))) {
-    const int rc = launch_factor_solve_f2(h, d_rhs, d_x, kernel, info, dry);
-    if (rc != 1) return rc;
-    if (kernel != CADNIP_LUK_AUTO) return CADNIP_BADARG;     // the forced kernel does not apply: nothing was launched
-  }
-  return launch_lu(h, "lu_factor_solve", 1, 1, fuse, d_rhs, d_x, info, dry);
-}
+int launch_factor(CadnipHandle* h, bool fuse) { return launch_lu(h, "lu_factor", 1, 0, fuse, nullptr, nullptr, lu_plain_threads(h, true)); }
+int launch_solve(CadnipHandle* h, const double* d_rhs, double* d_x) { return launch_lu(h, "lu_solve", 0, 1, false, d_rhs, d_x, lu_plain_threads(h, false)); }
 
 }  // namespace cadnip

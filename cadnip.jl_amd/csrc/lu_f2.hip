@@ -1,11 +1,17 @@
 // lu_f2.hip -- per-op refactor + solve (launch_factor_solve: the KLU step of a per-op Newton round, sweeps.jl:600 /
-// solve.jl:667-670) executed with the fused kernel's entry program: J = G + gamma C scattered into a per-wave work array
-// in LDS, the unified factor / forward / backward program of f2_program.cpp run pass by pass (lane-packed entries, DPP
-// group sums, the dense core in registers), x gathered back.  One wave per sweep instance, LU_WPB instances per workgroup
-// sharing ONE copy of the program tables in LDS -- the first per-op LU (k_lu, kernels.hip) fetched every level's indices
-// from global memory behind three dependent loads and took 52 us for the DFF at B = 1024.
-// k_lu remains for what this program cannot do: factor-only / solve-only (the callback ABI's cadnip_factor /
-// cadnip_solve keep the factors in HBM) and circuits whose program does not fit.
+// solve.jl:667-670) executed with the fused kernel's entry program: J = G + gamma C scattered into a work array in LDS, the
+// unified factor / forward / backward program of f2_program.cpp run on it (the dense core in registers), x gathered back.
+// Four kernels, which differ in the shape of their loop and in where the program lives:
+//   k_lu_f2<W>     the pass program (lane-packed entries, term lists), one wave per instance, W instances per workgroup sharing ONE
+//                  copy of the tables in LDS; descriptor and first term of the next pass prefetched
+//   k_lu_f2s<W>    the step program (straight-line steps of three terms per lane), otherwise the same; descriptors staged in LDS
+//   k_lu_f2_mw<4>  the pass program, four waves per instance: the passes of a level dealt round-robin to the waves
+//   k_lu_steps<4>  the step program, four waves per instance: descriptors prefetched from global memory, only W in LDS
+// What they share is written once: the team (LuTeam), the load (lu_load), one step (step_open / step_finish), the dense core's
+// dispatch (DENSE_CORE, fused2_kernel.hpp), the store and the flag rule (lu_store), the arguments (LuArgs).  The entry of a pass is
+// written out in both pass kernels (see k_lu_f2_mw).
+// lu_f2_plan chooses among them and k_lu (kernels.hip: level by level on the LU program, factors in LDS or HBM), which also serves
+// what this program cannot do: factor-only / solve-only (the callback ABI's cadnip_factor / cadnip_solve keep the factors in HBM).
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <stdlib.h>
@@ -13,17 +19,92 @@
 
 namespace cadnip {
 
-struct LuF2Args {
-  const unsigned* tab; int off[S_NSEC]; int tab_len;
-  int tab_lo;                                   // k_lu_f2s: the staged table range starts at this word (load map, permutations)
-  const uint4* steps; int steps_len, ts_pre, ts_post;   // k_lu_f2s: the one-wave step program (f2_build_steps), 16-byte lane descriptors
+struct LuArgs {
+  const unsigned* tab; int off[S_NSEC];          // the packed tables in global memory, section offsets in words
+  int tab_len, tab_lo;                           // the words [tab_lo, tab_lo + tab_len) are staged in LDS (k_lu_steps: none)
+  const uint4* steps; int steps_len;             // the step program (f2_build_steps), 16-byte lane descriptors; len in 64-bit words
+  int n_pre, n_post;                             // passes or steps before / after the dense core
   const double *G, *C, *gamma, *rhs; double* x;
   const int* active; int* flags;
-  int B, n, nnz, lu_words, n_pre, n_post, nc, dn0;
+  int B, n, nnz, lu_words, nc, dn0;
 };
 
+// The threads that work on one instance: one wave (NW = 1, whatever the workgroup holds) or a workgroup of NW waves
+template <int NW> struct LuTeam {
+  static constexpr int NT = 64 * NW;
+  const int lane, idx;                           // idx: 0 .. NT - 1
+  __device__ __forceinline__ explicit LuTeam(int tid) : lane(tid & 63), idx(NW == 1 ? tid & 63 : tid) {}
+  __device__ __forceinline__ void sync() const { if constexpr (NW == 1) CADNIP_WAVE_SYNC(); else __syncthreads(); }
+};
+
+// W := 0 [, the steps' constant words], J = G + gamma C at its L\U positions (every pattern entry has its own word: plain stores),
+// rhs in pivot-row order.  loadpos: csr entry -> W word, rowof: unknown -> rhs word (LDS or global copies of the table sections)
+template <bool CONSTS, class Team>
+__device__ __forceinline__ void lu_load(const LuArgs& f, int inst, const Team& t, double* W, int nW, const u16* loadpos, const u16* rowof) {
+  for (int i = t.idx; i < (nW >> 1); i += Team::NT) ((double2*)W)[i] = make_double2(0.0, 0.0);   // nW is even (f2_program.cpp)
+  if (CONSTS && t.idx == 0) { W[nW] = 0.0; W[nW + 1] = 1.0; }                                    // (f2_build_steps)
+  t.sync();
+  const double* G = f.G + (size_t)inst * f.nnz;
+  const double* C = f.C + (size_t)inst * f.nnz;
+  const double gam = f.gamma[inst];
+  for (int e = t.idx; e < f.nnz; e += Team::NT) W[loadpos[e]] = G[e] + gam * C[e];   // coalesced reads of the CSR arrays
+  const double* rhs = f.rhs + (size_t)inst * f.n;
+  for (int i = t.idx; i < f.n; i += Team::NT) W[rowof[i]] = rhs[i];
+  t.sync();
+}
+
+// x gathered through qinv (unknown -> solution word); a non-finite solution or a bad pivot (`bad`, any lane) raises flag bit 0
+template <class Team>
+__device__ __forceinline__ void lu_store(const LuArgs& f, int inst, const Team& t, const double* W, const u16* qinv, int bad) {
+  double* x = f.x + (size_t)inst * f.n;
+  for (int i = t.idx; i < f.n; i += Team::NT) { const double v = W[qinv[i]]; if (!isfinite(v)) bad = 1; x[i] = v; }
+  if (wave_any(bad) && t.lane == 0) atomicOr(&f.flags[inst], 1);
+}
+
+// One straight-line step of a lane from its 16-byte descriptor (f2_build_steps): word offsets of the entry, its pivot and the factors of
+// three multiply-add terms, a flag in every field's top bit -- and the eight values.  (Two functions: k_lu_f2s requests its next
+// descriptor between them, behind the operands in the LDS queue.)
+struct StepEntry { double* pp; double piv, a0v, b0v, a1v, b1v, a2v, b2v, acc0; };
+__device__ __forceinline__ StepEntry step_open(double* W, const uint4 D) {
+  StepEntry e;
+  e.pp = W + (D.x & 0x7FFFu);
+  e.piv = W[(D.x >> 16) & 0x7FFFu];
+  e.a0v = W[D.y & 0x7FFFu]; e.b0v = W[(D.y >> 16) & 0x7FFFu];
+  e.a1v = W[D.z & 0x7FFFu]; e.b1v = W[(D.z >> 16) & 0x7FFFu];
+  e.a2v = W[D.w & 0x7FFFu]; e.b2v = W[(D.w >> 16) & 0x7FFFu];
+  e.acc0 = *e.pp;
+  return e;
+}
+// ... finished: the three terms, the sums over the lane group, the division with the pivot test, the store -- to the entry, or to the lane's
+// trash word where the lane does not lead its group.  UNIFORM_FLAGS: skip the sums beyond the step's widest group and the division of a
+// step without one (both flags are the same in every lane: k_lu_f2s); else all four sums and the division always (a lane without a pivot
+// divides by the constant 1: k_lu_steps)
+template <bool UNIFORM_FLAGS>
+__device__ __forceinline__ void step_finish(double* W, const uint4 D, const StepEntry& e, unsigned trash_w, int& bad) {
+  unsigned maxlg = 4, div = 1;
+  if constexpr (UNIFORM_FLAGS) {
+    const unsigned fz = __builtin_amdgcn_readfirstlane(D.z), fw = __builtin_amdgcn_readfirstlane(D.w);
+    maxlg = ((fz >> 15) & 1u) | ((fz >> 30) & 2u) | ((fw >> 13) & 4u);
+    div = fw >> 31;
+  }
+  const unsigned lg = (D.x >> 31) | ((D.y >> 14) & 2u) | ((D.y >> 29) & 4u);
+  double part = fma(e.a2v, e.b2v, fma(e.a1v, e.b1v, e.a0v * e.b0v));
+  if (maxlg >= 1) { const double o = dpp_f64<0xB1>(part); part += lg >= 1 ? o : 0.0; }
+  if (maxlg >= 2) { const double o = dpp_f64<0x4E>(part); part += lg >= 2 ? o : 0.0; }
+  if (maxlg >= 3) { const double o = dpp_f64<0x141>(part); part += lg >= 3 ? o : 0.0; }
+  if (maxlg >= 4) { const double o = dpp_f64<0x140>(part); part += lg >= 4 ? o : 0.0; }
+  double acc = e.acc0 - part;
+  if (div) {
+    if (e.piv == 0.0 || !isfinite(e.piv)) bad = 1;
+    acc = fast_div(acc, e.piv);
+  }
+  *((D.x & 0x8000u) ? e.pp : W + trash_w) = acc;
+}
+
+// The pass program, one wave per instance.  Software pipeline: the lane descriptor and the first term of pass p + 1 and the pass
+// descriptor of pass p + 2 are requested while pass p runs
 template <int WPB>
-__global__ void __launch_bounds__(64 * WPB) k_lu_f2(LuF2Args f) {
+__global__ void __launch_bounds__(64 * WPB) k_lu_f2(LuArgs f) {
   extern __shared__ double sm[];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), n = f.n;
   {
@@ -36,27 +117,17 @@ __global__ void __launch_bounds__(64 * WPB) k_lu_f2(LuF2Args f) {
   if (inst >= f.B || !f.active[inst]) return;
   const unsigned* tab = (const unsigned*)sm;
   const LdsLu<double*> L = lds_lu((double*)sm, f.tab_len, 0, f.lu_words, n, false, w, WPB);
-  const int nW = L.nW;
   double* W = L.W;
   const u16* loadpos = (const u16*)(tab + f.off[S_LOADPOS]);
   const u64* laned = (const u64*)(tab + f.off[S_ENT]);
   const unsigned* term = tab + f.off[S_TERM];
+  // pass descriptors are wave-uniform: scalar loads from the table's copy in global memory (fused2_kernel.hpp)
   typedef const __attribute__((address_space(4))) u64* PassPtr;
   const PassPtr passd = (PassPtr)(const u64*)(f.tab + f.off[S_LEV]);
   const u16* qinv = (const u16*)(tab + f.off[S_QINV]);
   const u16* rowof = (const u16*)(tab + f.off[S_ROWOF]);
-  for (int i = lane; i < (nW >> 1); i += 64) ((double2*)W)[i] = make_double2(0.0, 0.0);   // nW is even (f2_program.cpp)
-  CADNIP_WAVE_SYNC();
-  {
-    // J = G + gamma C at its L\U positions (every pattern entry has its own word: plain stores), rhs in pivot-row order
-    const double* G = f.G + (size_t)inst * f.nnz;
-    const double* C = f.C + (size_t)inst * f.nnz;
-    const double gam = f.gamma[inst];
-    for (int e = lane; e < f.nnz; e += 64) W[loadpos[e]] = G[e] + gam * C[e];   // coalesced reads of the CSR arrays
-    const double* rhs = f.rhs + (size_t)inst * n;
-    for (int i = lane; i < n; i += 64) W[rowof[i]] = rhs[i];
-  }
-  CADNIP_WAVE_SYNC();
+  const LuTeam<1> team(tid);
+  lu_load<false>(f, inst, team, W, L.nW, loadpos, rowof);
   int bad = 0;
   auto run_passes = [&](const int p_first, const int p_count) {
     if (p_count <= 0) return;
@@ -105,16 +176,11 @@ __global__ void __launch_bounds__(64 * WPB) k_lu_f2(LuF2Args f) {
   };
   run_passes(0, f.n_pre);
   if (f.nc > 0) {
-    const int yc0 = f.lu_words + n - f.nc;
-    if (f.nc == 8) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, false);
-    else if (f.nc == 12) dense_core_solve<12, 0>(W, f.dn0, yc0, lane, bad, false);
-    else dense_core_solve<F2_NCMAX, 0>(W, f.dn0, yc0, lane, bad, false);
+    DENSE_CORE(0, f.nc, W, f.dn0, f.lu_words + n - f.nc, lane, bad, false);
     CADNIP_WAVE_SYNC();
   }
   run_passes(f.n_pre, f.n_post);
-  double* x = f.x + (size_t)inst * n;
-  for (int i = lane; i < n; i += 64) { const double v = W[qinv[i]]; if (!isfinite(v)) bad = 1; x[i] = v; }
-  if (wave_any(bad) && lane == 0) atomicOr(&f.flags[inst], 1);
+  lu_store(f, inst, team, W, qinv, bad);
 }
 
 // The same kernel on the fused sweep kernel's STEP program (f2_program.cpp: f2_build_steps; fused2_kernel.hpp: run_steps): straight-line
@@ -122,7 +188,7 @@ __global__ void __launch_bounds__(64 * WPB) k_lu_f2(LuF2Args f) {
 // the load map and the permutations of the table, the step descriptors, the instances' work arrays.  Taken when the descriptors fit (a long
 // dependency chain has one step per link: the pass program is the compact form).
 template <int WPB>
-__global__ void __launch_bounds__(64 * WPB) k_lu_f2s(LuF2Args f) {
+__global__ void __launch_bounds__(64 * WPB) k_lu_f2s(LuArgs f) {
   extern __shared__ double sm[];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), n = f.n;
   {
@@ -139,23 +205,12 @@ __global__ void __launch_bounds__(64 * WPB) k_lu_f2s(LuF2Args f) {
   const unsigned* tab = (const unsigned*)sm;
   const LdsLu<double*> L = lds_lu((double*)sm, f.tab_len, f.steps_len, f.lu_words, n, true, w, WPB);
   const uint4* tdesc = (const uint4*)L.desc;
-  const int nW = L.nW;
   double* W = L.W;
   const u16* loadpos = (const u16*)(tab + (f.off[S_LOADPOS] - f.tab_lo));
   const u16* qinv = (const u16*)(tab + (f.off[S_QINV] - f.tab_lo));
   const u16* rowof = (const u16*)(tab + (f.off[S_ROWOF] - f.tab_lo));
-  for (int i = lane; i < (nW >> 1); i += 64) ((double2*)W)[i] = make_double2(0.0, 0.0);   // nW is even (f2_program.cpp)
-  if (lane == 0) { W[nW] = 0.0; W[nW + 1] = 1.0; }                                        // the steps' constant words
-  CADNIP_WAVE_SYNC();
-  {
-    const double* G = f.G + (size_t)inst * f.nnz;
-    const double* C = f.C + (size_t)inst * f.nnz;
-    const double gam = f.gamma[inst];
-    for (int e = lane; e < f.nnz; e += 64) W[loadpos[e]] = G[e] + gam * C[e];
-    const double* rhs = f.rhs + (size_t)inst * n;
-    for (int i = lane; i < n; i += 64) W[rowof[i]] = rhs[i];
-  }
-  CADNIP_WAVE_SYNC();
+  const LuTeam<1> team(tid);
+  lu_load<true>(f, inst, team, W, L.nW, loadpos, rowof);
   int bad = 0;
   const unsigned trash_w = (unsigned)(f.lu_words + n + lane);
   auto run_steps = [&](const int s_first, const int s_count) {
@@ -163,43 +218,20 @@ __global__ void __launch_bounds__(64 * WPB) k_lu_f2s(LuF2Args f) {
     const uint4* dp = tdesc + (size_t)s_first * 64 + lane;
     uint4 D = dp[0];
     for (int si = 0; si < s_count; ++si) {
-      double* const pp = W + (D.x & 0x7FFFu);
-      const double piv = W[(D.x >> 16) & 0x7FFFu];
-      const double a0v = W[D.y & 0x7FFFu], b0v = W[(D.y >> 16) & 0x7FFFu];
-      const double a1v = W[D.z & 0x7FFFu], b1v = W[(D.z >> 16) & 0x7FFFu];
-      const double a2v = W[D.w & 0x7FFFu], b2v = W[(D.w >> 16) & 0x7FFFu];
-      const double acc0 = *pp;
+      const StepEntry e = step_open(W, D);
       const uint4 Dn = dp[(size_t)(si + 1) * 64];
-      const unsigned fz = __builtin_amdgcn_readfirstlane(D.z), fw = __builtin_amdgcn_readfirstlane(D.w);
-      const unsigned maxlg = ((fz >> 15) & 1u) | ((fz >> 30) & 2u) | ((fw >> 13) & 4u);
-      const unsigned lg = (D.x >> 31) | ((D.y >> 14) & 2u) | ((D.y >> 29) & 4u);
-      double part = fma(a2v, b2v, fma(a1v, b1v, a0v * b0v));
-      if (maxlg >= 1) { const double o = dpp_f64<0xB1>(part); part += lg >= 1 ? o : 0.0; }
-      if (maxlg >= 2) { const double o = dpp_f64<0x4E>(part); part += lg >= 2 ? o : 0.0; }
-      if (maxlg >= 3) { const double o = dpp_f64<0x141>(part); part += lg >= 3 ? o : 0.0; }
-      if (maxlg >= 4) { const double o = dpp_f64<0x140>(part); part += lg >= 4 ? o : 0.0; }
-      double acc = acc0 - part;
-      if (fw >> 31) {
-        if (piv == 0.0 || !isfinite(piv)) bad = 1;
-        acc = fast_div(acc, piv);
-      }
-      *((D.x & 0x8000u) ? pp : W + trash_w) = acc;
+      step_finish<true>(W, D, e, trash_w, bad);
       D = Dn;
     }
     CADNIP_WAVE_SYNC();
   };
-  run_steps(0, f.ts_pre);
+  run_steps(0, f.n_pre);
   if (f.nc > 0) {
-    const int yc0 = f.lu_words + n - f.nc;
-    if (f.nc == 8) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, false);
-    else if (f.nc == 12) dense_core_solve<12, 0>(W, f.dn0, yc0, lane, bad, false);
-    else dense_core_solve<F2_NCMAX, 0>(W, f.dn0, yc0, lane, bad, false);
+    DENSE_CORE(0, f.nc, W, f.dn0, f.lu_words + n - f.nc, lane, bad, false);
     CADNIP_WAVE_SYNC();
   }
-  run_steps(f.ts_pre, f.ts_post);
-  double* x = f.x + (size_t)inst * n;
-  for (int i = lane; i < n; i += 64) { const double v = W[qinv[i]]; if (!isfinite(v)) bad = 1; x[i] = v; }
-  if (wave_any(bad) && lane == 0) atomicOr(&f.flags[inst], 1);
+  run_steps(f.n_pre, f.n_post);
+  lu_store(f, inst, team, W, qinv, bad);
 }
 
 // Few instances (a single transient, a handful of corners): one wave per instance leaves the chip empty and walks the passes one after
@@ -207,7 +239,7 @@ __global__ void __launch_bounds__(64 * WPB) k_lu_f2s(LuF2Args f) {
 // one instance: the passes of a level are dealt round-robin to the waves (they touch different entries and read only earlier levels), a
 // workgroup barrier closes the level, the dense core is wave 0's.  No software pipeline: with so few waves the kernel is latency-bound anyway.
 template <int WPI>
-__global__ void __launch_bounds__(64 * WPI) k_lu_f2_mw(LuF2Args f) {
+__global__ void __launch_bounds__(64 * WPI) k_lu_f2_mw(LuArgs f) {
   extern __shared__ double sm[];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), n = f.n;
   {
@@ -219,7 +251,6 @@ __global__ void __launch_bounds__(64 * WPI) k_lu_f2_mw(LuF2Args f) {
   if (inst >= f.B || !f.active[inst]) return;                 // (uniform over the workgroup: nobody is left waiting at a barrier)
   const unsigned* tab = (const unsigned*)sm;
   const LdsLu<double*> L = lds_lu((double*)sm, f.tab_len, 0, f.lu_words, n, false, 0, 1);
-  const int nW = L.nW;
   double* W = L.W;
   const u16* loadpos = (const u16*)(tab + f.off[S_LOADPOS]);
   const u64* laned = (const u64*)(tab + f.off[S_ENT]);
@@ -228,17 +259,8 @@ __global__ void __launch_bounds__(64 * WPI) k_lu_f2_mw(LuF2Args f) {
   const PassPtr passd = (PassPtr)(const u64*)(f.tab + f.off[S_LEV]);
   const u16* qinv = (const u16*)(tab + f.off[S_QINV]);
   const u16* rowof = (const u16*)(tab + f.off[S_ROWOF]);
-  for (int i = tid; i < (nW >> 1); i += 64 * WPI) ((double2*)W)[i] = make_double2(0.0, 0.0);
-  __syncthreads();
-  {
-    const double* G = f.G + (size_t)inst * f.nnz;
-    const double* C = f.C + (size_t)inst * f.nnz;
-    const double gam = f.gamma[inst];
-    for (int e = tid; e < f.nnz; e += 64 * WPI) W[loadpos[e]] = G[e] + gam * C[e];
-    const double* rhs = f.rhs + (size_t)inst * n;
-    for (int i = tid; i < n; i += 64 * WPI) W[rowof[i]] = rhs[i];
-  }
-  __syncthreads();
+  const LuTeam<WPI> team(tid);
+  lu_load<false>(f, inst, team, W, L.nW, loadpos, rowof);   // (its first barrier: the tables are staged)
   int bad = 0;
   auto run_passes = [&](const int p_first, const int p_count) {
     int in_level = 0;
@@ -247,6 +269,8 @@ __global__ void __launch_bounds__(64 * WPI) k_lu_f2_mw(LuF2Args f) {
       const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)pd), hi = __builtin_amdgcn_readfirstlane((unsigned)(pd >> 32));
       const int T = hi & 0x7F, maxlg = (hi >> 8) & 7, hasdiv = (hi >> 11) & 1, fence = (hi >> 12) & 1;
       if (in_level % WPI == w && T > 0) {
+        // (the same entry text as k_lu_f2's, on purpose: through shared functions the two uniform branches of this loop came out with
+        // the opposite sense and the kernel measured 0.1 us slower on the flip-flop at B = 1100 -- DESIGN.md section 5)
         const bool act = lane < T;
         const u64 D = laned[lo + (act ? lane : T - 1)];
         const unsigned pos = (unsigned)D & 0xFFFFu, dg = (unsigned)(D >> 16) & 0xFFFFu, t0 = (unsigned)(D >> 32) & 0xFFFFu;
@@ -275,83 +299,40 @@ __global__ void __launch_bounds__(64 * WPI) k_lu_f2_mw(LuF2Args f) {
   };
   run_passes(0, f.n_pre);
   if (f.nc > 0) {
-    if (w == 0) {
-      const int yc0 = f.lu_words + n - f.nc;
-      if (f.nc == 8) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, false);
-      else if (f.nc == 12) dense_core_solve<12, 0>(W, f.dn0, yc0, lane, bad, false);
-      else dense_core_solve<F2_NCMAX, 0>(W, f.dn0, yc0, lane, bad, false);
-    }
+    if (w == 0) DENSE_CORE(0, f.nc, W, f.dn0, f.lu_words + n - f.nc, lane, bad, false);
     __syncthreads();
   }
   run_passes(f.n_pre, f.n_post);
-  double* x = f.x + (size_t)inst * n;
-  for (int i = tid; i < n; i += 64 * WPI) { const double v = W[qinv[i]]; if (!isfinite(v)) bad = 1; x[i] = v; }
-  if (wave_any(bad) && lane == 0) atomicOr(&f.flags[inst], 1);
+  lu_store(f, inst, team, W, qinv, bad);
 }
 
 // The same refactor + solve as straight-line STEPS for a team of four waves per instance (f2_program.cpp: f2_build_steps with nw = 4):
-// every thread owns one 16-byte descriptor per step -- word offsets of the entry, its pivot and the factors of up to three multiply-add
-// terms; steps are list-scheduled (an entry runs in the first step behind its operands' last writers that has a lane group free), a
-// barrier closes each.  The descriptors are per thread: they are fetched from global memory a CHUNK of steps ahead into registers (the
-// loads of chunk c + 1 are in flight while chunk c runs), nothing of the program lives in LDS -- only the work array does, so a circuit
-// whose tables do not fit beside it (the PSP103 ring: 87 steps x 256 threads; 116 with one term per lane and level-aligned steps) runs
-// here all the same.  For few instances -- where k_lu_f2's one wave per instance walks 100+ passes alone.
-struct LuStepArgs {
-  const uint4* desc; int n_pre, n_post;
-  const u16 *loadpos, *rowof, *qinv;              // global copies of the table sections (csr entry -> W word, unknown -> rhs word, unknown -> solution word)
-  const double *G, *C, *gamma, *rhs; double* x;
-  const int* active; int* flags;
-  int B, n, nnz, lu_words, nc, dn0;
-};
+// every thread owns one 16-byte descriptor per step; steps are list-scheduled (an entry runs in the first step behind its operands' last
+// writers that has a lane group free), a barrier closes each.  The descriptors are per thread: they are fetched from global memory a CHUNK
+// of steps ahead into registers (the loads of chunk c + 1 are in flight while chunk c runs), nothing of the program lives in LDS -- only
+// the work array does, and the load map and the permutations are read from the table in global memory -- so a circuit whose tables do not
+// fit beside it (the PSP103 ring: 87 steps x 256 threads; 116 with one term per lane and level-aligned steps) runs here all the same.
+// For few instances -- where k_lu_f2's one wave per instance walks 100+ passes alone.
 #define LU_CHUNK 8
 template <int NW>
-__global__ void __launch_bounds__(64 * NW) k_lu_steps(LuStepArgs f) {
+__global__ void __launch_bounds__(64 * NW) k_lu_steps(LuArgs f) {
   constexpr int NT = 64 * NW;
   extern __shared__ double sm[];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), n = f.n;
   const int inst = blockIdx.x;
   if (inst >= f.B || !f.active[inst]) return;                 // (uniform over the workgroup)
   const LdsLu<double*> L = lds_lu((double*)sm, 0, 0, f.lu_words, n, true, 0, 1);
-  const int nW = L.nW;
   double* W = L.W;
-  for (int i = tid; i < (nW >> 1); i += NT) ((double2*)W)[i] = make_double2(0.0, 0.0);
-  if (tid == 0) { W[nW] = 0.0; W[nW + 1] = 1.0; }            // the steps' constant words (f2_build_steps)
   // this thread's descriptors of the first chunk: requested before the matrix is loaded
-  const uint4* dp = f.desc + tid;
+  const uint4* dp = f.steps + tid;
   uint4 cur[LU_CHUNK], nxt[LU_CHUNK];
   const int n_steps = f.n_pre + f.n_post;
 #pragma unroll
   for (int k = 0; k < LU_CHUNK; ++k) cur[k] = dp[(size_t)(k < n_steps ? k : 0) * NT];
-  __syncthreads();
-  {
-    const double* G = f.G + (size_t)inst * f.nnz;
-    const double* C = f.C + (size_t)inst * f.nnz;
-    const double gam = f.gamma[inst];
-    for (int e = tid; e < f.nnz; e += NT) W[f.loadpos[e]] = G[e] + gam * C[e];
-    const double* rhs = f.rhs + (size_t)inst * n;
-    for (int i = tid; i < n; i += NT) W[f.rowof[i]] = rhs[i];
-  }
-  __syncthreads();
+  const LuTeam<NW> team(tid);
+  lu_load<true>(f, inst, team, W, L.nW, (const u16*)(f.tab + f.off[S_LOADPOS]), (const u16*)(f.tab + f.off[S_ROWOF]));
   int bad = 0;
   const unsigned trash_w = (unsigned)(f.lu_words + n + lane);
-  auto step = [&](const uint4 D) {
-    double* const pp = W + (D.x & 0x7FFFu);
-    const double piv = W[(D.x >> 16) & 0x7FFFu];
-    const double a0v = W[D.y & 0x7FFFu], b0v = W[(D.y >> 16) & 0x7FFFu];
-    const double a1v = W[D.z & 0x7FFFu], b1v = W[(D.z >> 16) & 0x7FFFu];
-    const double a2v = W[D.w & 0x7FFFu], b2v = W[(D.w >> 16) & 0x7FFFu];
-    const double acc0 = *pp;
-    const unsigned lg = (D.x >> 31) | ((D.y >> 14) & 2u) | ((D.y >> 29) & 4u);
-    double part = fma(a2v, b2v, fma(a1v, b1v, a0v * b0v));
-    { const double o = dpp_f64<0xB1>(part); part += lg >= 1 ? o : 0.0; }
-    { const double o = dpp_f64<0x4E>(part); part += lg >= 2 ? o : 0.0; }
-    { const double o = dpp_f64<0x141>(part); part += lg >= 3 ? o : 0.0; }
-    { const double o = dpp_f64<0x140>(part); part += lg >= 4 ? o : 0.0; }
-    if (piv == 0.0 || !isfinite(piv)) bad = 1;
-    const double acc = fast_div(acc0 - part, piv);
-    *((D.x & 0x8000u) ? pp : W + trash_w) = acc;
-    __syncthreads();
-  };
   // chunks of LU_CHUNK steps; the dense core sits between step n_pre - 1 and step n_pre
   for (int c0 = 0; c0 < n_steps; c0 += LU_CHUNK) {
 #pragma unroll
@@ -360,55 +341,50 @@ __global__ void __launch_bounds__(64 * NW) k_lu_steps(LuStepArgs f) {
     for (int k = 0; k < LU_CHUNK; ++k) {
       const int sidx = c0 + k;
       if (sidx == f.n_pre && f.nc > 0) {                     // (uniform)
-        if (w == 0) {
-          const int yc0 = f.lu_words + n - f.nc;
-          if (f.nc == 8) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, false);
-          else if (f.nc == 12) dense_core_solve<12, 0>(W, f.dn0, yc0, lane, bad, false);
-          else dense_core_solve<F2_NCMAX, 0>(W, f.dn0, yc0, lane, bad, false);
-        }
+        if (w == 0) DENSE_CORE(0, f.nc, W, f.dn0, f.lu_words + n - f.nc, lane, bad, false);
         __syncthreads();
       }
-      if (sidx < n_steps) step(cur[k]);
+      if (sidx < n_steps) { step_finish<false>(W, cur[k], step_open(W, cur[k]), trash_w, bad); __syncthreads(); }
     }
 #pragma unroll
     for (int k = 0; k < LU_CHUNK; ++k) cur[k] = nxt[k];
   }
   if (f.n_post == 0 && f.nc > 0) {                            // (no step behind the core: it has not run yet)
-    if (w == 0) {
-      const int yc0 = f.lu_words + n - f.nc;
-      if (f.nc == 8) dense_core_solve<8, 0>(W, f.dn0, yc0, lane, bad, false);
-      else if (f.nc == 12) dense_core_solve<12, 0>(W, f.dn0, yc0, lane, bad, false);
-      else dense_core_solve<F2_NCMAX, 0>(W, f.dn0, yc0, lane, bad, false);
-    }
+    if (w == 0) DENSE_CORE(0, f.nc, W, f.dn0, f.lu_words + n - f.nc, lane, bad, false);
     __syncthreads();
   }
-  double* x = f.x + (size_t)inst * n;
-  for (int i = tid; i < n; i += NT) { const double v = W[f.qinv[i]]; if (!isfinite(v)) bad = 1; x[i] = v; }
-  if (wave_any(bad) && lane == 0) atomicOr(&f.flags[inst], 1);
+  lu_store(f, inst, team, W, (const u16*)(f.tab + f.off[S_QINV]), bad);
 }
 
-// What launch_factor_solve_f2 runs -- the one place that decides, and the only reader of CADNIP_LU_STEPS / _WPI / _F2S.
-// kernel: CADNIP_LUK_AUTO (the choice below, switches included) or one forced kernel (switches and batch rules ignored, the LDS limits kept;
-// W of k_lu_f2s / k_lu_f2 still from B).  The batch rules count 256 compute units where the device has not been asked yet (DESIGN.md
-// section 6, findings)
-struct LuPlan { int kernel, wpb, wpi, pre, post, tab_lo, tab_len; size_t shmem; };   // kernel -1: the program kernels do not apply
-static LuPlan lu_f2_plan(CadnipHandle* h, int kernel) {
+// THE plan of launch_factor_solve: the one place that decides which kernel runs and with what geometry, and the only reader of
+// CADNIP_LU_PLAIN / _STEPS / _WPI / _F2S (read at every call).  kernel: CADNIP_LUK_AUTO (the choice below, switches included) or one forced
+// kernel (switches and batch rules ignored, the LDS limits kept; W of k_lu_f2s / k_lu_f2 still from B).  kernel -1: the forced kernel does
+// not apply.  When no program kernel applies, auto runs k_lu.  The batch rules count 256 compute units where the device has not been asked
+// yet (findings).  The first six members are what cadnip_factor_solve reports (info [6])
+struct LuPlan { int kernel, wpb, wpi, nc, pre, post, tab_lo, tab_len; size_t shmem; };   // wpb, wpi: waves per workgroup / per instance; pre, post: steps or passes before / after the dense core
+static LuPlan lu_f2_plan(CadnipHandle* h, bool fuse, int kernel) {
   const FusedState& S = h->f2;
   const bool any = kernel == CADNIP_LUK_AUTO;
-  const LuPlan none{-1, 0, 0, 0, 0, 0, 0, 0};
+  const LuPlan none{-1, 0, 0, 0, 0, 0, 0, 0, 0};
+  // k_lu: forced, CADNIP_LU_PLAIN set (diagnostic: the kernels must agree), a Jacobian that is not fused (J from d_J), or nothing else applies
+  const int plain_waves = lu_plain_threads(h, true) / 64;
+  const LuPlan plain{CADNIP_LUK_PLAIN, plain_waves, plain_waves, 0, 0, 0, 0, 0, 0};
+  if (!fuse || kernel == CADNIP_LUK_PLAIN || (any && getenv("CADNIP_LU_PLAIN"))) return plain;
+  const LuPlan other = any ? plain : none;
+  if (fused2_tables(h)) return other;                      // (only the linear-solve prefix of the tables has to fit: the LDS limits below)
   auto bytes = [&](int tab_len, int desc_len, bool consts, int waves) { return lds_bytes(lds_lu((size_t)0, tab_len, desc_len, S.lu_words, h->n, consts, 0, waves)); };
   // at most two instances per CU: the straight-line steps of a team of four waves per instance (k_lu_steps).  CADNIP_LU_STEPS = 0 | 1 forces the choice
   if (any || kernel == CADNIP_LUK_STEPS4) {
     const char* e = any ? getenv("CADNIP_LU_STEPS") : nullptr;
     const bool steps = !any || (e ? atoi(e) != 0 : h->B <= 2 * S.n_cu_hint());
-    if (steps && S.steps4.d && bytes(0, 0, true, 1) <= LDS_BUDGET) return LuPlan{CADNIP_LUK_STEPS4, 4, 4, S.steps4.n_steps[0], S.steps4.n_steps[1], 0, 0, bytes(0, 0, true, 1)};
+    if (steps && S.steps4.d && bytes(0, 0, true, 1) <= LDS_BUDGET) return LuPlan{CADNIP_LUK_STEPS4, 4, 4, S.nc, S.steps4.n_steps[0], S.steps4.n_steps[1], 0, 0, bytes(0, 0, true, 1)};
     if (!any) return none;
   }
   // a few instances of a circuit with many passes: several waves per instance (k_lu_f2_mw).  CADNIP_LU_WPI forces 1 / 4 (diagnostic)
   if (any || kernel == CADNIP_LUK_F2MW) {
     const char* e = any ? getenv("CADNIP_LU_WPI") : nullptr;
     const int wpi = !any ? 4 : e ? atoi(e) : (h->B * 4 <= S.n_cu_hint() && S.n_pre + S.n_post >= 32 ? 4 : 1);
-    if (wpi == 4 && bytes(S.lu_len, 0, false, 1) <= LDS_BUDGET) return LuPlan{CADNIP_LUK_F2MW, 4, 4, S.n_pre, S.n_post, 0, S.lu_len, bytes(S.lu_len, 0, false, 1)};
+    if (wpi == 4 && bytes(S.lu_len, 0, false, 1) <= LDS_BUDGET) return LuPlan{CADNIP_LUK_F2MW, 4, 4, S.nc, S.n_pre, S.n_post, 0, S.lu_len, bytes(S.lu_len, 0, false, 1)};
     if (!any) return none;
   }
   // many instances: one wave each, 8 per workgroup unless fewer still put a workgroup on every CU
@@ -419,44 +395,46 @@ static LuPlan lu_f2_plan(CadnipHandle* h, int kernel) {
   if (S.steps1.d && (any ? !(e && atoi(e) == 0) : kernel == CADNIP_LUK_F2S)) {
     const int lo = S.off[S_LOADPOS] & ~3;
     if (bytes(S.lu_len - lo, S.steps1.len, true, 8) <= LDS_BUDGET)
-      return LuPlan{CADNIP_LUK_F2S, wpb, 1, S.steps1.n_steps[0], S.steps1.n_steps[1], lo, S.lu_len - lo, bytes(S.lu_len - lo, S.steps1.len, true, wpb)};
+      return LuPlan{CADNIP_LUK_F2S, wpb, 1, S.nc, S.steps1.n_steps[0], S.steps1.n_steps[1], lo, S.lu_len - lo, bytes(S.lu_len - lo, S.steps1.len, true, wpb)};
   }
   if (!any && kernel != CADNIP_LUK_F2) return none;
   while (wpb > 1 && bytes(S.lu_len, 0, false, wpb) > LDS_BUDGET) wpb >>= 1;
-  if (bytes(S.lu_len, 0, false, wpb) > LDS_BUDGET) return none;
-  return LuPlan{CADNIP_LUK_F2, wpb, 1, S.n_pre, S.n_post, 0, S.lu_len, bytes(S.lu_len, 0, false, wpb)};
+  if (bytes(S.lu_len, 0, false, wpb) > LDS_BUDGET) return other;
+  return LuPlan{CADNIP_LUK_F2, wpb, 1, S.nc, S.n_pre, S.n_post, 0, S.lu_len, bytes(S.lu_len, 0, false, wpb)};
 }
 
-// 0 = done with the program kernel; 1 = not applicable (auto: the caller falls back to k_lu; a forced kernel: CADNIP_BADARG); < 0 never.
-// info [6] (optional): kernel, waves per workgroup, waves per instance, nc, steps or passes before / after the dense core.  dry: choose and
-// fill info, launch nothing
-int launch_factor_solve_f2(CadnipHandle* h, const double* d_rhs, double* d_x, int kernel, int* info, bool dry) {
-  if (!h->analyzed || fused2_tables(h)) return 1;          // (only the linear-solve prefix of the tables has to fit: the plan checks)
+// the arguments of the program kernel of plan p
+static LuArgs lu_args(const CadnipHandle* h, const LuPlan& p, const double* d_rhs, double* d_x) {
   const FusedState& S = h->f2;
-  const LuPlan p = lu_f2_plan(h, kernel);
-  if (p.kernel < 0) return 1;
-  if (info) { info[0] = p.kernel; info[1] = p.wpb; info[2] = p.wpi; info[3] = S.nc; info[4] = p.pre; info[5] = p.post; }
+  const StepList& steps = p.kernel == CADNIP_LUK_STEPS4 ? S.steps4 : S.steps1;
+  const bool stepped = p.kernel == CADNIP_LUK_STEPS4 || p.kernel == CADNIP_LUK_F2S;
+  LuArgs f{};
+  f.tab = S.d_tab; for (int i = 0; i < S_NSEC; ++i) f.off[i] = S.off[i];
+  f.tab_lo = p.tab_lo; f.tab_len = p.tab_len;
+  if (stepped) { f.steps = (const uint4*)steps.d; f.steps_len = steps.len; }
+  f.G = h->d_G; f.C = h->d_C; f.gamma = h->d_gamma; f.rhs = d_rhs; f.x = d_x; f.active = h->d_active; f.flags = h->d_flags;
+  f.B = h->B; f.n = h->n; f.nnz = h->nnz; f.lu_words = S.lu_words; f.n_pre = p.pre; f.n_post = p.post; f.nc = S.nc; f.dn0 = S.dn0;
+  return f;
+}
+
+// refactor of G + gamma C (fuse; else of d_J) followed by the solve.  kernel: CADNIP_LUK_*; a forced kernel needs the fused Jacobian, and one
+// that does not apply is CADNIP_BADARG with nothing launched.  info [6] (optional): kernel, waves per workgroup, waves per instance, nc, steps
+// or passes before / after the dense core (zeros for k_lu).  dry: choose and fill info, launch nothing
+int launch_factor_solve(CadnipHandle* h, bool fuse, const double* d_rhs, double* d_x, int kernel, int* info, bool dry) {
+  if (kernel < CADNIP_LUK_AUTO || kernel > CADNIP_LUK_PLAIN || (kernel != CADNIP_LUK_AUTO && !fuse)) return CADNIP_BADARG;
+  if (!h->analyzed) return CADNIP_NOTREADY;
+  const LuPlan p = lu_f2_plan(h, fuse, kernel);
+  if (p.kernel < 0) return CADNIP_BADARG;
+  if (info) { info[0] = p.kernel; info[1] = p.wpb; info[2] = p.wpi; info[3] = p.nc; info[4] = p.pre; info[5] = p.post; }
   if (dry) return CADNIP_OK;
+  if (p.kernel == CADNIP_LUK_PLAIN) return launch_lu(h, "lu_factor_solve", 1, 1, fuse, d_rhs, d_x, 64 * p.wpb);
   ProfScope ps(h, "lu_factor_solve");
+  const LuArgs f = lu_args(h, p, d_rhs, d_x);
   const int grid = p.wpi > 1 ? h->B : (h->B + p.wpb - 1) / p.wpb;   // a workgroup per instance, or per wpb instances
-  if (p.kernel == CADNIP_LUK_STEPS4) {
-    LuStepArgs g;
-    g.desc = (const uint4*)S.steps4.d; g.n_pre = p.pre; g.n_post = p.post;
-    g.loadpos = (const u16*)(S.d_tab + S.off[S_LOADPOS]); g.rowof = (const u16*)(S.d_tab + S.off[S_ROWOF]); g.qinv = (const u16*)(S.d_tab + S.off[S_QINV]);
-    g.G = h->d_G; g.C = h->d_C; g.gamma = h->d_gamma; g.rhs = d_rhs; g.x = d_x; g.active = h->d_active; g.flags = h->d_flags;
-    g.B = h->B; g.n = h->n; g.nnz = h->nnz; g.lu_words = S.lu_words; g.nc = S.nc; g.dn0 = S.dn0;
-    TRY_RC(lds_launch(k_lu_steps<4>, grid, 256, p.shmem, h->stream, g));
-  } else {
-    LuF2Args f{};
-    f.tab = S.d_tab; for (int i = 0; i < S_NSEC; ++i) f.off[i] = S.off[i];
-    f.tab_lo = p.tab_lo; f.tab_len = p.tab_len;
-    if (p.kernel == CADNIP_LUK_F2S) { f.steps = (const uint4*)S.steps1.d; f.steps_len = S.steps1.len; f.ts_pre = p.pre; f.ts_post = p.post; }
-    f.G = h->d_G; f.C = h->d_C; f.gamma = h->d_gamma; f.rhs = d_rhs; f.x = d_x; f.active = h->d_active; f.flags = h->d_flags;
-    f.B = h->B; f.n = h->n; f.nnz = h->nnz; f.lu_words = S.lu_words; f.n_pre = S.n_pre; f.n_post = S.n_post; f.nc = S.nc; f.dn0 = S.dn0;
-    if (p.kernel == CADNIP_LUK_F2MW) TRY_RC(lds_launch(k_lu_f2_mw<4>, grid, 256, p.shmem, h->stream, f));
-    else if (p.kernel == CADNIP_LUK_F2S) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_lu_f2s<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, f); }));
-    else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_lu_f2<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, f); }));
-  }
+  if (p.kernel == CADNIP_LUK_STEPS4) TRY_RC(lds_launch(k_lu_steps<4>, grid, 256, p.shmem, h->stream, f));
+  else if (p.kernel == CADNIP_LUK_F2MW) TRY_RC(lds_launch(k_lu_f2_mw<4>, grid, 256, p.shmem, h->stream, f));
+  else if (p.kernel == CADNIP_LUK_F2S) TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_lu_f2s<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, f); }));
+  else TRY_RC(with_wpb(p.wpb, [&](auto W) { return lds_launch(k_lu_f2<decltype(W)::value>, grid, 64 * W.value, p.shmem, h->stream, f); }));
   HIP_TRY(hipGetLastError());
   return CADNIP_OK;
 }
