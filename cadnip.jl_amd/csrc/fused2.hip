@@ -8,6 +8,8 @@
 //     each other.  VAR 0, the benchmark's kernel: lean device set (linear elements, sources, plain sp_mos1), every device emits its residual
 //     directly (devices.hpp, Rn), the linear solve runs from list-scheduled step descriptors staged behind the lean range of the tables.
 //     VAR 3: VAR 0 with the default transient call's switches fixed at compile time (lds_layout.hpp: f2_fixed_ok), taken whenever they hold.
+//     VAR 4: VAR 3 with the circuit's block list fixed as well -- voltage sources, one pass of plain sp_mos1, capacitors: a CMOS cell
+//     (lds_layout.hpp: f2_shape_ok) --, taken whenever the list has that shape.
 //     VAR 1: direct residuals for every device type, the linear solve as the pass program of the full table.  VAR 2 (diagnostic,
 //     CADNIP_F2_NODIRECT=1): the assembled residual r = J u + C beta - b from a J*u pass over the resident matrix.
 //   * team kernel k_fteam<NW, STEP> (fused_team_kernel.hpp): 2 or 4 waves share one instance when the batch cannot fill the chip; STEP
@@ -203,6 +205,14 @@ static int fused2_blocks(CadnipHandle* h) {
     S.rc_blk = first_of(CADNIP_DEV_CAPACITOR, CADNIP_DEV_RESISTOR);
     S.src_blk = first_of(CADNIP_DEV_VSOURCE, CADNIP_DEV_ISOURCE);
     S.src_count = S.src_blk >= 0 ? hb[S.src_blk].count : 0;
+    S.src_type = S.src_blk >= 0 ? hb[S.src_blk].type : -1;
+    S.rc_type = S.rc_blk >= 0 ? hb[S.rc_blk].type : -1;
+    S.rc_count = S.rc_blk >= 0 ? hb[S.rc_blk].count : 0;
+    S.dev_type = -1; S.dev_plain = 0; S.dev_count = 0;
+    if (nb == 3 && S.src_blk >= 0 && S.rc_blk >= 0) {       // a list of three: the block beside the two pinned ones
+      const F2Block& D = hb[3 - S.src_blk - S.rc_blk];
+      S.dev_type = D.type; S.dev_plain = D.mos1_plain; S.dev_count = D.count;
+    }
     S.lean = true;
     for (int i = 0; i < nb; ++i) {
       const int ty = hb[i].type;
@@ -232,7 +242,7 @@ static int fused2_blocks(CadnipHandle* h) {
 }
 
 // The one place that decides what a fused launch runs, and the only reader of the diagnostic switches CADNIP_F2_NODIRECT / _TEAM / _WPB / _STEPS_PACKED /
-// _SRC_CACHE / _FIXED
+// _SRC_CACHE / _FIXED / _SHAPE
 // (CADNIP_F2_NC: f2_prepare, where the tables are built; CADNIP_F2_DEBUG prints the plan, launch_fused2).
 static bool env_is_zero(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }
 
@@ -318,6 +328,9 @@ F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode, const TranArgs
   // way) keeps the generic kernel, and so do CADNIP_F2_STEPS_PACKED=1 and CADNIP_F2_SRC_CACHE=0 through step_predec / src_words.
   p.fixed = topt && f2_fixed_ok(mode == F2_TRAN, p.var == 0, topt->newton_mode, p.step_predec, p.src_words, h->n, S.nc, topt->max_order, topt->step_rule,
                                 topt->use_pcnr, !env_is_zero("CADNIP_F2_FIXED"));
+  // ... and of the fixed form its shape form (k_fused2<wpb, false, 4>) when the circuit's block list is a CMOS cell's: voltage sources, one pass of
+  // plain sp_mos1, capacitors -- f2_shape_ok is the list.  CADNIP_F2_SHAPE=0 (diagnostic, tests: bit-identical results either way) keeps variant 3.
+  p.shape = f2_shape_ok(p.fixed, S.n_blk, S.src_type, S.src_count, S.rc_type, S.rc_count, S.dev_type, S.dev_plain, S.dev_count, !env_is_zero("CADNIP_F2_SHAPE"));
   p.wpb = wpb; p.shmem = shmem; p.grid = std::min((h->B + wpb - 1) / wpb, S.n_cu * wg_per_cu); p.rc = CADNIP_OK;
   return p;
 }
@@ -365,8 +378,9 @@ static int launch_fused2(CadnipHandle* h, const TranArgs& t, int rounds, const F
     else TRY_RC(fteam_launch(p.nw, p.grid, p.shmem, h->stream, f));
   } else {
     const size_t tab_b = (size_t)p.tab_len / 2 * 8, desc_b = (size_t)lds_sweep_desc_words(f.team_desc_len, p.step_predec) * 8;
-    if (debug) fprintf(stderr, "[cadnip f2] B %d n_cu %d wpb %d grid %d shmem %zu (tables %zu, steps %zu, per instance %zu) rounds %d nc %d passes %d+%d steps %d+%d / %d (%s) variant %d src-cache %d fixed %d\n", h->B, S.n_cu, p.wpb, p.grid, p.shmem, tab_b, desc_b, (p.shmem - tab_b - desc_b) / p.wpb, rounds, S.nc, S.n_pre, S.n_post, f.ts_pre, f.ts_post, f.ts_fwd, p.step_predec ? "pre-decoded" : "packed", p.var, p.src_words, p.fixed ? 1 : 0);
-    TRY_RC(p.fixed ? f2_launch_variant<3>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
+    if (debug) fprintf(stderr, "[cadnip f2] B %d n_cu %d wpb %d grid %d shmem %zu (tables %zu, steps %zu, per instance %zu) rounds %d nc %d passes %d+%d steps %d+%d / %d (%s) variant %d src-cache %d shape %d fixed %d\n", h->B, S.n_cu, p.wpb, p.grid, p.shmem, tab_b, desc_b, (p.shmem - tab_b - desc_b) / p.wpb, rounds, S.nc, S.n_pre, S.n_post, f.ts_pre, f.ts_post, f.ts_fwd, p.step_predec ? "pre-decoded" : "packed", p.var, p.src_words, p.shape ? 1 : 0, p.fixed ? 1 : 0);
+    TRY_RC(p.shape ? f2_launch_variant<4>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
+         : p.fixed ? f2_launch_variant<3>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
          : p.var == 0 ? f2_launch_variant<0>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
          : p.var == 1 ? f2_launch_variant<1>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f)
                       : f2_launch_variant<2>(p.wpb, dc != nullptr, p.grid, p.shmem, h->stream, f));

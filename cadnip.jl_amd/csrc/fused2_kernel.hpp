@@ -1,6 +1,6 @@
 // fused2_kernel.hpp -- the fused Newton kernel itself (template k_fused2<WPB, DC, VAR>) and its argument block.  Included by
-// fused2.hip (host side: tables, launch geometry) and by the four translation units that instantiate the kernel, one per
-// variant (fused2_v0/1/2/3.hip), so that the variants compile in parallel.  See fused2.hip for the design notes.
+// fused2.hip (host side: tables, launch geometry) and by the five translation units that instantiate the kernel, one per
+// variant (fused2_v0/1/2/3/4.hip), so that the variants compile in parallel.  See fused2.hip for the design notes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "devices.hpp"
@@ -354,9 +354,13 @@ __device__ __forceinline__ void dense_core_solve(double* W, int dn0, int yc0, in
 // r = J u + C beta - b (diagnostic, CADNIP_F2_NODIRECT=1), every device type; 3 = variant 0 with the default transient call's switches
 // fixed at compile time (lds_layout.hpp: f2_fixed_ok is the list; fused2.hip: fused2_plan decides): Newton mode 1, pre-decoded steps, source
 // cache on, core of 8, no PCNR, max_order <= 2, step_rule 0, n <= 256.  Same statements, same order: results are variant 0's to the bit.
+// 4 = variant 3 with the circuit's block list fixed as well, to the shape of a CMOS-cell deck (lds_layout.hpp: f2_shape_ok is the list): three
+// blocks -- the pinned voltage sources (<= 64), the pinned capacitors (<= 64), one plain sp_mos1 block of one lane-pair pass (<= 32).  No block
+// loop, no type tests, no second pinned device per lane; counts, bases and the sp_mos1 block's index stay what the launch reads.
 template <int WPB, bool DC, int VAR>
 __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
-  constexpr bool DIRECT = VAR != 2, LEAN = VAR == 0 || VAR == 3, FIXED = VAR == 3;
+  constexpr bool DIRECT = VAR != 2, LEAN = VAR == 0 || VAR == 3 || VAR == 4, FIXED = VAR == 3 || VAR == 4, SHAPE = VAR == 4;
+  constexpr int RCQ = SHAPE ? 1 : 2;        // pinned capacitor / resistor devices per lane (the shape form's block has at most 64)
   static_assert(!(FIXED && DC), "the fixed form is a transient kernel");
   extern __shared__ double sm[];
   // w is the same for all lanes of a wave: say so (readfirstlane), or every address derived from it lives in VGPRs
@@ -416,17 +420,18 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   // independent-source block (one per lane) are stamped from registers -- four matrix words, the residual words of
   // their rows and their unknowns, as 16-bit offsets.  They depend on the circuit only, so they are read once per
   // launch; a lane without a device points everything at its trash word / ground.
-  unsigned rc_gp[2][2] = {{0, 0}, {0, 0}}, rc_row[2] = {0, 0}, rc_nd[2] = {0, 0}, src_gp[2] = {0, 0}, src_row[2] = {0, 0}, src_nd[2] = {0, 0};
+  // (shape form, SHAPE: both blocks exist, the first holds capacitors, at most 64 -- one device per lane --, the second voltage sources)
+  unsigned rc_gp[RCQ][2] = {}, rc_row[RCQ] = {}, rc_nd[RCQ] = {}, src_gp[2] = {0, 0}, src_row[2] = {0, 0}, src_nd[2] = {0, 0};
   int rc_count = 0, rc_type = 0, src_count = 0, src_type = 0;
   if constexpr (DIRECT) {
     const unsigned tr = (unsigned)(f.nnz_lu + n + lane0);
     auto row_of = [&](int node) -> unsigned { return node < 0 ? tr : (unsigned)rowof[node]; };
-    if (f.rc_blk >= 0) {
+    if (SHAPE ? true : f.rc_blk >= 0) {
       const F2Block B = load_block(f.blk, f.rc_blk);
       rc_count = B.count; rc_type = B.type;
       const short* nd = nodes + B.nodes_off;
 #pragma unroll
-      for (int q = 0; q < 2; ++q) {
+      for (int q = 0; q < RCQ; ++q) {
         const int dev = lane0 + 64 * q;
         unsigned p[4] = {tr, tr, tr, tr};
         int np = -1, nn = -1;
@@ -434,14 +439,14 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
           np = nd[dev]; nn = nd[B.count + dev];
 #pragma unroll
           for (int k = 0; k < 4; ++k)
-            p[k] = B.type == CADNIP_DEV_CAPACITOR ? (unsigned)cdesc[B.c_base + k * B.count + dev] & 0xFFFFu : (unsigned)gpos[B.g_base + k * B.count + dev];
+            p[k] = (SHAPE ? true : B.type == CADNIP_DEV_CAPACITOR) ? (unsigned)cdesc[B.c_base + k * B.count + dev] & 0xFFFFu : (unsigned)gpos[B.g_base + k * B.count + dev];
         }
         rc_gp[q][0] = p[0] | p[1] << 16; rc_gp[q][1] = p[2] | p[3] << 16;
         rc_row[q] = row_of(np) | row_of(nn) << 16;
         rc_nd[q] = ((unsigned)np & 0xFFFFu) | ((unsigned)nn & 0xFFFFu) << 16;
       }
     }
-    if (f.src_blk >= 0) {
+    if (SHAPE ? true : f.src_blk >= 0) {
       const F2Block B = load_block(f.blk, f.src_blk);
       src_count = B.count; src_type = B.type;
       const short* nd = nodes + B.nodes_off;
@@ -449,7 +454,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
       int np = -1, nn = -1, ni = -1;
       if (lane0 < B.count) {
         np = nd[lane0]; nn = nd[B.count + lane0];
-        if (B.type == CADNIP_DEV_VSOURCE) {
+        if (SHAPE ? true : B.type == CADNIP_DEV_VSOURCE) {
           ni = nd[2 * B.count + lane0];
 #pragma unroll
           for (int k = 0; k < 4; ++k) p[k] = (unsigned)gpos[B.g_base + k * B.count + lane0];
@@ -500,12 +505,12 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   // DC state of this instance: settle flag of the PCNR loop (solve.jl:640-657), Newton solves done in this launch
   int dc_state = 0, dc_iters = 0, dc_first = 0;
   if (DC) { dc_state = __builtin_amdgcn_readfirstlane(kargs()->dcstate[inst]); dc_first = f.dc_initjct && __builtin_amdgcn_readfirstlane(kargs()->cold[inst]); }
-  double rc_val[2] = {0.0, 0.0};   // values of the first capacitor / resistor block: constant for the instance, kept in registers
-  if (f.rc_blk >= 0) {
+  double rc_val[RCQ] = {};         // values of the first capacitor / resistor block: constant for the instance, kept in registers
+  if (SHAPE ? true : f.rc_blk >= 0) {
     const F2Block B = load_block(f.blk, f.rc_blk);
     const double* par = B.par + (size_t)inst * B.n_par * B.count;
 #pragma unroll
-    for (int q = 0; q < 2; ++q) { const int dev = lane0 + 64 * q; rc_val[q] = par[dev < B.count ? dev : 0]; }
+    for (int q = 0; q < RCQ; ++q) { const int dev = lane0 + 64 * q; rc_val[q] = par[dev < B.count ? dev : 0]; }
   }
   // source segment cache of this residence (src_cache.hpp; LDS behind beta): a DC source's entry answers every time point, every other
   // source starts with an entry that cannot hit and caches the PWL segment its first evaluation finds
@@ -560,18 +565,18 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
         const double x = a0 * us[i] + betas[i];
         return nd16 == 0xFFFFu ? 0.0 : x;
       };
-      if (f.rc_blk >= 0) {
-        const bool cap = rc_type == CADNIP_DEV_CAPACITOR;
-        double jv[2], cur[2];
+      if (SHAPE ? true : f.rc_blk >= 0) {
+        const bool cap = SHAPE ? true : rc_type == CADNIP_DEV_CAPACITOR;
+        double jv[RCQ], cur[RCQ];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < RCQ; ++q) {
           const unsigned np = rc_nd[q] & 0xFFFFu, nn = rc_nd[q] >> 16;
           const double xp = cap ? dat(np) : at(np), xn = cap ? dat(nn) : at(nn);
           jv[q] = cap ? a0 * rc_val[q] : rc_val[q];
           cur[q] = rc_val[q] * (xp - xn);
         }
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
+        for (int q = 0; q < RCQ; ++q) {
           if (q == 1 && rc_count <= 64) break;             // (the second device of a lane exists only beyond 64: its stamps would all go to the trash word)
           if (refresh) {
             atomicAdd(&W[rc_gp[q][0] & 0xFFFFu], jv[q]); atomicAdd(&W[rc_gp[q][0] >> 16], -jv[q]);
@@ -581,7 +586,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
         }
       }
       CADNIP_TRACE_POINT(14);
-      if (f.src_blk >= 0) {
+      if (SHAPE ? true : f.src_blk >= 0) {
         if (DC || !src_have || tcur != src_t) {
           // a new time point: the lane's cached segment answers it from LDS when the time lies inside it ...
           const int cl = src_cache_lanes(src_count);
@@ -617,7 +622,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
         }
         CADNIP_TRACE_USE(src_val);
         CADNIP_TRACE_POINT(15);
-        if (src_type == CADNIP_DEV_VSOURCE) {
+        if (SHAPE ? true : src_type == CADNIP_DEV_VSOURCE) {
           // branch rows / columns +-1 (devices.hpp: branch4); KCL rows carry u[I], the branch row V(p) - V(n) - v
           const double ui = at(src_nd[1]), vd = at(src_nd[0] & 0xFFFFu) - at(src_nd[0] >> 16) - src_val;
           if (refresh) {
@@ -632,6 +637,25 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
       }
       CADNIP_TRACE_POINT(13);
     }
+    if constexpr (SHAPE) {
+      // shape form: what the loop below does for the one block that is left -- plain sp_mos1, at most 32 devices: one lane-pair pass
+      const int bi = 3 - f.rc_blk - f.src_blk;            // (three blocks: the one that is neither pinned)
+      const F2Block B = load_block(f.blk, bi);
+      const double* par = B.par + (size_t)inst * B.n_par * B.count;
+      const int side = lane & 1;
+      const int dv = lane >> 1;
+      const bool valid = dv < B.count;
+      LdsCtx d{nodes + B.nodes_off, B.ipar, par, f.wave, B.count, valid ? dv : B.count - 1, tcur, dmode, dinit};
+      if (!refresh) {                      // round on kept factors: residuals only
+        AccumOutT<true, DIRECT, false> s{W, betas, a0, gpos + B.g_base, cdesc + B.c_base, brow + B.b_base, B.count, d.dev, valid ? 0u : trash_w, us, rowof, trash_w};
+        stamp_mos1_pair(d, us, s, lw, side, valid);
+      } else {
+        AccumOutT<true, DIRECT> s{W, betas, a0, gpos + B.g_base, cdesc + B.c_base, brow + B.b_base, B.count, d.dev, valid ? 0u : trash_w, us, rowof, trash_w};
+        stamp_mos1_pair(d, us, s, lw, side, valid);
+      }
+      CADNIP_TRACE_POINT(8);
+    }
+    if constexpr (!SHAPE)                  // (shape form: no loop, and nothing of its body is instantiated -- the two other blocks were pinned whole)
     for (int bi = 0; bi < f.n_blk; ++bi) {
       if (DIRECT && ((bi == f.rc_blk && rc_count <= 128) || (bi == f.src_blk && src_count <= 64))) continue;   // all of it was pinned
       const F2Block B = load_block(f.blk, bi);

@@ -120,6 +120,9 @@ struct FusedState {
   void* d_blk = nullptr;
   int n_blk = 0, rc_blk = -1, src_blk = -1;   // first capacitor / resistor block, first independent-source block of the list
   int src_count = 0;          // devices of block src_blk (the first 64 are pinned to lanes and may have their segment cached: src_cache.hpp)
+  // the block list as lds_layout.hpp: f2_shape_ok reads it: types and counts of the two pinned blocks and of the one block beside them (of a
+  // list of three; a type of -1: no such block)
+  int src_type = -1, rc_type = -1, rc_count = 0, dev_type = -1, dev_plain = 0, dev_count = 0;
   int par_words = 0;          // team kernel: doubles of the LDS-staged sp_mos1 parameter rows of one instance
   bool lean = false;          // only device types of the lean kernel variant
   // buffers of the launches
@@ -380,6 +383,7 @@ struct F2Plan {
   bool keep_factors = false;  // Newton mode 1 / single step: kept factors in HBM
   int src_words = 0;          // sweep kernel: doubles of the per-instance source segment cache in LDS (src_cache.hpp), 0 = the launch runs without it
   bool fixed = false;         // sweep kernel, variant 0: the launch takes the fixed form k_fused2<wpb, false, 3> (lds_layout.hpp: f2_fixed_ok)
+  bool shape = false;         // ... and of it the shape form k_fused2<wpb, false, 4>: the circuit's block list is fixed as well (lds_layout.hpp: f2_shape_ok)
 };
 // topt: the transient options of the call the plan is for (null: none -- the fixed form is then never chosen)
 F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode, const TranArgs* topt = nullptr);

@@ -8,6 +8,7 @@
 // (f2_program.cpp) -- so every work array W (cleared as double2) and every descriptor area (read as uint4) starts on 16 bytes.
 #pragma once
 #include <stddef.h>
+#include "../../include/cadnip_hip.h"   // device type codes (f2_shape_ok)
 #ifdef __HIPCC__
 #include <type_traits>
 #define LDS_HD __host__ __device__ __forceinline__
@@ -52,6 +53,19 @@ LDS_HD bool f2_fixed_ok(bool tran, bool lean, int newton_mode, bool step_predec,
                         int use_pcnr, bool enabled) {
   return tran && lean && newton_mode == 1 && step_predec && src_words > 0 && n <= 256 && nc == 8 && max_order <= 2 && step_rule == 0 &&
          use_pcnr == 0 && enabled;
+}
+// ---- ... and its SHAPE form (k_fused2<WPB, false, 4>): the fixed form with the circuit's block list fixed as well, to what every CMOS-cell
+// characterisation deck has -- voltage sources, plain sp_mos1 transistors, capacitors, nothing else.  THE list of what that kernel assumes beyond
+// f2_fixed_ok (`fixed`); a launch that misses one condition takes variant 3 (or 0), which computes the same to the bit.  The facts come from the
+// block list of fused2.hip: fused2_blocks -- n_blk blocks, of which src_* is the pinned source block (F2Args::src_blk), rc_* the pinned
+// capacitor / resistor block (F2Args::rc_blk) and dev_* the remaining one (a type of -1: there is no such block).  With three blocks, one of them
+// the first of the source types and another the first of the R / C types, each is the only one of its kind.  The counts: a pinned block of at
+// most 64 has one device per lane and nothing left for the block loop; 32 lane-paired sp_mos1 devices are one pass of a wave.
+// `enabled`: CADNIP_F2_SHAPE is not 0 (diagnostic, tests; fused2_plan reads it and calls this).
+LDS_HD bool f2_shape_ok(bool fixed, int n_blk, int src_type, int src_count, int rc_type, int rc_count, int dev_type, int dev_plain, int dev_count,
+                        bool enabled) {
+  return fixed && n_blk == 3 && src_type == CADNIP_DEV_VSOURCE && src_count <= 64 && rc_type == CADNIP_DEV_CAPACITOR && rc_count <= 64 &&
+         dev_type == CADNIP_DEV_MOS1 && dev_plain != 0 && dev_count <= 32 && enabled;
 }
 // 64-bit words of the descriptor area: desc_len as uploaded (two per lane and step), plus one flag byte per lane and step when pre-decoded
 LDS_HD int lds_sweep_desc_words(int desc_len, bool predec) { return desc_len + (predec ? desc_len / 16 : 0); }
