@@ -885,12 +885,12 @@ int ac_lu_prepare(CadnipHandle* h, bool adjoint) {
   return adjoint ? ac_adjoint_tables(h) : CADNIP_OK;
 }
 
-// the arguments both kernels share; the output pointers are the plain sweep's
-static AcArgs ac_args(CadnipHandle* h, int n_freq, long s0, int n_sys, double gmin) {
+// the arguments every family shares: the handle's tables, the call's grid and -- the first input of every sweep -- omega; the family's
+// launcher points b_ac and the outputs at its own slots of io
+static AcArgs ac_args(CadnipHandle* h, const AcIo& io, int n_freq, long s0, int n_sys, double gmin) {
   const LUProgram& P = h->lu;
-  AcArgs a;
-  a.G = h->d_G; a.C = h->d_C; a.omega = h->ac.d_omega; a.bac = h->ac.d_bac; a.diag_flag = h->d_diag_flag; a.nodiag = h->ac.d_nodiag; a.gmin = gmin;
-  a.x = h->ac.d_x; a.berr = h->ac.d_berr; a.flags = h->ac.d_flags;
+  AcArgs a{};
+  a.G = h->d_G; a.C = h->d_C; a.omega = io.din(0); a.diag_flag = h->d_diag_flag; a.nodiag = h->ac.d_nodiag; a.gmin = gmin;
   a.rowptr = h->d_rowptr; a.colidx = h->d_colidx; a.load_dst = h->d_load_dst; a.ent_pos = h->d_ent_pos; a.ent_diag = h->d_ent_diag;
   a.ent_ptr = h->d_ent_ptr; a.term_a = h->d_term_a; a.term_b = h->d_term_b; a.lev_ptr = h->d_lev_ptr;
   a.lu_rowptr = h->d_lu_rowptr; a.lu_col = h->d_lu_col; a.lu_diag = h->d_lu_diag; a.rperm = h->d_rperm; a.cperm = h->d_cperm;
@@ -928,18 +928,25 @@ static int ac_launch(CadnipHandle* h, const AcLaunch& L, const char* name_lds, c
   return CADNIP_OK;
 }
 
-int launch_ac_lu(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin) {
-  if (L.memory < 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
-  const AcArgs a = ac_args(h, n_freq, s0, n_sys, gmin);
+// ... of a family with an overlay form: Sys<AcOvl> when the handle has one set, else Sys<AcNoOvl>, the statements without
+template <template <class> class Sys, class Args>
+static int ac_launch_ovl(CadnipHandle* h, const AcLaunch& L, const char* name_lds, const char* name_hbm, const Args& args) {
   const AcOvl v = ac_ovl(h);
-  return v.n > 0 ? ac_launch(h, L, "ac_lu", "ac_lu_hbm", AcLuSys<AcOvl>{a, v}) : ac_launch(h, L, "ac_lu", "ac_lu_hbm", AcLuSys<AcNoOvl>{a, {}});
+  return v.n > 0 ? ac_launch(h, L, name_lds, name_hbm, Sys<AcOvl>{args, v}) : ac_launch(h, L, name_lds, name_hbm, Sys<AcNoOvl>{args, {}});
 }
 
-// the transposed-solve tables and the adjoint's output pointers over ac_args
-static AcAdjArgs ac_adj_args(CadnipHandle* h, int n_freq, long s0, int n_sys, double gmin) {
+int launch_ac_lu(CadnipHandle* h, const AcLaunch& L, const AcIo& io, int n_freq, long s0, int n_sys, double gmin) {
+  if (L.memory < 0 || n_sys <= 0 || h->ac.dirty) return CADNIP_BADARG;
+  AcArgs a = ac_args(h, io, n_freq, s0, n_sys, gmin);
+  a.bac = io.din(1); a.x = io.dout(0); a.berr = io.dout(1); a.flags = io.iout(2);
+  return ac_launch_ovl<AcLuSys>(h, L, "ac_lu", "ac_lu_hbm", a);
+}
+
+// the transposed-solve tables over ac_args
+static AcAdjArgs ac_adj_args(CadnipHandle* h, const AcIo& io, int n_freq, long s0, int n_sys, double gmin) {
   AcState& A = h->ac;
-  AcAdjArgs t;
-  t.a = ac_args(h, n_freq, s0, n_sys, gmin);
+  AcAdjArgs t{};
+  t.a = ac_args(h, io, n_freq, s0, n_sys, gmin);
   t.t_colptr = A.d_t_colptr; t.t_pos = A.d_t_pos; t.t_row = A.d_t_row; t.t_diag = A.d_t_diag;
   t.ut_rows = A.d_ut_rows; t.ut_lev_ptr = A.d_ut_lev_ptr; t.lt_rows = A.d_lt_rows; t.lt_lev_ptr = A.d_lt_lev_ptr;
   t.a_colptr = A.d_a_colptr; t.a_row = A.d_a_row; t.a_pos = A.d_a_pos;
@@ -947,63 +954,51 @@ static AcAdjArgs ac_adj_args(CadnipHandle* h, int n_freq, long s0, int n_sys, do
   return t;
 }
 
-int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x) {
+int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& L, const AcIo& io, int n_freq, long s0, int n_sys, double gmin, int n_pairs) {
   AcState& A = h->ac;
   if (L.memory < 0 || n_sys <= 0 || n_pairs <= 0 || A.dirty || !A.adj_ready) return CADNIP_BADARG;
-  AcAdjArgs t = ac_adj_args(h, n_freq, s0, n_sys, gmin);
-  t.a.x = want_x ? A.d_adj_x : nullptr; t.a.berr = A.d_adj_berr; t.a.flags = A.d_adj_flags;
-  t.pairs = A.d_pairs; t.h = A.d_h; t.n_pairs = n_pairs;
-  const AcOvl v = ac_ovl(h);
-  return v.n > 0 ? ac_launch(h, L, "ac_adj", "ac_adj_hbm", AcAdjSys<AcOvl>{t, v}) : ac_launch(h, L, "ac_adj", "ac_adj_hbm", AcAdjSys<AcNoOvl>{t, {}});
+  AcAdjArgs t = ac_adj_args(h, io, n_freq, s0, n_sys, gmin);
+  t.a.bac = io.din(1); t.pairs = io.iin(2); t.n_pairs = n_pairs;
+  t.h = io.dout(0); t.a.x = io.dout(1); t.a.berr = io.dout(2); t.a.flags = io.iout(3);
+  return ac_launch_ovl<AcAdjSys>(h, L, "ac_adj", "ac_adj_hbm", t);
 }
 
-int launch_ac_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x) {
+int launch_ac_multi(CadnipHandle* h, const AcLaunch& L, const AcIo& io, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs) {
+  if (L.memory < 0 || n_sys <= 0 || n_rhs < 1 || n_pairs < 0 || (n_pairs == 0 && !io.out[1]) || h->ac.dirty) return CADNIP_BADARG;
+  AcMultiArgs t{};
+  t.a = ac_args(h, io, n_freq, s0, n_sys, gmin);
+  t.rhs = io.din(1); t.rhs_stride = (long)n_rhs * h->n; t.pairs = io.iin(2); t.n_rhs = n_rhs; t.n_pairs = n_pairs;
+  t.h = io.dout(0); t.a.x = io.dout(1); t.a.berr = io.dout(2); t.a.flags = io.iout(3);
+  return ac_launch_ovl<AcLuMultiSys>(h, L, "ac_lu_multi", "ac_lu_multi_hbm", t);
+}
+
+int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& L, const AcIo& io, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs) {
   AcState& A = h->ac;
-  if (L.memory < 0 || n_sys <= 0 || n_rhs < 1 || n_pairs < 0 || (n_pairs == 0 && !want_x) || A.dirty) return CADNIP_BADARG;
-  AcMultiArgs t;
-  t.a = ac_args(h, n_freq, s0, n_sys, gmin);
-  t.a.bac = nullptr; t.a.x = want_x ? A.d_multi_x : nullptr; t.a.berr = A.d_multi_berr; t.a.flags = A.d_multi_flags;
-  t.rhs = A.d_multi_rhs; t.rhs_stride = (long)n_rhs * h->n;
-  t.pairs = A.d_multi_pairs; t.h = A.d_multi_h; t.n_rhs = n_rhs; t.n_pairs = n_pairs;
-  const AcOvl v = ac_ovl(h);
-  return v.n > 0 ? ac_launch(h, L, "ac_lu_multi", "ac_lu_multi_hbm", AcLuMultiSys<AcOvl>{t, v})
-                 : ac_launch(h, L, "ac_lu_multi", "ac_lu_multi_hbm", AcLuMultiSys<AcNoOvl>{t, {}});
+  if (L.memory < 0 || n_sys <= 0 || n_rhs < 1 || n_pairs < 0 || (n_pairs == 0 && !io.out[1]) || A.dirty || !A.adj_ready) return CADNIP_BADARG;
+  AcAdjMultiArgs u{};
+  u.t = ac_adj_args(h, io, n_freq, s0, n_sys, gmin);
+  u.rhs = io.din(1); u.rhs_stride = (long)n_rhs * h->n; u.t.pairs = io.iin(2); u.n_rhs = n_rhs; u.t.n_pairs = n_pairs;
+  u.t.h = io.dout(0); u.t.a.x = io.dout(1); u.t.a.berr = io.dout(2); u.t.a.flags = io.iout(3);
+  return ac_launch_ovl<AcAdjMultiSys>(h, L, "ac_adj_multi", "ac_adj_multi_hbm", u);
 }
 
-int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x) {
-  AcState& A = h->ac;
-  if (L.memory < 0 || n_sys <= 0 || n_rhs < 1 || n_pairs < 0 || (n_pairs == 0 && !want_x) || A.dirty || !A.adj_ready) return CADNIP_BADARG;
-  AcAdjMultiArgs u;
-  u.t = ac_adj_args(h, n_freq, s0, n_sys, gmin);
-  u.t.a.bac = nullptr; u.t.a.x = want_x ? A.d_multi_x : nullptr; u.t.a.berr = A.d_multi_berr; u.t.a.flags = A.d_multi_flags;
-  u.t.pairs = A.d_multi_pairs; u.t.h = A.d_multi_h; u.t.n_pairs = n_pairs;
-  u.rhs = A.d_multi_rhs; u.rhs_stride = (long)n_rhs * h->n; u.n_rhs = n_rhs;
-  const AcOvl v = ac_ovl(h);
-  return v.n > 0 ? ac_launch(h, L, "ac_adj_multi", "ac_adj_multi_hbm", AcAdjMultiSys<AcOvl>{u, v})
-                 : ac_launch(h, L, "ac_adj_multi", "ac_adj_multi_hbm", AcAdjMultiSys<AcNoOvl>{u, {}});
-}
-
-int launch_ac_sens(CadnipHandle* h, const AcLaunch& L, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, bool db, const int* pair, bool want_x) {
+int launch_ac_sens(CadnipHandle* h, const AcLaunch& L, const AcIo& io, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, const int* pair) {
   AcState& A = h->ac;
   if (L.memory < 0 || n_sys <= 0 || n_base < 1 || n_par < 1 || !pair || A.dirty || !A.adj_ready) return CADNIP_BADARG;
-  AcSensArgs u;
-  u.t = ac_adj_args(h, n_freq, s0, n_sys, gmin);
-  u.t.a.bac = A.d_sens_bac; u.t.a.x = want_x ? A.d_sens_x : nullptr; u.t.a.berr = A.d_sens_berr; u.t.a.flags = A.d_sens_flags;
-  u.t.pairs = nullptr; u.t.h = nullptr; u.t.n_pairs = 0;
-  u.base = A.d_sens_idx; u.plus = u.base + n_base; u.minus = u.plus + (size_t)n_base * n_par;
-  u.scale = A.d_sens_scale; u.db = db ? A.d_sens_db : nullptr; u.c = A.d_sens_c;
-  u.y = A.d_sens_y; u.s = A.d_sens_s; u.n_par = n_par; u.p = pair[0]; u.q = pair[1];
+  AcSensArgs u{};
+  u.t = ac_adj_args(h, io, n_freq, s0, n_sys, gmin);
+  u.base = io.iin(1); u.plus = io.iin(2); u.minus = io.iin(3); u.scale = io.din(4); u.t.a.bac = io.din(5); u.db = io.din(6); u.c = io.din(7);
+  u.y = io.dout(0); u.s = io.dout(1); u.t.a.x = io.dout(2); u.t.a.berr = io.dout(3); u.t.a.flags = io.iout(4);
+  u.n_par = n_par; u.p = pair[0]; u.q = pair[1];
   return ac_launch(h, L, "ac_sens", "ac_sens_hbm", AcSensSys{u});
 }
 
-int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& L, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs) {
-  AcState& A = h->ac;
-  if (L.memory < 0 || n_sys <= 0 || m < 1 || m > h->n || !(tol > 0.0 && tol < 1.0) || n_pairs < 0 || A.dirty) return CADNIP_BADARG;
-  AcArnArgs u;
-  u.a = ac_args(h, n_shift, s0, n_sys, gmin);
-  u.a.bac = A.d_arn_bac; u.a.x = nullptr; u.a.berr = A.d_arn_berr; u.a.flags = A.d_arn_flags;
-  u.pairs = A.d_arn_pairs; u.H = A.d_arn_H; u.beta = A.d_arn_beta; u.l = A.d_arn_l; u.V = A.d_arn_V; u.meff = A.d_arn_meff;
-  u.tol = tol; u.m = m; u.n_pairs = n_pairs;
+int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& L, const AcIo& io, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs) {
+  if (L.memory < 0 || n_sys <= 0 || m < 1 || m > h->n || !(tol > 0.0 && tol < 1.0) || n_pairs < 0 || h->ac.dirty) return CADNIP_BADARG;
+  AcArnArgs u{};
+  u.a = ac_args(h, io, n_shift, s0, n_sys, gmin);
+  u.a.bac = io.din(1); u.pairs = io.iin(2); u.tol = tol; u.m = m; u.n_pairs = n_pairs;
+  u.H = io.dout(0); u.l = io.dout(1); u.V = io.dout(2); u.beta = io.dout(3); u.meff = io.iout(4); u.a.berr = io.dout(5); u.a.flags = io.iout(6);
   return ac_launch(h, L, "ac_arnoldi", "ac_arnoldi_hbm", AcArnoldiSys{u});
 }
 

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <functional>
 #include <algorithm>
+#include <initializer_list>
 #include <stdio.h>
 #include <string.h>
 #include <string>
@@ -31,20 +32,14 @@ template <class T>
 int dev_upload(T** p, const std::vector<T>& v) { return dev_upload(p, v.data(), v.size()); }
 #define TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 
-// Device buffers of ONE capacity, grown on demand (the AC sweeps' transfer buffers): below `need` units every buffer of the group is freed,
-// then each is allocated (zeroed) to need x its own `words` elements, in the order given; the capacity reads 0 until all of them stand
-template <class T> struct AcBuf { T** p; size_t words; };
-template <class T> AcBuf<T> ac_buf(T** p, size_t words = 1) { return AcBuf<T>{p, words}; }
-template <class... T>
-int ac_grow(size_t* cap, size_t need, AcBuf<T>... bufs) {
-  if (*cap >= need) return CADNIP_OK;
-  auto drop = [](auto** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } };
-  (drop(bufs.p), ...);
-  *cap = 0;
-  int rc = CADNIP_OK;
-  ((rc = rc ? rc : dev_alloc(bufs.p, need * bufs.words)), ...);
-  if (rc) return rc;
-  *cap = need;
+// A slot of the AC sweeps' transfer pool (internal.hpp: AcState), grown on demand: below `need` bytes the buffer is freed, then allocated
+// (zeroed) to exactly `need`; the capacity reads 0 until the allocation stands, so a failed one leaves the handle usable
+int ac_reserve(AcSlot& s, size_t need) {
+  if (s.cap_bytes >= need) return CADNIP_OK;
+  if (s.p) { (void)hipFree(s.p); s.p = nullptr; }
+  s.cap_bytes = 0;
+  TRY(dev_alloc((char**)&s.p, need));
+  s.cap_bytes = need;
   return CADNIP_OK;
 }
 
@@ -249,13 +244,12 @@ void cadnip_destroy(CadnipHandle* h) {
                   h->d_resid, h->d_delta, h->d_limit_w, h->d_LU, h->d_tmp, h->d_flags, h->d_active, h->d_nonfinite, h->d_gshunt, h->d_srcfact, h->d_cold, h->d_load_src, h->d_load_dst, h->d_ent_pos,
                   h->d_ent_diag, h->d_ent_ptr, h->d_term_a, h->d_term_b, h->d_lev_ptr, h->d_lu_rowptr, h->d_lu_col, h->d_lu_diag, h->d_rperm,
                   h->d_cperm, h->d_fwd_rows, h->d_fwd_lev_ptr, h->d_bwd_rows, h->d_bwd_lev_ptr,
-                  h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_bac, h->ac.d_omega, h->ac.d_x, h->ac.d_berr, h->ac.d_flags, h->ac.d_work,
+                  h->ac.d_piv_rows, h->ac.d_piv_lev_ptr, h->ac.d_nodiag, h->ac.d_work,
                   h->ac.d_ovl_pos, h->ac.d_ovl_map, h->ac.d_ovl_val};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   h->ac.each_adjoint_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
-  h->ac.each_multi_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
-  h->ac.each_sens_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
-  h->ac.each_arn_buffer([](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; });
+  for (AcSlot& s : h->ac.in) if (s.p) (void)hipFree(s.p);
+  for (AcSlot& s : h->ac.out) if (s.p) (void)hipFree(s.p);
   h->f2.release();
   for (auto& g : h->step_graph) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (auto& b : h->blocks) {
@@ -862,118 +856,85 @@ int cadnip_ac_plan_info(CadnipHandle* h, int64_t out[4]) {
   return CADNIP_OK;
 }
 
+// The one host path of the six AC families.  A sweep is S systems, its transfers and a launch:
+//   ins   {host, bytes}: uploaded whole, once per call, into slot i of the pool (omega is the first input of every family); a null host or
+//         no bytes: the call has no such input -- no buffer, no upload, a null device pointer;
+//   outs  {host, bytes per system}: slot o holds one chunk of systems and is downloaded after each chunk to host + s0 * bytes; a null host or
+//         no bytes: not wanted -- no buffer, no download, a null device pointer -- unless `keep` names it the kernel's own storage, which is
+//         then allocated and not downloaded;
+//   launch(plan, s0, ns, io): the family's launcher for systems [s0, s0 + ns) on the device pointers io.
+// The systems are cut into chunks of at most AC_CHUNK_BYTES of solution (sys_bytes per system; AcChunks above), so the pool -- allocated on
+// first use, kept by the handle, released in cadnip_destroy -- stays bounded however large S is.  A plan that is refused returns
+// CADNIP_BADARG before anything is touched.  Uploads are blocking copies at entry (the stream is idle), downloads follow a stream
+// synchronisation.  The caller has validated its arguments
+struct AcIn { const void* host; size_t bytes; };
+struct AcOut { void* host; size_t sys_bytes; bool keep = false; };
+struct AcSweep { size_t S, sys_bytes; int32_t wpb; bool sens = false, adjoint = false; };   // sens: the four-vector layout; adjoint: the transposed tables
+using AcLaunchFn = std::function<int(const AcLaunch&, long, int, const AcIo&)>;
+static int ac_sweep(CadnipHandle* h, const AcSweep& sw, std::initializer_list<AcIn> ins, std::initializer_list<AcOut> outs, int32_t* info, const AcLaunchFn& launch) {
+  if (ins.size() > AC_MAX_IN || outs.size() > AC_MAX_OUT) return CADNIP_BADARG;
+  const AcChunks ch(h, sw.S, sw.sys_bytes, sw.wpb, sw.sens);
+  if (!ch.ok()) return CADNIP_BADARG;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  TRY(ac_lu_prepare(h, sw.adjoint));
+  AcState& A = h->ac;
+  AcIo io{};
+  int i = 0, o = 0;
+  for (const AcIn& t : ins) { if (t.host && t.bytes) { TRY(ac_reserve(A.in[i], t.bytes)); io.in[i] = A.in[i].p; } ++i; }
+  for (const AcOut& t : outs) { if ((t.host || t.keep) && t.sys_bytes) { TRY(ac_reserve(A.out[o], ch.chunk * t.sys_bytes)); io.out[o] = A.out[o].p; } ++o; }
+  i = 0;
+  for (const AcIn& t : ins) { if (io.in[i]) HIP_TRY(hipMemcpy(io.in[i], t.host, t.bytes, hipMemcpyHostToDevice)); ++i; }
+  for (size_t s0 = 0; s0 < sw.S; s0 += ch.chunk) {
+    const size_t ns = std::min(ch.chunk, sw.S - s0);
+    TRY(launch(ch.of(ns), (long)s0, (int)ns, io));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    o = 0;
+    for (const AcOut& t : outs) { if (t.host && io.out[o]) HIP_TRY(hipMemcpy((char*)t.host + s0 * t.sys_bytes, io.out[o], ns * t.sys_bytes, hipMemcpyDeviceToHost)); ++o; }
+  }
+  ac_report(h, ch, info);
+  return CADNIP_OK;
+}
+
 // The AC sweep x[b][f] = (G[b] + gmin [node diagonals] + j omega[f] C[b])^-1 b_ac[b] on the G / C of the last cadnip_rebuild, with the handle's
-// pivot order: S = B n_freq systems through AcLuSys (ac_lu.hip).  Uploads are blocking copies at entry (the stream is idle), downloads follow a
-// stream synchronisation.  The systems are processed in chunks of at most AC_CHUNK_BYTES of solution (16 n bytes each; AcChunks above), so
-// the device output buffers -- allocated on first use, kept by the handle, released in cadnip_destroy -- stay bounded however large B F is.
+// pivot order: S = B n_freq systems through AcLuSys (ac_lu.hip); a system's solution is 16 n bytes
 int cadnip_ac_solve(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, const double* bac_host, int32_t wpb, double* x_host,
                     double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || !bac_host || !x_host || !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
   if (!ac_overlay_grid_ok(h, n_freq, omega)) return CADNIP_BADARG;
-  const size_t B = h->B, n = h->n, F = n_freq, S = B * F;
-  const AcChunks ch(h, S, 16 * n, wpb);
-  if (!ch.ok()) return CADNIP_BADARG;
-  const size_t chunk = ch.chunk;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  TRY(ac_lu_prepare(h));
-  AcState& A = h->ac;
-  if (!A.d_bac) TRY(dev_alloc(&A.d_bac, B * n * 2));
-  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
-  TRY(ac_grow(&A.cap_sys, chunk, ac_buf(&A.d_x, n * 2), ac_buf(&A.d_berr), ac_buf(&A.d_flags)));
-  HIP_TRY(hipMemcpy(A.d_bac, bac_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
-  for (size_t s0 = 0; s0 < S; s0 += chunk) {
-    const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_lu(h, ch.of(ns), n_freq, (long)s0, (int)ns, gmin));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(berr_host + s0, A.d_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags_host + s0, A.d_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  ac_report(h, ch, info);
-  return CADNIP_OK;
+  const size_t B = h->B, n = h->n, F = n_freq;
+  return ac_sweep(h, {B * F, 16 * n, wpb}, {{omega, 8 * F}, {bac_host, 16 * B * n}}, {{x_host, 16 * n}, {berr_host, 8}, {flags_host, 4}}, info,
+                  [&](const AcLaunch& L, long s0, int ns, const AcIo& io) { return launch_ac_lu(h, L, io, n_freq, s0, ns, gmin); });
 }
 
 // The adjoint sweep x[b][f] = (A[b][f])^-T c[b] with A as above, and of it the probe differences h[b][f][k] = x[p_k] - x[n_k]: S = B n_freq
-// systems through AcAdjSys (ac_lu.hip), which factors exactly as AcLuSys does and solves through the transposed tables.  Same rules as
-// cadnip_ac_solve; a system's device output is 16 (K + n [x wanted]) bytes.  Buffers live in AcState.
+// systems through AcAdjSys (ac_lu.hip), which factors exactly as AcLuSys does and solves through the transposed tables; a system's solution
+// is 16 (K + n [x wanted]) bytes
 int cadnip_ac_adjoint(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, const double* c_host, int32_t n_pairs, const int32_t* pairs,
                       int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || !c_host || n_pairs < 1 || !pairs || !h_host || !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
   if (!ac_overlay_grid_ok(h, n_freq, omega)) return CADNIP_BADARG;
-  const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_pairs;
+  const size_t B = h->B, n = h->n, F = n_freq, K = n_pairs;
   for (size_t k = 0; k < 2 * K; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
-  const bool want_x = x_host != nullptr;
-  const AcChunks ch(h, S, 16 * (K + (want_x ? n : 0)), wpb);
-  if (!ch.ok()) return CADNIP_BADARG;
-  const size_t chunk = ch.chunk;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  TRY(ac_lu_prepare(h, true));
-  AcState& A = h->ac;
-  if (!A.d_bac) TRY(dev_alloc(&A.d_bac, B * n * 2));
-  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
-  if (A.cap_pairs < K || A.cap_adj_sys < chunk) {             // d_h is [systems][pairs]: either growing reallocates it
-    const size_t ck = std::max(A.cap_pairs, K), cs = std::max(A.cap_adj_sys, chunk);
-    void* old[] = {A.d_pairs, A.d_h, A.d_adj_berr, A.d_adj_flags};
-    for (void* p : old) if (p) (void)hipFree(p);
-    A.d_pairs = nullptr; A.d_h = nullptr; A.d_adj_berr = nullptr; A.d_adj_flags = nullptr; A.cap_pairs = 0; A.cap_adj_sys = 0;
-    TRY(dev_alloc(&A.d_pairs, ck * 2)); TRY(dev_alloc(&A.d_h, cs * ck * 2)); TRY(dev_alloc(&A.d_adj_berr, cs)); TRY(dev_alloc(&A.d_adj_flags, cs));
-    A.cap_pairs = ck; A.cap_adj_sys = cs;
-  }
-  if (want_x) TRY(ac_grow(&A.cap_adj_x, chunk, ac_buf(&A.d_adj_x, n * 2)));
-  HIP_TRY(hipMemcpy(A.d_bac, c_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_pairs, pairs, K * 2 * sizeof(int), hipMemcpyHostToDevice));
-  for (size_t s0 = 0; s0 < S; s0 += chunk) {
-    const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_adjoint(h, ch.of(ns), n_freq, (long)s0, (int)ns, gmin, n_pairs, want_x));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(h_host + s0 * K * 2, A.d_h, ns * K * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * n * 2, A.d_adj_x, ns * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(berr_host + s0, A.d_adj_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags_host + s0, A.d_adj_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  ac_report(h, ch, info);
-  return CADNIP_OK;
+  const AcSweep sw{B * F, 16 * (K + (x_host ? n : 0)), wpb, false, true};
+  return ac_sweep(h, sw, {{omega, 8 * F}, {c_host, 16 * B * n}, {pairs, 8 * K}}, {{h_host, 16 * K}, {x_host, 16 * n}, {berr_host, 8}, {flags_host, 4}}, info,
+                  [&](const AcLaunch& L, long s0, int ns, const AcIo& io) { return launch_ac_adjoint(h, L, io, n_freq, s0, ns, gmin, n_pairs); });
 }
 
 // The multi-column sweep x[b][f][k] = (A[b][f])^-1 b[b][k] with A as above: S = B n_freq systems through AcLuMultiSys (ac_lu.hip), which factors
-// each system once, exactly as AcLuSys does, and runs the solve, the refinement and the backward error per column.  Same rules as
-// cadnip_ac_solve; a system's device output is 16 K (n_pairs + n [x wanted]) bytes.  Buffers live in AcState.
-// cadnip_ac_adjoint_multi is the same call on A^T: x[b][f][k] = (A[b][f])^-T c[b][k] through AcAdjMultiSys, with the transposed tables built on first use.
+// each system once, exactly as AcLuSys does, and runs the solve, the refinement and the backward error per column; a system's solution is
+// 16 K (n_pairs + n [x wanted]) bytes.  cadnip_ac_adjoint_multi is the same call on A^T: x[b][f][k] = (A[b][f])^-T c[b][k] through AcAdjMultiSys
 static int ac_multi_call(CadnipHandle* h, bool adjoint, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* b_host, int32_t n_pairs,
                          const int32_t* pairs, int32_t wpb, double* h_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || n_rhs < 1 || !b_host || n_pairs < 0 || (n_pairs > 0 && (!pairs || !h_host)) || (n_pairs == 0 && !x_host) ||
       !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
   if (!ac_overlay_grid_ok(h, n_freq, omega)) return CADNIP_BADARG;
-  const size_t B = h->B, n = h->n, F = n_freq, S = B * F, K = n_rhs, P = n_pairs;
+  const size_t B = h->B, n = h->n, F = n_freq, K = n_rhs, P = n_pairs;
   for (size_t k = 0; k < 2 * P; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
-  const bool want_x = x_host != nullptr;
-  const AcChunks ch(h, S, 16 * K * (P + (want_x ? n : 0)), wpb);
-  if (!ch.ok()) return CADNIP_BADARG;
-  const size_t chunk = ch.chunk;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  TRY(ac_lu_prepare(h, adjoint));
-  AcState& A = h->ac;
-  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
-  TRY(ac_grow(&A.cap_multi_rhs, B * K * n, ac_buf(&A.d_multi_rhs, 2)));
-  if (P) { TRY(ac_grow(&A.cap_multi_pairs, P, ac_buf(&A.d_multi_pairs, 2))); TRY(ac_grow(&A.cap_multi_h, chunk * K * P, ac_buf(&A.d_multi_h, 2))); }
-  if (want_x) TRY(ac_grow(&A.cap_multi_x, chunk * K * n, ac_buf(&A.d_multi_x, 2)));
-  TRY(ac_grow(&A.cap_multi_cols, chunk * K, ac_buf(&A.d_multi_berr), ac_buf(&A.d_multi_flags)));
-  HIP_TRY(hipMemcpy(A.d_multi_rhs, b_host, B * K * n * 2 * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
-  if (P) HIP_TRY(hipMemcpy(A.d_multi_pairs, pairs, P * 2 * sizeof(int), hipMemcpyHostToDevice));
-  for (size_t s0 = 0; s0 < S; s0 += chunk) {
-    const size_t ns = std::min(chunk, S - s0);
-    TRY((adjoint ? launch_ac_adjoint_multi : launch_ac_multi)(h, ch.of(ns), n_freq, (long)s0, (int)ns, gmin, n_rhs, n_pairs, want_x));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (P) HIP_TRY(hipMemcpy(h_host + s0 * K * P * 2, A.d_multi_h, ns * K * P * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * K * n * 2, A.d_multi_x, ns * K * n * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(berr_host + s0 * K, A.d_multi_berr, ns * K * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags_host + s0 * K, A.d_multi_flags, ns * K * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  ac_report(h, ch, info);
-  return CADNIP_OK;
+  const AcSweep sw{B * F, 16 * K * (P + (x_host ? n : 0)), wpb, false, adjoint};
+  return ac_sweep(h, sw, {{omega, 8 * F}, {b_host, 16 * B * K * n}, {pairs, 8 * P}}, {{h_host, 16 * K * P}, {x_host, 16 * K * n}, {berr_host, 8 * K}, {flags_host, 4 * K}}, info,
+                  [&](const AcLaunch& L, long s0, int ns, const AcIo& io) {
+                    return (adjoint ? launch_ac_adjoint_multi : launch_ac_multi)(h, L, io, n_freq, s0, ns, gmin, n_rhs, n_pairs);
+                  });
 }
 
 int cadnip_ac_solve_multi(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_rhs, const double* b_host, int32_t n_pairs,
@@ -988,98 +949,42 @@ int cadnip_ac_adjoint_multi(CadnipHandle* h, int32_t n_freq, const double* omega
 
 // The sensitivity sweep: per (base instance b, frequency f) the response y = x[p] - x[n] of A x = b_ac and its derivatives with respect to n_par
 // parameters, s[k] = lambda^T (db[b][k] - (dG + j w dC) x) with A^T lambda = c and dG / dC the differences of the G / C of instances
-// plus[b][k] and minus[b][k] times scale[b][k] -- S = n_base n_freq systems through AcSensSys (ac_lu.hip), one factorisation each.  Same rules
-// as cadnip_ac_solve; a system's device output is 16 (1 + K + 2 n [x wanted]) bytes.  Buffers live in AcState.
+// plus[b][k] and minus[b][k] times scale[b][k] -- S = n_base n_freq systems through AcSensSys (ac_lu.hip), one factorisation each; a system's
+// solution is 16 (1 + K + 2 n [x wanted]) bytes
 int cadnip_ac_sens(CadnipHandle* h, int32_t n_freq, const double* omega, double gmin, int32_t n_base, const int32_t* base, int32_t n_par, const int32_t* plus,
                    const int32_t* minus, const double* scale, const double* bac_host, const double* db_host, const double* c_host, const int32_t* pair,
                    int32_t wpb, double* y_host, double* s_host, double* x_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_freq <= 0 || !omega || n_base < 1 || !base || n_par < 1 || !plus || !minus || !scale || !bac_host || !c_host || !pair || !y_host || !s_host ||
       !berr_host || !flags_host || !info || !h->analyzed) return CADNIP_BADARG;
   if (h->ac.ovl_n > 0) return CADNIP_BADARG;                    // the bilinear forms over perturbed stamps do not know the overlay
-  const size_t B = h->B, n = h->n, F = n_freq, NB = n_base, K = n_par, S = NB * F;
+  const size_t B = h->B, n = h->n, F = n_freq, NB = n_base, K = n_par;
   for (size_t b = 0; b < NB; ++b) if (base[b] < 0 || base[b] >= (int32_t)B) return CADNIP_BADARG;
   for (size_t k = 0; k < NB * K; ++k) if (plus[k] < 0 || plus[k] >= (int32_t)B || minus[k] < 0 || minus[k] >= (int32_t)B) return CADNIP_BADARG;
   if (pair[0] < -1 || pair[0] >= (int32_t)n || pair[1] < -1 || pair[1] >= (int32_t)n || (pair[0] == -1 && pair[1] == -1)) return CADNIP_BADARG;
-  const bool want_x = x_host != nullptr, db = db_host != nullptr;
-  const AcChunks ch(h, S, 16 * (1 + K + (want_x ? 2 * n : 0)), wpb, true);
-  if (!ch.ok()) return CADNIP_BADARG;
-  const size_t chunk = ch.chunk;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  TRY(ac_lu_prepare(h, true));
-  AcState& A = h->ac;
-  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
-  if (!A.d_sens_c) TRY(dev_alloc(&A.d_sens_c, n * 2));
-  TRY(ac_grow(&A.cap_sens_idx, NB + 2 * NB * K, ac_buf(&A.d_sens_idx)));
-  TRY(ac_grow(&A.cap_sens_scale, NB * K, ac_buf(&A.d_sens_scale)));
-  TRY(ac_grow(&A.cap_sens_bac, NB * n, ac_buf(&A.d_sens_bac, 2)));
-  if (db) TRY(ac_grow(&A.cap_sens_db, NB * K * n, ac_buf(&A.d_sens_db, 2)));
-  TRY(ac_grow(&A.cap_sens_sys, chunk, ac_buf(&A.d_sens_y, 2), ac_buf(&A.d_sens_berr, 2)));
-  TRY(ac_grow(&A.cap_sens_cols, chunk * K, ac_buf(&A.d_sens_s, 2), ac_buf(&A.d_sens_flags)));
-  if (want_x) TRY(ac_grow(&A.cap_sens_x, chunk, ac_buf(&A.d_sens_x, 4 * n)));
-  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_sens_idx, base, NB * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_sens_idx + NB, plus, NB * K * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_sens_idx + NB + NB * K, minus, NB * K * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_sens_scale, scale, NB * K * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_sens_bac, bac_host, NB * n * 2 * sizeof(double), hipMemcpyHostToDevice));
-  if (db) HIP_TRY(hipMemcpy(A.d_sens_db, db_host, NB * K * n * 2 * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_sens_c, c_host, n * 2 * sizeof(double), hipMemcpyHostToDevice));
-  for (size_t s0 = 0; s0 < S; s0 += chunk) {
-    const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_sens(h, ch.of(ns), n_freq, (long)s0, (int)ns, gmin, n_base, n_par, db, pair, want_x));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(y_host + s0 * 2, A.d_sens_y, ns * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(s_host + s0 * K * 2, A.d_sens_s, ns * K * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (want_x) HIP_TRY(hipMemcpy(x_host + s0 * 4 * n, A.d_sens_x, ns * 4 * n * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(berr_host + s0 * 2, A.d_sens_berr, ns * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags_host + s0 * K, A.d_sens_flags, ns * K * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  ac_report(h, ch, info);
-  return CADNIP_OK;
+  const AcSweep sw{NB * F, 16 * (1 + K + (x_host ? 2 * n : 0)), wpb, true, true};
+  return ac_sweep(h, sw,
+                  {{omega, 8 * F}, {base, 4 * NB}, {plus, 4 * NB * K}, {minus, 4 * NB * K}, {scale, 8 * NB * K}, {bac_host, 16 * NB * n}, {db_host, 16 * NB * K * n}, {c_host, 16 * n}},
+                  {{y_host, 16}, {s_host, 16 * K}, {x_host, 32 * n}, {berr_host, 16}, {flags_host, 4 * K}}, info,
+                  [&](const AcLaunch& L, long s0, int ns, const AcIo& io) { return launch_ac_sens(h, L, io, n_freq, s0, ns, gmin, n_base, n_par, pair); });
 }
 
 // The Arnoldi sweep: per (instance b, shift s) m steps of K = A^-1 C started at A^-1 b_ac[b], A = G[b] + gmin + j omega[s] C[b] -- S = B n_shift
-// systems through AcArnoldiSys (ac_lu.hip), one factorisation and up to m + 1 columns each.  Same rules as cadnip_ac_solve; a system's device
-// output is 16 ((m+1) m + m n_pairs + (m+1) n) bytes and a few words -- the basis is the kernel's own storage and counts whether the caller
-// wants it or not -- and a single system beyond AC_CHUNK_BYTES runs as a chunk of one.  Buffers live in AcState.
+// systems through AcArnoldiSys (ac_lu.hip), one factorisation and up to m + 1 columns each; a system's solution is
+// 16 ((m+1) m + m n_pairs + (m+1) n) bytes -- the basis is the kernel's own storage (`keep`) and counts whether the caller wants it or not --
+// and a single system beyond AC_CHUNK_BYTES runs as a chunk of one
 int cadnip_ac_arnoldi(CadnipHandle* h, int32_t n_shift, const double* omega, double gmin, const double* b_host, int32_t m, double breakdown_tol,
                       int32_t n_pairs, const int32_t* pairs, int32_t wpb, double* H_host, double* beta_host, int32_t* meff_host, double* l_host,
                       double* v_host, double* berr_host, int32_t* flags_host, int32_t* info) {
   if (!h || n_shift <= 0 || !omega || !b_host || m < 1 || !(breakdown_tol > 0.0 && breakdown_tol < 1.0) || n_pairs < 0 || (n_pairs > 0 && (!pairs || !l_host)) ||
       !H_host || !beta_host || !meff_host || !berr_host || !flags_host || !info || !h->analyzed || m > h->n) return CADNIP_BADARG;
   if (h->ac.ovl_n > 0) return CADNIP_BADARG;                    // A with an overlay is not a (G, C) pencil
-  const size_t B = h->B, n = h->n, F = n_shift, S = B * F, P = n_pairs, M = m;
+  const size_t B = h->B, n = h->n, F = n_shift, P = n_pairs, M = m;
   for (size_t k = 0; k < 2 * P; ++k) if (pairs[k] < -1 || pairs[k] >= (int32_t)n) return CADNIP_BADARG;
   const size_t hw = (M + 1) * M, lw = M * P, vw = (M + 1) * n;           // complex words of a system's H, l, V
-  const AcChunks ch(h, S, 16 * (hw + lw + vw), wpb, true);               // the work arrays are the sensitivity family's: four n-vectors
-  if (!ch.ok()) return CADNIP_BADARG;
-  const size_t chunk = ch.chunk;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  TRY(ac_lu_prepare(h));
-  AcState& A = h->ac;
-  TRY(ac_grow(&A.cap_freq, F, ac_buf(&A.d_omega)));
-  TRY(ac_grow(&A.cap_arn_bac, B * n, ac_buf(&A.d_arn_bac, 2)));
-  TRY(ac_grow(&A.cap_arn_H, chunk * hw, ac_buf(&A.d_arn_H, 2)));
-  TRY(ac_grow(&A.cap_arn_V, chunk * vw, ac_buf(&A.d_arn_V, 2)));
-  if (P) { TRY(ac_grow(&A.cap_arn_pairs, P, ac_buf(&A.d_arn_pairs, 2))); TRY(ac_grow(&A.cap_arn_l, chunk * lw, ac_buf(&A.d_arn_l, 2))); }
-  TRY(ac_grow(&A.cap_arn_sys, chunk, ac_buf(&A.d_arn_beta), ac_buf(&A.d_arn_berr), ac_buf(&A.d_arn_meff), ac_buf(&A.d_arn_flags)));
-  HIP_TRY(hipMemcpy(A.d_arn_bac, b_host, B * n * 2 * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(A.d_omega, omega, F * sizeof(double), hipMemcpyHostToDevice));
-  if (P) HIP_TRY(hipMemcpy(A.d_arn_pairs, pairs, P * 2 * sizeof(int), hipMemcpyHostToDevice));
-  for (size_t s0 = 0; s0 < S; s0 += chunk) {
-    const size_t ns = std::min(chunk, S - s0);
-    TRY(launch_ac_arnoldi(h, ch.of(ns), n_shift, (long)s0, (int)ns, gmin, m, breakdown_tol, n_pairs));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(H_host + s0 * hw * 2, A.d_arn_H, ns * hw * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (P) HIP_TRY(hipMemcpy(l_host + s0 * lw * 2, A.d_arn_l, ns * lw * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (v_host) HIP_TRY(hipMemcpy(v_host + s0 * vw * 2, A.d_arn_V, ns * vw * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(beta_host + s0, A.d_arn_beta, ns * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(meff_host + s0, A.d_arn_meff, ns * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(berr_host + s0, A.d_arn_berr, ns * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(flags_host + s0, A.d_arn_flags, ns * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  ac_report(h, ch, info);
-  return CADNIP_OK;
+  const AcSweep sw{B * F, 16 * (hw + lw + vw), wpb, true, false};         // the work arrays are the sensitivity family's: four n-vectors
+  return ac_sweep(h, sw, {{omega, 8 * F}, {b_host, 16 * B * n}, {pairs, 8 * P}},
+                  {{H_host, 16 * hw}, {l_host, 16 * lw}, {v_host, 16 * vw, true}, {beta_host, 8}, {meff_host, 4}, {berr_host, 8}, {flags_host, 4}}, info,
+                  [&](const AcLaunch& L, long s0, int ns, const AcIo& io) { return launch_ac_arnoldi(h, L, io, n_shift, s0, ns, gmin, m, breakdown_tol, n_pairs); });
 }
 
 int cadnip_lu_stats(CadnipHandle* h, int32_t* nnz_lu, int32_t* n_terms, int32_t* n_levels, int32_t* n_fwd, int32_t* n_bwd) {

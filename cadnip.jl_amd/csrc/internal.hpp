@@ -133,55 +133,38 @@ struct FusedState {
   void release();             // frees every device buffer; the next use builds everything again
 };
 
-// AC sweep (ac_lu.hip, cadnip_ac_solve): device buffers allocated on first use, and the pivot lists of the complex factorisation -- the rows
-// whose diagonal is final after the load (list 0) / after factor level l (list l + 1); ~row marks a constant-1 pivot (LUProgram::unit)
+// One transfer buffer of the AC sweeps' pool; cap_bytes reads 0 until an allocation stands (api.hip: ac_reserve)
+struct AcSlot { void* p = nullptr; size_t cap_bytes = 0; };
+enum { AC_MAX_IN = 8, AC_MAX_OUT = 7 };    // the most a family transfers: the sensitivity sweep's inputs, the Arnoldi sweep's outputs
+// The device buffers of the running sweep's transfers, in the order its entry point lists them (the launchers below name each family's
+// order); null: a transfer this call does not make
+struct AcIo {
+  void *in[AC_MAX_IN], *out[AC_MAX_OUT];
+  const double* din(int i) const { return (const double*)in[i]; }
+  const int* iin(int i) const { return (const int*)in[i]; }
+  double* dout(int o) const { return (double*)out[o]; }
+  int* iout(int o) const { return (int*)out[o]; }
+};
+
+// AC sweeps (ac_lu.hip; api.hip: ac_sweep): the pivot lists of the complex factorisation -- the rows whose diagonal is final after the load
+// (list 0) / after factor level l (list l + 1); ~row marks a constant-1 pivot (LUProgram::unit) -- and ONE pool of transfer buffers for all
+// six families.  Only one sweep runs at a time, between an idle stream and a drained one, so slot i is whatever the running sweep's i-th
+// input / output is: grown on demand to that transfer's bytes, never shrunk, holding whatever the last sweep left (every family's kernel
+// writes every word it downloads).  A handle's resident transfer memory is its largest sweep's, not the sum over the families it has run
 struct AcState {
   bool dirty = true;                       // the LU program changed: the pivot lists are built again
   int *d_piv_rows = nullptr, *d_piv_lev_ptr = nullptr;
   unsigned char* d_nodiag = nullptr;       // [n] 1 = a voltage node whose diagonal is not in the pattern: its gmin lives in the residuals only
-  double *d_bac = nullptr, *d_omega = nullptr, *d_x = nullptr, *d_berr = nullptr;
-  int* d_flags = nullptr;
-  size_t cap_freq = 0, cap_sys = 0;        // frequencies d_omega holds, systems the output buffers hold
-  // adjoint sweep (AcAdjSys, cadnip_ac_adjoint): the transposed-solve tables of the LU program (lu_transpose.hpp), built with the pivot
-  // lists under `dirty` but only once the adjoint path is asked for (`adj_ready`), and its own transfer buffers
+  AcSlot in[AC_MAX_IN], out[AC_MAX_OUT];   // the pool: uploaded whole once per call / one chunk of systems, downloaded per chunk
+  // the adjoint families: the transposed-solve tables of the LU program (lu_transpose.hpp), built with the pivot lists under `dirty` but
+  // only once an adjoint path is asked for (`adj_ready`)
   bool adj_ready = false;
   int *d_t_colptr = nullptr, *d_t_pos = nullptr, *d_t_row = nullptr, *d_t_diag = nullptr;
   int *d_ut_rows = nullptr, *d_ut_lev_ptr = nullptr, *d_lt_rows = nullptr, *d_lt_lev_ptr = nullptr;
   int *d_a_colptr = nullptr, *d_a_row = nullptr, *d_a_pos = nullptr;
   int n_ut_lev = 0, n_lt_lev = 0;
-  int* d_pairs = nullptr;                  // [K][2] probe pairs of the call
-  double *d_h = nullptr, *d_adj_x = nullptr, *d_adj_berr = nullptr;
-  int* d_adj_flags = nullptr;
-  size_t cap_pairs = 0, cap_adj_sys = 0, cap_adj_x = 0;   // pairs d_pairs and a system of d_h hold, systems of the outputs, systems of d_adj_x
-  // multi-column sweeps (AcLuMultiSys, cadnip_ac_solve_multi; AcAdjMultiSys, cadnip_ac_adjoint_multi -- the same shapes, one set serves both):
-  // their own transfer buffers, each grown on demand to the capacity beside it
-  double *d_multi_rhs = nullptr, *d_multi_h = nullptr, *d_multi_x = nullptr, *d_multi_berr = nullptr;   // [B][K][n], [S][K][pairs], [S][K][n] complex; [S][K]
-  int *d_multi_pairs = nullptr, *d_multi_flags = nullptr;                                              // [pairs][2]; [S][K]
-  size_t cap_multi_rhs = 0, cap_multi_h = 0, cap_multi_x = 0, cap_multi_pairs = 0, cap_multi_cols = 0; // complex words, complex words, complex words, pairs, (system, column)s
-  template <class F> void each_multi_buffer(F f) {
-    f((void**)&d_multi_rhs); f((void**)&d_multi_h); f((void**)&d_multi_x); f((void**)&d_multi_berr); f((void**)&d_multi_pairs); f((void**)&d_multi_flags);
-  }
-  // sensitivity sweep (AcSensSys, cadnip_ac_sens): its own transfer buffers, each grown on demand to the capacity beside it
-  int* d_sens_idx = nullptr;                                   // base [NB] | plus [NB][K] | minus [NB][K]
-  double *d_sens_scale = nullptr, *d_sens_bac = nullptr, *d_sens_db = nullptr, *d_sens_c = nullptr;   // [NB][K]; [NB][n], [NB][K][n], [n] complex
-  double *d_sens_y = nullptr, *d_sens_berr = nullptr, *d_sens_s = nullptr, *d_sens_x = nullptr;       // [S] complex, [S][2]; [S][K] complex; [S][2][n] complex
-  int* d_sens_flags = nullptr;                                 // [S][K]
-  size_t cap_sens_idx = 0, cap_sens_scale = 0, cap_sens_bac = 0, cap_sens_db = 0;   // ints, doubles, complex words, complex words
-  size_t cap_sens_sys = 0, cap_sens_cols = 0, cap_sens_x = 0;                       // systems (y, berr), (system, column)s (s, flags), systems of d_sens_x
-  template <class F> void each_sens_buffer(F f) {
-    f((void**)&d_sens_idx); f((void**)&d_sens_scale); f((void**)&d_sens_bac); f((void**)&d_sens_db); f((void**)&d_sens_c);
-    f((void**)&d_sens_y); f((void**)&d_sens_berr); f((void**)&d_sens_s); f((void**)&d_sens_x); f((void**)&d_sens_flags);
-  }
-  // Arnoldi sweep (AcArnoldiSys, cadnip_ac_arnoldi): its own transfer buffers, each grown on demand to the capacity beside it
-  double *d_arn_bac = nullptr, *d_arn_H = nullptr, *d_arn_beta = nullptr, *d_arn_l = nullptr, *d_arn_V = nullptr, *d_arn_berr = nullptr;   // [B][n], [S][m+1][m], -, [S][m][pairs], [S][m+1][n] complex; beta, berr [S]
-  int *d_arn_pairs = nullptr, *d_arn_meff = nullptr, *d_arn_flags = nullptr;                                                              // [pairs][2]; [S]; [S]
-  size_t cap_arn_bac = 0, cap_arn_H = 0, cap_arn_l = 0, cap_arn_V = 0, cap_arn_pairs = 0, cap_arn_sys = 0;   // complex words (four); pairs; systems (beta, berr, meff, flags)
-  template <class F> void each_arn_buffer(F f) {
-    f((void**)&d_arn_bac); f((void**)&d_arn_H); f((void**)&d_arn_beta); f((void**)&d_arn_l); f((void**)&d_arn_V); f((void**)&d_arn_berr);
-    f((void**)&d_arn_pairs); f((void**)&d_arn_meff); f((void**)&d_arn_flags);
-  }
   // HBM-resident form (k_ac_hbm; cadnip_ac_set_memory, ac_hbm_plan.hpp): the setting, the persistent waves' workspace
-  // (grown on demand like the buffers above, released with the handle) and what the last AC / adjoint call ran (cadnip_ac_plan_info)
+  // (grown on demand like the pool, released with the handle) and what the last AC / adjoint call ran (cadnip_ac_plan_info)
   int memory = CADNIP_AC_LDS, max_waves = 0;
   double* d_work = nullptr; size_t cap_work = 0;   // cap_work: bytes
   int n_cu = 0;                                    // compute units of the device (queried by the first HBM plan)
@@ -194,8 +177,7 @@ struct AcState {
   double* d_ovl_val = nullptr;
   template <class F> void each_adjoint_buffer(F f) {
     f((void**)&d_t_colptr); f((void**)&d_t_pos); f((void**)&d_t_row); f((void**)&d_t_diag); f((void**)&d_ut_rows); f((void**)&d_ut_lev_ptr);
-    f((void**)&d_lt_rows); f((void**)&d_lt_lev_ptr); f((void**)&d_a_colptr); f((void**)&d_a_row); f((void**)&d_a_pos); f((void**)&d_pairs);
-    f((void**)&d_h); f((void**)&d_adj_x); f((void**)&d_adj_berr); f((void**)&d_adj_flags);
+    f((void**)&d_lt_rows); f((void**)&d_lt_lev_ptr); f((void**)&d_a_colptr); f((void**)&d_a_row); f((void**)&d_a_pos);
   }
 };
 
@@ -325,25 +307,24 @@ struct AcLaunch {
 AcLaunch ac_launch_plan(CadnipHandle* h, long n_sys, int wpb_req, bool sens = false);
 // the pivot lists of the current LU program, on demand; adjoint: the transposed-solve tables (lu_transpose.hpp) as well
 int ac_lu_prepare(CadnipHandle* h, bool adjoint = false);
-// systems [s0, s0 + n_sys) of the B x n_freq grid (s = b * n_freq + f) into h->ac.d_x / d_berr / d_flags from index 0
-int launch_ac_lu(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin);
-// ... of A^T x = c (c in h->ac.d_bac) through AcAdjSys: h[k] = x[p_k] - x[n_k] for the n_pairs pairs of h->ac.d_pairs into h->ac.d_h, berr and
-// flags into d_adj_berr / d_adj_flags, x into d_adj_x with want_x -- all from index 0
-int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_pairs, bool want_x);
-// ... of A x_k = b_k for the n_rhs columns per instance in h->ac.d_multi_rhs through AcLuMultiSys (one factorisation per system): per (system,
-// column) the n_pairs probe differences into d_multi_h, x into d_multi_x with want_x, berr and flags into d_multi_berr / d_multi_flags
-int launch_ac_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x);
-// ... of A^T x_k = c_k for the n_rhs columns per instance in h->ac.d_multi_rhs through AcAdjMultiSys (one factorisation per system; needs
-// ac_lu_prepare(h, true)): the outputs as launch_ac_multi, in the same buffers
-int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs, bool want_x);
-// systems [s0, s0 + n_sys) of the n_base x n_freq grid of cadnip_ac_sens (s = b * n_freq + f, b an index into the base list) through AcSensSys
-// (needs ac_lu_prepare(h, true); p must come from ac_launch_plan(.., sens = true)): inputs and outputs in the d_sens_* buffers, outputs from
-// index 0; n_par columns, db: a db buffer was uploaded (else zeros), pair: the output pair
-int launch_ac_sens(CadnipHandle* h, const AcLaunch& p, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, bool db, const int* pair, bool want_x);
-// systems [s0, s0 + n_sys) of the B x n_shift grid of cadnip_ac_arnoldi (s = b * n_shift + shift) through AcArnoldiSys (p must come from
-// ac_launch_plan(.., sens = true): the same four n-vectors): inputs and outputs in the d_arn_* buffers, outputs from index 0; m steps,
-// breakdown tolerance tol, n_pairs probe pairs
-int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& p, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs);
+// The launchers of the six families: systems [s0, s0 + n_sys) of the call's grid (s = b * n_freq + f) under the plan p, inputs read from and
+// outputs written (from index 0) to the buffers of io.  `in:` / `out:` name the order of io's slots; an output the caller does not want is null.
+// in: omega, b_ac [B][n].  out: x, berr, flags
+int launch_ac_lu(CadnipHandle* h, const AcLaunch& p, const AcIo& io, int n_freq, long s0, int n_sys, double gmin);
+// A^T x = c through AcAdjSys (needs ac_lu_prepare(h, true)).  in: omega, c [B][n], pairs [n_pairs][2].  out: h[k] = x[p_k] - x[n_k], x (optional), berr, flags
+int launch_ac_adjoint(CadnipHandle* h, const AcLaunch& p, const AcIo& io, int n_freq, long s0, int n_sys, double gmin, int n_pairs);
+// A x_k = b_k for n_rhs columns per instance through AcLuMultiSys (one factorisation per system).  in: omega, rhs [B][n_rhs][n], pairs (none with
+// n_pairs == 0).  out: per (system, column) h (none with n_pairs == 0), x (optional; required with n_pairs == 0), berr, flags
+int launch_ac_multi(CadnipHandle* h, const AcLaunch& p, const AcIo& io, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs);
+// ... of A^T x_k = c_k through AcAdjMultiSys (needs ac_lu_prepare(h, true)): the slots of launch_ac_multi
+int launch_ac_adjoint_multi(CadnipHandle* h, const AcLaunch& p, const AcIo& io, int n_freq, long s0, int n_sys, double gmin, int n_rhs, int n_pairs);
+// the n_base x n_freq grid of cadnip_ac_sens (b an index into the base list) through AcSensSys (needs ac_lu_prepare(h, true); p must come from
+// ac_launch_plan(.., sens = true)); n_par columns, pair: the output pair.  in: omega, base [NB], plus [NB][n_par], minus, scale, b_ac [NB][n],
+// db [NB][n_par][n] (optional: zeros), c [n].  out: y, s, x and lambda (optional), berr [2], flags [n_par]
+int launch_ac_sens(CadnipHandle* h, const AcLaunch& p, const AcIo& io, int n_freq, long s0, int n_sys, double gmin, int n_base, int n_par, const int* pair);
+// the B x n_shift grid of cadnip_ac_arnoldi through AcArnoldiSys (p must come from ac_launch_plan(.., sens = true): the same four n-vectors); m
+// steps, breakdown tolerance tol.  in: omega, b_ac [B][n], pairs (none with n_pairs == 0).  out: H, l (none with n_pairs == 0), V, beta, meff, berr, flags
+int launch_ac_arnoldi(CadnipHandle* h, const AcLaunch& p, const AcIo& io, int n_shift, long s0, int n_sys, double gmin, int m, double tol, int n_pairs);
 // delay.hip: the transient's delayed stamps (cadnip_tran_set_delay), asynchronous on h->stream.  The driver passes its own per-instance arrays:
 // status (0 = running), t (accepted time), u0 (newest accepted vector [B][n])
 void delay_release(CadnipHandle* h);                                       // frees everything; no spec is set afterwards
