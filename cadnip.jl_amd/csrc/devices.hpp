@@ -631,13 +631,28 @@ __device__ inline D3 m1_qdep(const D3& v, double Cb, double Cbsw, double tBulkPo
   return D3(0.0);
 }
 
+// How the sp_mos1 code reads an unknown and names a residual row: through the context.  A context in memory (DevCtxT) holds node indices --
+// u[node], ground tested where a terminal may be grounded, rows looked up by the writer.  The register view of the sweep kernel's shape form
+// (M1PairView, below) holds resolved words instead; its overloads follow its definition.  `slot`: which of the pair path's residual targets (M1R_*).
+enum { M1R_LA = 0, M1R_LB, M1R_ROW, M1R_SI, M1R_Q0, M1R_P0, M1R_Q1, M1R_P1 };
+template <class Ctx> struct m1_pinned { static constexpr bool value = false; };
+template <class Ctx> __device__ __forceinline__ double m1_ul(const Ctx&, const double* u, int l) { return u[l]; }             // an unknown that is never ground
+template <class Ctx> __device__ __forceinline__ double m1_volt(const Ctx&, const double* u, int node) { return volt(u, node); }
+template <class Ctx, class Out> __device__ __forceinline__ double m1_du(const Ctx&, const Out& s, int node) { return s.du(node); }
+template <class Ctx, class Out> __device__ __forceinline__ void m1_Rn(const Ctx&, const Out& s, int, int node, double v) { s.Rn(node, v); }
+template <class Ctx> __device__ __forceinline__ int m1_vdep(const Ctx& d) { return d.ipar[d.dev]; }
+template <class Ctx> __device__ __forceinline__ int m1_qbit(const Ctx&, int vdep, int, int r) { return (vdep >> r) & 1; }   // reactive branch r (this lane's it-th) has a charge unknown
+template <class Ctx> __device__ __forceinline__ int m1_side(const Ctx&, int, int n_s, int n_d, bool D) { return D ? n_d : n_s; }   // of two nodes this lane's
+template <class Ctx> __device__ __forceinline__ int m1_nq(const Ctx& d, int, int r) { return node_of(d, 10 + r); }              // the charge unknown of reactive branch r
+template <class Ctx> __device__ __forceinline__ double par_side(const Ctx& d, int ks, int kd, bool D) { return par_of(d, D ? kd : ks); }   // a parameter of this lane's junction
+
 // $limit sites of the load section (mos1.va:919-980): limited branch voltages w = (vgs, vds, vbs, vbd), sign-adjusted
 // (The limiters keep IEEE division: (vnew - vold) / vt and o_vbs / (2 sqrt(tPhi)) qualify for m1_quot, vnew / vt does not, but the three of them
 // as fast quotients cost k_fused2<8, false, 3> a seventh spilled VGPR, and they run only in the rounds that are not quiet -- DESIGN.md section 9, round 7.)
 template <class Ctx>
 __device__ inline void m1_limit(const Ctx& d, const double* u, double type, double vt, double tPhi, double tVbi, double gamma, double Vg, double Vb,
                                 double Vdi, double Vsi, int l0, int l1, int l2, int l3, double& w_gs, double& w_ds, double& w_bs, double& w_bd) {
-  double o_vgs = type * u[l0], o_vds = type * u[l1], o_vbs = type * u[l2], o_vbd = type * u[l3];
+  double o_vgs = type * m1_ul(d, u, l0), o_vds = type * m1_ul(d, u, l1), o_vbs = type * m1_ul(d, u, l2), o_vbd = type * m1_ul(d, u, l3);
   double vbs = type * (Vb - Vsi), vgs = type * (Vg - Vsi), vds = type * (Vdi - Vsi);
   double vbd = vbs - vds, vgd = vgs - vds, vgdo = o_vgs - o_vds;
   // Quiet rounds.  The three limiters return their argument unchanged when the iterate has moved little since the last one: DEVfetlim
@@ -873,18 +888,21 @@ template <class Ctx, class Out>
 __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out& s, double* limit_w_base, int side, bool valid) {
   const double CS = CADNIP_CHARGE_SCALE;
   const bool D = side != 0;
+  // a parameter of this lane's junction: the register view holds it resolved (par_side); any other context picks the row, as it always did
+#define M1_PSIDE(ks, kd) (m1_pinned<Ctx>::value ? par_side(d, ks, kd, D) : par_of(d, D ? kd : ks))
   int nd = node_of(d, 0), ng = node_of(d, 1), ns = node_of(d, 2), nb = node_of(d, 3), ndi = node_of(d, 4), nsi = node_of(d, 5);
   int l0 = node_of(d, 6), l1 = node_of(d, 7), l2 = node_of(d, 8), l3 = node_of(d, 9);
-  double Vd = volt(u, nd), Vg = volt(u, ng), Vs = volt(u, ns), Vb = volt(u, nb), Vdi = volt(u, ndi), Vsi = volt(u, nsi);
-  // parameters are fetched where they are first needed, not up front: 36 values held across the limiting code would not
-  // fit into the registers of a two-waves-per-SIMD kernel
+  double Vd = m1_volt(d, u, nd), Vg = m1_volt(d, u, ng), Vs = m1_volt(d, u, ns), Vb = m1_volt(d, u, nb), Vdi = m1_volt(d, u, ndi), Vsi = m1_volt(d, u, nsi);
+  // A context in memory fetches its parameters where they are first needed, in three groups, not up front: the generic sweep kernels have no
+  // registers to hold them in across the limiting code (k_fused2<8, false, 3> stands at 256 VGPRs with spills).  The shape form has them
+  // and hands in the register view (M1PairView): every par_of / par_side below is then a register, loaded once per residence.
   double type = par_of(d, M1_TYPE), vt = par_of(d, M1_VT), tPhi = par_of(d, M1_TPHI), tVbi = par_of(d, M1_TVBI);
   double gamma = par_of(d, M1_GAMMA);
   // second group, needed after the limiting code: requested now so that the memory latency (the parameter blocks of the
   // resident instances exceed the L2) passes behind the limiting arithmetic
-  const double mf = par_of(d, M1_MFACTOR), gmin_p = par_of(d, M1_GMIN), isat = par_of(d, D ? M1_DSATCUR : M1_SSATCUR);
+  const double mf = par_of(d, M1_MFACTOR), gmin_p = par_of(d, M1_GMIN), isat = M1_PSIDE(M1_SSATCUR, M1_DSATCUR);
   const double lambda = par_of(d, M1_LAMBDA), Beta = par_of(d, M1_BETA);
-  const int vdep = Out::DIRECT ? d.ipar[d.dev] : 0;       // bit r: reactive branch r uses a charge unknown
+  const int vdep = Out::DIRECT ? m1_vdep(d) : 0;          // bit r: reactive branch r uses a charge unknown
   __builtin_amdgcn_sched_barrier(0);
   // (trace build: the node and u reads have returned | the first parameter group has | what is left of the load section)
   CADNIP_TRACE_USE(Vd); CADNIP_TRACE_USE(Vg); CADNIP_TRACE_USE(Vs); CADNIP_TRACE_USE(Vb); CADNIP_TRACE_USE(Vdi); CADNIP_TRACE_USE(Vsi);
@@ -894,14 +912,15 @@ __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out&
   CADNIP_TRACE_POINT(20);
   double w_gs, w_ds, w_bs, w_bd;
   m1_limit(d, u, type, vt, tPhi, tVbi, gamma, Vg, Vb, Vdi, Vsi, l0, l1, l2, l3, w_gs, w_ds, w_bs, w_bd);
-  if (limit_w_base && valid && !D) { limit_w_base[l0] = w_gs; limit_w_base[l1] = w_ds; limit_w_base[l2] = w_bs; limit_w_base[l3] = w_bd; }
+  if constexpr (!m1_pinned<Ctx>::value)     // (the register view has no node indices to write limit_w by; its kernel runs without PCNR)
+    if (limit_w_base && valid && !D) { limit_w_base[l0] = w_gs; limit_w_base[l1] = w_ds; limit_w_base[l2] = w_bs; limit_w_base[l3] = w_bd; }
   CADNIP_TRACE_POINT(21);
   {   // g_lim rows (vasim.jl:3134-3136): two limit variables per lane
     const double gl[6] = {1.0, -1.0, 1.0, 1.0, -1.0, 1.0};
     s.Gv(6 * side, gl);
     if constexpr (Out::DIRECT) {   // r_l = u_l - (V_p - V_n) for (g,s_int), (d_int,s_int) | (b,s_int), (b,d_int)
-      s.Rn(D ? l2 : l0, u[D ? l2 : l0] - ((D ? Vb : Vg) - Vsi));
-      s.Rn(D ? l3 : l1, u[D ? l3 : l1] - (D ? Vb - Vdi : Vdi - Vsi));
+      m1_Rn(d, s, M1R_LA, m1_side(d, M1R_LA, l0, l2, D), m1_ul(d, u, m1_side(d, M1R_LA, l0, l2, D)) - ((D ? Vb : Vg) - Vsi));
+      m1_Rn(d, s, M1R_LB, m1_side(d, M1R_LB, l1, l3, D), m1_ul(d, u, m1_side(d, M1R_LB, l1, l3, D)) - (D ? Vb - Vdi : Vdi - Vsi));
     }
   }
   CADNIP_TRACE_POINT(22);
@@ -910,8 +929,8 @@ __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out&
   const D3 vj = m1_sel(D, dvbd, c);
   const double gmin_m = fast_div(gmin_p, mf);                      // mf > 0 (the multiplicity); gmin >= 0, a zero's sign is IEEE's for mf > 0.  isat: this lane's junction, source side or drain side
   // third group (depletion charge of this lane's junction), in flight during the junction and channel arithmetic
-  const double q_cb = par_of(d, D ? M1_CBD : M1_CBS), q_cbsw = par_of(d, D ? M1_CBDSW : M1_CBSSW), q_pot = par_of(d, M1_TBULKPOT), q_dep = par_of(d, M1_TDEPCAP);
-  const double q_mj = par_of(d, M1_MJ), q_mjsw = par_of(d, M1_MJSW), q_f2 = par_of(d, D ? M1_F2D : M1_F2S), q_f3 = par_of(d, D ? M1_F3D : M1_F3S), q_f4 = par_of(d, D ? M1_F4D : M1_F4S);
+  const double q_cb = M1_PSIDE(M1_CBS, M1_CBD), q_cbsw = M1_PSIDE(M1_CBSSW, M1_CBDSW), q_pot = par_of(d, M1_TBULKPOT), q_dep = par_of(d, M1_TDEPCAP);
+  const double q_mj = par_of(d, M1_MJ), q_mjsw = par_of(d, M1_MJSW), q_f2 = M1_PSIDE(M1_F2S, M1_F2D), q_f3 = M1_PSIDE(M1_F3S, M1_F3D), q_f4 = M1_PSIDE(M1_F4S, M1_F4D);
   __builtin_amdgcn_sched_barrier(0);
   const D3 cj = m1_junction(vj, vt, gmin_m, isat), co = m1_swap_pair(cj);
   const D3 cbs = m1_sel(D, co, cj), cbd = m1_sel(D, cj, co);
@@ -943,7 +962,7 @@ __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out&
     s.B(br, -Ieq);
     if constexpr (Out::DIRECT) {   // the row's residual is the branch current itself plus the lim_rhs anchoring terms
       const D3 I = m1_sel(D, I4, I3);
-      s.Rn(D ? ndi : nb, mf * I.v + (mf * type * I.p[0]) * dW_gs + (mf * type * I.p[1]) * dW_ds + (mf * type * I.p[2]) * dW_bs);
+      m1_Rn(d, s, M1R_ROW, D ? ndi : nb, mf * I.v + (mf * type * I.p[0]) * dW_gs + (mf * type * I.p[1]) * dW_ds + (mf * type * I.p[2]) * dW_bs);
     }
   }
   {   // row I(s_int): both lanes form it, each emits two of its four entries; the source-side lane owns the b entry
@@ -955,7 +974,7 @@ __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out&
     s.Gk(k2, v2);
     if (Out::DIRECT || !D) s.B(5, -Ieq);   // the source-side lane owns the b entry (a store-type writer must see one writer per slot)
     if constexpr (Out::DIRECT)
-      s.Rn(nsi, D ? 0.0 : mf * I5.v + (mf * type * I5.p[0]) * dW_gs + (mf * type * I5.p[1]) * dW_ds + (mf * type * I5.p[2]) * dW_bs);
+      m1_Rn(d, s, M1R_SI, nsi, D ? 0.0 : mf * I5.v + (mf * type * I5.p[0]) * dW_gs + (mf * type * I5.p[1]) * dW_ds + (mf * type * I5.p[2]) * dW_bs);
   }
   CADNIP_TRACE_POINT(26);
   // depletion charge of this lane's junction (after the current rows: fewer values live at once), swapped like the current
@@ -980,7 +999,7 @@ __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out&
     // Only one of the two forms of a branch lands in the matrix: the slots of the other one lead to trash words (no
     // charge unknown / no linear entries in the pattern).  The direct-residual variants know which (vdep) and leave the
     // dead half out; q_g = 0 here, so branch 0 stamps nothing at all.
-    const bool cs_form = !Out::DIRECT || ((vdep >> r) & 1), lin_form = !Out::DIRECT || (!((vdep >> r) & 1) && r != 0);
+    const bool cs_form = !Out::DIRECT || m1_qbit(d, vdep, it, r), lin_form = !Out::DIRECT || (!m1_qbit(d, vdep, it, r) && r != 0);
     if (cs_form) s.Gv(48 + 7 * r, gq);
     double bc = mf * q.v;
 #pragma unroll
@@ -992,16 +1011,78 @@ __device__ inline void stamp_mos1_pair(const Ctx& d, const double* u, const Out&
       // branch node of reactive branch r: g, b, d_int, s_int.  Charge-state form (vasim.jl:3433-3472) when the branch was
       // flagged voltage dependent: r_q = u_q - CS (q + lim terms), r_p += du_q / CS; else the linear form r_p += sum dq_k du_k.
       const int np = r == 0 ? ng : r == 1 ? nb : r == 2 ? ndi : nsi;
-      if ((vdep >> r) & 1) {
-        const int nq = node_of(d, 10 + r);
-        s.Rn(nq, u[nq] - CS * (mf * q.v + fa * dW_gs + fb * dW_ds + fc * dW_bs));
-        s.Rn(np, s.du(nq) * (1.0 / CS));
+      if (m1_qbit(d, vdep, it, r)) {
+        const int nq = m1_nq(d, it, r);
+        m1_Rn(d, s, M1R_Q0 + 2 * it, nq, m1_ul(d, u, nq) - CS * (mf * q.v + fa * dW_gs + fb * dW_ds + fc * dW_bs));
+        m1_Rn(d, s, M1R_P0 + 2 * it, np, m1_du(d, s, nq) * (1.0 / CS));
       } else if (r != 0) {
-        s.Rn(np, dq[1] * s.du(ng) + dq[3] * s.du(nb) + dq[4] * s.du(ndi) + dq[5] * s.du(nsi));
+        m1_Rn(d, s, M1R_P0 + 2 * it, np, dq[1] * m1_du(d, s, ng) + dq[3] * m1_du(d, s, nb) + dq[4] * m1_du(d, s, ndi) + dq[5] * m1_du(d, s, nsi));
       }
     }
   }
+#undef M1_PSIDE
   CADNIP_TRACE_POINT(27);
+}
+
+// ---- register view of ONE lane of the pair path (sweep kernel, shape form: fused2_kernel.hpp, k_fused2<.., 4>) --------------------------
+// With at most 32 plain devices a lane serves the same device and the same junction side for a whole launch, so everything stamp_mos1_pair
+// reads that is not an iterate is held in registers:
+//   * per launch (the circuit's): where its operands lie -- six terminals, four limit unknowns, the charge-unknown pair of its side -- as
+//     16-bit byte offsets from the instance's W, two to a register (lds_layout.hpp: lds_m1pin_operand; ground is the constant word 0.0, so
+//     a terminal voltage is one unconditional read); the W words of its eight residual targets, M1R_* order (lds_m1pin_row; ground is
+//     the lane's trash word).  No vdep word: a branch has a charge unknown exactly when its pinned offset is not ground (m1_qbit);
+//   * per residence (the instance's): the 19 parameters the pair path uses on a plain card (m1_pair_load_params), the side-dependent ones
+//     resolved to this lane's junction in the source-side slot, as in M1RegView.
+// TVTO, SVCRIT and DVCRIT -- the non-quiet limiter's and initjct's -- stay memory reads, through `mem`.  A "node" of this view is the operand's
+// byte offset.  Indices are literals at every use, so the arrays are registers.
+template <class ParMem>
+struct M1PairView {
+  double p[M1_GMIN + 1];
+  unsigned opd[6];             // nd | ng, ns | nb, ndi | nsi, l0 | l1, l2 | l3, this side's charge unknowns (it 0 | it 1)
+  unsigned row[4];             // M1R_LA | M1R_LB, M1R_ROW | M1R_SI, M1R_Q0 | M1R_P0, M1R_Q1 | M1R_P1
+  int initjct;
+  const double* W;             // the instance's work array: operands are read at W + offset
+  unsigned gnd, beta;          // the offset that stands for ground; bytes from a word of u to the same word of beta
+  ParMem mem;                  // k -> parameter k of this lane's device, from memory
+};
+template <class M> struct m1_pinned<M1PairView<M>> { static constexpr bool value = true; };
+template <class M> __device__ __forceinline__ int m1_half(const M1PairView<M>&, const unsigned (&a)[6], int k) { return (int)((a[k >> 1] >> (16 * (k & 1))) & 0xFFFFu); }
+template <class M> __device__ __forceinline__ int node_of(const M1PairView<M>& d, int k) { return m1_half(d, d.opd, k); }      // k = 0 .. 9
+template <class M> __device__ __forceinline__ double par_of(const M1PairView<M>& d, int k) {
+  return k == M1_TVTO || k == M1_SVCRIT || k == M1_DVCRIT ? d.mem(k) : d.p[k];
+}
+template <class M> __device__ __forceinline__ double par_side(const M1PairView<M>& d, int ks, int, bool) { return d.p[ks]; }
+template <class M> __device__ __forceinline__ int m1_vdep(const M1PairView<M>&) { return 0; }
+// (a branch without a charge unknown has ground there, structure.py: the pinned offset says which form the branch takes, no vdep word is held)
+template <class M> __device__ __forceinline__ int m1_qbit(const M1PairView<M>& d, int, int it, int) { return (unsigned)m1_half(d, d.opd, 10 + it) != d.gnd; }
+template <class M> __device__ __forceinline__ int m1_side(const M1PairView<M>& d, int slot, int, int, bool D) { return D ? m1_half(d, d.opd, 8 + (slot - M1R_LA)) : m1_half(d, d.opd, 6 + (slot - M1R_LA)); }
+template <class M> __device__ __forceinline__ int m1_nq(const M1PairView<M>& d, int it, int) { return m1_half(d, d.opd, 10 + it); }
+template <class M> __device__ __forceinline__ double m1_ul(const M1PairView<M>& d, const double*, int off) { return *(const double*)((const char*)d.W + off); }
+template <class M> __device__ __forceinline__ double m1_volt(const M1PairView<M>& d, const double* u, int off) { return m1_ul(d, u, off); }
+template <class M, class Out> __device__ __forceinline__ double m1_du(const M1PairView<M>& d, const Out& s, int off) {
+  const double x = s.a0 * m1_ul(d, nullptr, off) + m1_ul(d, nullptr, off + (int)d.beta);    // (a grounded terminal reads two words of u, in bounds, for nothing)
+  return (unsigned)off == d.gnd ? 0.0 : x;
+}
+template <class M, class Out> __device__ __forceinline__ void m1_Rn(const M1PairView<M>& d, const Out& s, int slot, int, double v) {
+  s.Rw((d.row[slot >> 1] >> (16 * (slot & 1))) & 0xFFFFu, v);
+}
+// the slots of p that are held: 13 parameters of the device, 6 of a junction (source-side slot | the drain side's row)
+#define M1_PAIR_BOTH {M1_TYPE, M1_VT, M1_TPHI, M1_TVBI, M1_GAMMA, M1_MFACTOR, M1_GMIN, M1_LAMBDA, M1_BETA, M1_TBULKPOT, M1_TDEPCAP, M1_MJ, M1_MJSW}
+#define M1_PAIR_SIDED {{M1_SSATCUR, M1_DSATCUR}, {M1_CBS, M1_CBD}, {M1_CBSSW, M1_CBDSW}, {M1_F2S, M1_F2D}, {M1_F3S, M1_F3D}, {M1_F4S, M1_F4D}}
+// (one sweep instance: its parameter block `par` [34][count], device `dev`, this lane's junction side)
+template <class M> __device__ __forceinline__ void m1_pair_load_params(M1PairView<M>& v, const double* par, int count, int dev, bool D) {
+  constexpr int both[13] = M1_PAIR_BOTH, sided[6][2] = M1_PAIR_SIDED;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) v.p[both[i]] = par[both[i] * count + dev];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) v.p[sided[i][0]] = par[(D ? sided[i][1] : sided[i][0]) * count + dev];
+}
+template <class M, class F> __device__ __forceinline__ void m1_pair_each_param(M1PairView<M>& v, F&& fn) {
+  constexpr int both[13] = M1_PAIR_BOTH, sided[6][2] = M1_PAIR_SIDED;
+#pragma unroll
+  for (int i = 0; i < 13; ++i) fn(v.p[both[i]]);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) fn(v.p[sided[i][0]]);
 }
 
 // ---- sp_mos1 for a TEAM of waves (fused_team_kernel.hpp: several waves per sweep instance) --------------------------
@@ -1027,7 +1108,6 @@ struct M1RegView {
 __device__ __forceinline__ int node_of(const M1RegView& d, int k) { return d.nd[k]; }
 __device__ __forceinline__ double par_of(const M1RegView& d, int k) { return d.p[k]; }
 __device__ __forceinline__ double par_side(const M1RegView& d, int ks, int, bool) { return d.p[ks]; }
-template <class Ctx> __device__ __forceinline__ double par_side(const Ctx& d, int ks, int kd, bool D) { return par_of(d, D ? kd : ks); }
 __device__ __forceinline__ int node_side(const M1RegView& d, int ks, int kd, bool D) { return D ? d.nd[kd] : d.nd[ks]; }
 template <class Ctx> __device__ __forceinline__ int node_side(const Ctx& d, int ks, int kd, bool D) { return node_of(d, D ? kd : ks); }
 // (one sweep instance: its parameter block `par` [M1_NPAR][count], device `dev`, this lane's junction side)

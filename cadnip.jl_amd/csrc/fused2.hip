@@ -330,7 +330,9 @@ F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode, const TranArgs
                                 topt->use_pcnr, !env_is_zero("CADNIP_F2_FIXED"));
   // ... and of the fixed form its shape form (k_fused2<wpb, false, 4>) when the circuit's block list is a CMOS cell's: voltage sources, one pass of
   // plain sp_mos1, capacitors -- f2_shape_ok is the list.  CADNIP_F2_SHAPE=0 (diagnostic, tests: bit-identical results either way) keeps variant 3.
-  p.shape = f2_shape_ok(p.fixed, S.n_blk, S.src_type, S.src_count, S.rc_type, S.rc_count, S.dev_type, S.dev_plain, S.dev_count, !env_is_zero("CADNIP_F2_SHAPE"));
+  // (its sp_mos1 lanes address u by 16-bit byte offsets from W: lds_m1pin_ok)
+  p.shape = f2_shape_ok(p.fixed, S.n_blk, S.src_type, S.src_count, S.rc_type, S.rc_count, S.dev_type, S.dev_plain, S.dev_count, !env_is_zero("CADNIP_F2_SHAPE")) &&
+            lds_m1pin_ok(S.lu_words, h->n);
   p.wpb = wpb; p.shmem = shmem; p.grid = std::min((h->B + wpb - 1) / wpb, S.n_cu * wg_per_cu); p.rc = CADNIP_OK;
   return p;
 }

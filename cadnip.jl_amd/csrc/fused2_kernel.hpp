@@ -122,6 +122,11 @@ struct AccumOutT {
     if (!DIRECT) return;
     atomicAdd(&W[tg(node < 0 ? trash : (unsigned)rowof[node])], v);
   }
+  // ... to a row resolved beforehand (the shape form's pinned sp_mos1 words: ground is already the lane's trash word)
+  __device__ __forceinline__ void Rw(unsigned word, double v) const {
+    if (!DIRECT) return;
+    atomicAdd(&W[tg(word)], v);
+  }
   __device__ __forceinline__ void G(int k, double v) const {
     if (!JAC) return;
     if (__builtin_constant_p(v) && v == 0.0) return;     // structurally zero stamps cost nothing
@@ -184,6 +189,17 @@ struct AccumOutT {
 };
 
 typedef DevCtxT<short> LdsCtx;
+
+// shape form: the memory side of the sp_mos1 register view (devices.hpp: M1PairView) -- parameter k of device `dev` of block `bi`, instance `inst`.
+// The block is read where the parameter is wanted (the limiting code of a round that is not quiet), not held across the rounds.
+struct F2M1ParMem {
+  int bi, inst, dev;
+  __device__ __forceinline__ double operator()(int k) const {
+    const F2ArgsK ka = kargs();
+    const F2Block B = load_block(ka->blk, bi);
+    return (B.par + (size_t)inst * B.n_par * B.count)[k * B.count + dev];
+  }
+};
 
 // LEAN: the circuit holds linear elements, independent sources and lane-paired sp_mos1 only (those are stamped by
 // stamp_mos1_pair in the kernel body).  The models left out are the register-hungry ones: with them compiled in, the
@@ -423,6 +439,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
   // (shape form, SHAPE: both blocks exist, the first holds capacitors, at most 64 -- one device per lane --, the second voltage sources)
   unsigned rc_gp[RCQ][2] = {}, rc_row[RCQ] = {}, rc_nd[RCQ] = {}, src_gp[2] = {0, 0}, src_row[2] = {0, 0}, src_nd[2] = {0, 0};
   int rc_count = 0, rc_type = 0, src_count = 0, src_type = 0;
+  M1PairView<F2M1ParMem> m1v;               // shape form only: this lane's sp_mos1 device and junction side
   if constexpr (DIRECT) {
     const unsigned tr = (unsigned)(f.nnz_lu + n + lane0);
     auto row_of = [&](int node) -> unsigned { return node < 0 ? tr : (unsigned)rowof[node]; };
@@ -463,6 +480,28 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
       src_gp[0] = p[0] | p[1] << 16; src_gp[1] = p[2] | p[3] << 16;
       src_row[0] = row_of(np) | row_of(nn) << 16; src_row[1] = row_of(ni);
       src_nd[0] = ((unsigned)np & 0xFFFFu) | ((unsigned)nn & 0xFFFFu) << 16; src_nd[1] = (unsigned)ni & 0xFFFFu;
+    }
+    // (shape form: the third block is one lane-pair pass of plain sp_mos1 -- lane 2j + s serves junction side s of device j for the whole launch, so
+    // its operand offsets and residual words are pinned too: devices.hpp, M1PairView; a lane without a device takes the last device's, as the
+    // round does, and its writer's sink keeps its stamps out.  vdep is read here only: a branch without a charge unknown pins ground)
+    if constexpr (SHAPE) {
+      const F2Block B = load_block(f.blk, 3 - f.rc_blk - f.src_blk);
+      const short* nd = nodes + B.nodes_off;
+      const int dv = lane0 >> 1, dev = dv < B.count ? dv : B.count - 1, sd = lane0 & 1;
+      const int vdep = B.ipar[dev];
+      auto node = [&](int k) -> int { return nd[k * B.count + dev]; };
+      auto qnode = [&](int r) -> int { return ((vdep >> r) & 1) ? node(10 + r) : -1; };   // the charge unknown of reactive branch r, where it has one
+      auto opd2 = [&](int na, int nb) -> unsigned { return lds_m1pin_operand(na, f.nnz_lu, n) | lds_m1pin_operand(nb, f.nnz_lu, n) << 16; };
+      auto row2 = [&](int na, int nb) -> unsigned { return lds_m1pin_row(rowof, na, tr) | lds_m1pin_row(rowof, nb, tr) << 16; };
+#pragma unroll
+      for (int j = 0; j < 5; ++j) m1v.opd[j] = opd2(node(2 * j), node(2 * j + 1));
+      m1v.opd[5] = opd2(qnode(sd), qnode(2 + sd));
+      m1v.row[0] = sd ? row2(node(8), node(9)) : row2(node(6), node(7));           // M1R_LA | M1R_LB
+      m1v.row[1] = row2(sd ? node(4) : node(3), node(5));                          // M1R_ROW | M1R_SI
+      m1v.row[2] = row2(qnode(sd), sd ? node(3) : node(1));                        // M1R_Q0 | M1R_P0: branch g | b
+      m1v.row[3] = row2(qnode(2 + sd), sd ? node(5) : node(4));                    // M1R_Q1 | M1R_P1: branch d_int | s_int
+      m1v.initjct = 0;
+      m1v.gnd = lds_m1pin_operand(-1, f.nnz_lu, n); m1v.beta = 8u * (unsigned)n;
     }
   }
 #ifdef CADNIP_TRACE
@@ -511,6 +550,13 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
     const double* par = B.par + (size_t)inst * B.n_par * B.count;
 #pragma unroll
     for (int q = 0; q < RCQ; ++q) { const int dev = lane0 + 64 * q; rc_val[q] = par[dev < B.count ? dev : 0]; }
+  }
+  // (shape form) ... and the sp_mos1 parameters of this lane's device and junction side: the instance's, so loaded at every pick-up -- a second
+  // instance from the queue, an instance resumed after a launch seam -- and held in registers while it is resident
+  if constexpr (SHAPE) {
+    const F2Block B = load_block(f.blk, 3 - f.rc_blk - f.src_blk);
+    const int dv = lane0 >> 1;
+    m1_pair_load_params(m1v, B.par + (size_t)inst * B.n_par * B.count, B.count, dv < B.count ? dv : B.count - 1, (lane0 & 1) != 0);
   }
   // source segment cache of this residence (src_cache.hpp; LDS behind beta): a DC source's entry answers every time point, every other
   // source starts with an entry that cannot hit and caches the PWL segment its first evaluation finds
@@ -640,18 +686,27 @@ __global__ void __launch_bounds__(64 * WPB) k_fused2(F2Args f) {
     if constexpr (SHAPE) {
       // shape form: what the loop below does for the one block that is left -- plain sp_mos1, at most 32 devices: one lane-pair pass
       const int bi = 3 - f.rc_blk - f.src_blk;            // (three blocks: the one that is neither pinned)
+      // ... on the lane's register view (m1v: operand offsets, residual words and parameters pinned above).  What is left to read: u, and in a
+      // refactoring round the matrix targets from the LDS tables
       const F2Block B = load_block(f.blk, bi);
-      const double* par = B.par + (size_t)inst * B.n_par * B.count;
       const int side = lane & 1;
       const int dv = lane >> 1;
       const bool valid = dv < B.count;
-      LdsCtx d{nodes + B.nodes_off, B.ipar, par, f.wave, B.count, valid ? dv : B.count - 1, tcur, dmode, dinit};
+      const int dev = valid ? dv : B.count - 1;
+      // (made opaque in place every round: what the compiler derives from a pinned word or parameter -- an unpacked half, an address, 1 - mj --
+      // then lives in this round, as it does today, not in registers of its own across the whole residence)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) asm volatile("" : "+v"(m1v.opd[j]));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(m1v.row[j]));
+      m1_pair_each_param(m1v, [](double& x) { asm volatile("" : "+v"(x)); });
+      m1v.W = W; m1v.mem = F2M1ParMem{bi, inst, dev};
       if (!refresh) {                      // round on kept factors: residuals only
-        AccumOutT<true, DIRECT, false> s{W, betas, a0, gpos + B.g_base, cdesc + B.c_base, brow + B.b_base, B.count, d.dev, valid ? 0u : trash_w, us, rowof, trash_w};
-        stamp_mos1_pair(d, us, s, lw, side, valid);
+        AccumOutT<true, DIRECT, false> s{W, betas, a0, gpos + B.g_base, cdesc + B.c_base, brow + B.b_base, B.count, dev, valid ? 0u : trash_w, us, rowof, trash_w};
+        stamp_mos1_pair(m1v, us, s, lw, side, valid);
       } else {
-        AccumOutT<true, DIRECT> s{W, betas, a0, gpos + B.g_base, cdesc + B.c_base, brow + B.b_base, B.count, d.dev, valid ? 0u : trash_w, us, rowof, trash_w};
-        stamp_mos1_pair(d, us, s, lw, side, valid);
+        AccumOutT<true, DIRECT> s{W, betas, a0, gpos + B.g_base, cdesc + B.c_base, brow + B.b_base, B.count, dev, valid ? 0u : trash_w, us, rowof, trash_w};
+        stamp_mos1_pair(m1v, us, s, lw, side, valid);
       }
       CADNIP_TRACE_POINT(8);
     }

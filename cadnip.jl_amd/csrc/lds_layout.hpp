@@ -67,6 +67,18 @@ LDS_HD bool f2_shape_ok(bool fixed, int n_blk, int src_type, int src_count, int 
   return fixed && n_blk == 3 && src_type == CADNIP_DEV_VSOURCE && src_count <= 64 && rc_type == CADNIP_DEV_CAPACITOR && rc_count <= 64 &&
          dev_type == CADNIP_DEV_MOS1 && dev_plain != 0 && dev_count <= 32 && enabled;
 }
+// ---- ... and the words the shape form PINS for its sp_mos1 lanes (fused2_kernel.hpp; devices.hpp: M1PairView).  A lane serves one device and one
+// junction side for a whole launch, so what the circuit alone decides is resolved once, as 16-bit halves like the pinned capacitor / source words:
+//   * an operand -- a terminal voltage, a limit or charge unknown -- as the BYTE offset of its word of u from the instance's W (u lies behind
+//     W | consts, lds_sweep); ground (node < 0) is the constant word 0.0, so that reading a voltage is one unconditional read of the same 0.0;
+//   * a residual target as the WORD of W that `rowof` names for the unknown; ground is the lane's trash word.
+// Byte offsets of u need W | consts | u below 8192 words: lds_m1pin_ok (one more condition of the shape form; fused2.hip: fused2_plan).
+LDS_HD bool lds_m1pin_ok(int lu_words, int n) { return lds_work_words(lu_words, n) + LDS_CONSTS + n <= 8192; }
+LDS_HD unsigned lds_m1pin_operand(int node, int lu_words, int n) {
+  const int nW = lds_work_words(lu_words, n);
+  return (unsigned)(node < 0 ? nW : nW + LDS_CONSTS + node) << 3;
+}
+template <class T> LDS_HD unsigned lds_m1pin_row(const T* rowof, int node, unsigned trash_word) { return node < 0 ? trash_word : (unsigned)rowof[node]; }
 // 64-bit words of the descriptor area: desc_len as uploaded (two per lane and step), plus one flag byte per lane and step when pre-decoded
 LDS_HD int lds_sweep_desc_words(int desc_len, bool predec) { return desc_len + (predec ? desc_len / 16 : 0); }
 
