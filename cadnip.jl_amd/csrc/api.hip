@@ -1098,9 +1098,20 @@ int upload_homotopy(CadnipHandle* h, const double* gshunt, const double* srcfact
   if (srcfact) sf.assign(srcfact, srcfact + B);
   bool any = false;
   for (size_t i = 0; i < B; ++i) if (g[i] != 0.0 || sf[i] < 1.0) any = true;
-  HIP_TRY(hipMemcpy(h->d_gshunt, g.data(), B * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->d_srcfact, sf.data(), B * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors go out of scope
+  // A sweep step comes here four times (two cadnip_set_spec, the DC run's first Newton run, the DC run's exit) with the values the
+  // device has already: an array goes up only when its bytes differ from the last upload
+  bool sent = false;
+  auto put = [&](double* dev, std::vector<double>& held, const std::vector<double>& v) -> int {
+    if (held.size() == B && memcmp(held.data(), v.data(), B * sizeof(double)) == 0) return CADNIP_OK;
+    held.clear();
+    HIP_TRY(hipMemcpy(dev, v.data(), B * sizeof(double), hipMemcpyHostToDevice));
+    held = v;
+    sent = true;
+    return CADNIP_OK;
+  };
+  TRY_RC(put(h->d_gshunt, h->held_gshunt, g));
+  TRY_RC(put(h->d_srcfact, h->held_srcfact, sf));
+  if (sent) HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors go out of scope
   h->homotopy = any;
   return CADNIP_OK;
 }

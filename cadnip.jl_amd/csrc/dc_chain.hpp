@@ -13,6 +13,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <limits>
+#include <memory>
 #include <vector>
 
 namespace cadnip {
@@ -21,7 +23,8 @@ namespace cadnip {
 struct DCLogEntry { int inst, stage; double value; int ok; long long iters; };
 
 struct DCChainOpts {
-  int use_pcnr, cold_start, fused, use_stepping;
+  int use_pcnr, cold_start, fused, use_stepping;   // cold_start 2 (CADNIP_DC_COLD_ZERO) without a mask: cold from the all-zero state, `u` is output only
+                                                   // (nothing of it is read); with a mask it is 1 and u is read -- masked rows come back untouched
   bool has_limits;             // the circuit has limit variables (stage 1 exists only then)
   double gshunt, srcFact;      // the spec's values: what every instance outside a ladder is stamped with, and the gshunt ladder's target
   const int* participate;      // [B] or null = everyone; 0 = the instance sits the call out (no run, u untouched, converged 0)
@@ -34,7 +37,8 @@ struct DCChainOpts {
 struct DCRun {
   int stage, use_pcnr, cold_start, fused;
   const int* part;                    // [B]
-  const double* u;                    // [B][n] start states (the caller's array on the first run)
+  const double* u;                    // [B][n] start states (the caller's array on the first run); null = all zero (the first run of a
+                                      // zero start, cold_start 2): the runner makes its own zeros, nothing is handed over
   const double *gshunt, *srcFact;     // [B]
   int* status;                        // [B] 1 = converged
   long long* iters;                   // [B] Newton solves
@@ -118,7 +122,21 @@ int dc_chain(const DCChainOpts& o, int B_, int n_, double* u, int* converged, Ru
   res = DCChainResult();
   // per-instance start state of the next run / states after the last run.  `start` and `U` are built only when the first run leaves
   // someone unsolved: the usual case -- everybody converges in stage 0 -- hands the caller's array to the runner and gets it back filled
-  std::vector<double> start, U, R(B * n);
+  std::vector<double> start, U;
+  // R, the end states of a run that does not go straight to the caller, is allocated and NOT initialised: in the usual case no run's
+  // dest() is R, and zero-filling B * n doubles on fresh pages for nothing was a measurable part of the call.  No uninitialised word
+  // is ever read: R is read in two places only, take_all and the ladders' digest loop in `stepping`, both after run() has returned 0
+  // and both for rows with part[i] != 0 alone -- the very rows the runner of that run has just filled (DCRun: the runner writes the end
+  // states of the instances in `part` to dest(), which is R whenever res.direct is false; after a direct run R is not looked at).
+  // CADNIP_DC_CHAIN_POISON (tests) fills R with NaN instead, so that a read of a row no runner wrote would show in the results
+  const std::unique_ptr<double[]> R_store(new double[B * n]);
+  double* const R = R_store.get();
+#ifdef CADNIP_DC_CHAIN_POISON
+  std::fill(R, R + B * n, std::numeric_limits<double>::quiet_NaN());
+#endif
+  // a zero start: nothing of `u` is read, the first run starts from the runner's own zeros (DCRun::u null)
+  const bool zero_start = o.cold_start == 2 && !o.participate;
+  const int cold_start = o.cold_start == 2 && !zero_start ? 1 : o.cold_start;
   std::vector<int> fin(B, 0), status(B), part(B, 1);
   std::vector<long long> iters(B);
   std::vector<double> gsh(B, o.gshunt), sfc(B, o.srcFact);
@@ -126,9 +144,10 @@ int dc_chain(const DCChainOpts& o, int B_, int n_, double* u, int* converged, Ru
   for (size_t i = 0; i < B; ++i) if (masked(i)) { part[i] = 0; fin[i] = 1; }   // (fin: no stage picks them up)
   auto n_open = [&]() { int k = 0; for (size_t i = 0; i < B; ++i) k += !fin[i]; return k; };
   auto row = [&](std::vector<double>& v, size_t i) { return v.begin() + i * n; };
+  auto Rrow = [&](size_t i) { return R + i * n; };
   // one Newton run of the instances in `part`; rung: the term that is stepped ([B], null: none)
   auto run = [&](int stage, int use_pcnr, int cold_start, int fused, const double* from, const double* rung, double* R_direct) -> int {
-    const DCRun r{stage, use_pcnr, cold_start, fused, part.data(), from, gsh.data(), sfc.data(), status.data(), iters.data(), R.data(), R_direct, B_};
+    const DCRun r{stage, use_pcnr, cold_start, fused, part.data(), from, gsh.data(), sfc.data(), status.data(), iters.data(), R, R_direct, B_};
     if (int rc = runner(r)) return rc;
     res.direct = R_direct && r.dest() == R_direct;
     for (size_t i = 0; i < B; ++i)
@@ -136,7 +155,7 @@ int dc_chain(const DCChainOpts& o, int B_, int n_, double* u, int* converged, Ru
     return 0;
   };
   // the instances of the run leave it with its end state, solved or not
-  auto take_all = [&]() { for (size_t i = 0; i < B; ++i) if (part[i]) { std::copy(row(R, i), row(R, i + 1), row(U, i)); if (status[i] == 1) fin[i] = 1; } };
+  auto take_all = [&]() { for (size_t i = 0; i < B; ++i) if (part[i]) { std::copy(Rrow(i), Rrow(i + 1), row(U, i)); if (status[i] == 1) fin[i] = 1; } };
   // stages 2 and 3: one ladder per open instance, all ladders advanced by one run per round
   auto stepping = [&](int stage, auto rule, std::vector<double>& term, double spec_value) -> int {
     std::vector<Ladder<decltype(rule)>> L(B);
@@ -153,7 +172,7 @@ int dc_chain(const DCChainOpts& o, int B_, int n_, double* u, int* converged, Ru
       for (size_t i = 0; i < B; ++i) {
         if (!part[i]) continue;
         const bool ok = status[i] == 1;
-        if (ok) L[i].u.assign(row(R, i), row(R, i + 1));
+        if (ok) L[i].u.assign(Rrow(i), Rrow(i + 1));
         const Next next = rule.digest(L[i].s, ok);
         if (next == AGAIN) continue;
         L[i].over = true;
@@ -164,12 +183,13 @@ int dc_chain(const DCChainOpts& o, int B_, int n_, double* u, int* converged, Ru
   };
   // ---- stage 0: PCNR (or plain Newton) from the caller's start point
   if (n_open())
-    if (int rc = run(0, o.use_pcnr, o.cold_start, o.fused, u, nullptr, o.participate ? nullptr : u)) return rc;
+    if (int rc = run(0, o.use_pcnr, cold_start, o.fused, zero_start ? nullptr : u, nullptr, o.participate ? nullptr : u)) return rc;
   if (res.direct) {
     if (converged) std::fill(converged, converged + B, 1);
     return 0;
   }
-  start.assign(u, u + B * n);
+  if (zero_start) start.assign(B * n, 0.0);   // (u holds whatever the caller allocated; every row of it is overwritten below)
+  else start.assign(u, u + B * n);
   U = start;
   take_all();
   // ---- stage 1: plain Newton from the caller's start point, for those PCNR did not solve

@@ -41,12 +41,61 @@ struct Driver {
   int* part = nullptr;        // [B] 1 = the instance takes part in the DC Newton run being started (k_dc_init)
   size_t out_cap = 0, brk_cap = 0, save_cap = 0, obs_cap = 0;
   std::vector<DCLogEntry> dc_log;   // what the DC fallback chain did, one entry per (instance, Newton run): cadnip_dc_log_*
+  // The option arrays of cadnip_tran_run as the device holds them: host copies of what was last uploaded to breaks, save_t, obs, atol
+  // and emask (`is` false: the device array holds something else).  A run with the same options as the last -- corner sweeps,
+  // optimisation loops -- uploads nothing.  The writers of those five device arrays are dalloc's zero fill (through ensure_driver for
+  // atol and emask, before anything is held; through drealloc for the others, which drops the copy) and sync_option; every kernel
+  // takes them through TranArgs as pointers to const.
+  template <class T> struct Held { std::vector<T> v; bool is = false; };
+  Held<double> held_breaks, held_save_t, held_atol, held_emask;
+  Held<int> held_obs;
+  hipEvent_t ev[2] = {nullptr, nullptr};   // the fused transient's look-ahead (cadnip_tran_run); made on first use, released with the handle
+  void* stage = nullptr; size_t stage_cap = 0;   // pinned host buffer the drivers' state and result transfers pass through (to_caller / from_caller)
 };
 
 namespace {
 #define TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 template <class T> int dalloc(T** p, size_t c) { if (*p) return CADNIP_OK; HIP_TRY(hipMalloc((void**)p, (c ? c : 1) * sizeof(T))); HIP_TRY(hipMemset(*p, 0, (c ? c : 1) * sizeof(T))); return CADNIP_OK; }
-template <class T> int drealloc(T** p, size_t* cap, size_t c) { if (*p && *cap >= c) return CADNIP_OK; if (*p) (void)hipFree(*p); *p = nullptr; *cap = c; return dalloc(p, c); }
+// (`held`: the Driver::Held flag of the array -- a new allocation holds zeros, not the last upload)
+template <class T> int drealloc(T** p, size_t* cap, size_t c, bool* held = nullptr) { if (*p && *cap >= c) return CADNIP_OK; if (held) *held = false; if (*p) (void)hipFree(*p); *p = nullptr; *cap = c; return dalloc(p, c); }
+// Brings the device array `dev` to src[0..c): a blocking upload, unless the device holds exactly these bytes already.  *sent is set when
+// something went up (the caller then synchronises once)
+template <class T> int sync_option(T* dev, Driver::Held<T>& held, const T* src, size_t c, bool* sent) {
+  if (held.is && held.v.size() == c && (c == 0 || memcmp(held.v.data(), src, c * sizeof(T)) == 0)) return CADNIP_OK;
+  held.is = false;
+  if (c) { HIP_TRY(hipMemcpy(dev, src, c * sizeof(T), hipMemcpyHostToDevice)); *sent = true; }
+  held.v.assign(src, src + c);
+  held.is = true;
+  return CADNIP_OK;
+}
+
+// The drivers' transfers between device memory and memory of the caller's (or vectors of their own that live for one call) pass through
+// one pinned buffer of the driver's, and a host copy.  Given a pageable array of this size the runtime's copy registers the array's
+// pages with the device and keeps the registration for reuse; when the caller frees the array afterwards -- every sweep step frees the
+// previous step's results -- unmapping registered pages makes the kernel driver evict and restore the process's queues, and the next call
+// that waits for the device stands still for 20 - 30 ms (with results copied straight into fresh arrays,
+// every second sweep step; how often depends on the caller's allocator).  Memory the driver owns is registered once and never unmapped
+// while in use.  The price is the host copy, about 0.1 ms per MB into pages the caller has not touched yet.
+int stage_fit(Driver* d, size_t bytes) {
+  if (d->stage && d->stage_cap >= bytes) return CADNIP_OK;
+  if (d->stage) (void)hipHostFree(d->stage);
+  d->stage = nullptr; d->stage_cap = 0;
+  HIP_TRY(hipHostMalloc(&d->stage, bytes ? bytes : 1, hipHostMallocDefault));
+  d->stage_cap = bytes ? bytes : 1;
+  return CADNIP_OK;
+}
+int to_caller(CadnipHandle* h, void* dst, const void* dev, size_t bytes) {
+  TRY(stage_fit(h->drv, bytes));
+  HIP_TRY(hipMemcpy(h->drv->stage, dev, bytes, hipMemcpyDeviceToHost));
+  memcpy(dst, h->drv->stage, bytes);
+  return CADNIP_OK;
+}
+int from_caller(CadnipHandle* h, void* dev, const void* src, size_t bytes) {
+  TRY(stage_fit(h->drv, bytes));
+  memcpy(h->drv->stage, src, bytes);
+  HIP_TRY(hipMemcpy(dev, h->drv->stage, bytes, hipMemcpyHostToDevice));
+  return CADNIP_OK;
+}
 
 // Every device buffer of the driver with the element count it is allocated with; ensure_driver allocates and cadnip_driver_free
 // releases by walking this one list
@@ -350,6 +399,8 @@ void cadnip_driver_free(CadnipHandle* h) {
   if (!h || !h->drv) return;
   Driver* d = h->drv;
   (void)each_buffer(d, 0, 0, [](auto** p, size_t) { if (*p) (void)hipFree(*p); return CADNIP_OK; });
+  for (hipEvent_t e : d->ev) if (e) (void)hipEventDestroy(e);
+  if (d->stage) (void)hipHostFree(d->stage);
   delete d;
   h->drv = nullptr;
 }
@@ -375,9 +426,14 @@ int cadnip_dc_run(CadnipHandle* h, const CadnipDCOpts* o, double* u_host, int32_
   const size_t B = h->B, n = h->n;
   auto w0 = std::chrono::steady_clock::now();
   d->dc_log.clear();
+  // CADNIP_DC_COLD_ZERO: the all-zero start state is made on the device, by the zero-fill kernel on the handle's stream (ordered with the
+  // kernels queued behind it, kernels.hip: dev_zero_async) -- u_host is not read and B * n doubles of zeros do not cross the bus.
+  // k_dc_init finds every row zero, as after an upload of zeros
+  const bool zero_start = o->cold_start == CADNIP_DC_COLD_ZERO && !o->participate;
   // the symbolic phase needs one numeric Jacobian: stamp once at the start point
   if (!h->analyzed) {
-    HIP_TRY(hipMemcpy(h->d_u, u_host, B * n * sizeof(double), hipMemcpyHostToDevice));
+    if (zero_start) TRY_RC(dev_zero_async(h, h->d_u, B * n * sizeof(double)));
+    else TRY(from_caller(h, h->d_u, u_host, B * n * sizeof(double)));
     TRY(restore_masks(h, false));
     TRY_RC(dev_zero_async(h, h->d_gamma, B * sizeof(double)));
     TRY_RC(dev_zero_async(h, h->d_t, B * sizeof(double)));
@@ -401,13 +457,14 @@ int cadnip_dc_run(CadnipHandle* h, const CadnipDCOpts* o, double* u_host, int32_
   std::vector<long long> cnt(B * 4);
   auto device_run = [&](const DCRun& r) -> int {
     // (blocking copies: the stream is idle here, and the start state must be in place before the first kernel is queued -- see k_publish_int)
-    HIP_TRY(hipMemcpy(h->d_u, r.u, B * n * sizeof(double), hipMemcpyHostToDevice));
+    if (r.u) TRY(from_caller(h, h->d_u, r.u, B * n * sizeof(double)));
+    else TRY_RC(dev_zero_async(h, h->d_u, B * n * sizeof(double)));   // (a zero start's first run)
     HIP_TRY(hipMemcpy(d->part, r.part, B * sizeof(int), hipMemcpyHostToDevice));
     TRY(upload_homotopy(h, r.gshunt, r.srcFact));
     TRY(dc_newton(h, o->abstol, o->maxiters, r.use_pcnr, r.cold_start, r.fused, d->part));
-    HIP_TRY(hipMemcpy(r.status, d->status, B * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(r.dest(), h->d_u, B * n * sizeof(double), hipMemcpyDeviceToHost));   // (straight to the caller when the first run solved everybody)
-    HIP_TRY(hipMemcpy(cnt.data(), d->cnt, B * 4 * sizeof(long long), hipMemcpyDeviceToHost));
+    TRY(to_caller(h, r.status, d->status, B * sizeof(int)));
+    TRY(to_caller(h, r.dest(), h->d_u, B * n * sizeof(double)));   // (the caller's own array when the first run solved everybody)
+    TRY(to_caller(h, cnt.data(), d->cnt, B * 4 * sizeof(long long)));
     for (size_t i = 0; i < B; ++i) r.iters[i] = cnt[i * 4];
     return CADNIP_OK;
   };
@@ -416,7 +473,7 @@ int cadnip_dc_run(CadnipHandle* h, const CadnipDCOpts* o, double* u_host, int32_
   TRY(dc_chain(chain, h->B, h->n, u_host, converged_host, device_run, d->dc_log, res));
   // the device holds the final states (after a direct run it does already); every instance is left active for subsequent ABI calls
   // (and subject to a cadnip_set_initjct of the caller's)
-  if (!res.direct) HIP_TRY(hipMemcpy(h->d_u, u_host, B * n * sizeof(double), hipMemcpyHostToDevice));
+  if (!res.direct) TRY(from_caller(h, h->d_u, u_host, B * n * sizeof(double)));
   TRY(restore_masks(h, true));
   if (st) {
     memset(st, 0, sizeof(*st));
@@ -449,21 +506,23 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
   Driver* d = h->drv;
   const size_t B = h->B, n = h->n;
   const int n_obs = o->n_obs > 0 ? o->n_obs : (int)n;
-  TRY(drealloc(&d->breaks, &d->brk_cap, (size_t)o->n_break));
-  TRY(drealloc(&d->save_t, &d->save_cap, (size_t)o->n_save));
-  TRY(drealloc(&d->obs, &d->obs_cap, (size_t)n_obs));
+  TRY(drealloc(&d->breaks, &d->brk_cap, (size_t)o->n_break, &d->held_breaks.is));
+  TRY(drealloc(&d->save_t, &d->save_cap, (size_t)o->n_save, &d->held_save_t.is));
+  TRY(drealloc(&d->obs, &d->obs_cap, (size_t)n_obs, &d->held_obs.is));
   TRY(drealloc(&d->out, &d->out_cap, B * (size_t)o->n_save * n_obs));
-  if (o->n_break) HIP_TRY(hipMemcpy(d->breaks, o->breaks, o->n_break * sizeof(double), hipMemcpyHostToDevice));
-  if (o->n_save) HIP_TRY(hipMemcpy(d->save_t, o->save_t, o->n_save * sizeof(double), hipMemcpyHostToDevice));
+  // the option arrays go up only where they differ from what the device holds (Driver::Held)
+  bool sent = false;
+  TRY(sync_option(d->breaks, d->held_breaks, o->breaks, (size_t)o->n_break, &sent));
+  TRY(sync_option(d->save_t, d->held_save_t, o->save_t, (size_t)o->n_save, &sent));
   std::vector<int> obs(n_obs);
   for (int i = 0; i < n_obs; ++i) obs[i] = o->n_obs > 0 ? o->obs[i] : i;
-  HIP_TRY(hipMemcpy(d->obs, obs.data(), n_obs * sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d->atol, o->abstol, n * sizeof(double), hipMemcpyHostToDevice));
+  TRY(sync_option(d->obs, d->held_obs, (const int*)obs.data(), (size_t)n_obs, &sent));
+  TRY(sync_option(d->atol, d->held_atol, o->abstol, n, &sent));
   std::vector<double> emask(n, 1.0);
   int n_err = (int)n;
   if (o->err_mask) { n_err = 0; for (size_t i = 0; i < n; ++i) { emask[i] = o->err_mask[i] != 0.0 ? 1.0 : 0.0; n_err += emask[i] != 0.0; } }
-  HIP_TRY(hipMemcpy(d->emask, emask.data(), n * sizeof(double), hipMemcpyHostToDevice));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  TRY(sync_option(d->emask, d->held_emask, (const double*)emask.data(), n, &sent));
+  if (sent) HIP_TRY(hipStreamSynchronize(h->stream));
   if (o->max_order >= 3) { TRY(dalloc(&d->u3, B * n)); TRY(dalloc(&d->hp3, B)); }
   TranArgs a = tran_args(h, o, n_obs, n_err);
   // Delayed stamps (cadnip_tran_set_delay, delay.hip): no step may reach past the smallest delay, so that the delayed value is a known number
@@ -492,9 +551,8 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
     // The host stays one launch ahead: launch k+1 is queued before the running-instance count of launch k is read,
     // so the GPU never waits for the host between launches.  Once every instance has finished, the one launch
     // already in the queue finds nothing to do (each wave reads its status and exits).
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIP_TRY(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+    hipEvent_t* const ev = d->ev;
+    for (int s = 0; s < 2; ++s) if (!ev[s]) HIP_TRY(hipEventCreateWithFlags(&ev[s], hipEventDisableTiming));
     int slot = 0;
     bool have_prev = false;
     while (launches < max_it) {
@@ -511,7 +569,6 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
       slot ^= 1;
     }
     hipError_t es = hipStreamSynchronize(h->stream);
-    (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
     if (es != hipSuccess) { set_last_error("hipStreamSynchronize", es); return CADNIP_HIPERROR; }
     if (!rc && running > 0) rc = count_running(h, &running);
   }
@@ -535,9 +592,9 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
   if (rc) return rc;
   std::vector<long long> cnt(B * 4);
   std::vector<int> status(B);
-  HIP_TRY(hipMemcpy(cnt.data(), d->cnt, B * 4 * sizeof(long long), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(status.data(), d->status, B * sizeof(int), hipMemcpyDeviceToHost));
-  if (out_host && o->n_save) HIP_TRY(hipMemcpy(out_host, d->out, B * (size_t)o->n_save * n_obs * sizeof(double), hipMemcpyDeviceToHost));
+  TRY(to_caller(h, cnt.data(), d->cnt, B * 4 * sizeof(long long)));
+  TRY(to_caller(h, status.data(), d->status, B * sizeof(int)));
+  if (out_host && o->n_save) TRY(to_caller(h, out_host, d->out, B * (size_t)o->n_save * n_obs * sizeof(double)));
   CadnipRunStats s; memset(&s, 0, sizeof(s));
   for (size_t i = 0; i < B; ++i) {
     s.newton_iters += cnt[i * 4 + 0]; s.steps_accepted += cnt[i * 4 + 1]; s.steps_rejected += cnt[i * 4 + 2]; s.newton_failures += cnt[i * 4 + 3];

@@ -228,6 +228,7 @@ struct CadnipHandle {
   // per-instance homotopy parameters of the DC fallback chain (solve.jl:720-850); equal to spec.gshunt / spec.srcFact
   // except while cadnip_dc_run walks an instance through gshunt / source stepping
   double *d_gshunt = nullptr, *d_srcfact = nullptr;
+  std::vector<double> held_gshunt, held_srcfact;   // what upload_homotopy (their only writer) last put there; empty = nothing known
   bool homotopy = false;     // some instance has gshunt != 0 or srcFact < 1: the fused kernel (no homotopy terms) must not run
   // device: per-instance state [B][..]
   double *d_u = nullptr, *d_du = nullptr, *d_t = nullptr, *d_gamma = nullptr;

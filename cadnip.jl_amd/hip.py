@@ -74,6 +74,9 @@ class SpecC(C.Structure):
     _fields_ = [("mode", C.c_int32), ("gmin", C.c_double), ("gshunt", C.c_double), ("srcFact", C.c_double)]
 
 
+DC_COLD_ZERO = 2   # include/cadnip_hip.h: CADNIP_DC_COLD_ZERO
+
+
 class DCOptsC(C.Structure):
     _fields_ = [("abstol", C.c_double), ("maxiters", C.c_int32), ("use_pcnr", C.c_int32), ("cold_start", C.c_int32),
                 ("use_stepping", C.c_int32), ("fused", C.c_int32), ("participate", _I)]
@@ -583,11 +586,13 @@ class Handle:
     def dc_run(self, u0=None, abstol=1e-10, maxiters=100, use_pcnr=True, cold_start=True, use_stepping=True,
                raise_on_fail=False, fused=False, participate=None):
         """``participate``: boolean mask [B]; instances with False sit the run out (u unchanged, converged False)."""
-        u = self._bn(0.0 if u0 is None else u0).copy()
+        # a cold start of everyone from zero: the device makes the zeros (CADNIP_DC_COLD_ZERO), u is output only
+        zero = u0 is None and bool(cold_start) and participate is None
+        u = np.empty((self.B, self.st.n)) if zero else self._bn(0.0 if u0 is None else u0).copy()
         conv = np.zeros(self.B, dtype=np.int32)
         st = RunStatsC()
         pm = None if participate is None else np.ascontiguousarray(np.asarray(participate, dtype=bool).astype(np.int32))
-        o = DCOptsC(abstol, maxiters, int(use_pcnr), int(cold_start), int(use_stepping), int(fused), None if pm is None else _ip(pm))
+        o = DCOptsC(abstol, maxiters, int(use_pcnr), DC_COLD_ZERO if zero else int(cold_start), int(use_stepping), int(fused), None if pm is None else _ip(pm))
         rc = self.lib.cadnip_dc_run(self.h, C.byref(o), _dp(u), _ip(conv), C.byref(st))
         if rc not in (OK, NOCONV) or (rc == NOCONV and raise_on_fail):
             _check(rc, "cadnip_dc_run")

@@ -362,11 +362,15 @@ int cadnip_ac_plan_info(CadnipHandle* h, int64_t out[4]);
  * The loops run on the host and launch the kernels above on the handle's stream; the
  * per-instance convergence / step decisions are evaluated on the device (one lane-group
  * per instance) so that B desynchronised instances need no per-iteration PCIe traffic. */
+/* CadnipDCOpts::cold_start = CADNIP_DC_COLD_ZERO: a cold start from the all-zero state whose start point is made on the device -- u_host is
+ * output only, nothing of it is read or uploaded.  Honoured when `participate` is NULL; with a mask it means 1 and u_host is read as ever,
+ * because masked rows must come back untouched. */
+#define CADNIP_DC_COLD_ZERO 2
 typedef struct {
   double abstol;          /* ||G u - b||_2 < abstol      solve.jl:640 (1e-10 dc!, 1e-9 CedarTranOp) */
   int32_t maxiters;       /* solve.jl:600 */
   int32_t use_pcnr;       /* PCNR corrector u[lim] = limit_w  solve.jl:682-688 */
-  int32_t cold_start;     /* seed limit vars + initjct       solve.jl:615-625 */
+  int32_t cold_start;     /* non-zero: seed limit vars + initjct  solve.jl:615-625; CADNIP_DC_COLD_ZERO: that, from zeros made on the device */
   int32_t use_stepping;   /* gshunt / source stepping fallbacks solve.jl:909-925 */
   int32_t fused;          /* non-zero: the first attempt (PCNR / Newton at the handle's spec) runs in the fused kernel
                              (csrc/fused2.hip, DC mode); the fallback homotopies always use the per-op kernels */
