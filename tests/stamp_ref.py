@@ -163,31 +163,38 @@ class Check:
         return "Check(%s worst ratio %.3g, %d failing %s)" % (self.what, self.ratio, self.bad.shape[0], self.bad[:5].tolist())
 
 
+def sums_and_bounds(vals, ptr, shape, extra=None, scale=1.0, rho=0.0, slack=None):
+    """(ref, bound, k) of check_sums for outputs of shape `shape` [..., n_out], all long double but k: the long-double sums
+    (sum of vals per entry + extra) * scale, the entrywise bound (rho + gamma_{k+1} + gamma^ld_{k+1}) * S + slack and the term counts."""
+    vals = np.asarray(vals, dtype=np.float64)
+    ptr = np.asarray(ptr, dtype=np.int64)
+    cnt = np.diff(ptr)
+    ref = _segsum(vals.astype(LD), ptr)
+    S = _segsum(np.abs(vals).astype(LD), ptr)
+    k = np.broadcast_to(cnt, shape).astype(np.float64)
+    if extra is not None:
+        ex = np.broadcast_to(np.asarray(extra, dtype=np.float64), shape)
+        ref = ref + ex.astype(LD)
+        S = S + np.abs(ex).astype(LD)
+        k = k + (ex != 0.0)
+    sc = np.asarray(scale, dtype=np.float64)
+    if sc.ndim:
+        sc = sc.reshape(sc.shape + (1,) * (len(shape) - sc.ndim))
+    ref = ref * sc.astype(LD)
+    S = S * sc.astype(LD)
+    bound = (rho + gamma(k + 1) + gamma(k + 1, U_LD)).astype(LD) * S
+    if slack is not None:
+        bound = bound + _segsum(np.asarray(slack, dtype=np.float64).astype(LD), ptr) * sc.astype(LD)
+    return ref, bound, k
+
+
 def check_sums(got, vals, ptr, extra=None, scale=1.0, rho=0.0, slack=None, what=""):
     """got [..., n_out] against (sum of vals per entry + extra) * scale.  vals [..., n_contrib] (flattened entry by entry, pointers ptr);
     extra [n_out] or [..., n_out] (gshunt), scale scalar or [...] (srcFact).  Bound per entry: (rho + gamma_{k+1} + gamma^ld_{k+1}) * S with
     S = (sum |c_i| + |extra|) * scale, k = number of terms; slack: per contribution allowance of the device evaluation, added to the bound (summed per entry, times scale).  An entry with no term at all
     must be exactly 0."""
     got = np.asarray(got, dtype=np.float64)
-    vals = np.asarray(vals, dtype=np.float64)
-    ptr = np.asarray(ptr, dtype=np.int64)
-    cnt = np.diff(ptr)
-    ref = _segsum(vals.astype(LD), ptr)
-    S = _segsum(np.abs(vals).astype(LD), ptr)
-    k = np.broadcast_to(cnt, got.shape).astype(np.float64)
-    if extra is not None:
-        ex = np.broadcast_to(np.asarray(extra, dtype=np.float64), got.shape)
-        ref = ref + ex.astype(LD)
-        S = S + np.abs(ex).astype(LD)
-        k = k + (ex != 0.0)
-    sc = np.asarray(scale, dtype=np.float64)
-    if sc.ndim:
-        sc = sc.reshape(sc.shape + (1,) * (got.ndim - sc.ndim))
-    ref = ref * sc.astype(LD)
-    S = S * sc.astype(LD)
-    bound = (rho + gamma(k + 1) + gamma(k + 1, U_LD)).astype(LD) * S
-    if slack is not None:
-        bound = bound + _segsum(np.asarray(slack, dtype=np.float64).astype(LD), ptr) * sc.astype(LD)
+    ref, bound, k = sums_and_bounds(vals, ptr, got.shape, extra, scale, rho, slack)
     err = np.abs(got.astype(LD) - ref)
     empty = k == 0
     fin = np.isfinite(got) & np.isfinite(np.asarray(ref, dtype=np.float64))
@@ -210,6 +217,21 @@ def check_stamp(got_G, got_C, got_b, ref, rho=0.0, st=None, u=None):
     return (check_sums(got_G, ref.vg, ref.pg, extra=ref.gdiag, rho=r0, slack=slack("g", st.g_slots if st else None), what="G"),
             check_sums(got_C, ref.vc, ref.pc, rho=r0, slack=slack("c", st.c_slots if st else None), what="C"),
             check_sums(got_b, ref.vb, ref.pb, scale=ref.srcFact, rho=r0, slack=slack("b", st.b_slots if st else None), what="b"))
+
+
+def stamp_bounds(ref, rho=0.0, st=None, u=None):
+    """What check_stamp holds one instance's G, C and b to, as numbers: ((G_ref, E_G), (C_ref, E_C), (b_ref, E_b)), long double, G and C
+    [nnz] in the handle's CSR order and b [n] -- the long-double sums of the Stamp's contributions and the entrywise bounds
+    gamma_{k+1} S plus the RHO / FLOOR allowances of the slots (same arguments as check_stamp)."""
+    sc = slot_scales(st, ref, u) if st is not None and rho else None
+
+    def slack(which, slots):
+        return None if sc is None else rho_of(st, which, slots, rho) * sc[which] + floor_of(st, which, slots)
+    r0 = 0.0 if st is not None else rho
+    g = sums_and_bounds(ref.vg, ref.pg, (len(ref.pg) - 1,), extra=ref.gdiag, rho=r0, slack=slack("g", st.g_slots if st else None))
+    c = sums_and_bounds(ref.vc, ref.pc, (len(ref.pc) - 1,), rho=r0, slack=slack("c", st.c_slots if st else None))
+    b = sums_and_bounds(ref.vb, ref.pb, (len(ref.pb) - 1,), scale=ref.srcFact, rho=r0, slack=slack("b", st.b_slots if st else None))
+    return g[:2], c[:2], b[:2]
 
 
 def slot_scales(st, ref, u=None):
