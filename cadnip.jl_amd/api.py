@@ -213,9 +213,18 @@ class TranSolution:
         self.u = np.asarray(u)          # [n_save, n]
         self.stats = stats
         self.retcode = retcode
+        # tran(..., sens=[names]): d u / d p_k at the save times [K, n_save, n], the names, the parameter steps of the central differences
+        # [K] and the flag (1: a sensitivity solve met a bad pivot or a non-finite value, NaN from that step on); None / empty without it
+        self.sens, self.sens_params, self.sens_steps, self.sens_flag = None, [], None, 0
 
     def __getitem__(self, name):
         return self.u[:, self.st.index_of(name)]
+
+    def sensitivity(self, name, param):
+        """d ``name`` / d ``param`` at the save times [n_save], of a run asked for with ``sens=``."""
+        if self.sens is None or param not in self.sens_params:
+            raise KeyError("no sensitivity with respect to %r was computed (tran(..., sens=[...]))" % (param,))
+        return self.sens[self.sens_params.index(param)][:, self.st.index_of(name)]
 
     def __call__(self, t, name=None):
         cols = self.u if name is None else self.u[:, self.st.index_of(name)]
@@ -263,6 +272,7 @@ class BatchSimulator:
         self.B = int(np.asarray(packed[0]).shape[0])
         self.params, self.temps = {}, np.full(self.B, spec.temp)
         self._vscale = float(vscale)
+        self.device = device
         self.h = hip.Handle(st, self.B, device)
         self.h.set_params([np.ascontiguousarray(p, dtype=np.float64) for p in packed])
         self.h.set_spec(mode=spec.mode if spec.mode in ("dcop", "tran", "tranop") else "tran", gmin=spec.gmin, gshunt=spec.gshunt, srcFact=spec.srcFact)
@@ -287,6 +297,7 @@ class BatchSimulator:
         self.params, self.temps = params, temps
         p0 = {k: float(v[0]) for k, v in params.items()}
         self.st = st if st is not None else discover(mc.circuit, p0)
+        self.device = device
         self.h = hip.Handle(self.st, B, device)
         self.h.set_params(pack_params(self.st, mc.circuit, params, temps, B, gmin=mc.spec.gmin, tnom_c=mc.spec.tnom))
         self.h.set_spec(mode=mc.spec.mode if mc.spec.mode in ("dcop", "tran", "tranop") else "tran",
@@ -403,7 +414,8 @@ class BatchSimulator:
             total["stages"] += 1
         return u, conv, total
 
-    def tran(self, tspan, abstol, reltol, saveat, initializealg="tranop", u0=None, warmup_dt=1e-12, delays="refuse", delay_depth=0, **kw):
+    def tran(self, tspan, abstol, reltol, saveat, initializealg="tranop", u0=None, warmup_dt=1e-12, delays="refuse", delay_depth=0, sens=None,
+             sens_rel_step=1e-4, **kw):
         """``initializealg``: "tranop" = CedarTranOp, a DC solve in :tranop mode at t0 (dcop.jl:160-212); "uic" = CedarUICOp
         (dcop.jl:109-151, 304-411): no DC solve -- the run starts from ``u0`` (zeros by default) and the integrator's first
         steps, backward Euler from ``warmup_dt``, relax the algebraic constraints (for oscillators and for circuits whose
@@ -415,13 +427,21 @@ class BatchSimulator:
         of ``delay_depth`` (0 = 1024) accepted points per instance, linearly interpolated; the steps are clamped to the smallest delay,
         the source break points are propagated through the delays (``delay_breakpoints``; stats["delay_breaks"] /
         ["delay_breaks_truncated"]), and the run uses the per-op kernels whatever ``fused`` says.  A delay that is not positive and
-        finite at any point is a ValueError.  A circuit without a delayed element runs exactly as without the keyword."""
+        finite at any point is a ValueError.  A circuit without a delayed element runs exactly as without the keyword.
+
+        ``sens``: names of circuit parameters, or "temp", each once -- the forward (direct) sensitivities d u / d p_k of the trajectory on
+        the step sequence the run takes (``_tran_sens``; csrc/tran_sens.hip).  They take no part in the error test or the step choice:
+        states, counters and statuses are bit for bit those of the run without the keyword on the same pivot order (the composite sample
+        of ``analyze``, taken here if no order has been chosen yet).  stats then carries "sens" [B, K, n_save, n_obs], "sens_steps" [B, K],
+        "sens_flag" [B], "sens_names" and "sens_params" = K.  Without ``sens`` nothing new is called and no instance is added."""
         st = self.st
         if initializealg not in ("tranop", "uic"):
             raise ValueError("initializealg must be 'tranop' or 'uic'")
         if delays not in ("refuse", "history"):
             raise ValueError("delays must be 'refuse' or 'history'")
         breaks = expand_breakpoints(st.breakpoints, tspan)
+        if sens is not None:
+            return self._tran_sens(tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, breaks, sens, sens_rel_step, kw)
         if self.mc is not None and has_delay(self.mc.circuit):
             if delays == "refuse":
                 refuse_delay(self.mc.circuit, "tran", "a transient needs the delayed quantity's history: ask for it with delays=\"history\" "
@@ -445,6 +465,34 @@ class BatchSimulator:
                 self.h.analyze_values(restore[0])
         stats["delay_breaks"], stats["delay_breaks_truncated"] = n_new, truncated
         return out, per, stats
+
+    def _tran_sens(self, tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, breaks, sens, rel_step, kw):
+        """the run of ``tran`` with ``sens``: every point becomes a group base | twin | p_k + delta_k | p_k - delta_k of one resident batch
+        (``sens_expand``) on a handle of its own with this simulator's pivot order; only the bases are initialised and integrate"""
+        if self.mc is None:
+            raise ValueError("tran: sens needs the circuit description; a simulator made from packed parameters has none")
+        names, values, steps, expanded, per = sens_prepare(self.mc, self.points, sens, rel_step, tspan)
+        if not self._analyzed or getattr(self, "pivot_sample", None) is None:
+            self.analyze()
+        G, K = len(self.points), len(names)
+        members = np.arange(G * per, dtype=np.int32).reshape(G, per)
+        is_base = np.zeros(G * per, dtype=bool)
+        is_base[members[:, 0]] = True
+        obs = kw.get("obs")
+        n_obs = self.st.n if obs is None or len(obs) == 0 else len(obs)
+        if isinstance(u0, np.ndarray) and u0.ndim == 2:
+            u0 = np.repeat(u0, per, axis=0)
+        inner = BatchSimulator(self.mc, expanded, self.device, st=self.st)
+        try:
+            inner.analyze(sample=self.pivot_sample)
+            inner.h.tran_set_sens(members, steps, len(saveat), n_obs, kw.get("max_order", 2))
+            out, per_inst, stats = inner._tran(tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, breaks, kw, participate=is_base,
+                                               after_init=lambda: inner.h.tran_sens_init(zero=initializealg == "uic"))
+            s, flag = inner.h.tran_sens_get()
+        finally:
+            inner.close()
+        stats.update(sens=s, sens_steps=steps, sens_values=values, sens_flag=flag, sens_names=names, sens_params=K)
+        return out[is_base], per_inst[is_base], stats
 
     def delay_spec(self):
         """The delayed stamps of the circuit at the simulator's points as ``hip.Handle.tran_set_delay`` takes them, from the one pure function
@@ -484,7 +532,10 @@ class BatchSimulator:
         self._analyzed = True
         return base
 
-    def _tran(self, tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, breaks, kw, before_run=lambda: None):
+    def _tran(self, tspan, abstol, reltol, saveat, initializealg, u0, warmup_dt, breaks, kw, before_run=lambda: None, participate=None,
+              after_init=lambda: None):
+        """``participate`` (mask [B], None = all): who gets the tranop DC solve; ``after_init``: called with the start state on the handle,
+        before the mode is switched to the transient's"""
         st = self.st
         if initializealg == "uic":
             if isinstance(u0, dict):          # {unknown name: value}: the usual .IC form
@@ -496,6 +547,7 @@ class BatchSimulator:
             if not self._analyzed:     # pivot order from the Jacobian the first steps will meet (h = warmup_dt)
                 self.analyze_at(start, t=tspan[0], gamma=1.0 / (10.0 * warmup_dt))
             self.h.set_u(start)
+            after_init()
             self.h.set_spec(mode="tran")
             kw.setdefault("h0", warmup_dt)
             before_run()
@@ -504,9 +556,12 @@ class BatchSimulator:
             return out, per, stats
         if not self._analyzed:
             self.analyze()
-        u0_, conv, dcs = self.dc(abstol=1e-9, mode="tranop", fused=bool(kw.get("fused", False)))
+        u0_, conv, dcs = self.dc(abstol=1e-9, mode="tranop", fused=bool(kw.get("fused", False)), participate=participate)
+        if participate is not None:
+            conv = conv | ~np.asarray(participate, dtype=bool)
         if not np.all(conv):
             raise RuntimeError("transient initialisation (CedarTranOp) failed for %d instance(s)" % int((~conv).sum()))
+        after_init()
         self.h.set_spec(mode="tran")
         before_run()
         out, per, stats = self.h.tran_run(tspan[0], tspan[1], abstol, reltol, breaks=breaks, save_t=saveat, **kw)
@@ -1775,6 +1830,77 @@ def sens_gpu_sweep(h, st, G_ref, C_ref, base, plus, minus, scale, bac, out, db, 
     return [(y[a], s[a]) for a in range(len(base))]
 
 
+def sens_expand(mc, pts, params, rel_step, twin=False):
+    """The perturbed batch of ``sensitivity`` and of ``tran(..., sens=)``: point i -> expanded points i * per + [0 | 1 + 2 k | 2 + 2 k] =
+    base | p_k + delta_k | p_k - delta_k (``twin``: a second copy of the base behind it, everything after it one further), with delta_k =
+    rel_step |p_k| (rel_step when p_k == 0; rel_step (T + 273.15) for "temp").  Returns (values [P, K], steps [P, K], expanded, per)."""
+    K = len(params)
+    per = 1 + int(bool(twin)) + 2 * K
+    values, steps, expanded = np.zeros((len(pts), K)), np.zeros((len(pts), K)), []
+    for i, pt in enumerate(pts):
+        expanded.append(dict(pt))
+        if twin:
+            expanded.append(dict(pt))
+        for k, nm in enumerate(params):
+            v = float(pt.get(nm, mc.spec.temp if nm == "temp" else mc.params.get(nm)))
+            d = rel_step * (v + 273.15) if nm == "temp" else rel_step * abs(v) if v != 0 else rel_step
+            values[i, k], steps[i, k] = v, d
+            for sgn in (1.0, -1.0):
+                q = dict(pt)
+                q[nm] = v + sgn * d
+                expanded.append(q)
+    return values, steps, expanded, per
+
+
+def sens_breaks(mc, point, tspan):
+    """the source break points inside ``tspan`` of the circuit at ``point``.  Source waveforms hold plain numbers today, so no parameter
+    moves them; ``sens_prepare`` compares base and variant all the same, and a waveform that learns to take a Param is caught there"""
+    from .structure import wave_breakpoints
+    specs = [wave_breakpoints(d.wave) for d in mc.circuit.devices if d.wave is not None]
+    return expand_breakpoints([b for b in specs if b is not None], tspan)
+
+
+def sens_prepare(mc, pts, sens, rel_step, tspan):
+    """Everything ``tran(..., sens=)`` refuses, before any device work, and the expanded batch: (names, values, steps, expanded, per).
+    ValueError: an empty list, a name twice, a name that is neither a circuit parameter nor "temp", a rel_step that is not positive, a
+    step that changes the structure of the circuit or moves a source break point (the derivative on a frozen grid does not exist there).
+    NotImplementedError: a delayed element (its history would need a sensitivity ring of its own) or a behavioural source (its stamp
+    carries no Jacobian entries, so G is not dF/du)."""
+    names = [sens] if isinstance(sens, str) else list(sens)
+    if not names or len(set(names)) != len(names):
+        raise ValueError("tran: sens needs at least one parameter name, each once")
+    for nm in names:
+        if nm != "temp" and nm not in mc.params:
+            raise ValueError("tran: %s is not a parameter of the circuit (parameters: %s, or \"temp\")" % (nm, sorted(mc.params)))
+    if not rel_step > 0:
+        raise ValueError("tran: sens_rel_step must be positive")
+    if has_delay(mc.circuit):
+        raise NotImplementedError("tran: sens with a delayed element (%s) is not built: the delayed value's own sensitivity would need a history ring"
+                                  % ", ".join(d.name for d in mc.circuit.devices if "delay" in d.params))
+    bsrc = [d.name for d in mc.circuit.devices if d.type in ("BV", "BI")]
+    if bsrc:
+        raise NotImplementedError("tran: sens with a behavioural source (%s) is not built: its stamp carries no Jacobian entries, so G is not dF/du there"
+                                  % ", ".join(bsrc))
+    values, steps, expanded, per = sens_expand(mc, pts, names, rel_step, twin=True)
+    cls_of = {}
+    for ci, (members, _) in enumerate(structure_classes(mc, expanded)):
+        for j in members:
+            cls_of[j] = ci
+    if len({cls_of[i * per] for i in range(len(pts))}) > 1:
+        raise ValueError("tran: sens needs every point of the sweep to share one structure (its unknowns and its pattern)")
+    for i in range(len(pts)):
+        base_breaks = sens_breaks(mc, expanded[i * per], tspan)
+        for k, nm in enumerate(names):
+            for j in (i * per + 2 + 2 * k, i * per + 3 + 2 * k):
+                if cls_of[j] != cls_of[i * per]:
+                    raise ValueError("tran: a step of %g in %s at point %d changes the structure of the circuit (its unknowns or its pattern): "
+                                     "the derivative does not exist there" % (steps[i, k], nm, i))
+                if not np.array_equal(sens_breaks(mc, expanded[j], tspan), base_breaks):
+                    raise ValueError("tran: a step of %g in %s at point %d moves a source break point: the derivative of the trajectory on a "
+                                     "frozen step grid does not exist there" % (steps[i, k], nm, i))
+    return names, values, steps, expanded, per
+
+
 def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device=0, solver="host", memory="lds"):
     """Small-signal sensitivities (SPICE's .SENS on an AC sweep): the response y of ``output`` over ``freqs`` (hertz) as ``ac`` gives it, and
     dy/dp_k for every parameter of ``params`` -- names of circuit parameters, or "temp" -- from ONE factorisation per (point, frequency): with
@@ -1807,18 +1933,7 @@ def sensitivity(target, output, params, freqs, rel_step=1e-4, gmin=1e-12, device
             raise ValueError("sensitivity: %s is not a parameter of the circuit (parameters: %s, or \"temp\")" % (nm, sorted(mc.params)))
     K, omegas = len(params), 2.0 * np.pi * freqs
     # the perturbed batch: point i -> instances i (1 + 2 K) + [0 | 1 + 2 k | 2 + 2 k] = base | p_k + delta | p_k - delta
-    per = 1 + 2 * K
-    values, steps, expanded = np.zeros((len(pts), K)), np.zeros((len(pts), K)), []
-    for i, pt in enumerate(pts):
-        expanded.append(dict(pt))
-        for k, nm in enumerate(params):
-            v = float(pt.get(nm, mc.spec.temp if nm == "temp" else mc.params.get(nm)))
-            d = rel_step * (v + 273.15) if nm == "temp" else rel_step * abs(v) if v != 0 else rel_step
-            values[i, k], steps[i, k] = v, d
-            for sgn in (1.0, -1.0):
-                q = dict(pt)
-                q[nm] = v + sgn * d
-                expanded.append(q)
+    values, steps, expanded, per = sens_expand(mc, pts, params, rel_step)
     cls_of = {}
     classes = structure_classes(mc, expanded)
     for ci, (members, st) in enumerate(classes):
@@ -2223,7 +2338,16 @@ def tran(target, tspan, abstol=1e-10, reltol=1e-8, saveat=None, device=0, **kw):
     refused (NotImplementedError) unless the call says ``delays="history"``: then the handle keeps a history ring of ``delay_depth``
     accepted points per instance and integrates the delay-differential system (``BatchSimulator.tran``).  "refuse"
     stays the default for now -- flipping it is a later change.  An instance whose delayed look-up fell off the ring has retcode
-    "DelayHistoryOverflow"."""
+    "DelayHistoryOverflow".
+
+    ``sens=[names]`` (circuit parameters or "temp", each once; ``sens_rel_step=1e-4``): the forward sensitivities of the trajectory with
+    respect to those parameters, on the step sequence the run takes (``BatchSimulator.tran``): ``sol.sens``
+    [K, n_save, n], ``sol.sens_params``, ``sol.sens_steps``, ``sol.sens_flag``, ``sol.sensitivity(name, param)``; a CircuitSweep gives one
+    such result per point, and stats["sens_params"] is K.  What is refused, before any device work: ``sens_prepare``."""
+    if kw.get("sens") is not None:
+        mc_ = target.circuit if isinstance(target, CircuitSweep) else target
+        sens_prepare(mc_, target.points() if isinstance(target, CircuitSweep) else [{}], kw["sens"], kw.get("sens_rel_step", 1e-4),
+                     (float(tspan[0]), float(tspan[1])))
     if kw.get("delays", "refuse") not in ("refuse", "history"):
         raise ValueError("delays must be 'refuse' or 'history'")
     if kw.get("delays", "refuse") == "refuse":
@@ -2241,10 +2365,14 @@ def tran(target, tspan, abstol=1e-10, reltol=1e-8, saveat=None, device=0, **kw):
         sim = BatchSimulator(target, None, device)
     try:
         out, per, stats = sim.tran(tspan, _resolve_abstol(abstol, sim.st), reltol, saveat, **kw)
+        sens = {k: stats.pop(k) for k in ("sens", "sens_steps", "sens_values", "sens_flag", "sens_names") if k in stats}
         sols = []
         for i in range(sim.B):
             s = {"nnonliniter": int(per[i, 0]), "naccept": int(per[i, 1]), "nreject": int(per[i, 2])}
             sols.append(TranSolution(sim.st, saveat, out[i], s, TRAN_RETCODES.get(int(per[i, 3]), "Failure")))
+            if sens:
+                sols[-1].sens, sols[-1].sens_params = sens["sens"][i], list(sens["sens_names"])
+                sols[-1].sens_steps, sols[-1].sens_flag = sens["sens_steps"][i], int(sens["sens_flag"][i])
         if isinstance(target, CircuitSweep):
             res = SweepResult(target.points(), sols)
             res.stats = stats

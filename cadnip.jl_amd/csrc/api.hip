@@ -239,6 +239,7 @@ void cadnip_destroy(CadnipHandle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   cadnip_driver_free(h);
   delay_release(h);
+  sens_release(h);
   void* ptrs[] = {h->d_rowptr, h->d_colidx, h->d_to_ref, h->d_g_ptr, h->d_g_slots, h->d_c_ptr, h->d_c_slots, h->d_b_ptr, h->d_b_slots,
                   h->d_diag_flag, h->d_prep, h->d_long_rows, h->d_wave, h->d_limit_init, h->d_u, h->d_du, h->d_t, h->d_gamma, h->d_G, h->d_C, h->d_b, h->d_J,
                   h->d_resid, h->d_delta, h->d_limit_w, h->d_LU, h->d_tmp, h->d_flags, h->d_active, h->d_nonfinite, h->d_gshunt, h->d_srcfact, h->d_cold, h->d_load_src, h->d_load_dst, h->d_ent_pos,

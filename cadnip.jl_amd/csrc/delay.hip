@@ -164,6 +164,7 @@ extern "C" int cadnip_tran_set_delay(CadnipHandle* h, const CadnipDelaySpec* s) 
     delay_release(h);
     return CADNIP_OK;
   }
+  if (h->sns.n_group > 0) return CADNIP_BADARG;     // a sensitivity spec stands (cadnip_tran_set_sens): the two settings exclude each other
   if (s->n_term < 0 || s->n_pos <= 0 || s->depth < 0 || s->depth == 1 || !s->tau || !s->w) return CADNIP_BADARG;
   DelayPlan P;
   if (!delay_plan_build(h->n, h->nnz, h->h_rowptr.data(), h->h_colidx.data(), s->n_pos, s->pos, s->n_term, s->term_pos, s->term_row, s->term_col, P))

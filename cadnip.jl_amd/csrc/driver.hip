@@ -532,12 +532,19 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
   if (delayed) { a.hmax = fmin(a.hmax, h->dly.tau_min); a.h0 = fmin(a.h0, a.hmax); }
   struct DelayGuard { CadnipHandle* h; bool on; ~DelayGuard() { if (on) { (void)launch_delay_clear(h); (void)hipStreamSynchronize(h->stream); } } } delay_guard{h, delayed};
   // the per-op kernels take over where the fused kernel cannot run: external generated models (they exist in the per-op stamping kernel only), a
-  // circuit too large for the LDS-resident kernel, Newton mode 1 on a circuit outside the lean device set, a handle with delayed stamps
-  const bool use_fused = o->fused && fused2_plan(h, F2_TRAN, o->newton_mode).circuit_ok;
+  // circuit too large for the LDS-resident kernel, Newton mode 1 on a circuit outside the lean device set, a handle with delayed stamps or with
+  // a sensitivity spec
+  // Parameter sensitivities (cadnip_tran_set_sens, tran_sens.hip): the spec was sized for these save points, observers and history depth, and
+  // s(t0) must have been given since the last run
+  const bool sens = h->sns.n_group > 0;
+  if (sens && (h->sns.n_save != o->n_save || h->sns.n_obs != n_obs || h->sns.nh != (a.max_order >= 3 ? 4 : 3))) return CADNIP_BADARG;
+  if (sens && !h->sns.inited) return CADNIP_NOTREADY;
+  const bool use_fused = !sens && o->fused && fused2_plan(h, F2_TRAN, o->newton_mode).circuit_ok;
   struct ModeGuard { CadnipHandle* h; int saved; ~ModeGuard() { h->spec.mode = saved; } } mode_guard{h, h->spec.mode};
   h->spec.mode = 1;   // :tran (restored on every exit path)
   hipLaunchKernelGGL(k_tran_init, dim3(h->B), dim3(64), 0, h->stream, a);
   if (delayed) TRY(launch_delay_init(h, a.t0));
+  if (sens) { h->sns.inited = false; TRY(launch_sens_begin(h, a)); }
   HIP_TRY(hipStreamSynchronize(h->stream));
   auto w0 = std::chrono::steady_clock::now();
   int64_t launches = 0;
@@ -578,10 +585,12 @@ int cadnip_tran_run(CadnipHandle* h, const CadnipTranOpts* o, double* out_host, 
       if (delayed) { rc = launch_delay_apply(h, d->status); if (rc) break; }
       rc = launch_residual(h, h->d_du); if (rc) break;
       rc = launch_factor_solve(h, true, h->d_resid, h->d_delta); if (rc) break;
+      if (sens) { rc = launch_sens_snapshot(h, a); if (rc) break; }
       { ProfScope ps(h, "tran_update");
         if (h->n >= 4096) hipLaunchKernelGGL(k_tran_update<256>, dim3(h->B), dim3(256), 0, h->stream, a);
         else hipLaunchKernelGGL(k_tran_update<64>, dim3(h->B), dim3(64), 0, h->stream, a); }
       if (delayed) { rc = launch_delay_record(h, d->t, d->u0, d->status); if (rc) break; }
+      if (sens) { rc = launch_sens_stage(h, a); if (rc) break; }
       ++launches;
     }
     if (rc) break;

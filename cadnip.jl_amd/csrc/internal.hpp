@@ -8,6 +8,7 @@
 #include "stamp_plan.hpp"   // StampShape
 #include "ac_hbm_plan.hpp"  // AcHbmPlan
 #include "delay_plan.hpp"   // DelayPlan
+#include "tran_sens_plan.hpp"
 // rows of the derived sp_mos1 parameter card (devices.hpp: enum M1_*) that cadnip_set_params inspects
 #define CADNIP_MOS1_PAR_OXCAP 8
 #define CADNIP_MOS1_PAR_GD 30
@@ -198,6 +199,24 @@ struct DelayState {
   }
 };
 
+// Transient parameter sensitivities (cadnip_tran_set_sens; tran_sens.hip, tran_sens_plan.hpp): the group table, the sensitivity history and
+// output, and the snapshot of the bases' controller state that one stage works from.  n_group == 0: no spec is set -- nothing is allocated
+// and cadnip_tran_run launches nothing new
+struct SensState {
+  int n_group = 0, K = 0, nh = 0, n_save = 0, n_obs = 0;
+  bool inited = false;                            // cadnip_tran_sens_init has run since the last transient
+  int *d_members = nullptr, *d_slot_of = nullptr; // [n_group][2 + 2 K]; [B] group * (2 + 2 K) + member, -1 = in no group
+  double* d_delta = nullptr;                      // [n_group][K]
+  double *d_hist = nullptr, *d_out = nullptr;     // [n_group][K][nh][n] newest first; [n_group][K][n_save][n_obs]
+  double *d_snap = nullptr, *d_alpha = nullptr;   // [n_group][4] t, h, hprev, hpp before the update; [n_group][4] a0 .. a3 of the accepted step
+  int *d_snap_i = nullptr, *d_accept = nullptr, *d_flag = nullptr;   // [n_group][3] nhist, order, save_idx; [n_group]; [n_group]
+  long long* d_snap_cnt = nullptr;                // [n_group] accepted-step counter before the update
+  template <class F> void each_buffer(F f) {
+    f((void**)&d_members); f((void**)&d_slot_of); f((void**)&d_delta); f((void**)&d_hist); f((void**)&d_out); f((void**)&d_snap); f((void**)&d_alpha);
+    f((void**)&d_snap_i); f((void**)&d_accept); f((void**)&d_flag); f((void**)&d_snap_cnt);
+  }
+};
+
 }  // namespace cadnip
 
 struct CadnipHandle {
@@ -251,6 +270,7 @@ struct CadnipHandle {
   cadnip::FusedState f2;      // the LDS-resident kernels' tables, step lists and buffers (fused2.hip, lu_f2.hip)
   cadnip::AcState ac;         // AC sweep: pivot lists and transfer buffers (ac_lu.hip; released with the handle's other buffers in cadnip_destroy)
   cadnip::DelayState dly;     // transient: delayed stamps and their history ring (delay.hip; released in cadnip_destroy)
+  cadnip::SensState sns;     // transient: parameter sensitivities (tran_sens.hip; released in cadnip_destroy)
   // driver state (allocated lazily)
   struct Driver* drv = nullptr;
   // profiling
@@ -333,6 +353,12 @@ int launch_delay_init(CadnipHandle* h, double t0);                         // v_
 int launch_delay_apply(CadnipHandle* h, int* d_status);                    // G -= W, b[row] -= sum w ud(col, tcur - tau) where the rebuild stamped; ends an instance whose look-up overflows
 int launch_delay_record(CadnipHandle* h, const double* d_t, const double* d_u0, int* d_status);   // appends accepted points
 int launch_delay_clear(CadnipHandle* h);                                   // zeroes the rows of b that only k_delay_apply writes
+// tran_sens.hip: the transient's sensitivity stage (cadnip_tran_set_sens), asynchronous on h->stream; t: the arguments of the run's controller kernels
+struct TranArgs;
+void sens_release(CadnipHandle* h);                                        // frees everything; no spec is set afterwards
+int launch_sens_begin(CadnipHandle* h, const TranArgs& t);                 // after k_tran_init: parks every member but the bases, writes s(t0) to the save points at or before t0
+int launch_sens_snapshot(CadnipHandle* h, const TranArgs& t);              // before k_tran_update: the bases' step in flight
+int launch_sens_stage(CadnipHandle* h, const TranArgs& t);                 // after k_tran_update: gather, restamp, residual, right-hand sides, one LU launch, record
 int upload_homotopy(CadnipHandle* h, const double* gshunt /* [B] or null = spec */, const double* srcfact /* [B] or null = spec */);
 int restore_masks(CadnipHandle* h, bool cold);   // api.hip: d_active (and with `cold` d_cold, first) back to all ones, as blocking copies: every instance takes part again
 int launch_calib_copy(CadnipHandle* h, long n, int reps);

@@ -30,7 +30,7 @@ EXPORTS = [
     "cadnip_create", "cadnip_destroy", "cadnip_set_params", "cadnip_set_spec", "cadnip_set_initjct",
     "cadnip_rebuild", "cadnip_residual", "cadnip_jacobian", "cadnip_jacobian_dense", "cadnip_ode_rhs", "cadnip_ode_jacobian", "cadnip_get_GCb", "cadnip_get_contributions", "cadnip_analyze",
     "cadnip_analyze_values", "cadnip_factor", "cadnip_solve", "cadnip_factor_solve", "cadnip_lu_order", "cadnip_ac_solve", "cadnip_ac_adjoint", "cadnip_ac_solve_multi", "cadnip_ac_adjoint_multi", "cadnip_ac_sens", "cadnip_ac_arnoldi", "cadnip_ac_set_memory", "cadnip_ac_set_overlay", "cadnip_ac_plan_info", "cadnip_newton_step", "cadnip_newton_step_fused", "cadnip_debug_step_time", "cadnip_lu_stats", "cadnip_dc_run",
-    "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_set_delay", "cadnip_tran_delay_info", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
+    "cadnip_dc_log_size", "cadnip_dc_log_get", "cadnip_tran_set_delay", "cadnip_tran_delay_info", "cadnip_tran_set_sens", "cadnip_tran_sens_init", "cadnip_tran_sens_get", "cadnip_tran_sens_info", "cadnip_tran_run", "cadnip_tran_state", "cadnip_dev_ptr", "cadnip_stream", "cadnip_set_u", "cadnip_get_u", "cadnip_get_flags",
     "cadnip_sync", "cadnip_debug_copy", "cadnip_debug_stamp_time", "cadnip_profile_enable", "cadnip_profile_read", "cadnip_version",
     "cadnip_host_lu_analyze", "cadnip_host_lu_analyze_leaves", "cadnip_host_lu_size", "cadnip_host_lu_blocks", "cadnip_host_lu_get", "cadnip_host_lu_free", "cadnip_host_lu_transpose",
     "cadnip_host_f2_build", "cadnip_host_f2_size", "cadnip_host_f2_get", "cadnip_host_f2_free", "cadnip_host_f2_team_steps", "cadnip_host_f2_steps",
@@ -93,6 +93,10 @@ class TranOptsC(C.Structure):
 class DelaySpecC(C.Structure):
     _fields_ = [("n_pos", C.c_int32), ("pos", _I), ("n_term", C.c_int32), ("term_pos", _I), ("term_row", _I), ("term_col", _I),
                 ("tau", _D), ("w", _D), ("depth", C.c_int32)]
+
+
+class SensSpecC(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("K", C.c_int32), ("members", _I), ("delta", _D), ("nh", C.c_int32), ("n_save", C.c_int32), ("n_obs", C.c_int32)]
 
 
 # per-instance status of a transient (cadnip_tran_run's per_inst_host[:, 3]): CADNIP_TRAN_DELAY_OVERFLOW
@@ -664,6 +668,48 @@ class Handle:
     def tran_clear_delay(self):
         """cadnip_tran_set_delay with no spec: ``tran_run`` is again exactly what it is on a new handle."""
         _check(self.lib.cadnip_tran_set_delay(self.h, None), "cadnip_tran_set_delay")
+
+    def tran_set_sens(self, members, delta, n_save, n_obs=None, max_order=2):
+        """cadnip_tran_set_sens: from now on ``tran_run`` computes the forward sensitivities of the groups ``members`` [G, 2 + 2 K] -- rows
+        {base, twin, p_0 + delta_0, p_0 - delta_0, ...} of instance indices whose parameters the caller has set accordingly -- with the
+        parameter steps ``delta`` [G, K] (csrc/tran_sens.hip, csrc/tran_sens_plan.hpp).  Only the bases integrate; the other members are
+        parked and their rows of ``tran_run``'s results mean nothing.  ``n_save`` / ``n_obs`` (None: all n) / ``max_order``: those of the
+        runs to come.  Each run needs a ``tran_sens_init`` before it, runs on the per-op kernels whatever ``fused`` says, and leaves its
+        results to ``tran_sens_get``.  Arrays of the wrong shape raise ValueError; an index out of range, an instance named twice, a delta
+        that is not positive and finite, results beyond 256 MiB or a delay spec in force raise CadnipError(CADNIP_BADARG) and leave the
+        previous setting in force."""
+        mem = np.ascontiguousarray(np.asarray(members, dtype=np.int32))
+        dl = np.ascontiguousarray(np.asarray(delta, dtype=np.float64))
+        if mem.ndim != 2 or dl.ndim != 2 or dl.shape[0] != mem.shape[0] or mem.shape[1] != 2 + 2 * dl.shape[1] or dl.shape[1] == 0:
+            raise ValueError("members must be [G, 2 + 2 K] and delta [G, K] for G groups and K >= 1 parameters")
+        if mem.shape[0] == 0:
+            return self.tran_clear_sens()
+        spec = SensSpecC(mem.shape[0], dl.shape[1], _ip(mem), _dp(dl), 4 if max_order >= 3 else 3, int(n_save), self.st.n if n_obs is None else int(n_obs))
+        _check(self.lib.cadnip_tran_set_sens(self.h, C.byref(spec)), "cadnip_tran_set_sens")
+
+    def tran_clear_sens(self):
+        """cadnip_tran_set_sens with no spec: ``tran_run`` is again exactly what it is on a new handle."""
+        _check(self.lib.cadnip_tran_set_sens(self.h, None), "cadnip_tran_set_sens")
+
+    def tran_sens_init(self, zero=False):
+        """cadnip_tran_sens_init: s(t0) of every group -- zeros with ``zero`` (the start state was given), else -G^-1 d(G u - b)/dp at the
+        handle's current state, an operating point (call it after the tranop ``dc_run``, before the mode is switched)."""
+        _check(self.lib.cadnip_tran_sens_init(self.h, C.c_int32(1 if zero else 0)), "cadnip_tran_sens_init")
+
+    def tran_sens_info(self):
+        """cadnip_tran_sens_info: {n_group, K, per (members of a group), nh, n_save, n_obs} of the spec in force (zeros without one)."""
+        out = (C.c_int32 * 6)()
+        _check(self.lib.cadnip_tran_sens_info(self.h, out), "cadnip_tran_sens_info")
+        return dict(zip(("n_group", "K", "per", "nh", "n_save", "n_obs"), (int(x) for x in out)))
+
+    def tran_sens_get(self):
+        """cadnip_tran_sens_get: (s [G, K, n_save, n_obs], flags [G]) of the last ``tran_run``; flag 1: a solve of the group met a bad pivot
+        or a non-finite value, its sensitivities are NaN from that step on."""
+        i = self.tran_sens_info()
+        s = np.zeros((i["n_group"], i["K"], i["n_save"], i["n_obs"]))
+        fl = np.zeros(max(i["n_group"], 1), dtype=np.int32)
+        _check(self.lib.cadnip_tran_sens_get(self.h, _dp(s) if s.size else None, _ip(fl)), "cadnip_tran_sens_get")
+        return s, fl[:i["n_group"]]
 
     def tran_state(self):
         t, hh, o = np.empty(self.B), np.empty(self.B), np.empty(self.B, dtype=np.int32)

@@ -463,6 +463,43 @@ int cadnip_tran_set_delay(CadnipHandle* h, const CadnipDelaySpec* spec);
 /* The plan the handle built from the spec in force -- the sizes k_delay_init / k_delay_apply / k_delay_record index by:
  * out = {n_pos (distinct positions), n_rows (distinct delayed rows of b), n_taps (distinct term_col), n_term, depth}; all zero without a spec */
 int cadnip_tran_delay_info(CadnipHandle* h, int32_t out[5]);
+/* Parameter sensitivities of the transient, forward (direct, staggered) method -- a handle setting, none by default.  The resident batch is
+ * laid out in groups of 2 + 2 K instances: members[g] = {base, twin, p_0 + delta_0, p_0 - delta_0, p_1 + delta_1, ...}.  The caller has given
+ * the twin the base's parameters and member 2 + 2 k / 3 + 2 k the base's with parameter k moved by +- delta[g][k] (cadnip_set_params).  Only
+ * the bases integrate: cadnip_tran_run parks every other member (status 1, never active in the time loop; its rows of the per-instance
+ * arrays are scratch, its rows of out_host / per_inst_host mean nothing) and, after each round's step controller, runs one stage for the
+ * groups whose base has just ACCEPTED a step (csrc/tran_sens.hip; arithmetic in csrc/tran_sens_plan.hpp):
+ *   (G + a0 C) s_k,n = -(F(p_k + delta_k) - F(p_k - delta_k)) / (2 delta_k) - C sum_{j >= 1} a_j s_k,n-j,    F = C u' + G u - b
+ * with G, C restamped on the twin at the accepted point (u_n, t_n), F on the +- members at the same (u_n, u'_n, t_n), a_j the BDF
+ * coefficients of the accepted step, and all K systems of all accepting groups solved in one launch of the per-op LU.  One defect pass
+ * follows, because G + a0 C need not be the Jacobian of F (a capacitance that depends on u but is stamped into C): the +- members are
+ * restamped at (u_n +- delta_k s_k, u'_n +- delta_k s'_k) as well, the difference of their residuals over 2 delta_k -- the total central
+ * difference along the trajectory, zero for the exact s_k -- is solved on the same matrix and subtracted.  s_k = du_n/dp_k is
+ * the exact derivative of the discrete trajectory on the step sequence the run took (up to the central difference in p); it takes no part
+ * in the error test or the step choice, and the bases' states, counters and statuses are bit for bit those of the run without the setting.
+ * Save points are interpolated with the weights the states get.  A group whose solve met a bad pivot or a non-finite value gets flag 1
+ * and NaN from that step on; its states run on.  Such a run uses the per-op kernels whatever CadnipTranOpts::fused says.
+ * nh: history depth, 3, or 4 for runs with max_order >= 3; n_save / n_obs: those of the runs to come (cadnip_tran_run answers
+ * CADNIP_BADARG to other values, or to a max_order that does not fit nh, and CADNIP_NOTREADY without a cadnip_tran_sens_init since the
+ * last run).  The arrays are copied.  spec == NULL or n_group == 0 clears the setting and frees its memory.  CADNIP_BADARG -- the previous
+ * setting stays in force -- with a member index outside [0, B), an instance named twice, a delta that is not a positive finite number, nh
+ * other than 3 / 4, n_obs outside [1, n], history plus output beyond 256 MiB (8 n_group K (nh n + n_save n_obs) bytes), or while a delay
+ * spec is set; cadnip_tran_set_delay is refused likewise while this setting stands. */
+typedef struct {
+  int32_t n_group, K;
+  const int32_t* members;   /* [n_group][2 + 2 K] instance indices */
+  const double* delta;      /* [n_group][K] parameter steps, > 0 */
+  int32_t nh, n_save, n_obs;
+} CadnipSensSpec;
+int cadnip_tran_set_sens(CadnipHandle* h, const CadnipSensSpec* spec);
+/* s(t0) of every group, before each cadnip_tran_run.  zero != 0: s = 0 (the start state was given).  Otherwise the handle's current state
+ * is an operating point and s = -G^-1 d(G u - b)/dp there, by the same stage with every a_j = 0: call it after the :tranop cadnip_dc_run and
+ * before the mode is switched (needs cadnip_analyze*). */
+int cadnip_tran_sens_init(CadnipHandle* h, int32_t zero);
+/* results of the last run: out_s [n_group][K][n_save][n_obs], flags [n_group] (either may be NULL) */
+int cadnip_tran_sens_get(CadnipHandle* h, double* out_s, int32_t* flags);
+/* the sizes the kernels index by: out = {n_group, K, members per group, nh, n_save, n_obs}; all zero without a spec */
+int cadnip_tran_sens_info(CadnipHandle* h, int32_t out[6]);
 /* starts from the handle's current state u (e.g. left by cadnip_dc_run in :tranop mode);
  * out_host [B][n_save][n_obs]; per_inst_host [B][4] = {newton_iters, accepted, rejected, status}; status 1 = reached t1, -1 / -2 = the step
  * fell below hmin after a failed error test / Newton iteration, CADNIP_TRAN_DELAY_OVERFLOW = see cadnip_tran_set_delay */
