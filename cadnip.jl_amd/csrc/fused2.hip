@@ -3,7 +3,7 @@
 // The kernels keep all the Newton rounds of a launch on the chip: the circuit *structure* (tables, step descriptors) resident in LDS and
 // shared by the workgroup, each instance's Jacobian, right-hand side, solution and BDF history term resident in LDS, the step controller's
 // scalars in registers; HBM is touched for device parameters, the predictor / history vectors and the outputs.  lds_layout.hpp is the map
-// of that LDS block for every kernel; fused2_plan() below decides which kernel runs and with what:
+// of that LDS block for every kernel; launch_plan.hpp (f2_choose, through fused2_plan() below) decides which kernel runs and with what:
 //   * sweep kernel k_fused2<WPB, DC, VAR> (fused2_kernel.hpp): WPB instances per workgroup, one 64-lane wave each, waves never wait for
 //     each other.  VAR 0, the benchmark's kernel: lean device set (linear elements, sources, plain sp_mos1), every device emits its residual
 //     directly (devices.hpp, Rn), the linear solve runs from list-scheduled step descriptors staged behind the lean range of the tables.
@@ -184,8 +184,8 @@ int fused2_tables(CadnipHandle* h) {
   return CADNIP_OK;
 }
 
-// device-block descriptors of the fused kernels: rebuilt when the tables were, or when cadnip_set_params changed a block (sp_mos1 pairing);
-// also decides whether the circuit stays within the lean device set
+// device-block descriptors of the fused kernels: rebuilt when the tables were, or when cadnip_set_params changed a block (sp_mos1 pairing)
+// (whether the list stays within the lean device set: launch_plan.hpp, f2_lean)
 static int fused2_blocks(CadnipHandle* h) {
   { int rc = fused2_tables(h); if (rc) return rc; }
   FusedState& S = h->f2;
@@ -213,16 +213,6 @@ static int fused2_blocks(CadnipHandle* h) {
       const F2Block& D = hb[3 - S.src_blk - S.rc_blk];
       S.dev_type = D.type; S.dev_plain = D.mos1_plain; S.dev_count = D.count;
     }
-    S.lean = true;
-    for (int i = 0; i < nb; ++i) {
-      const int ty = hb[i].type;
-      const bool heavy = ty == CADNIP_DEV_DIODE || ty == CADNIP_DEV_DIODECAP || ty == CADNIP_DEV_SIMPLEMOS || ty == CADNIP_DEV_BVSOURCE ||
-                         ty == CADNIP_DEV_BISOURCE || ty == CADNIP_DEV_VA || (ty == CADNIP_DEV_MOS1 && !hb[i].mos1_plain);
-      if (heavy) S.lean = false;
-    }
-    // ... and its linear solve runs from step descriptors staged in LDS: a circuit whose steps do not fit beside the tables and eight
-    // instances (long dependency chains: an RC ladder has one step per section) takes the full variant, whose pass program is compact
-    if (!S.steps1.d || lds_bytes(lds_sweep((size_t)0, S.lean_end - S.lean_lo, S.steps1.len, S.lu_words, h->n, 0, 8)) > LDS_BUDGET) S.lean = false;
     S.n_blk = nb;
     // team kernel (fused_team_kernel.hpp): the parameter rows of the lane-paired sp_mos1 blocks are staged in LDS
     // ... of what the register-resident first pass over the first block does not cover (more than 32 MOSFETs, several blocks)
@@ -241,99 +231,60 @@ static int fused2_blocks(CadnipHandle* h) {
   return CADNIP_OK;
 }
 
-// The one place that decides what a fused launch runs, and the only reader of the diagnostic switches CADNIP_F2_NODIRECT / _TEAM / _WPB / _STEPS_PACKED /
-// _SRC_CACHE / _FIXED / _SHAPE
-// (CADNIP_F2_NC: f2_prepare, where the tables are built; CADNIP_F2_DEBUG prints the plan, launch_fused2).
-static bool env_is_zero(const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; }
+// ---- the launch plan: launch_plan.hpp decides (f2_choose, lu_choose); what follows gathers what it reads and carries its effects out ----
+// compute units of the device: asked once per handle, when a plan first gets as far as a rule that reads them
+static int device_cus(CadnipHandle* h) {
+  FusedState& S = h->f2;
+  if (S.n_cu > 0) return CADNIP_OK;
+  int cu = 0;
+  const hipError_t e = hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, h->device);
+  if (e != hipSuccess || cu <= 0) { set_last_error("hipDeviceGetAttribute", e); return CADNIP_HIPERROR; }
+  S.n_cu = cu;
+  return CADNIP_OK;
+}
+
+static StepFacts step_facts(const StepList& L) { StepFacts s; s.present = L.d != nullptr; s.len = L.len; for (int i = 0; i < 3; ++i) s.n_steps[i] = L.n_steps[i]; return s; }
+
+int plan_facts(CadnipHandle* h, bool tables, bool blocks, PlanFacts& f) {
+  FusedState& S = h->f2;
+  f.B = h->B; f.n = h->n;
+  for (auto& b : h->blocks) f.nb += b.count > 0;
+  f.va_ext = h->va_ext; f.analyzed = h->analyzed; f.delayed = h->dly.n_term > 0;
+  f.homotopy = h->homotopy || h->spec.gshunt != 0.0 || h->spec.srcFact < 1.0;
+  f.tables = tables && fused2_tables(h) == CADNIP_OK;
+  if (!f.tables) return CADNIP_OK;                        // (no rule reads further, and no HIP call has been made)
+  TRY_RC(device_cus(h));
+  f.n_cu = S.n_cu;
+  f.lu_words = S.lu_words; f.nc = S.nc; f.n_pre = S.n_pre; f.n_post = S.n_post;
+  f.lu_len = S.lu_len; f.lean_lo = S.lean_lo; f.lean_end = S.lean_end; f.full_len = S.full_len; f.loadpos_off = S.off[S_LOADPOS];
+  f.steps1 = step_facts(S.steps1); f.steps4 = step_facts(S.steps4); f.team[0] = step_facts(S.team[0]); f.team[1] = step_facts(S.team[1]);
+  if (!blocks || !f2_circuit_fits(f)) return CADNIP_OK;
+  TRY_RC(fused2_blocks(h));
+  f.par_words = S.par_words; f.n_blk = S.n_blk;
+  f.src_blk = S.src_blk; f.src_type = S.src_type; f.src_count = S.src_count; f.rc_type = S.rc_type; f.rc_count = S.rc_count;
+  f.dev_type = S.dev_type; f.dev_plain = S.dev_plain; f.dev_count = S.dev_count;
+  int nb = 0;                                             // (the handle's order; fused2_blocks sorts its copy)
+  for (auto& b : h->blocks)
+    if (b.count > 0 && nb < F2_MAX_BLOCKS) f.blk[nb++] = BlockFacts{b.type, b.mos1_plain ? 1 : 0};
+  return CADNIP_OK;
+}
+
+// The diagnostic switches CADNIP_F2_NODIRECT / _TEAM / _WPB / _STEPS_PACKED / _SRC_CACHE / _FIXED / _SHAPE, read at every plan: tests change
+// them between simulators of one process (CADNIP_F2_NC: f2_prepare, where the tables are built; CADNIP_F2_DEBUG prints the plan, launch_fused2)
+static int env_switch(const char* name) { const char* e = getenv(name); return e ? atoi(e) : SW_UNSET; }
+static F2Switches f2_switches() {
+  return F2Switches{env_switch("CADNIP_F2_NODIRECT"), env_switch("CADNIP_F2_TEAM"), env_switch("CADNIP_F2_WPB"), env_switch("CADNIP_F2_STEPS_PACKED"),
+                    env_switch("CADNIP_F2_SRC_CACHE"), env_switch("CADNIP_F2_FIXED"), env_switch("CADNIP_F2_SHAPE")};
+}
 
 F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode, const TranArgs* topt) {
   F2Plan p;
+  PlanFacts f;
+  if (int rc = plan_facts(h, !h->va_ext && h->analyzed, true, f)) { p.rc = rc; return p; }
+  const F2CallOpts co = topt ? F2CallOpts{topt->newton_mode, topt->max_order, topt->step_rule, topt->use_pcnr} : F2CallOpts{};
+  static_cast<F2Choice&>(p) = f2_choose(f, f2_switches(), mode, newton_mode, topt ? &co : nullptr);
   FusedState& S = h->f2;
-  p.rc = CADNIP_BADARG;
-  // external generated models exist in the per-op stamping kernel only; an un-analyzed handle is the entry points' CADNIP_NOTREADY
-  if (h->va_ext || !h->analyzed) return p;
-  if (fused2_tables(h)) return p;                       // (the tables cannot address the circuit)
-  int nb = 0;
-  for (auto& b : h->blocks) nb += b.count > 0;
-  // one instance beside the FULL table has to fit, whichever range the chosen kernel stages (findings)
-  if (nb > F2_MAX_BLOCKS || lds_bytes(lds_sweep((size_t)0, S.full_len, 0, S.lu_words, h->n, 0, 1)) > LDS_BUDGET) return p;
-  if (int rc = fused2_blocks(h)) { p.rc = rc; return p; }
-  // every device type emits its residual directly (devices.hpp, Rn); CADNIP_F2_NODIRECT=1 selects the assembled form
-  // r = J u + C beta - b instead (diagnostic: the two must agree)
-  const bool direct = !getenv("CADNIP_F2_NODIRECT"), lean = direct && S.lean;
-  // IDA-style Jacobian reuse (Newton mode 1) and the single step exist in the lean direct-residual variant only: a circuit with other
-  // device types (diodes, behavioural sources, sp_mos1 with series resistances, built-in Verilog-A modules ...) takes the per-op kernels
-  p.keep_factors = mode != F2_DC && (newton_mode || mode == F2_STEP);
-  if (p.keep_factors && !lean) return p;
-  // delayed stamps (cadnip_tran_set_delay) and their history ring exist beside the per-op kernels only (delay.hip); DC ignores them
-  if (mode == F2_TRAN && h->dly.n_term > 0) return p;
-  p.circuit_ok = true;
-  if (h->homotopy || h->spec.gshunt != 0.0 || h->spec.srcFact < 1.0) return p;   // homotopies run on the per-op path
-  if (S.n_cu <= 0) {
-    int cu = 0;
-    if (hipError_t e = hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, h->device)) { set_last_error("hipDeviceGetAttribute", e); p.rc = CADNIP_HIPERROR; return p; }
-    S.n_cu = cu > 0 ? cu : 256;
-  }
-  p.var = !direct ? 2 : S.lean ? 0 : 1;
-  p.tab_len = S.full_len;
-  if (lean) { p.tab_lo = S.lean_lo; p.tab_len = S.lean_end - S.lean_lo; }   // the lean kernels stage [permutations | stamp and node tables] only
-  // Few instances: a team of waves per instance (fused_team_kernel.hpp) -- the latency of ONE transient is what counts when the batch
-  // cannot fill the chip.  Transient, direct residuals, lean device set.  CADNIP_F2_TEAM = 0 | 2 | 4 forces the choice (diagnostic, tests).
-  if (mode != F2_DC && lean) {
-    // at most one instance per CU: a team of four waves (one per SIMD); at most two: teams of two waves, two workgroups per CU (their LDS allows it);
-    // beyond that the sweep kernel's one wave per instance
-    int nw = h->B <= S.n_cu ? 4 : h->B <= 2 * S.n_cu ? 2 : 0;
-    if (const char* e = getenv("CADNIP_F2_TEAM")) nw = atoi(e) >= 4 ? 4 : atoi(e) >= 2 ? 2 : 0;
-    if (mode == F2_STEP) nw = 4;
-    const StepList& T = S.team[nw / 4];
-    const size_t shmem = lds_bytes(lds_team((size_t)0, p.tab_len, nw ? T.len : 0, S.lu_words, h->n, S.par_words, nw));
-    if (nw && T.d && shmem <= LDS_BUDGET) {
-      const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(LDS_BUDGET / shmem, (size_t)(16 / nw)));
-      p.nw = nw; p.steps = &T; p.shmem = shmem; p.grid = std::min(h->B, S.n_cu * wg_per_cu); p.rc = CADNIP_OK;
-      return p;
-    }
-  }
-  if (mode == F2_STEP) return p;                        // (no team kernel for this circuit: the caller takes the per-op kernels)
-  // waves (= instances) per workgroup: 8 (two waves per SIMD) when they fit into LDS; fewer when the whole batch is then
-  // still resident in one generation with a workgroup on every CU -- a wave runs about 20 % faster with half as many
-  // neighbours on its CU (1024 instances: 4 per workgroup on 256 CUs, 57.7 M iterations/s, against 48.1 M as 8 x 128)
-  if (lean) p.steps = &S.steps1;   // the lean variant's linear solve runs from step descriptors (f2_build_steps) staged behind the tables
-  auto bytes = [&](int wpb) { return lds_bytes(lds_sweep((size_t)0, p.tab_len, p.steps ? p.steps->len : 0, S.lu_words, h->n, 0, wpb)); };
-  int wpb = 8;
-  if (const char* e = getenv("CADNIP_F2_WPB")) wpb = atoi(e) >= 8 ? 8 : atoi(e) >= 4 ? 4 : atoi(e) >= 2 ? 2 : 1;   // diagnostic: cap the waves per workgroup
-  while (wpb > 1 && (bytes(wpb) > LDS_BUDGET || S.n_cu * (wpb / 2) >= h->B)) wpb >>= 1;
-  if (bytes(wpb) > LDS_BUDGET) return p;
-  // resident workgroups only: the instances beyond them are handed out by the in-kernel queue as waves become free
-  const int wg_per_cu = (int)std::max<size_t>(1, std::min<size_t>(LDS_BUDGET / bytes(wpb), (size_t)(32 / wpb)));
-  // The step descriptors are staged pre-decoded (lds_layout.hpp: lds_step_predecode) when every word of a work array has a 16-bit byte
-  // offset and the flag bytes fit without costing a resident instance: neither wpb nor the workgroups per CU may change for them.  Otherwise,
-  // and under CADNIP_F2_STEPS_PACKED=1 (diagnostic, tests: the two decodes must agree to the bit), the kernel decodes the packed words.
-  size_t shmem = bytes(wpb);
-  if (p.steps && lds_steps_predec_ok(S.lu_words, h->n) && !getenv("CADNIP_F2_STEPS_PACKED")) {
-    const size_t pd = lds_bytes(lds_sweep((size_t)0, p.tab_len, lds_sweep_desc_words(p.steps->len, true), S.lu_words, h->n, 0, wpb));
-    if (pd <= LDS_BUDGET && (int)std::max<size_t>(1, std::min<size_t>(LDS_BUDGET / pd, (size_t)(32 / wpb))) == wg_per_cu) { p.step_predec = true; shmem = pd; }
-  }
-  // Transient launches of the direct-residual variants keep the segment each pinned source is on in LDS (src_cache.hpp), under the same rule: the
-  // region may cost neither a wave per workgroup (wpb stands as chosen above) nor a workgroup per CU.  Otherwise, and under CADNIP_F2_SRC_CACHE=0
-  // (diagnostic, tests: bit-identical results either way), every new time point evaluates its sources from global memory as before.
-  if (mode == F2_TRAN && direct && S.src_blk >= 0 && !env_is_zero("CADNIP_F2_SRC_CACHE")) {
-    const int sw = src_cache_words(S.src_count), dw = p.steps ? lds_sweep_desc_words(p.steps->len, p.step_predec) : 0;
-    if (src_cache_fits(p.tab_len, dw, S.lu_words, h->n, wpb, sw)) {
-      p.src_words = sw;
-      shmem = lds_bytes(lds_sweep((size_t)0, p.tab_len, dw, S.lu_words, h->n, 0, wpb, sw));
-    }
-  }
-  // The default transient call on a lean circuit takes the fixed form of variant 0 (k_fused2<wpb, false, 3>: the call's switches are compile-time
-  // constants there); f2_fixed_ok is the list of what that kernel assumes.  CADNIP_F2_FIXED=0 (diagnostic, tests: bit-identical results either
-  // way) keeps the generic kernel, and so do CADNIP_F2_STEPS_PACKED=1 and CADNIP_F2_SRC_CACHE=0 through step_predec / src_words.
-  p.fixed = topt && f2_fixed_ok(mode == F2_TRAN, p.var == 0, topt->newton_mode, p.step_predec, p.src_words, h->n, S.nc, topt->max_order, topt->step_rule,
-                                topt->use_pcnr, !env_is_zero("CADNIP_F2_FIXED"));
-  // ... and of the fixed form its shape form (k_fused2<wpb, false, 4>) when the circuit's block list is a CMOS cell's: voltage sources, one pass of
-  // plain sp_mos1, capacitors -- f2_shape_ok is the list.  CADNIP_F2_SHAPE=0 (diagnostic, tests: bit-identical results either way) keeps variant 3.
-  // (its sp_mos1 lanes address u by 16-bit byte offsets from W: lds_m1pin_ok)
-  p.shape = f2_shape_ok(p.fixed, S.n_blk, S.src_type, S.src_count, S.rc_type, S.rc_count, S.dev_type, S.dev_plain, S.dev_count, !env_is_zero("CADNIP_F2_SHAPE")) &&
-            lds_m1pin_ok(S.lu_words, h->n);
-  p.wpb = wpb; p.shmem = shmem; p.grid = std::min((h->B + wpb - 1) / wpb, S.n_cu * wg_per_cu); p.rc = CADNIP_OK;
+  p.steps = p.step_list == F2_STEPS_1 ? &S.steps1 : p.step_list == F2_STEPS_TEAM2 ? &S.team[0] : p.step_list == F2_STEPS_TEAM4 ? &S.team[1] : nullptr;
   return p;
 }
 

@@ -16,7 +16,6 @@ typedef unsigned long long u64;
 #define NOPOS 0xFFFFu
 #define F2_NCMAX 16   // largest core the in-register dense solve is unrolled for
 #define F2_JU 18      // J*u entries per lane and chunk
-#define F2_MAX_BLOCKS 32   // device blocks of one circuit (one per built-in type, one per Verilog-A module); more: per-op path
 
 // table sections (offsets in 32-bit words, every section 8-byte aligned)
 enum { S_GPOS = 0, S_CDESC, S_BROW, S_NZ, S_ENT, S_TERM, S_LEV, S_QINV, S_NODES, S_ROWOF, S_LOADPOS, S_NSEC };   // S_LOADPOS: csr entry -> W word (lu_f2.hip)
@@ -54,7 +53,7 @@ struct F2Args {
   double* lufac;                    // [B][nnz_lu] kept factors of the instances that are not resident (between launches / while queued)
   const unsigned long long* team_desc; int team_desc_len;   // team kernel (fused_team_kernel.hpp): step descriptors of the linear solve (f2_program.cpp: f2_build_team)
   int ts_pre, ts_post, ts_fwd;      // ... steps of the pre-core, post-core and forward-only lists
-  int step_predec;                  // sweep kernel, lean variant: 1 = the descriptors are staged pre-decoded (lds_layout.hpp: lds_step_predecode; fused2.hip: fused2_plan decides)
+  int step_predec;                  // sweep kernel, lean variant: 1 = the descriptors are staged pre-decoded (lds_layout.hpp: lds_step_predecode; launch_plan.hpp: f2_choose decides)
   int src_words;                    // sweep kernel, direct-residual variants, transient: doubles of an instance's source segment cache (src_cache.hpp; lds_layout.hpp: lds_sweep), 0 = none
   int par_words;                    // team kernel: doubles of the LDS-staged sp_mos1 parameter rows (F2Block::lds_par)
   int step_refresh; double *step_resid, *step_norm;   // team kernel, STEP mode (cadnip_newton_step_fused): refactor or use f.lufac; optional outputs
@@ -368,7 +367,7 @@ __device__ __forceinline__ void dense_core_solve(double* W, int dn0, int yc0, in
 
 // VAR: 0 = direct residuals, lean device set; 1 = direct residuals, every device type; 2 = assembled residual
 // r = J u + C beta - b (diagnostic, CADNIP_F2_NODIRECT=1), every device type; 3 = variant 0 with the default transient call's switches
-// fixed at compile time (lds_layout.hpp: f2_fixed_ok is the list; fused2.hip: fused2_plan decides): Newton mode 1, pre-decoded steps, source
+// fixed at compile time (lds_layout.hpp: f2_fixed_ok is the list; launch_plan.hpp: f2_choose decides): Newton mode 1, pre-decoded steps, source
 // cache on, core of 8, no PCNR, max_order <= 2, step_rule 0, n <= 256.  Same statements, same order: results are variant 0's to the bit.
 // 4 = variant 3 with the circuit's block list fixed as well, to the shape of a CMOS-cell deck (lds_layout.hpp: f2_shape_ok is the list): three
 // blocks -- the pinned voltage sources (<= 64), the pinned capacitors (<= 64), one plain sp_mos1 block of one lane-pair pass (<= 32).  No block

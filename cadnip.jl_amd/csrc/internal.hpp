@@ -9,6 +9,7 @@
 #include "ac_hbm_plan.hpp"  // AcHbmPlan
 #include "delay_plan.hpp"   // DelayPlan
 #include "tran_sens_plan.hpp"
+#include "launch_plan.hpp"  // PlanFacts, F2Mode, F2Choice
 // rows of the derived sp_mos1 parameter card (devices.hpp: enum M1_*) that cadnip_set_params inspects
 #define CADNIP_MOS1_PAR_OXCAP 8
 #define CADNIP_MOS1_PAR_GD 30
@@ -117,7 +118,7 @@ struct FusedState {
   StepList steps1;            // one wave per instance (lean sweep kernel, k_lu_f2s): three-term list-scheduled steps, two words per lane
   StepList steps4;            // ... for a team of four waves, read from global memory (k_lu_steps)
   StepList team[2];           // team kernel: teams of 2 (three-term steps) / 4 waves (one-term level-aligned steps)
-  // device-block descriptors and what they decide (fused2.hip: fused2_blocks)
+  // device-block descriptors and the facts of their list (fused2.hip: fused2_blocks)
   void* d_blk = nullptr;
   int n_blk = 0, rc_blk = -1, src_blk = -1;   // first capacitor / resistor block, first independent-source block of the list
   int src_count = 0;          // devices of block src_blk (the first 64 are pinned to lanes and may have their segment cached: src_cache.hpp)
@@ -125,12 +126,10 @@ struct FusedState {
   // list of three; a type of -1: no such block)
   int src_type = -1, rc_type = -1, rc_count = 0, dev_type = -1, dev_plain = 0, dev_count = 0;
   int par_words = 0;          // team kernel: doubles of the LDS-staged sp_mos1 parameter rows of one instance
-  bool lean = false;          // only device types of the lean kernel variant
   // buffers of the launches
   int* d_queue = nullptr;     // dynamic instance queue
   double* d_lufac = nullptr; size_t lufac_cap = 0;   // Newton mode 1: kept factors of the non-resident instances [B][lu_words]
-  int n_cu = 0;               // compute units of the device (queried by the first fused launch; MI355X: 256)
-  int n_cu_hint() const { return n_cu > 0 ? n_cu : 256; }
+  int n_cu = 0;               // compute units of the device (queried by the handle's first launch plan, fused2.hip: plan_facts; MI355X: 256)
   void release();             // frees every device buffer; the next use builds everything again
 };
 
@@ -378,20 +377,15 @@ struct FusedStepIO { const double *u, *du, *gamma, *t; double *gamma_keep, *t_ke
 int launch_fused_step(CadnipHandle* h, int refresh, const FusedStepIO& io);
 int launch_va_setup(CadnipHandle* h, DeviceBlock& b);                        // stamp_csr.hip: the setup pass of a generated external model's block
 int fused2_tables(CadnipHandle* h);                                        // builds the packed tables on demand; CADNIP_OK: they exist
-// What a fused launch would run (fused2.hip: fused2_plan).  rc != CADNIP_OK: the fused kernels do not apply now, and launch_fused2_* return
+// The facts both launch planners read (launch_plan.hpp), gathered from the handle.  tables: build the packed tables first if need be; blocks:
+// and, for a circuit the fused kernels can address, the block descriptors.  Once the tables exist the device is asked for its compute units,
+// at the handle's first such call (a handle that is refused before, or takes k_lu whatever the tables hold, makes no HIP call here as before).
+// Returns the failure of that query or of the descriptors' upload
+int plan_facts(CadnipHandle* h, bool tables, bool blocks, PlanFacts& f);
+// What a fused launch would run (fused2.hip: fused2_plan; launch_plan.hpp: f2_choose decides).  rc != CADNIP_OK: the fused kernels do not apply now, and launch_fused2_* return
 // rc; !circuit_ok: they never apply to this circuit / Newton mode -- the drivers take the per-op kernels (still on the GPU) instead
-enum F2Mode { F2_TRAN, F2_DC, F2_STEP };
-struct F2Plan {
-  int rc = CADNIP_OK; bool circuit_ok = false;
-  int nw = 0;                 // team kernel k_fteam<nw>; 0: sweep kernel k_fused2<wpb, dc, var>
-  int var = 0, wpb = 0, grid = 0; size_t shmem = 0;
-  int tab_lo = 0, tab_len = 0;          // staged table range (32-bit words)
-  const StepList* steps = nullptr;      // step descriptors staged behind it (null: the pass program of the full table)
-  bool step_predec = false;   // sweep kernel: the descriptors are staged pre-decoded, a flag byte per lane and step behind them (lds_layout.hpp)
-  bool keep_factors = false;  // Newton mode 1 / single step: kept factors in HBM
-  int src_words = 0;          // sweep kernel: doubles of the per-instance source segment cache in LDS (src_cache.hpp), 0 = the launch runs without it
-  bool fixed = false;         // sweep kernel, variant 0: the launch takes the fixed form k_fused2<wpb, false, 3> (lds_layout.hpp: f2_fixed_ok)
-  bool shape = false;         // ... and of it the shape form k_fused2<wpb, false, 4>: the circuit's block list is fixed as well (lds_layout.hpp: f2_shape_ok)
+struct F2Plan : F2Choice {             // what launch_plan.hpp: f2_choose chose, and ...
+  const StepList* steps = nullptr;      // ... the step list it named: the descriptors staged behind the tables (null: the pass program of the full table)
 };
 // topt: the transient options of the call the plan is for (null: none -- the fixed form is then never chosen)
 F2Plan fused2_plan(CadnipHandle* h, F2Mode mode, int newton_mode, const TranArgs* topt = nullptr);

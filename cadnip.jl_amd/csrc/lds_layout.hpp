@@ -10,6 +10,7 @@
 #include <stddef.h>
 #include "../../include/cadnip_hip.h"   // device type codes (f2_shape_ok)
 #ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 #include <type_traits>
 #define LDS_HD __host__ __device__ __forceinline__
 #else
@@ -17,6 +18,7 @@
 #endif
 
 #define F2_TRASH 64        // per-instance trash words (one per lane) that absorb stamps into ground rows / columns
+#define F2_MAX_BLOCKS 32   // device blocks of one circuit (one per built-in type, one per Verilog-A module); more: per-op path
 #define LDS_BUDGET ((size_t)160 * 1024)   // LDS of a gfx950 compute unit = the most one workgroup may ask for
 #define LDS_OPTIN ((size_t)64 * 1024)     // above this a kernel needs hipFuncAttributeMaxDynamicSharedMemorySize raised (lds_launch)
 
@@ -34,7 +36,7 @@ LDS_HD int lds_work_words(int lu_words, int n) { return lu_words + n + F2_TRASH;
 //   * the lane's group width and the step's two uniform flags go to one byte per lane and step behind the descriptors:
 //     bits 4-6 log2 of the lane group's width, bit 3 "an entry of this step divides", bits 0-2 log2 of the step's widest group --
 //     `lg >= k` is `byte >= 16 k`, one compare against an inline constant.
-// Byte offsets need every word of W | consts below 8192: lds_steps_predec_ok; the launch plan (fused2.hip: fused2_plan) decides.
+// Byte offsets need every word of W | consts below 8192: lds_steps_predec_ok; the launch plan (launch_plan.hpp: f2_choose) decides.
 struct StepPredec { unsigned x, y, z, w, flags; };
 LDS_HD StepPredec lds_step_predecode(unsigned x, unsigned y, unsigned z, unsigned w, unsigned trash_word) {
   StepPredec r;
@@ -48,7 +50,7 @@ LDS_HD StepPredec lds_step_predecode(unsigned x, unsigned y, unsigned z, unsigne
 LDS_HD bool lds_steps_predec_ok(int lu_words, int n) { return lu_words + n + F2_TRASH + LDS_CONSTS <= 8192; }
 // ---- the sweep kernel's FIXED form (k_fused2<WPB, false, 3>, fused2_kernel.hpp): the lean transient kernel with every switch of the default
 // call a compile-time constant.  THE list of what that kernel assumes; a launch that misses one condition takes the generic variant 0, which
-// computes the same to the bit.  `enabled`: CADNIP_F2_FIXED is not 0 (diagnostic, tests; fused2.hip: fused2_plan reads it and calls this).
+// computes the same to the bit.  `enabled`: CADNIP_F2_FIXED is not 0 (diagnostic, tests; launch_plan.hpp: f2_choose is handed it and calls this).
 LDS_HD bool f2_fixed_ok(bool tran, bool lean, int newton_mode, bool step_predec, int src_words, int n, int nc, int max_order, int step_rule,
                         int use_pcnr, bool enabled) {
   return tran && lean && newton_mode == 1 && step_predec && src_words > 0 && n <= 256 && nc == 8 && max_order <= 2 && step_rule == 0 &&
@@ -61,7 +63,7 @@ LDS_HD bool f2_fixed_ok(bool tran, bool lean, int newton_mode, bool step_predec,
 // capacitor / resistor block (F2Args::rc_blk) and dev_* the remaining one (a type of -1: there is no such block).  With three blocks, one of them
 // the first of the source types and another the first of the R / C types, each is the only one of its kind.  The counts: a pinned block of at
 // most 64 has one device per lane and nothing left for the block loop; 32 lane-paired sp_mos1 devices are one pass of a wave.
-// `enabled`: CADNIP_F2_SHAPE is not 0 (diagnostic, tests; fused2_plan reads it and calls this).
+// `enabled`: CADNIP_F2_SHAPE is not 0 (diagnostic, tests; f2_choose is handed it and calls this).
 LDS_HD bool f2_shape_ok(bool fixed, int n_blk, int src_type, int src_count, int rc_type, int rc_count, int dev_type, int dev_plain, int dev_count,
                         bool enabled) {
   return fixed && n_blk == 3 && src_type == CADNIP_DEV_VSOURCE && src_count <= 64 && rc_type == CADNIP_DEV_CAPACITOR && rc_count <= 64 &&
@@ -72,7 +74,7 @@ LDS_HD bool f2_shape_ok(bool fixed, int n_blk, int src_type, int src_count, int 
 //   * an operand -- a terminal voltage, a limit or charge unknown -- as the BYTE offset of its word of u from the instance's W (u lies behind
 //     W | consts, lds_sweep); ground (node < 0) is the constant word 0.0, so that reading a voltage is one unconditional read of the same 0.0;
 //   * a residual target as the WORD of W that `rowof` names for the unknown; ground is the lane's trash word.
-// Byte offsets of u need W | consts | u below 8192 words: lds_m1pin_ok (one more condition of the shape form; fused2.hip: fused2_plan).
+// Byte offsets of u need W | consts | u below 8192 words: lds_m1pin_ok (one more condition of the shape form; launch_plan.hpp: f2_choose).
 LDS_HD bool lds_m1pin_ok(int lu_words, int n) { return lds_work_words(lu_words, n) + LDS_CONSTS + n <= 8192; }
 LDS_HD unsigned lds_m1pin_operand(int node, int lu_words, int n) {
   const int nW = lds_work_words(lu_words, n);
@@ -147,10 +149,15 @@ template <class P> LDS_HD LdsAcSens<P> lds_ac_sens(P base, int nnz_lu, int n, in
 template <class L> LDS_HD size_t lds_bytes(const L& l) { return (size_t)l.end * 8; }   // of a layout taken from base (size_t)0
 
 #ifdef __HIPCC__
+void set_last_error(const char* what, hipError_t e);   // api.hip (declared here too: this header stands alone, whatever includes it first)
 // launch `kernel` with `shmem` bytes of dynamic LDS, opting in to more than LDS_OPTIN first
 template <class K, class... A>
 static int lds_launch(K kernel, int grid, int threads, size_t shmem, hipStream_t stream, const A&... args) {
-  if (shmem > LDS_OPTIN) HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  if (shmem > LDS_OPTIN)
+    if (hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)) {
+      set_last_error("hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize)", e);
+      return CADNIP_HIPERROR;
+    }
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), shmem, stream, args...);
   return CADNIP_OK;
 }

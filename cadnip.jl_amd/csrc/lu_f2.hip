@@ -10,7 +10,7 @@
 // What they share is written once: the team (LuTeam), the load (lu_load), one step (step_open / step_finish), the dense core's
 // dispatch (DENSE_CORE, fused2_kernel.hpp), the store and the flag rule (lu_store), the arguments (LuArgs).  The entry of a pass is
 // written out in both pass kernels (see k_lu_f2_mw).
-// lu_f2_plan chooses among them and k_lu (kernels.hip: level by level on the LU program, factors in LDS or HBM), which also serves
+// launch_plan.hpp: lu_choose chooses among them and k_lu (kernels.hip: level by level on the LU program, factors in LDS or HBM), which also serves
 // what this program cannot do: factor-only / solve-only (the callback ABI's cadnip_factor / cadnip_solve keep the factors in HBM).
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -356,51 +356,30 @@ __global__ void __launch_bounds__(64 * NW) k_lu_steps(LuArgs f) {
   lu_store(f, inst, team, W, (const u16*)(f.tab + f.off[S_QINV]), bad);
 }
 
-// THE plan of launch_factor_solve: the one place that decides which kernel runs and with what geometry, and the only reader of
-// CADNIP_LU_PLAIN / _STEPS / _WPI / _F2S (read at every call).  kernel: CADNIP_LUK_AUTO (the choice below, switches included) or one forced
-// kernel (switches and batch rules ignored, the LDS limits kept; W of k_lu_f2s / k_lu_f2 still from B).  kernel -1: the forced kernel does
-// not apply.  When no program kernel applies, auto runs k_lu.  The batch rules count 256 compute units where the device has not been asked
-// yet (findings).  The first six members are what cadnip_factor_solve reports (info [6])
-struct LuPlan { int kernel, wpb, wpi, nc, pre, post, tab_lo, tab_len; size_t shmem; };   // wpb, wpi: waves per workgroup / per instance; pre, post: steps or passes before / after the dense core
-static LuPlan lu_f2_plan(CadnipHandle* h, bool fuse, int kernel) {
-  const FusedState& S = h->f2;
-  const bool any = kernel == CADNIP_LUK_AUTO;
-  const LuPlan none{-1, 0, 0, 0, 0, 0, 0, 0, 0};
-  // k_lu: forced, CADNIP_LU_PLAIN set (diagnostic: the kernels must agree), a Jacobian that is not fused (J from d_J), or nothing else applies
-  const int plain_waves = lu_plain_threads(h, true) / 64;
-  const LuPlan plain{CADNIP_LUK_PLAIN, plain_waves, plain_waves, 0, 0, 0, 0, 0, 0};
-  if (!fuse || kernel == CADNIP_LUK_PLAIN || (any && getenv("CADNIP_LU_PLAIN"))) return plain;
-  const LuPlan other = any ? plain : none;
-  if (fused2_tables(h)) return other;                      // (only the linear-solve prefix of the tables has to fit: the LDS limits below)
-  auto bytes = [&](int tab_len, int desc_len, bool consts, int waves) { return lds_bytes(lds_lu((size_t)0, tab_len, desc_len, S.lu_words, h->n, consts, 0, waves)); };
-  // at most two instances per CU: the straight-line steps of a team of four waves per instance (k_lu_steps).  CADNIP_LU_STEPS = 0 | 1 forces the choice
-  if (any || kernel == CADNIP_LUK_STEPS4) {
-    const char* e = any ? getenv("CADNIP_LU_STEPS") : nullptr;
-    const bool steps = !any || (e ? atoi(e) != 0 : h->B <= 2 * S.n_cu_hint());
-    if (steps && S.steps4.d && bytes(0, 0, true, 1) <= LDS_BUDGET) return LuPlan{CADNIP_LUK_STEPS4, 4, 4, S.nc, S.steps4.n_steps[0], S.steps4.n_steps[1], 0, 0, bytes(0, 0, true, 1)};
-    if (!any) return none;
+// The plan of launch_factor_solve: launch_plan.hpp decides (lu_choose); here its facts are gathered -- the tables built unless k_lu runs whatever
+// they hold -- and CADNIP_LU_PLAIN / _STEPS / _WPI / _F2S read, at every call and only where they count: a forced kernel ignores them.  This
+// sits in the per-op Newton loop, where the choice used to cost two to four getenv calls depending on how far it got: the four are read in
+// ONE pass over the environment (the first entry of a name counts, as for getenv), so that no batch size pays more look-ups than before
+extern "C" char** environ;
+static LuSwitches lu_switches() {
+  static const char* const names[4] = {"PLAIN=", "STEPS=", "WPI=", "F2S="};
+  int v[4] = {SW_UNSET, SW_UNSET, SW_UNSET, SW_UNSET};
+  for (char** e = environ; e && *e; ++e) {
+    if (strncmp(*e, "CADNIP_LU_", 10)) continue;
+    for (int i = 0; i < 4; ++i) {
+      const size_t nl = strlen(names[i]);
+      if (v[i] == SW_UNSET && !strncmp(*e + 10, names[i], nl)) v[i] = atoi(*e + 10 + nl);
+    }
   }
-  // a few instances of a circuit with many passes: several waves per instance (k_lu_f2_mw).  CADNIP_LU_WPI forces 1 / 4 (diagnostic)
-  if (any || kernel == CADNIP_LUK_F2MW) {
-    const char* e = any ? getenv("CADNIP_LU_WPI") : nullptr;
-    const int wpi = !any ? 4 : e ? atoi(e) : (h->B * 4 <= S.n_cu_hint() && S.n_pre + S.n_post >= 32 ? 4 : 1);
-    if (wpi == 4 && bytes(S.lu_len, 0, false, 1) <= LDS_BUDGET) return LuPlan{CADNIP_LUK_F2MW, 4, 4, S.nc, S.n_pre, S.n_post, 0, S.lu_len, bytes(S.lu_len, 0, false, 1)};
-    if (!any) return none;
-  }
-  // many instances: one wave each, 8 per workgroup unless fewer still put a workgroup on every CU
-  int wpb = 8;
-  while (wpb > 1 && h->B < 256 * wpb / 2) wpb >>= 1;
-  // ... on the step program when its descriptors fit beside eight work arrays (CADNIP_LU_F2S = 0 keeps the passes); staged: the table from the load map on
-  const char* e = any ? getenv("CADNIP_LU_F2S") : nullptr;
-  if (S.steps1.d && (any ? !(e && atoi(e) == 0) : kernel == CADNIP_LUK_F2S)) {
-    const int lo = S.off[S_LOADPOS] & ~3;
-    if (bytes(S.lu_len - lo, S.steps1.len, true, 8) <= LDS_BUDGET)
-      return LuPlan{CADNIP_LUK_F2S, wpb, 1, S.nc, S.steps1.n_steps[0], S.steps1.n_steps[1], lo, S.lu_len - lo, bytes(S.lu_len - lo, S.steps1.len, true, wpb)};
-  }
-  if (!any && kernel != CADNIP_LUK_F2) return none;
-  while (wpb > 1 && bytes(S.lu_len, 0, false, wpb) > LDS_BUDGET) wpb >>= 1;
-  if (bytes(S.lu_len, 0, false, wpb) > LDS_BUDGET) return other;
-  return LuPlan{CADNIP_LUK_F2, wpb, 1, S.nc, S.n_pre, S.n_post, 0, S.lu_len, bytes(S.lu_len, 0, false, wpb)};
+  return LuSwitches{v[0], v[1], v[2], v[3]};
+}
+static int lu_f2_plan(CadnipHandle* h, bool fuse, int kernel, LuPlan& p) {
+  const LuSwitches sw = kernel == CADNIP_LUK_AUTO ? lu_switches() : LuSwitches();
+  PlanFacts f;
+  TRY_RC(plan_facts(h, !lu_takes_plain(sw, fuse, kernel), false, f));
+  f.lu_plain_threads = lu_plain_threads(h, true);
+  p = lu_choose(f, sw, fuse, kernel);
+  return CADNIP_OK;
 }
 
 // the arguments of the program kernel of plan p
@@ -423,7 +402,8 @@ static LuArgs lu_args(const CadnipHandle* h, const LuPlan& p, const double* d_rh
 int launch_factor_solve(CadnipHandle* h, bool fuse, const double* d_rhs, double* d_x, int kernel, int* info, bool dry) {
   if (kernel < CADNIP_LUK_AUTO || kernel > CADNIP_LUK_PLAIN || (kernel != CADNIP_LUK_AUTO && !fuse)) return CADNIP_BADARG;
   if (!h->analyzed) return CADNIP_NOTREADY;
-  const LuPlan p = lu_f2_plan(h, fuse, kernel);
+  LuPlan p;
+  TRY_RC(lu_f2_plan(h, fuse, kernel, p));
   if (p.kernel < 0) return CADNIP_BADARG;
   if (info) { info[0] = p.kernel; info[1] = p.wpb; info[2] = p.wpi; info[3] = p.nc; info[4] = p.pre; info[5] = p.post; }
   if (dry) return CADNIP_OK;

@@ -68,7 +68,7 @@ template <class P> LDS_HD void src_seg_store(P base, int count, int lane, const 
   base[lane] = e.t_lo; base[count + lane] = e.t_hi; base[2 * count + lane] = e.y_lo; base[3 * count + lane] = e.y_hi; base[4 * count + lane] = e.scale;
 }
 
-// ---- the plan's rule (fused2.hip: fused2_plan): the cache is taken only when it costs neither a wave per workgroup nor a workgroup per CU.
+// ---- the plan's rule (launch_plan.hpp: f2_choose): the cache is taken only when it costs neither a wave per workgroup nor a workgroup per CU.
 // Resident workgroups of the sweep kernel on one compute unit: by LDS, at most 32 waves
 LDS_HD int sweep_wg_per_cu(size_t bytes, int wpb) {
   size_t k = bytes ? LDS_BUDGET / bytes : 0, cap = (size_t)(32 / wpb);

@@ -298,7 +298,7 @@ inline int stamp_plan_build(const CadnipStructure& s, const std::vector<StampBlo
   return CADNIP_OK;
 }
 
-// ---- the launch geometry of one stamping pass (the analogue of fused2_plan / ac_lu_plan) ------------------------------------
+// ---- the launch geometry of one stamping pass (the analogue of launch_plan.hpp / ac_lu_plan) ------------------------------------
 // pair: the lane-pair path of an sp_mos1 block (plan[1]); readout: the operating-point read-out pass, which stages every slot in a
 // row of its own; pad: extra LDS bytes (experiments: occupancy as a function of the LDS request).
 // The dynamic LDS block, as the kernel carves it: ipw tiles (staged rows + tree scratch) | 3 scalars per instance | u of the tile's
